@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- kilobot-steps/s of the HIP world step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = ONE kb_step launch of ONE world substep (dt = 0.1 s; reference
 kilobots_env.py:168-190) over the whole env batch with fresh per-bot actions, i.e. exactly the
@@ -14,8 +14,12 @@ The timed state does not depend on --warmup: before the warm-up launches the sce
 `--settle` substeps and then further until the contact population is stationary (contacts per env
 within 1 % over 10 substeps); `contacts_per_env` in the JSON line is what the timed launches ran on.
 
-Behind the timed region (N = 1, never mixed into `value`): `with_sleep_state` (the instantiation that carries Box2D's sleep
-state), `fused_env_step` (10 substeps per launch) and `jammed_swarm` (the slow corner: the swarm jammed into one island).
+A plain run sets up, settles, warms up, times the K steps and prints the line. `--dump-outputs DIR` then also writes the state
+the last timed step left (what a caller of KilobotSim.step receives) as DIR/<name>.npy, for output-for-output comparisons of two
+builds on identical inputs.  `--full` adds everything else, behind the timed region (N = 1, never mixed into `value`): the audit
+pass with per-launch events, `with_sleep_state` (the instantiation that carries Box2D's sleep state), `fused_env_step` (10
+substeps per launch), `jammed_swarm` (the slow corner: the swarm jammed into one island), the `cfg2` / `cfg4` legs and the
+`cpu_baseline` of the oracle.
 
 N > 1: `--gpus N` without a torchrun environment starts N child processes itself (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, fresh children -- the parent never touches a GPU);
@@ -70,6 +74,10 @@ def parse_args(argv=None):
     ap.add_argument('--cpu-envs', type=int, default=64)
     ap.add_argument('--cpu-seconds', type=float, default=8.0)
     ap.add_argument('--traffic-json', default=os.path.join(ROOT, 'profiles', 'traffic_latest.json'))
+    ap.add_argument('--full', action='store_true',
+                    help='also the audit pass, the legs next to the headline (sleep state, fused, jammed, cfg2, cfg4) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the state after the last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
     ap.add_argument('--selftest-launcher', action='store_true',
                     help='CPU-only check of the rank launcher and the gather (gloo); no simulation')
     return ap.parse_args(argv)
@@ -188,6 +196,32 @@ def contacts_per_env(sim):
     return float(sim.ws_cnt.sum(dtype=torch.int64).item()) / sim.num_envs
 
 
+DUMP_FIELDS = ('x', 'y', 'theta', 'v', 'w', 'sleep_time', 'nbr_count', 'ox', 'oy', 'otheta', 'ovx', 'ovy', 'ow', 'osleep', 'status')
+DUMP_BUDGET = 60 << 20          # bytes of array data in all (the files stay under 64 MB)
+DUMP_SAMPLE_SEED = 12345
+
+
+def dump_outputs(sim, out_dir):
+    """The per-env state a caller of KilobotSim.step receives, as out_dir/<name>.npy: float tensors as float32, integer ones
+    (neighbour counts, status flags) as float64, which holds them exactly.  Where all envs exceed DUMP_BUDGET, a fixed seeded
+    sample of envs is written instead, the same for every field, and env_index.npy says which."""
+    import torch
+    fields = [(n, getattr(sim, n)) for n in DUMP_FIELDS if getattr(sim, n, None) is not None]
+    E = sim.num_envs
+    per_env = sum(t[0].numel() * (4 if t.is_floating_point() else 8) for _, t in fields)
+    idx = None
+    if per_env * E > DUMP_BUDGET:
+        m = max(1, DUMP_BUDGET // per_env)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(E, m, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    sel = None if idx is None else torch.from_numpy(idx).to(sim.device)
+    for name, t in fields:
+        a = (t if sel is None else t.index_select(0, sel)).cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), a.astype(np.float32 if t.is_floating_point() else np.float64))
+    if idx is not None:
+        np.save(os.path.join(out_dir, 'env_index.npy'), idx.astype(np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -273,7 +307,7 @@ def main():
         if stationary:
             break
     cpu_start = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         nc = min(args.cpu_envs, E)
         cpu_start = dict(x=sim.x[:nc].cpu().numpy(), y=sim.y[:nc].cpu().numpy(), theta=sim.theta[:nc].cpu().numpy(),
                          actions=[a[:nc].cpu().numpy() for a in actions])
@@ -297,16 +331,20 @@ def main():
     elapsed = elapsed_local
     kern_ms = ev_a.elapsed_time(ev_b) / K          # average launch duration over the timed region
     c_after = contacts_per_env(sim)
-    # audit pass: the same K launches again, each bracketed by its own events (first / last / min / max of the state that was timed)
-    ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(K)]
-    ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(K)]
-    for k in range(K):
-        ev0[k].record()
-        sim.step(1, actions=actions[k_act % n_sets])
-        ev1[k].record()
-        k_act += 1
-    torch.cuda.synchronize()
-    launch_ms = [a.elapsed_time(b) for a, b in zip(ev0, ev1)]
+    if args.dump_outputs and rank == 0:      # what the last timed step left, before the audit pass and the legs step on
+        dump_outputs(sim, args.dump_outputs)
+    launch_ms = None
+    if args.full:
+        # audit pass: the same K launches again, each bracketed by its own events (first / last / min / max of the state that was timed)
+        ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(K)]
+        ev1 = [torch.cuda.Event(enable_timing=True) for _ in range(K)]
+        for k in range(K):
+            ev0[k].record()
+            sim.step(1, actions=actions[k_act % n_sets])
+            ev1[k].record()
+            k_act += 1
+        torch.cuda.synchronize()
+        launch_ms = [a.elapsed_time(b) for a, b in zip(ev0, ev1)]
     rates = [E * N * K / elapsed_local]
     if dist is not None:
         t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
@@ -326,7 +364,7 @@ def main():
     # headline, never mixed into it (the results of this workload are the same bits either way: tests/test_sleeping.py); it takes
     # over the state right behind the timed region, before the fused launches change the contact population
     with_sleep = None
-    if rank == 0 and not args.no_fused and not args.sleep and not args.objects:
+    if rank == 0 and args.full and not args.no_fused and not args.sleep and not args.objects:
         okw2 = dict(okw, allow_sleep=1)
         sim2 = KilobotSim(E, N, device=dev, toi_walls=0 if args.no_toi else 1, **okw2)
         for name in ('x', 'y', 'theta', 'ws_key', 'ws_acc', 'ws_cnt'):
@@ -348,7 +386,7 @@ def main():
         del sim2
     # fused variant: one launch = one env.step = 10 substeps, state LDS-resident in between
     fused = None
-    if rank == 0 and not args.no_fused:
+    if rank == 0 and args.full and not args.no_fused:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         nf = max(2, min(10, K // 10))
@@ -368,7 +406,7 @@ def main():
     jammed = None
     plain = not (args.objects or args.sleep or args.sense > 0.0 or args.threads or args.no_toi or args.arena
                  or args.vel_iters != 10 or args.pos_iters != 10)
-    if rank == 0 and not args.no_fused and plain and world == 1:
+    if rank == 0 and args.full and not args.no_fused and plain and world == 1:
         from gym_kilobots_amd import _native as nat
         # (as many envs as the headline: with the 1024 of rounds 2 - 3m a third of them ran alone on their CU behind the first 768,
         #  1.8e9 instead of 2.2e9 on the same kernel)
@@ -397,7 +435,7 @@ def main():
     # next to the headline, never mixed into `value`: cfg2 (256 envs x 64 kilobots) and cfg4 (cfg3 + 4 pushable discs, every
     # second kilobot ramming ahead) right behind the settle AND 500 substeps later (the rammers pile up against the walls)
     cfg2 = cfg4 = None
-    if rank == 0 and not args.no_fused and plain and world == 1:
+    if rank == 0 and args.full and not args.no_fused and plain and world == 1:
         def timed(sim_, acts_, n_):
             e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0_.record()
@@ -487,9 +525,10 @@ def main():
                      'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_source,
                      'kernel': 'kb_step_kernel', 'avg_launch_ms': kern_ms,
                      'avg_launch_source': 'one HIP event pair around the K back-to-back launches of the timed region / K',
-                     'audit_pass': 'the K launches right behind the timed region, one event pair each: avg %.4f ms' % float(np.mean(launch_ms)),
-                     'first_launch_ms': launch_ms[0], 'last_launch_ms': launch_ms[-1],
-                     'min_launch_ms': float(np.min(launch_ms)), 'max_launch_ms': float(np.max(launch_ms)),
+                     **({} if launch_ms is None else {
+                         'audit_pass': 'the K launches right behind the timed region, one event pair each: avg %.4f ms' % float(np.mean(launch_ms)),
+                         'first_launch_ms': launch_ms[0], 'last_launch_ms': launch_ms[-1],
+                         'min_launch_ms': float(np.min(launch_ms)), 'max_launch_ms': float(np.max(launch_ms))}),
                      'algorithmic_bytes_per_launch': algo_bytes * E * N},
         'per_rank_kilobot_steps_per_s': rates,
         'fused_env_step': fused,

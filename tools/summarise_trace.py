@@ -9,7 +9,7 @@ import sys
 def main():
     path = sys.argv[1]
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 200
-    label = sys.argv[3] if len(sys.argv) > 3 else 'python3 bench.py --no-cpu-baseline'
+    label = sys.argv[3] if len(sys.argv) > 3 else 'python3 bench.py --full --no-cpu-baseline'
     rows = [r for r in csv.DictReader(open(path)) if 'kb_step_kernel' in r['Kernel_Name']]
     rows.sort(key=lambda r: int(r['Start_Timestamp']))
     # the headline instantiation only (bench.py's extra leg with the sleep state launches another one between the timed and the fused launches)
