@@ -171,7 +171,7 @@ def build_variant(name, defines, only=None, verbose=False, standalone=False):
     for s in sources():
         base = os.path.basename(s)[:-4]
         if only is not None and base != 'kb_abi' and not any(base.endswith(o) for o in only):
-            if not standalone:      # (standalone: the listed units define everything the C ABI references, e.g. -DKB_ONLY_BENCH)
+            if not standalone:      # (standalone: only the listed units' kernels, e.g. -DKB_ONLY_BENCH; the others' keys resolve to none)
                 reuse.append(os.path.join(HERE, '_obj', 'rel', base + '.o'))
             continue
         jobs.append((s, os.path.join(objdir, base + '.o'), list(defines), verbose))

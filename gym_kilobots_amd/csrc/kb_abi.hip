@@ -1,6 +1,6 @@
 // kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h) and two small elementwise kernels.
 //
-// The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_d*.hip):
+// The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
 // of the reference substep loop (gym_kilobots/envs/kilobots_env.py:168-190) run out of LDS / registers, poses are
 // written back once.  Per substep:
@@ -23,7 +23,6 @@
 //
 // Arithmetic: fp32, compiled with -ffp-contract=off; every expression is written in the operation order of the
 // specification so results do not depend on launch fusion, workgroup size or sharding.
-#include <cstdlib>
 #include <new>
 
 #include "kb_common.h"
@@ -245,6 +244,7 @@ struct kb_sim {
     int threads;
     int capL_regular;      // LDS staging entries of the regular image (the fixed-size sorted-bin image has its own: ldsb::CAPL)
     int tier;              // register budget of the kernels without objects: 0 = 128 VGPRs, 2 = 80 VGPRs (6 waves per SIMD)
+    kb_step_fn fn;         // the instantiation that runs the handle (resolve_kernel), nullptr if the library has none
 };
 
 // dynamic LDS of one env: the bucket tables scale with the waves of the workgroup, the object tables exist only in
@@ -298,8 +298,22 @@ static int resident_envs(int lds, int threads, int wps) {
 // register budget of a kernel without objects: 80 VGPRs (tier 2) where that holds more envs than 128 VGPRs
 static int pick_tier(const kb::Params &p, int threads, int lds) {
     if (p.M > 0 || p.drive_mode == KB_DRIVE_MIXED) return 0;
-    if (const char *t = getenv("KB_TIER")) return atoi(t) == 2 ? 2 : 0;      // experiment knob (A/B of the register budgets)
     return resident_envs(lds, threads, KB_COMPACT_WAVES_PER_SIMD) > resident_envs(lds, threads, KB_MIN_WAVES_PER_SIMD) ? 2 : 0;
+}
+
+kb_step_fn kb::kb_kernels[NUM_VARIANTS];
+
+// the kernel instantiation of a handle (drive law, light model, objects, workgroup size): resolved whenever its shape is
+// fixed (kb_create, kb_set_block_threads)
+static kb_step_fn resolve_kernel(const kb_sim *sim) {
+    const Params &p = sim->p;
+    bool discs = p.M > 0;
+    for (int f = 0; f < p.F; ++f) discs = discs && ot_kind(p.otab[f]) == KB_SHAPE_CIRCLE;
+    const bool fixed = uses_fixed_1024(p, sim->threads);
+    if (fixed && p.M == 0 && p.capL != ldsb::CAPL) return nullptr;      // (cannot happen: kb_create / kb_set_block_threads keep them in step)
+    const int i = variant_index(select_variant({p.drive_mode, p.light_type, p.M > 0, discs, p.sense_s > 0, p.allow_sleep != 0,
+                                                sim->threads, sim->tier, fixed}));
+    return i < 0 ? nullptr : kb_kernels[i];
 }
 
 extern "C" {
@@ -612,6 +626,7 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
         delete s;
         return fail(KB_ELDS, "kb_create: configuration needs more than 160 KiB of LDS per env");
     }
+    s->fn = resolve_kernel(s);
     *out = s;
     return KB_OK;
 }
@@ -669,36 +684,9 @@ int kb_set_actions(kb_sim *sim, const float *d_actions, void *stream) {
     return KB_OK;
 }
 
-// the kernel instantiation of a handle (drive law, light model, objects, workgroup size)
-static kb_step_fn select_kernel(const kb_sim *sim, const kb::Params &p) {
-    const bool obj = p.M > 0;
-    int objsel = obj ? (sim->threads <= 64 ? 2 : 1) : (sim->tier == 2 ? 3 : 0);     // one-wave workgroups with objects: the 256-VGPR instantiation; no objects: 128 or 80 VGPRs
-    // scenes whose objects are all discs: instantiations without the kilobot - polygon contact code (5 / 6)
-    bool discs = obj;
-    for (int f = 0; f < p.F; ++f) discs = discs && ot_kind(p.otab[f]) == KB_SHAPE_CIRCLE;
-    if (discs) objsel += 4;
-    if (p.allow_sleep) objsel |= KB_PICK_SLEEP;      // instantiations with the sleep state
-    switch (p.drive_mode) {
-    case KB_DRIVE_VELOCITY: {
-        // the flagship size has its own instantiation with a compile-time LDS layout
-        const bool fixed = uses_fixed_1024(p, sim->threads);
-        if (fixed && !obj && p.capL != ldsb::CAPL) return nullptr;      // (cannot happen: kb_create / kb_set_block_threads keep them in step)
-        return kb_pick_velocity(fixed ? (p.sense_s > 0 ? KB_PICK_FIXED_1024_SENSE : KB_PICK_FIXED_1024) : p.light_type,
-                                fixed ? ((discs ? 5 : (int)obj) | (p.allow_sleep ? KB_PICK_SLEEP : 0)) : objsel);
-    }
-    case KB_DRIVE_ACCEL: return kb_pick_accel(p.light_type, objsel);
-    case KB_DRIVE_MOTORS: return kb_pick_motors(p.light_type, objsel);
-    case KB_DRIVE_SIMPLE_PHOTOTAXIS: return kb_pick_simple_phototaxis(p.light_type, objsel);
-    case KB_DRIVE_PHOTOTAXIS: return kb_pick_phototaxis(p.light_type, objsel);
-    case KB_DRIVE_MIXED: return sim->threads == 64 ? kb_pick_mixed(p.light_type, p.allow_sleep)
-                                                   : (sim->threads == 64 * MAX_WAVES ? kb_pick_mixed_large(p.light_type, p.allow_sleep) : nullptr);
-    default: return nullptr;
-    }
-}
-
 int kb_resident_envs_per_cu(kb_sim *sim) {
     if (!sim) return fail(KB_EINVAL, "kb_resident_envs_per_cu: NULL handle");
-    kb_step_fn fn = select_kernel(sim, sim->p);
+    const kb_step_fn fn = sim->fn;
     if (!fn) return fail(KB_EINVAL, "kb_resident_envs_per_cu: no kernel for this configuration");
     if (sim->p.lds_total > 64 * 1024) {
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -722,7 +710,7 @@ int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, in
     p.light_action = d_light_action;
     p.n_substeps = n_substeps;
     p.flags = flags;
-    kb_step_fn fn = select_kernel(sim, p);
+    const kb_step_fn fn = sim->fn;
     if (!fn) return fail(KB_EINVAL, "kb_step: no kernel for this drive mode / light type");
     if (p.lds_total > 64 * 1024 && sim->attr_fn != reinterpret_cast<const void *>(fn)) {
         // the attribute belongs to the kernel, not to this sim: raise it to the hardware limit, so that sims of
@@ -827,6 +815,7 @@ int kb_set_block_threads(kb_sim *sim, int threads) {
     sim->p.islmin_off = bins_islmin_offset(sim->p, threads, capL, nullptr);
     sim->p.botlaw_off = (lds_image_bytes(sim->p, threads, capL) + 15) & ~15;
     sim->tier = pick_tier(sim->p, threads, need);
+    sim->fn = resolve_kernel(sim);
     return KB_OK;
 }
 

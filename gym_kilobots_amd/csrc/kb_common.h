@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "kilobots_hip.h"
+#include "kb_variant.h"
 
 namespace kb {
 
@@ -64,7 +65,6 @@ constexpr int MAX_WAVES = KB_MAX_WAVES;   // waves per workgroup
 constexpr int BK_PER_WAVE = NUM_CLS * RK;
 constexpr int MAX_BUCKETS = MAX_WAVES * BK_PER_WAVE;
 constexpr int BPT = KB_BPT;                // bots per thread (max): N <= BPT * blockDim.x
-constexpr int KB_LIGHT_GENERAL = 99;   // kernel template value: any light model other than NONE / single CIRCULAR
 constexpr int GIANT_ISLAND = 256;     // contacts; larger islands are swept by the whole workgroup
 constexpr int BIG_ISLAND = 16;        // contacts; islands from this size on are placed on waves one by one when the hash placement overloads a wave
 constexpr int KREG = KB_KREG;               // contacts a lane can keep in registers (register-resident solver)
@@ -794,20 +794,8 @@ __device__ __noinline__ void kb_sense_bins_hashed(const float2 *pos, const unsig
 }
 
 typedef void (*kb_step_fn)(const Params);
-constexpr int KB_PICK_SLEEP = 16;      // kb_pick_*(..., objects | KB_PICK_SLEEP): the instantiation with the sleep state
-constexpr int KB_PICK_FIXED_1024 = -1024, KB_PICK_FIXED_1024_SENSE = -1025;   // ... the same with the neighbour-sensing hook   // kb_pick_velocity: the num_bots == 1024 specialisations (no light; without / with objects)
-// one translation unit per drive law (kb_inst_d*.hip) instantiates its kernels and hands out the right one
-kb_step_fn kb_pick_velocity(int light_type, int objects);   // objects: 0 none, 1 yes, 2 yes + one-wave workgroup
-kb_step_fn kb_pick_velocity_discs(int light_type, int objects);   // objects: 5 discs, 6 discs + one-wave workgroup
-kb_step_fn kb_pick_accel(int light_type, int objects);
-kb_step_fn kb_pick_accel_discs(int light_type, int objects);   // objects: 0 none, 1 yes, 2 yes + one-wave workgroup
-kb_step_fn kb_pick_motors(int light_type, int objects);
-kb_step_fn kb_pick_motors_discs(int light_type, int objects);   // objects: 0 none, 1 yes, 2 yes + one-wave workgroup
-kb_step_fn kb_pick_simple_phototaxis(int light_type, int objects);
-kb_step_fn kb_pick_simple_phototaxis_discs(int light_type, int objects);   // objects: 0 none, 1 yes, 2 yes + one-wave workgroup
-kb_step_fn kb_pick_phototaxis(int light_type, int objects);
-kb_step_fn kb_pick_phototaxis_discs(int light_type, int objects);   // objects: 0 none, 1 yes, 2 yes + one-wave workgroup
-kb_step_fn kb_pick_mixed(int light_type, int sleep);                // KB_DRIVE_MIXED: one-wave workgroups (kb_inst_d5.hip)
-kb_step_fn kb_pick_mixed_large(int light_type, int sleep);          // ... beyond 128 kilobots: the full workgroup at 256 VGPRs (kb_inst_d5w.hip)
+// kb_step_kernel<kb_variants.v[i]> at [i], entered by the kb_inst_*.hip units that instantiate it (kb_step_kernel.h:
+// register_unit), nullptr where no linked unit does (kb_abi.hip)
+extern kb_step_fn kb_kernels[NUM_VARIANTS];
 
 }  // namespace kb

@@ -1,18 +1,7 @@
-// kernel instantiations for drive law KB_DRIVE_SIMPLE_PHOTOTAXIS in scenes whose objects are all discs: the kilobot - polygon
-// contact code and its per-slot registers fold away (POLY = false)
+// kernel instantiations for drive law KB_DRIVE_SIMPLE_PHOTOTAXIS in scenes whose objects are all discs (POLY = false)
 #include "kb_step_kernel.h"
 
 namespace kb {
-template <int LIGHT_TYPE>
-static kb_step_fn pick(int objects) {    // 5: objects, 6: objects + one-wave workgroup; | KB_PICK_SLEEP: with the sleep state
-    if (objects & KB_PICK_SLEEP)
-        return (objects & ~KB_PICK_SLEEP) == 6 ? kb_step_kernel<KB_DRIVE_SIMPLE_PHOTOTAXIS, LIGHT_TYPE, true, 0, 1, false, true, true>
-                                               : kb_step_kernel<KB_DRIVE_SIMPLE_PHOTOTAXIS, LIGHT_TYPE, true, 0, 0, false, true, true>;
-    return objects == 6 ? kb_step_kernel<KB_DRIVE_SIMPLE_PHOTOTAXIS, LIGHT_TYPE, true, 0, 1, false>
-                        : kb_step_kernel<KB_DRIVE_SIMPLE_PHOTOTAXIS, LIGHT_TYPE, true, 0, 0, false>;
-}
-kb_step_fn kb_pick_simple_phototaxis_discs(int light_type, int objects) {
-    if (light_type == KB_LIGHT_CIRCULAR) return pick<KB_LIGHT_CIRCULAR>(objects);
-    return pick<KB_LIGHT_GENERAL>(objects);
-}
+static constexpr bool in_unit(const Variant &v) { return v.drive == KB_DRIVE_SIMPLE_PHOTOTAXIS && !v.poly; }
+static const bool registered = register_unit<in_unit>();
 }  // namespace kb

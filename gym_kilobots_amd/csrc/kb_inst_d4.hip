@@ -1,11 +1,7 @@
-// kernel instantiations for drive law KB_DRIVE_PHOTOTAXIS
+// kernel instantiations for drive law KB_DRIVE_PHOTOTAXIS: without objects and with polygon objects
 #include "kb_step_kernel.h"
 
 namespace kb {
-kb_step_fn kb_pick_phototaxis(int light_type, int objects) {
-    if ((objects & ~KB_PICK_SLEEP) >= 5) return kb_pick_phototaxis_discs(light_type, objects);      // all objects are discs: kb_inst_d4_discs.hip
-    if (light_type == KB_LIGHT_CIRCULAR) return kb_pick_obj<KB_DRIVE_PHOTOTAXIS, KB_LIGHT_CIRCULAR>(objects);
-    // GradientLight, MomentumLight, CompositeLight: one general kernel
-    return kb_pick_obj<KB_DRIVE_PHOTOTAXIS, KB_LIGHT_GENERAL>(objects);
-}
+static constexpr bool in_unit(const Variant &v) { return v.drive == KB_DRIVE_PHOTOTAXIS && v.poly; }
+static const bool registered = register_unit<in_unit>();
 }  // namespace kb

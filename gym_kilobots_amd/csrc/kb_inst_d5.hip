@@ -1,16 +1,8 @@
-// kernel instantiations for KB_DRIVE_MIXED: any mix of the five drive laws in one env, one-wave workgroups (256 VGPRs: no spills),
-// the code path with per-body masses; with and without the sleep state
+// kernel instantiations for KB_DRIVE_MIXED: any mix of the five drive laws in one env, one-wave workgroups (256 VGPRs:
+// no spills), the code path with per-body masses
 #include "kb_step_kernel.h"
 
 namespace kb {
-template <int LIGHT_TYPE>
-static kb_step_fn pick(int sleep) {
-    return sleep ? kb_step_kernel<KB_DRIVE_MIXED, LIGHT_TYPE, true, 0, 1, true, true, true>
-                 : kb_step_kernel<KB_DRIVE_MIXED, LIGHT_TYPE, true, 0, 1, true, true, false>;
-}
-kb_step_fn kb_pick_mixed(int light_type, int sleep) {
-    if (light_type == KB_LIGHT_CIRCULAR) return pick<KB_LIGHT_CIRCULAR>(sleep);
-    if (light_type == KB_LIGHT_NONE) return pick<KB_LIGHT_NONE>(sleep);
-    return pick<KB_LIGHT_GENERAL>(sleep);      // GradientLight, MomentumLight, CompositeLight
-}
+static constexpr bool in_unit(const Variant &v) { return v.drive == KB_DRIVE_MIXED && v.tier == 1; }
+static const bool registered = register_unit<in_unit>();
 }  // namespace kb

@@ -1,11 +1,14 @@
 // kb_step_kernel.h -- the world-step kernel template (see kb_common.h for the overview).
 #pragma once
+#include <utility>
+
 #include "kb_common.h"
 #include "kb_objects.h"
 
 namespace kb {
 
-// One instantiation per (drive law, light model): keeps only that law's code (and registers) in the kernel.
+// One instantiation per (drive law, light model): keeps only that law's code (and registers) in the kernel.  kb_variant.h lists
+// the 176 instantiations of the library (the kb_inst_*.hip units compile slices of the list) and picks the one of a handle.
 // FN > 0: specialisation for num_bots == FN and the full workgroup (64 * KB_MAX_WAVES threads): every LDS offset, array
 // size and trip count is a compile-time constant instead of a value kept in scalar registers (with objects the size
 // of the contact staging area, and so the offsets behind it, stay run-time values: they depend on the fixture count).
@@ -17,7 +20,7 @@ namespace kb {
 // POLY = false: instantiation for scenes whose objects are all discs (BASELINE config 4): the kilobot - polygon contact
 // code and its per-slot registers fold away (half the register spills, + 9 % at cfg4).
 // SENSE = false: instantiation without the IR-range neighbour sensing hook (the fixed-size kernels are at their register
-// budget: the hook costs them 2 more spilled VGPRs, 20 B/lane of scratch traffic per launch); kb_step picks it when
+// budget: the hook costs them 2 more spilled VGPRs, 20 B/lane of scratch traffic per launch); picked when
 // kb_config.sense_radius == 0.
 // Kernels without objects use the compact LDS image (namespace ldsc).  TIER picks the register budget:
 //   0: 128 VGPRs (launch bounds of 4 waves per SIMD);
@@ -27,7 +30,7 @@ namespace kb {
 // The fixed-size kernel without objects is always tier 2.
 // SLEEP = true: b2World(doSleep=True) of kilobots_env.py:45 -- bodies carry b2Body::m_sleepTime, islands without an awake
 // body are not solved (b2World::Solve), islands at rest for b2_timeToSleep whose position constraints converged fall asleep
-// (b2Island::Solve).  Generic kernels and the fixed-size one without objects; kb_step picks it when kb_config.allow_sleep != 0.
+// (b2Island::Solve).  Generic kernels and the fixed-size one without objects; picked when kb_config.allow_sleep != 0.
 template <int DRIVE_MODE, int LIGHT_TYPE, bool OBJ, int FN = 0, int TIER = 0, bool POLY = true, bool SENSE = true, bool SLEEP = false>
 __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1 || TIER == 3) ? 2 : ((TIER == 2 || (FN != 0 && !OBJ)) ? KB_COMPACT_WAVES_PER_SIMD : KB_MIN_WAVES_PER_SIMD)) kb_step_kernel(const Params p) {
     constexpr bool WIDE = TIER == 1 || TIER == 3;       // (256 VGPRs: no register spills)
@@ -2468,20 +2471,28 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 }
 
 
-// instantiation chooser of the kb_inst_d*.hip units: objects = 0 none (128 VGPRs), 1 with objects, 2 with objects and a
-// one-wave workgroup (the WIDE instantiation), 3 none at 80 VGPRs (six waves per SIMD)
-template <int DRIVE_MODE, int LIGHT_TYPE>
-static kb_step_fn kb_pick_obj(int objects) {
-    if (objects & KB_PICK_SLEEP) {     // kb_config.allow_sleep: generic instantiations with the sleep state (none at 128 / 80 VGPRs, objects, objects + one wave)
-        const int o_ = objects & ~KB_PICK_SLEEP;
-        if (o_ == 2) return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, true, 0, 1, true, true, true>;
-        if (o_ == 1) return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, true, 0, 0, true, true, true>;
-        if (o_ == 3) return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, false, 0, 2, true, true, true>;
-        return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, false, 0, 0, true, true, true>;
-    }
-    if (objects == 2) return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, true, 0, 1>;
-    if (objects == 3) return kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, false, 0, 2>;
-    return objects ? kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, true> : kb_step_kernel<DRIVE_MODE, LIGHT_TYPE, false>;
+// The kb_inst_*.hip units: each instantiates the keys of kb_variants for which its IN_UNIT holds and enters them in kb_kernels
+// when the library is loaded.  The measurement builds keep only the instantiations they measure.
+constexpr bool in_build(const Variant &v) {
+#if defined(KB_ONLY_BENCH)      // tools/phase_ablation.py: the benchmark instantiation (fixed size, no objects, no sensing)
+    return v.fn == 1024 && !v.obj && !v.sense;
+#elif defined(KB_ONLY_JAM)      // tools/ab_jam.py: the jammed-swarm probe (SimplePhototaxis, circular light, no objects, no sleep state)
+    return v.drive == KB_DRIVE_SIMPLE_PHOTOTAXIS && v.light == KB_LIGHT_CIRCULAR && !v.obj && !v.sleep;
+#else
+    return true;
+#endif
 }
+template <bool (*IN_UNIT)(const Variant &), int I>
+void register_one() {
+    constexpr Variant v = kb_variants.v[I];
+    if constexpr (in_build(v) && IN_UNIT(v)) kb_kernels[I] = kb_step_kernel<v.drive, v.light, v.obj, v.fn, v.tier, v.poly, v.sense, v.sleep>;
+}
+template <bool (*IN_UNIT)(const Variant &), int... I>
+bool register_unit(std::integer_sequence<int, I...>) {
+    (register_one<IN_UNIT, I>(), ...);
+    return true;
+}
+template <bool (*IN_UNIT)(const Variant &)>
+bool register_unit() { return register_unit<IN_UNIT>(std::make_integer_sequence<int, NUM_VARIANTS>()); }
 
 }  // namespace kb
