@@ -242,78 +242,29 @@ struct kb_sim {
     bool bound;
     const void *attr_fn;   // kernel whose dynamic-LDS limit has been raised
     int threads;
-    int capL_regular;      // LDS staging entries of the regular image (the fixed-size sorted-bin image has its own: ldsb::CAPL)
-    int tier;              // register budget of the kernels without objects: 0 = 128 VGPRs, 2 = 80 VGPRs (6 waves per SIMD)
-    kb_step_fn fn;         // the instantiation that runs the handle (resolve_kernel), nullptr if the library has none
+    kb_step_fn fn;         // the instantiation that runs the handle (plan_launch), nullptr if the library has none
 };
-
-// dynamic LDS of one env: the bucket tables scale with the waves of the workgroup, the object tables exist only in
-// scenes with objects (namespace lds, kb_common.h)
-static bool uses_fixed_1024(const kb::Params &p, int threads) {   // the instantiation kb_step picks: the ONE place that decides
-    const long cap1024 = (4L * 1024 + 64 + 7) & ~7L;
-    if (p.allow_sleep && p.M > 0) return false;            // (the fixed-size instantiations with objects do not carry the sleep state)
-    return p.drive_mode == KB_DRIVE_VELOCITY && p.N == 1024 && p.light_type == KB_LIGHT_NONE && threads == 64 * kb::MAX_WAVES &&
-           kb::BPT * 64 * kb::MAX_WAVES == 1024 && p.NP == 1024 && p.NB == 1024 + KB_MAX_OBJECTS + 4 &&
-           (p.M > 0 || p.cap == (int)cap1024);      // (without objects the contact capacity is a compile-time constant of the kernel)
-}
-static int lds_image_bytes(const kb::Params &p, int threads, int capL);
-// sorted-bin image: where the per-island minimum of the sleep times (NB words, SLEEP kernels, idle arrays between the position
-// sweeps and the continuous step) lies -- over the bin boundaries, else over the staged pairs, else behind the image; *total
-// receives the bytes of the image including that area
-static int bins_islmin_offset(const kb::Params &p, int threads, int capL, int *total) {
-    const bool hc = p.hmask != 0 && !uses_fixed_1024(p, threads);
-    const int nw = threads / 64;
-    int tot = kb::ldsb::total(p.NB, p.NP, hc, capL, p.nhead, nw), off;
-    if (kb::ldsb::binE_size(p.nhead, nw) >= 4 * p.NB) off = kb::ldsb::binE(p.NB, p.NP, hc, capL);
-    else if (capL >= p.NB) off = kb::ldsb::con32(p.NB, p.NP, hc, capL, 0);
-    else { off = tot; if (p.allow_sleep) tot += (4 * p.NB + 15) & ~15; }
-    if (total) *total = tot;
-    return off;
-}
-static int lds_bytes_for(const kb::Params &p, int threads, int capL) {
-    const int img = lds_image_bytes(p, threads, capL);
-    // KB_DRIVE_MIXED: the drive law of every kilobot (one byte each) lies behind the image (Params.botlaw_off)
-    return p.drive_mode == KB_DRIVE_MIXED ? ((img + 15) & ~15) + ((p.NP + 15) & ~15) : img;
-}
-static int lds_image_bytes(const kb::Params &p, int threads, int capL) {
-    if (p.M == 0 && p.drive_mode != KB_DRIVE_MIXED) {      // kernels without objects: the sorted-bin image (namespace ldsb)
-        const bool fixed = uses_fixed_1024(p, threads);
-        int total = 0;
-        bins_islmin_offset(p, threads, fixed ? kb::ldsb::CAPL : capL, &total);
-        return total;
-    }
-    const bool objarea = p.M > 0 || p.drive_mode == KB_DRIVE_MIXED || uses_fixed_1024(p, threads);
-    return kb::lds::total(kb::lds::fixed(objarea, threads / 64), p.NB, capL, p.NP, p.nhead, p.nmc);
-}
-
-// workgroups of `threads` threads and `lds` bytes that one CU holds at a register budget of `wps` waves per SIMD
-// (LDS is handed out in granules: an image of 54 544 B got two workgroups per CU, one of 53 168 B three)
-static int resident_envs(int lds, int threads, int wps) {
-    const int LDS_CU = 160 * 1024, GRANULE = 1280;
-    const int byLds = LDS_CU / (((lds + GRANULE - 1) / GRANULE) * GRANULE);
-    const int byWaves = (4 * wps) / (threads / 64);
-    const int n = byLds < byWaves ? byLds : byWaves;
-    return n < 1 ? (byLds >= 1 ? 1 : 0) : n;
-}
-// register budget of a kernel without objects: 80 VGPRs (tier 2) where that holds more envs than 128 VGPRs
-static int pick_tier(const kb::Params &p, int threads, int lds) {
-    if (p.M > 0 || p.drive_mode == KB_DRIVE_MIXED) return 0;
-    return resident_envs(lds, threads, KB_COMPACT_WAVES_PER_SIMD) > resident_envs(lds, threads, KB_MIN_WAVES_PER_SIMD) ? 2 : 0;
-}
 
 kb_step_fn kb::kb_kernels[NUM_VARIANTS];
 
-// the kernel instantiation of a handle (drive law, light model, objects, workgroup size): resolved whenever its shape is
-// fixed (kb_create, kb_set_block_threads)
-static kb_step_fn resolve_kernel(const kb_sim *sim) {
-    const Params &p = sim->p;
-    bool discs = p.M > 0;
-    for (int f = 0; f < p.F; ++f) discs = discs && ot_kind(p.otab[f]) == KB_SHAPE_CIRCLE;
-    const bool fixed = uses_fixed_1024(p, sim->threads);
-    if (fixed && p.M == 0 && p.capL != ldsb::CAPL) return nullptr;      // (cannot happen: kb_create / kb_set_block_threads keep them in step)
-    const int i = variant_index(select_variant({p.drive_mode, p.light_type, p.M > 0, discs, p.sense_s > 0, p.allow_sleep != 0,
-                                                sim->threads, sim->tier, fixed}));
-    return i < 0 ? nullptr : kb_kernels[i];
+// what of a handle decides its launch shape (kb_launch.h); threads: the workgroup size asked for, 0 = choose
+static PlanInput plan_input(const kb_sim *s, int threads) {
+    const kb_config &c = s->cfg;
+    const int nfix = c.num_fixtures > 0 ? c.num_fixtures : c.num_objects;
+    bool discs = c.num_objects > 0;
+    for (int f = 0; f < nfix; ++f) discs = discs && c.obj_shape[f] == KB_SHAPE_CIRCLE;
+    return {c.num_bots, c.num_objects, nfix, discs, c.drive_mode, c.light_type, c.sense_radius > 0.0f, c.allow_sleep != 0,
+            s->p.ncell, c.contact_capacity, threads};
+}
+
+// the launch shape into the handle (kb_create, kb_set_block_threads)
+static void use_plan(kb_sim *s, const Plan &pl) {
+    Params &p = s->p;
+    p.cap = pl.cap; p.capL = pl.capL; p.nhead = pl.nhead; p.hmask = pl.hmask;
+    p.lds_total = pl.lds_total; p.islmin_off = pl.islmin_off; p.botlaw_off = pl.botlaw_off;
+    s->threads = pl.threads;
+    const int i = variant_index(pl.variant);
+    s->fn = i < 0 ? nullptr : kb_kernels[i];
 }
 
 extern "C" {
@@ -408,13 +359,6 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
         cell *= 2.0f;
     }
     p.ncell = p.gw * p.gh;
-    {   // sparse swarms: a hash table of the cells instead of one list head per cell (kb_step_kernel.h, `hashed`); only where
-        // it at least halves the table, and never for the fixed-size kernel
-        int H = 64;
-        while (H < 2 * cfg->num_bots) H <<= 1;
-        if (2 * H <= p.ncell && cfg->num_bots != 1024) { p.nhead = H; p.hmask = H - 1; }
-        else { p.nhead = p.ncell; p.hmask = 0; }
-    }
     p.h = cfg->dt;
     p.r_bot = cfg->bot_radius * WORLD_SCALE;
     const float m = cfg->bot_density * B2_PI * p.r_bot * p.r_bot;  // b2CircleShape::ComputeMass
@@ -432,7 +376,6 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
             p.im_mode[k] = mk > 0.0f ? 1.0f / mk : 0.0f;
         }
     }
-    p.botlaw_off = 0;
     // b2Island::Solve damping factor per step: Pade (Box2D >= 2.3.1) or the older clamped linear form
     auto damp = [&](float c) -> float {
         if (cfg->damping_model == KB_DAMPING_LINEAR) return kb_clampf_host(1.0f - p.h * c, 0.0f, 1.0f);
@@ -458,35 +401,6 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
     for (int i = 0; i < 2; ++i) {
         p.light_lo[i] = cfg->light_lo[i]; p.light_hi[i] = cfg->light_hi[i];
         p.act_lo[i] = cfg->light_act_lo[i]; p.act_hi[i] = cfg->light_act_hi[i];
-    }
-    long cap = (long)p.N * (p.N - 1) / 2 + 4L * p.N;
-    if (cap > 2304) cap = 2304;
-    if (cap < 4L * p.N + 64) cap = 4L * p.N + 64;
-    cap += 40L * cfg->num_objects;
-    if (cfg->contact_capacity > 0) cap = cfg->contact_capacity;
-    cap = (cap + 7) & ~7L;
-    p.cap = (int)cap;
-    // with objects the LDS staging area gives up a few entries to the manifold-constraint records, so that two envs
-    // of 1024 kilobots still share a CU
-    int capLmax = cfg->num_objects > 0 ? CAP_LDS - 8 * mc_candidates(nfix) : CAP_LDS;
-    // small swarms: stage what a packed cluster can produce (a hexagonal packing has < 3 contacts per kilobot, + walls) rather than all pairs, so
-    // that more one-wave envs fit a CU; a spawn that overlaps more than that takes the global staging slice
-    const int typical = 3 * p.N + 64 > 256 ? 3 * p.N + 64 : 256;
-    if (capLmax > typical) capLmax = typical;
-    p.capL = p.cap < capLmax ? p.cap : capLmax;
-    if (cfg->num_objects > 0 || cfg->drive_mode == KB_DRIVE_MIXED) {
-        // kernels with objects: the per-island minimum of the sleep times (N + M words) lies over the pair and info arrays of
-        // the LDS staging area, whatever contact_capacity says
-        int lo = ((((p.N + 3) & ~3) + KB_MAX_OBJECTS + 4 + 1) / 2 + 7) & ~7;
-        if (lo < 64) lo = 64;
-        if (p.capL < lo) p.capL = lo;
-    }
-    if (cfg->num_objects == 0 && cfg->drive_mode != KB_DRIVE_MIXED) {
-        // sorted-bin image: scratch arrays of the sort lie over the staging area (2 B per kilobot over 4 B per entry); a
-        // smaller contact_capacity still bounds what is staged (kernel: min(capL, cap))
-        int lo = ((((p.N + 3) & ~3) / 2) + 7) & ~7;
-        if (lo < 64) lo = 64;
-        if (p.capL < lo) p.capL = lo;
     }
     p.NP = (p.N + 3) & ~3;
     p.NB = p.NP + KB_MAX_OBJECTS + 4;
@@ -572,61 +486,9 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
     }
     p.solver_mode = cfg->solver_mode;
     p.toi_walls = cfg->toi_walls;
-    if (p.N > BPT * 64 * MAX_WAVES) { delete s; return fail(KB_EINVAL, "kb_create: num_bots exceeds bots-per-thread x workgroup size of this build"); }
-    const int LDS_CU = 160 * 1024;
-    {   // Workgroup size (measured on MI355X, 64 ... 1024 kilobots): one kilobot per thread and a power-of-two wave count
-        // (3 / 5 / 6 / 7-wave workgroups spread unevenly over the four SIMDs and lose a resident env), unless that costs
-        // a resident env (LDS fit vs 16 waves per CU) while many lanes would idle.  kb_set_block_threads overrides.
-        int T = 64;
-        while (T < p.N && T < 64 * MAX_WAVES) T <<= 1;
-        const int ldsT = lds_bytes_for(p, T, p.capL);
-        const int fit = LDS_CU / ldsT;
-        int resident = resident_envs(ldsT, T, KB_MIN_WAVES_PER_SIMD);
-        if (p.M == 0 && resident_envs(ldsT, T, KB_COMPACT_WAVES_PER_SIMD) > resident) resident = resident_envs(ldsT, T, KB_COMPACT_WAVES_PER_SIMD);
-        if (T > 64 && resident < fit && p.N * 100 < T * 85) T >>= 1;
-        // 257 ... 512 kilobots without objects: two per thread in a 4-wave workgroup (measured at 512: 1.06e10 against 9.3e9 with
-        // eight waves -- an 8-wave env takes a third of the CU's wave slots whatever its LDS image is)
-        if (p.M == 0 && p.drive_mode != KB_DRIVE_MIXED && p.N > 256 && p.N <= 512) T = 256;
-        // with objects, up to 128 kilobots run as one wave: that selects the spill-free 256-VGPR instantiation
-        // (kb_step), measured + 6 ... 9 % at 100 kilobots and - 3 % at 128 against two-wave workgroups
-        if (p.M > 0 && p.N <= BPT * 64) T = 64;
-        if (p.drive_mode == KB_DRIVE_MIXED) T = p.N <= BPT * 64 ? 64 : 64 * MAX_WAVES;       // the two spill-free instantiations (256 VGPRs)
-        s->threads = T;
-    }
-    if (p.M == 0 && p.drive_mode != KB_DRIVE_MIXED) {
-        // sorted-bin image (16 B per staged contact): give up staging entries where that lets the CU hold one more env -- a
-        // 1024-kilobot swarm down to the 688 of the fixed-size kernel (a settled swarm has ~ 0.55 contacts per kilobot; a
-        // jammed one is staged in the global slice whatever the LDS holds, and what it needs is resident envs)
-        // (smaller swarms: never below one contact per kilobot + 64 -- a settled lattice has ~ 0.5, a hexagonal cluster up to 3;
-        //  the largest staging area that reaches the best residency is taken)
-        const int lo = p.N > 512 ? ldsb::CAPL : (p.N + 64 > 128 ? (p.N + 64 + 7) & ~7 : 128);
-        auto res = [&](int c) {
-            const int l = lds_bytes_for(p, s->threads, c);
-            const int a = resident_envs(l, s->threads, KB_MIN_WAVES_PER_SIMD), b = resident_envs(l, s->threads, KB_COMPACT_WAVES_PER_SIMD);
-            return a > b ? a : b;
-        };
-        int best = res(p.capL), bestc = p.capL;
-        for (int c = p.capL - 8; c >= lo; c -= 8)
-            if (res(c) > best) { best = res(c); bestc = c; }
-        p.capL = bestc;
-    } else {   // trade a few staging entries for one more env per CU when the LDS footprint is just above a divisor of 160 KiB
-        const int fit = LDS_CU / lds_bytes_for(p, s->threads, p.capL);
-        const int lo = 5 * p.N / 2 + 64 > 256 ? 5 * p.N / 2 + 64 : 256;
-        int c = p.capL;
-        while (c - 8 >= lo && lds_bytes_for(p, s->threads, c) > LDS_CU / (fit + 1)) c -= 8;
-        if (fit >= 1 && lds_bytes_for(p, s->threads, c) <= LDS_CU / (fit + 1)) p.capL = c;
-    }
-    s->capL_regular = p.capL;
-    if (p.M == 0 && uses_fixed_1024(p, s->threads)) p.capL = ldsb::CAPL;
-    p.lds_total = lds_bytes_for(p, s->threads, p.capL);
-    p.islmin_off = bins_islmin_offset(p, s->threads, p.capL, nullptr);
-    p.botlaw_off = (lds_image_bytes(p, s->threads, p.capL) + 15) & ~15;
-    s->tier = pick_tier(p, s->threads, p.lds_total);
-    if (p.lds_total > LDS_CU) {
-        delete s;
-        return fail(KB_ELDS, "kb_create: configuration needs more than 160 KiB of LDS per env");
-    }
-    s->fn = resolve_kernel(s);
+    const Plan pl = plan_launch(plan_input(s, 0));
+    if (pl.status != KB_OK) { delete s; return fail(pl.status, "%s", pl.msg); }
+    use_plan(s, pl);
     *out = s;
     return KB_OK;
 }
@@ -689,7 +551,7 @@ int kb_resident_envs_per_cu(kb_sim *sim) {
     const kb_step_fn fn = sim->fn;
     if (!fn) return fail(KB_EINVAL, "kb_resident_envs_per_cu: no kernel for this configuration");
     if (sim->p.lds_total > 64 * 1024) {
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
         if (e2 != hipSuccess) return fail(KB_EHIP, "kb_resident_envs_per_cu: hipFuncSetAttribute: %s", hipGetErrorString(e2));
     }
     int n = 0;
@@ -716,7 +578,7 @@ int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, in
         // the attribute belongs to the kernel, not to this sim: raise it to the hardware limit, so that sims of
         // different sizes sharing one instantiation never lower it under each other
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
         if (e2 != hipSuccess) return fail(KB_EHIP, "kb_step: hipFuncSetAttribute: %s", hipGetErrorString(e2));
         sim->attr_fn = reinterpret_cast<const void *>(fn);
     }
@@ -802,20 +664,10 @@ int kb_contact_capacity(const kb_sim *sim) { return sim ? sim->p.cap : KB_EINVAL
 int kb_lds_staging_entries(const kb_sim *sim) { return sim ? sim->p.capL : KB_EINVAL; }
 int kb_block_threads(const kb_sim *sim) { return sim ? sim->threads : KB_EINVAL; }
 int kb_set_block_threads(kb_sim *sim, int threads) {
-    if (!sim || threads < 64 || threads > 64 * MAX_WAVES || (threads & 63)) return fail(KB_EINVAL, "kb_set_block_threads: multiple of 64 up to the build maximum");
-    if (sim->p.N > BPT * threads) return fail(KB_EINVAL, "kb_set_block_threads: need num_bots <= bots-per-thread x threads");
-    const int capL = (sim->p.M == 0 && uses_fixed_1024(sim->p, threads)) ? ldsb::CAPL : sim->capL_regular;
-    const int need = lds_bytes_for(sim->p, threads, capL);
-    if (need > 160 * 1024) return fail(KB_ELDS, "kb_set_block_threads: more than 160 KiB of LDS per env at this workgroup size");
-    if (sim->p.drive_mode == KB_DRIVE_MIXED && threads != 64 && threads != 64 * MAX_WAVES)
-        return fail(KB_EINVAL, "kb_set_block_threads: KB_DRIVE_MIXED runs as one-wave or full workgroups");
-    sim->threads = threads;
-    sim->p.capL = capL;
-    sim->p.lds_total = need;
-    sim->p.islmin_off = bins_islmin_offset(sim->p, threads, capL, nullptr);
-    sim->p.botlaw_off = (lds_image_bytes(sim->p, threads, capL) + 15) & ~15;
-    sim->tier = pick_tier(sim->p, threads, need);
-    sim->fn = resolve_kernel(sim);
+    if (!sim || threads == 0) return fail(KB_EINVAL, "kb_set_block_threads: multiple of 64 up to the build maximum");   // (0: plan_launch would choose)
+    const Plan pl = plan_launch(plan_input(sim, threads));
+    if (pl.status != KB_OK) return fail(pl.status, "%s", pl.msg);
+    use_plan(sim, pl);
     return KB_OK;
 }
 

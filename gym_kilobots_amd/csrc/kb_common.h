@@ -1,4 +1,4 @@
-// kb_common.h -- constants, kernel parameters, LDS layout and device helpers shared by the translation units.
+// kb_common.h -- constants, kernel parameters and device helpers shared by the translation units (the LDS layout: kb_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,7 +8,7 @@
 #include <type_traits>
 
 #include "kilobots_hip.h"
-#include "kb_variant.h"
+#include "kb_launch.h"
 
 namespace kb {
 
@@ -36,35 +36,13 @@ constexpr int MAX_CELLS = 8192;
 constexpr unsigned KEY_WALL = 0x10000u, KEY_OBJ = 0x20000u;
 constexpr int WALL_CODE = 0xFFF0;     // body id of wall w is WALL_CODE + w
 constexpr int OBJ_CODE = 0xFFE0;      // 16-bit warm-start key of object m (its body id is N + m)
-constexpr int MAXOBJ = KB_MAX_OBJECTS, OBJ_LIST = 64;   // OBJ_LIST: kilobots that may touch one fixture at a time
-constexpr int OT_WORDS_C = 7 + 4 * KB_MAX_POLY_VERTS;   // floats per fixture in the fixture table (kb_objects.h)
-constexpr int BT_WORDS_C = 6;                          // floats per object in the body table
-constexpr int MC_FIELDS_C = 37;                        // words per manifold-constraint record (kb_objects.h)
+constexpr int MAXOBJ = KB_MAX_OBJECTS;
 constexpr unsigned short EMPTY16 = 0xFFFFu;
 
-// contact classes in canonical order; +1 on E/N/NE/NW for odd base-cell parity
-constexpr int CLS_SAME = 0, CLS_E = 1, CLS_N = 3, CLS_NE = 5, CLS_NW = 7, CLS_WALL = 9,
-              CLS_BOT_OBJ = 10, NUM_CLS = 11;
-constexpr int RK = 4;                 // rank buckets per class; the last one holds every rank >= RK-1
-#ifndef KB_MAX_WAVES
-#define KB_MAX_WAVES 8
-#endif
-#ifndef KB_BPT
-#define KB_BPT 2
-#endif
 #ifndef KB_KREG
 #define KB_KREG 2
 #endif
-#ifndef KB_MIN_WAVES_PER_SIMD
-#define KB_MIN_WAVES_PER_SIMD 4
-#endif
-#ifndef KB_COMPACT_WAVES_PER_SIMD
-#define KB_COMPACT_WAVES_PER_SIMD 6     // the compact fixed-size kernel: 80 VGPRs, three 8-wave workgroups per CU
-#endif
-constexpr int MAX_WAVES = KB_MAX_WAVES;   // waves per workgroup
-constexpr int BK_PER_WAVE = NUM_CLS * RK;
 constexpr int MAX_BUCKETS = MAX_WAVES * BK_PER_WAVE;
-constexpr int BPT = KB_BPT;                // bots per thread (max): N <= BPT * blockDim.x
 constexpr int GIANT_ISLAND = 256;     // contacts; larger islands are swept by the whole workgroup
 constexpr int BIG_ISLAND = 16;        // contacts; islands from this size on are placed on waves one by one when the hash placement overloads a wave
 constexpr int KREG = KB_KREG;               // contacts a lane can keep in registers (register-resident solver)
@@ -74,147 +52,9 @@ constexpr int KREG = KB_KREG;               // contacts a lane can keep in regis
 #ifndef KB_KREG_BINS
 #define KB_KREG_BINS (2 * KB_NSOLVE_DIV)                  // ... in the kernels without objects, where only half the waves of a workgroup sweep (kb_regsolve_bins.inc)
 #endif
-constexpr int CAP_LDS = 1024;         // contacts staged in LDS; denser envs stage in the global scratch slice
 
 enum { M_NCON = 0, M_TOTAL = 1, M_ANY = 2, M_STATUS = 3, M_MAXISL = 4, M_PROF = 5, M_XTRA = 6, M_XFILL = 7, M_WCNT = 8, M_WAKE = 32 /* .. 63: one bit per kilobot (sleeping; the -DKB_PROFILE build keeps its stamps there and does not implement the wake rule) */, M_WFILL = 8 + MAX_WAVES, M_COUNT = 8 + 2 * MAX_WAVES };
 static_assert(M_COUNT <= 64, "misc area");
-
-// ---- LDS layout ----------------------------------------------------------------------------------
-// The small arrays come first: a few of fixed size, the bucket tables of the contact sort (they scale with the waves of
-// the workgroup) and -- only in kernels with objects -- the object tables; `fixed(obj, nw)` is where the arrays that
-// scale with the scene start.  Those are grouped by stride, so that every offset is (base + k * stride) of four scene
-// sizes.  The kernel recomputes offsets where they are used instead of keeping ~35 of them alive in scalar registers
-// for the whole launch; in the fixed-size instantiations all of this folds to constants.
-namespace lds {
-constexpr int A16(int x) { return (x + 15) & ~15; }
-constexpr int MISC = 0;
-constexpr int WSUM = MISC + A16(4 * 64);
-constexpr int BKSTART = WSUM + A16(4 * 16);
-// buckets of a workgroup of nw waves (the tables double as scratch of the island placement: >= 64 entries)
-__host__ __device__ constexpr int nbk(int nw) { return nw * BK_PER_WAVE < 64 ? 64 : nw * BK_PER_WAVE; }
-__host__ __device__ constexpr int bkfill(int nw) { return BKSTART + A16(4 * (nbk(nw) + 1)); }
-__host__ __device__ constexpr int bkmaxrank(int nw) { return bkfill(nw) + A16(4 * nbk(nw)); }
-__host__ __device__ constexpr int bklist(int nw) { return bkmaxrank(nw) + A16(4 * MAX_WAVES * NUM_CLS); }
-__host__ __device__ constexpr int nlist(int nw) { return bklist(nw) + A16(2 * nbk(nw)); }
-__host__ __device__ constexpr int objtab(int nw) { return nlist(nw) + 16; }   // object table: mass, shape
-// object areas, relative to objtab(nw)
-constexpr int OBJBODY = A16(4 * OT_WORDS_C * KB_MAX_OBJECTS);            // body table
-constexpr int OBJCNT = OBJBODY + A16(4 * BT_WORDS_C * KB_MAX_OBJECTS);
-constexpr int OBJLIST = OBJCNT + A16(4 * KB_MAX_OBJECTS);
-constexpr int OBJW = OBJLIST + A16(2 * KB_MAX_OBJECTS * OBJ_LIST);       // angular velocity, angle, angle at the start of the substep
-constexpr int OBJA = OBJW + A16(4 * KB_MAX_OBJECTS);
-constexpr int OBJA0 = OBJA + A16(4 * KB_MAX_OBJECTS);
-constexpr int MCMASK = OBJA0 + A16(4 * KB_MAX_OBJECTS);                  // per wave: which manifold constraints it owns (u64)
-constexpr int OBJSLP = MCMASK + A16(8 * (MAX_WAVES + 1));                // sleeping: b2Body::m_sleepTime of the objects (< 0: asleep)
-constexpr int OBJ_AREA = OBJSLP + A16(4 * KB_MAX_OBJECTS);
-__host__ __device__ constexpr int fixed(bool obj, int nw) { return objtab(nw) + (obj ? OBJ_AREA : 0); }
-// per-body 32-bit arrays (stride 4 * NB): px py vx vy x0 y0 dirCnt parent
-constexpr int BODY32_COUNT = 8;
-// per-contact 32-bit arrays (stride 4 * capL): sPair sInfo sAcc oldAcc;  16-bit (stride 2 * capL): cbk order oldKey
-constexpr int CON32_COUNT = 4, CON16_COUNT = 3;
-// per-bot 16-bit arrays (stride 2 * NP): wsOff newOff next cellOf;  8-bit (stride NP): wsCnt wsCntNew
-constexpr int BOT16_COUNT = 4, BOT8_COUNT = 2;
-// (fx = fixed(obj, nw))
-__host__ __device__ inline int body32(int fx, int NB, int k) { return fx + 4 * NB * k; }
-__host__ __device__ inline int con32(int fx, int NB, int capL, int k) { return body32(fx, NB, BODY32_COUNT) + 4 * capL * k; }
-__host__ __device__ inline int con16(int fx, int NB, int capL, int k) { return con32(fx, NB, capL, CON32_COUNT) + 2 * capL * k; }
-__host__ __device__ inline int bot16(int fx, int NB, int capL, int NP, int k) { return con16(fx, NB, capL, CON16_COUNT) + 2 * NP * k; }
-__host__ __device__ inline int bot8(int fx, int NB, int capL, int NP, int k) { return bot16(fx, NB, capL, NP, BOT16_COUNT) + NP * k; }
-__host__ __device__ inline int active(int fx, int NB, int capL, int NP) { return bot8(fx, NB, capL, NP, BOT8_COUNT); }
-__host__ __device__ inline int islwave(int fx, int NB, int capL, int NP) { return active(fx, NB, capL, NP) + 2 * NB; }   // u8 per body: wave that sweeps its island
-__host__ __device__ inline int head(int fx, int NB, int capL, int NP) { return (islwave(fx, NB, capL, NP) + NB + 15) & ~15; }
-__host__ __device__ inline int mcarea(int fx, int NB, int capL, int NP, int ncell) { return (head(fx, NB, capL, NP) + 2 * ncell + 4 + 15) & ~15; }
-// manifold-constraint records (objects only): MC_FIELDS words x nmc candidates, field-major
-__host__ __device__ inline int total(int fx, int NB, int capL, int NP, int ncell, int nmc) { return (mcarea(fx, NB, capL, NP, ncell) + 4 * MC_FIELDS_C * nmc + 15) & ~15; }
-}  // namespace lds
-
-// ---- compact LDS image: three envs of 1024 kilobots per CU --------------------------------------------------------------
-// What decides the throughput of the latency-bound step is how many envs a CU holds (profiles/: waves wait 60 % of their
-// cycles, no pipe is more than a third busy; 3 resident envs instead of 2 gave + 37 % at 480 kilobots).  Every kernel
-// without objects uses this image; the fixed-size one runs at 80 VGPRs (6 waves per SIMD = three 8-wave workgroups) with
-// 53 168 B instead of 80 416 B, the others pick the register budget that holds more envs (kb_create):
-//   - no image of the previous substep's warm-start list (6 B per entry): the label pass reads the packed list in HBM / L2;
-//   - the poses at the start of the substep (continuous step) are saved at integration time -- they do not change earlier --
-//     into arrays that are dead by then: x over [nextb | cellOf], y over dirCnt;
-//   - fixed-size kernel: the per-contact scratch of the contact sort / slot dealing (lCbk) lies over nextb (dead once the
-//     label pass is done and needed only before the integration; needs capL <= NP);
-//   - the bucket tables of the contact sort / island placement live in the cell-head area, which is dead once the label
-//     pass is done; the heads are cleared as a whole at the end of the substep;
-//   - 688 staged contacts (the settled benchmark scene has 550 +- 20 per env, at most 630 in 4096 envs; envs beyond take
-//     the global staging slice as before); no object tables.
-namespace ldsc {
-constexpr int CAPL = 688;                                                   // staged contacts of the fixed-size kernel
-__host__ __device__ constexpr int tables(int nw) { return lds::nlist(nw) + 16 - lds::BKSTART; }   // bucket tables, relative to the head area
-__host__ __device__ constexpr int pos(int) { return 320; }                 // (MISC 256 + WSUM 64 in front)
-__host__ __device__ constexpr int vel(int NB) { return pos(NB) + 8 * NB; }
-__host__ __device__ constexpr int dircnt(int NB) { return vel(NB) + 8 * NB; }
-__host__ __device__ constexpr int parent(int NB) { return dircnt(NB) + 4 * NB; }
-__host__ __device__ constexpr int con32(int NB, int capL, int k) { return parent(NB) + 4 * NB + 4 * capL * k; }      // lPair lInfo lAcc
-// 16-bit per-contact arrays: lOrder, and lCbk unless it lies over nextb (`fold`: only where capL <= NP, the fixed-size kernel)
-__host__ __device__ constexpr int con16(int NB, int capL, int k) { return con32(NB, capL, 3) + ((2 * capL + 3) & ~3) * k; }
-__host__ __device__ constexpr int bot16(int NB, int capL, int NP, bool fold, int k) { return con16(NB, capL, fold ? 1 : 2) + 2 * NP * k; }   // wsOff newOff nextb cellOf
-__host__ __device__ constexpr int bot8(int NB, int capL, int NP, bool fold, int k) { return bot16(NB, capL, NP, fold, 4) + NP * k; }        // wsCnt wsCntNew
-__host__ __device__ constexpr int active(int NB, int capL, int NP, bool fold) { return bot8(NB, capL, NP, fold, 2); }
-__host__ __device__ constexpr int islwave(int NB, int capL, int NP, bool fold) { return active(NB, capL, NP, fold) + 2 * NB; }
-__host__ __device__ constexpr int head(int NB, int capL, int NP, bool fold) { return (islwave(NB, capL, NP, fold) + NB + 15) & ~15; }
-__host__ __device__ inline int total(int NB, int capL, int NP, bool fold, int ncell, int nw) {
-    const int h = (2 * ncell + 4 + 15) & ~15;
-    return head(NB, capL, NP, fold) + (h > tables(nw) ? h : tables(nw));
-}
-}  // namespace ldsc
-
-// ---- sorted-bin LDS image (round 3): every kernel without objects ------------------------------------------------------
-// The broadphase is a counting sort of the kilobots by grid cell ("bins"; a hash of the cells for sparse swarms), and the
-// bodies LIVE in that order for the length of a substep: pos / vel / parent / ... are indexed by the kilobot's SLOT in the
-// sorted order, so the candidates of a stencil row are one contiguous run of slots (no list heads, no next pointers, no
-// indirection through an id).  A contact is stored at its position in the packed warm-start list of the substep
-// (newOff[owner] + slot of the owner's list), so StoreImpulses is a copy, and the previous substep's list is kept as an
-// LDS image (6 B per entry) that aliases arrays which only live between the island phase and the end of the substep.
-//   always            : misc | pos | vel
-//   parent            : union-find (emit .. sleep bookkeeping); start-of-substep angle of the TOI candidates behind it
-//   dircnt            : per-direction contact counts (find .. emit) -> island census / body depth -> startY (integrate .. TOI)
-//   botA              : [wsOff | wsCnt | idOf | (cellOfSlot: hashed bins)]; startX over its front (integrate .. TOI)
-//   botB              : [newOff | wsCntNew]
-//   con32 x 3         : lPair lInfo lAcc   (the arrival-order scratch of the sort lies over lInfo, the neighbour counters of
-//                                           the sensing pass over lAcc: both dead before the emit pass writes the records)
-//   act0              : position-solver island flags of even iterations (also "island has an awake body": cleared in the
-//                       drive phase, hence outside the aliased zone)
-//   zone              : [act1 | islWave | lOrder | lCbk]  aliased by the warm-start image [oldAcc | oldKey]
-//   binE              : bin boundaries (u16, entry i = kilobots in bins < i) -> bucket tables of the contact sort -> unused
-namespace ldsb {
-__host__ __device__ constexpr int A16(int x) { return (x + 15) & ~15; }
-__host__ __device__ constexpr int A4(int x) { return (x + 3) & ~3; }
-__host__ __device__ constexpr int pos() { return 320; }                       // (MISC 256 + WSUM 64 in front)
-__host__ __device__ constexpr int vel(int NB) { return pos() + 8 * NB; }
-__host__ __device__ constexpr int parent(int NB) { return vel(NB) + 8 * NB; }
-__host__ __device__ constexpr int dircnt(int NB) { return parent(NB) + 4 * NB; }
-__host__ __device__ constexpr int botA(int NB) { return dircnt(NB) + 4 * NB; }
-__host__ __device__ constexpr int botA_size(int NB, int NP, bool hc) { return A16((5 + (hc ? 2 : 0)) * NP > 4 * NB ? (5 + (hc ? 2 : 0)) * NP : 4 * NB); }
-__host__ __device__ constexpr int wsoff(int NB) { return botA(NB); }
-__host__ __device__ constexpr int wscnt(int NB, int NP) { return botA(NB) + 2 * NP; }
-__host__ __device__ constexpr int idof(int NB, int NP) { return botA(NB) + 3 * NP; }
-__host__ __device__ constexpr int cellofslot(int NB, int NP) { return botA(NB) + 5 * NP; }
-__host__ __device__ constexpr int botB(int NB, int NP, bool hc) { return botA(NB) + botA_size(NB, NP, hc); }
-__host__ __device__ constexpr int newoff(int NB, int NP, bool hc) { return botB(NB, NP, hc); }
-__host__ __device__ constexpr int wscntnew(int NB, int NP, bool hc) { return botB(NB, NP, hc) + 2 * NP; }
-__host__ __device__ constexpr int con32(int NB, int NP, bool hc, int capL, int k) { return A16(botB(NB, NP, hc) + 3 * NP) + 4 * capL * k; }
-__host__ __device__ constexpr int act0(int NB, int NP, bool hc, int capL) { return con32(NB, NP, hc, capL, 3); }
-__host__ __device__ constexpr int zone(int NB, int NP, bool hc, int capL) { return act0(NB, NP, hc, capL) + NB; }      // act1 follows act0 directly
-__host__ __device__ constexpr int islwave(int NB, int NP, bool hc, int capL) { return zone(NB, NP, hc, capL) + NB; }
-__host__ __device__ constexpr int order(int NB, int NP, bool hc, int capL) { return A4(islwave(NB, NP, hc, capL) + NB); }
-__host__ __device__ constexpr int cbk(int NB, int NP, bool hc, int capL) { return order(NB, NP, hc, capL) + A4(2 * capL); }
-__host__ __device__ constexpr int oldacc(int NB, int NP, bool hc, int capL) { return A4(zone(NB, NP, hc, capL)); }
-__host__ __device__ constexpr int oldkey(int NB, int NP, bool hc, int capL) { return oldacc(NB, NP, hc, capL) + 4 * capL; }
-__host__ __device__ constexpr int zone_end(int NB, int NP, bool hc, int capL) {
-    return cbk(NB, NP, hc, capL) + A4(2 * capL) > oldkey(NB, NP, hc, capL) + 2 * capL ? cbk(NB, NP, hc, capL) + A4(2 * capL) : oldkey(NB, NP, hc, capL) + 2 * capL;
-}
-__host__ __device__ constexpr int binE(int NB, int NP, bool hc, int capL) { return A16(zone_end(NB, NP, hc, capL)); }
-__host__ __device__ constexpr int bin_entries(int nbin) { return (nbin + 1 + 7) & ~7; }                 // u16 entries, whole 16-byte chunks
-__host__ __device__ constexpr int tables(int nw) { return lds::nlist(nw) + 16 - lds::BKSTART; }       // bucket tables, relative to binE
-__host__ __device__ inline int binE_size(int nbin, int nw) { return A16(2 * bin_entries(nbin) > tables(nw) ? 2 * bin_entries(nbin) : tables(nw)); }
-__host__ __device__ inline int total(int NB, int NP, bool hc, int capL, int nbin, int nw) { return binE(NB, NP, hc, capL) + binE_size(nbin, nw); }
-constexpr int CAPL = 688;                                                     // staged contacts of the fixed-size kernel
-}  // namespace ldsb
 
 struct Params {
     kb_buffers buf;

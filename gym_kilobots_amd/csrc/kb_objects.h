@@ -7,6 +7,7 @@
 // the same bits wherever it runs.
 #pragma once
 #include "kb_common.h"
+#include "kb_launch.h"
 
 namespace kb {
 
@@ -287,8 +288,6 @@ enum { MC_A = 0, MC_B, MC_TYPE /* type | count << 2 | vcount << 4 */, MC_ID /* i
        MC_NM0, MC_NM1, MC_TM0, MC_TM1, MC_K11, MC_K12, MC_K22, MC_N11, MC_N12, MC_N22, MC_FIELDS };
 
 static_assert(MC_FIELDS == MC_FIELDS_C, "manifold-constraint record size");
-// number of (object, partner) candidates of M objects: pairs in lexicographic order, then (object, wall)
-KB_HD int mc_candidates(int M) { return M * (M - 1) / 2 + 4 * M; }
 
 // body state as the contact solver sees it (b2Position, b2Velocity, inverse mass / inertia)
 struct BState { V2 c; float a; V2 v; float w; float m, i; };

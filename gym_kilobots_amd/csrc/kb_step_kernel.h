@@ -22,7 +22,7 @@ namespace kb {
 // SENSE = false: instantiation without the IR-range neighbour sensing hook (the fixed-size kernels are at their register
 // budget: the hook costs them 2 more spilled VGPRs, 20 B/lane of scratch traffic per launch); picked when
 // kb_config.sense_radius == 0.
-// Kernels without objects use the compact LDS image (namespace ldsc).  TIER picks the register budget:
+// Kernels without objects use the sorted-bin LDS image (namespace ldsb in kb_launch.h).  TIER picks the register budget:
 //   0: 128 VGPRs (launch bounds of 4 waves per SIMD);
 //   1: "WIDE", one-wave workgroups in scenes with objects: 256 VGPRs (2 waves per SIMD), no spills;
 //   2: 80 VGPRs (6 waves per SIMD): three 8-wave / six 4-wave workgroups per CU where the LDS image admits them;
@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     // bin per cell of the arena; a bin may then hold kilobots of several cells and every candidate's cell is checked.
     // The set of contacts and their canonical order (which use the cell coordinates) do not change.
     const bool hashed = FN == 0 && p.hmask != 0;
-    // LDS arrays (offsets: namespace lds / ldsb in kb_common.h)
+    // LDS arrays (offsets: namespace lds / ldsb in kb_launch.h)
     // (the fixed-size instantiations with objects keep room for the object tables: all their offsets are compile-time constants)
     const int fx = lds::fixed(OBJ || FN != 0, nw), ot_ = lds::objtab(nw);
     // positions, velocities and start-of-substep positions as (x, y) pairs: one 8-byte LDS access per body

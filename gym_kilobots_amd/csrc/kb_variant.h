@@ -64,8 +64,8 @@ struct Shape {
     int drive_mode, light_type;     // kb_config
     bool objects, all_discs;        // num_objects > 0; ... and every fixture is a circle
     bool sense, sleep;              // sense_radius > 0; allow_sleep
-    int threads, tier;              // workgroup size; register budget of the kernels without objects (kb_abi.hip: pick_tier)
-    bool fixed_1024;                // kb_abi.hip: uses_fixed_1024
+    int threads, tier;              // workgroup size; register budget of the kernels without objects (kb_launch.h: compact_tier)
+    bool fixed_1024;                // kb_launch.h: fixed_1024
 };
 
 constexpr Variant select_variant(const Shape &s) {
@@ -74,7 +74,7 @@ constexpr Variant select_variant(const Shape &s) {
     const bool poly = !(s.objects && s.all_discs);      // all discs: without the kilobot - polygon contact code
     if (s.fixed_1024) return {KB_DRIVE_VELOCITY, KB_LIGHT_NONE, s.objects, 1024, 0, poly, s.sense, s.sleep};
     if (s.drive_mode == KB_DRIVE_MIXED) return {KB_DRIVE_MIXED, L, true, 0, s.threads == 64 ? 1 : 3, true, true, s.sleep};
-    // with objects a one-wave workgroup runs the 256-VGPR instantiation; without, pick_tier decides between 128 and 80 VGPRs
+    // with objects a one-wave workgroup runs the 256-VGPR instantiation; without, compact_tier decides between 128 and 80 VGPRs
     return {s.drive_mode, L, s.objects, 0, s.objects ? (s.threads <= 64 ? 1 : 0) : s.tier, poly, true, s.sleep};
 }
 
