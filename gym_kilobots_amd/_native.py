@@ -19,6 +19,7 @@ MAX_POLY_VERTS = 4
 SHAPE_CIRCLE, SHAPE_BOX, SHAPE_POLYGON = range(3)
 OWS_COLS, OWS_WORDS = 12, 6
 MAX_BOTS = 1024
+MAX_NEIGHBORS = 16     # KB_MAX_NEIGHBORS: slots per kilobot of kb_sense_neighbors
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -75,7 +76,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -128,6 +129,8 @@ def load():
     lib.kb_get_state.restype = C.c_int
     lib.kb_sense.argtypes = [_P, C.c_float, _P, _P]
     lib.kb_sense.restype = C.c_int
+    lib.kb_sense_neighbors.argtypes = [_P, C.c_float, C.c_int, _P, _P, _P, _P]
+    lib.kb_sense_neighbors.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]

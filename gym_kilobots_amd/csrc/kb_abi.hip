@@ -95,24 +95,110 @@ __global__ void __launch_bounds__(256) kb_sense_kernel(const Params p, const int
     unsigned short *cellOf = nextb + p.NP;
     unsigned short *head = cellOf + p.NP;
     const size_t o = (size_t)e * N;
-    for (int c = tid; c < p.ncell; c += nt) head[c] = EMPTY16;
     for (int b = tid; b < p.NP / 2; b += nt) cnt16[b] = 0;
-    __syncthreads();
-    for (int b = tid; b < N; b += nt) {
-        const float bx = p.buf.x[o + b], by = p.buf.y[o + b];
-        pos[b].x = bx; pos[b].y = by;
-        int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
-        int cy = (int)floorf((by - p.ymin) * p.inv_cell);
-        cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
-        cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-        const int cell = cy * p.gw + cx;
-        cellOf[b] = (unsigned short)cell;
-        nextb[b] = (unsigned short)kb_exch16(head, cell, (unsigned)b);
-    }
-    __syncthreads();
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
     kb_sense_pass(pos, head, nextb, cellOf, cnt16, N, nt, tid, p.gw, p.gh, s, R2, 0);
     __syncthreads();
     for (int b = tid; b < N; b += nt) out[o + b] = (unsigned)reinterpret_cast<unsigned short *>(cnt16)[b];
+}
+
+// Nearest-neighbour lists with body-frame offsets on the current poses (kb_sense_neighbors): one workgroup per env, poses,
+// headings and the cell lists of the broadphase grid in LDS, one kilobot per lane.  Every kilobot walks the FULL stencil of
+// reach s (it needs its own ordered list, so the half-stencil trick of kb_sense_pass does not apply) and keeps the K best
+// keys (bits of d2) << 32 | j in registers: d2 >= 0, so the unsigned order of the key is the order by (d2, j).  A
+// candidate in range that beats the worst kept key runs down an unrolled compare-exchange chain (best[] stays sorted; every
+// index is a compile-time constant, so best[] never leaves the registers).  K: the requested k rounded up to 4, 8 or 16.
+// Rows are written per lane: slot i of kilobot a is one 16-byte store, its k slots are contiguous.
+template <int K>
+__global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const int s, const float R2, const int k, const int vec,
+                                                           int *d_index, float4 *d_rel, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int W = 8;      // list heads fetched together (one LDS round trip); most cells are empty
+    constexpr unsigned long long NONE = ~0ull;
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    float *th = reinterpret_cast<float *>(smem + 8 * p.NP);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + 12 * p.NP);
+    unsigned short *cellOf = nextb + p.NP;
+    unsigned short *head = cellOf + p.NP;
+    const size_t o = (size_t)e * N;
+    for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    for (int a = tid; a < N; a += nt) {
+        const int cell = cellOf[a];
+        const int cx = cell % p.gw, cy = cell / p.gw;
+        const float2 pa = pos[a];
+        unsigned long long best[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) best[i] = NONE;
+        unsigned cnt = 0;
+        const int y1 = min(cy + s, p.gh - 1), x0 = max(cx - s, 0), x1 = min(cx + s, p.gw - 1);
+        for (int oy = max(cy - s, 0); oy <= y1; ++oy) {
+            for (int xb = x0; xb <= x1; xb += W) {
+                unsigned cur[W];
+#pragma unroll
+                for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
+                        const float2 pb = pos[b];
+                        const unsigned nb = nextb[b];
+                        const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+                        const float dd = ex * ex + ey * ey;
+                        if ((int)b != a && !(dd > R2)) {
+                            cnt++;
+                            unsigned long long key = ((unsigned long long)__float_as_uint(dd) << 32) | b;
+                            if (key < best[K - 1]) {
+#pragma unroll
+                                for (int q = 0; q < K; ++q) {
+                                    const unsigned long long lo = key < best[q] ? key : best[q];
+                                    key = key < best[q] ? best[q] : key;
+                                    best[q] = lo;
+                                }
+                            }
+                        }
+                        b = nb;
+                    }
+                }
+            }
+        }
+        const float tha = th[a];
+        float sn, cs;
+        kb_sincosf(tha, sn, cs);
+        const size_t row = (o + a) * (size_t)k;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (i >= k) break;
+            const bool used = best[i] != NONE;
+            const unsigned j = used ? (unsigned)best[i] : (unsigned)a;
+            const float2 pb = pos[j];
+            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+            const float d2 = __uint_as_float((unsigned)(best[i] >> 32));
+            float4 r;
+            r.x = (cs * ex + sn * ey) / WORLD_SCALE;
+            r.y = (cs * ey - sn * ex) / WORLD_SCALE;
+            r.z = sqrtf(d2) / WORLD_SCALE;
+            r.w = th[j] - tha;
+            if (!used) r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            d_rel[row + i] = r;
+        }
+        if (vec) {      // k is a multiple of 4 and d_index is 16-byte aligned: four indices per store
+#pragma unroll
+            for (int i = 0; i < K; i += 4) {
+                if (i >= k) break;
+                int4 v;
+                v.x = (int)(unsigned)best[i]; v.y = (int)(unsigned)best[i + 1]; v.z = (int)(unsigned)best[i + 2]; v.w = (int)(unsigned)best[i + 3];
+                reinterpret_cast<int4 *>(d_index + row)[i >> 2] = v;      // (the low word of NONE is -1)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                if (i >= k) break;
+                d_index[row + i] = (int)(unsigned)best[i];
+            }
+        }
+        if (d_count) d_count[o + a] = cnt;
+    }
 }
 
 // The sensing point of a substep on its own (kb_light_sense): light.step + value_and_gradients at every kilobot's sensor
@@ -599,6 +685,26 @@ int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream) {
     hipLaunchKernelGGL(kb_sense_kernel, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, sense_reach(Rw, p.inv_cell), Rw * Rw, d_count);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(KB_EHIP, "kb_sense: %s", hipGetErrorString(err));
+    return KB_OK;
+}
+
+int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count, void *stream) {
+    if (!sim || !d_index || !d_rel) return fail(KB_EINVAL, "kb_sense_neighbors: NULL argument");
+    if (k < 1 || k > KB_MAX_NEIGHBORS) return fail(KB_EINVAL, "kb_sense_neighbors: 1 <= k <= KB_MAX_NEIGHBORS (16) required");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_neighbors: radius must be positive");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_neighbors: kb_bind() first");
+    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_neighbors: d_rel must be 16-byte aligned");
+    const Params &p = sim->p;
+    const float Rw = radius_m * WORLD_SCALE;
+    const size_t lds = (size_t)16 * p.NP + 2 * (size_t)p.ncell + 16;
+    const int vec = k % 4 == 0 && (reinterpret_cast<uintptr_t>(d_index) & 15u) == 0;
+    const auto fn = k <= 4 ? kb_neighbors_kernel<4> : k <= 8 ? kb_neighbors_kernel<8> : kb_neighbors_kernel<16>;
+    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
+    const int reach = Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh;
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, reach, Rw * Rw, k, vec,
+                       d_index, reinterpret_cast<float4 *>(d_rel), d_count);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_neighbors: %s", hipGetErrorString(err));
     return KB_OK;
 }
 

@@ -16,11 +16,14 @@ class BatchedKilobotsEnv(object):
 
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
-                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, **cfg):
+                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
-        reset() and after every status_interval-th step(): 'raise' | 'warn' | 'ignore' (one 4-byte device read each)."""
+        reset() and after every status_interval-th step(): 'raise' | 'warn' | 'ignore' (one 4-byte device read each).
+        neighbor_obs: (radius_m, k) adds the IR-range observation of a decentralised policy: neighbors() returns the k
+        nearest kilobots within radius_m of every kilobot in its own frame (KilobotSim.neighbors), and step() puts them
+        in its info dict under 'neighbors'.  None: reset() and step() are what they were, the info dict stays {}."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -36,6 +39,12 @@ class BatchedKilobotsEnv(object):
         self.env_offset = int(env_offset)
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
+        self.neighbor_obs = None
+        if neighbor_obs is not None:
+            radius_m, k = neighbor_obs
+            if not float(radius_m) > 0.0 or not 1 <= int(k) <= nat.MAX_NEIGHBORS:
+                raise ValueError('neighbor_obs must be (radius_m > 0, 1 <= k <= %d)' % nat.MAX_NEIGHBORS)
+            self.neighbor_obs = (float(radius_m), int(k))
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -121,7 +130,15 @@ class BatchedKilobotsEnv(object):
         if self._steps % self._status_interval == 0:
             self._check_status('step()')
         done = torch.zeros(self.num_envs, dtype=torch.bool, device=obs.device)
-        return obs, reward, done, {}
+        info = {} if self.neighbor_obs is None else {'neighbors': self.neighbors()}
+        return obs, reward, done, info
+
+    def neighbors(self):
+        """(index [E, N, k] int32, rel [E, N, k, 4] float32, count [E, N] int32) of the current poses for the
+        neighbor_obs=(radius_m, k) the env was created with: KilobotSim.neighbors."""
+        if self.neighbor_obs is None:
+            raise ValueError('create the env with neighbor_obs=(radius_m, k) to observe neighbours')
+        return self.sim.neighbors(*self.neighbor_obs)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

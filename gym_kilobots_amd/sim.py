@@ -239,6 +239,33 @@ class KilobotSim:
             nat.check(self._lib.kb_sense(self._h, float(radius_m), C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense')
         return out
 
+    def neighbors(self, radius_m, k, out=None, count=True):
+        """Nearest-neighbour lists on the current poses (kb_sense_neighbors; no reference counterpart): for every kilobot the
+        k nearest kilobots of its env within radius_m (centre to centre), ordered by distance, ties to the lower index.
+        Returns (index [E, N, k] int32, -1 in unused slots; rel [E, N, k, 4] float32 = (metres ahead, metres to the left,
+        distance in metres, heading of the neighbour minus the own heading), zeros in unused slots; count [E, N] int32 =
+        kilobots in range, which may exceed k -- or None with count=False).  out: a tuple of preallocated contiguous
+        tensors (index, rel[, count]) to write into."""
+        E, N, k = self.num_envs, self.num_bots, int(k)
+        if not 1 <= k <= nat.MAX_NEIGHBORS:
+            raise ValueError('k must be in 1..%d' % nat.MAX_NEIGHBORS)
+        shapes = [((E, N, k), torch.int32, 'index'), ((E, N, k, 4), torch.float32, 'rel')] + ([((E, N), torch.int32, 'count')] if count else [])
+        if out is None:
+            out = tuple(torch.empty(*s, dtype=d, device=self.device) for s, d, _ in shapes)
+        out = tuple(out)
+        if len(out) != len(shapes):
+            raise ValueError('out must be a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes)))
+        for t, (s, d, n) in zip(out, shapes):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
+                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
+            if t.device != self.device:
+                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+        pc = C.c_void_p(out[2].data_ptr()) if count else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_neighbors(self._h, float(radius_m), k, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
+                                                   pc, self._stream()), 'kb_sense_neighbors')
+        return (out[0], out[1], out[2] if count else None)
+
     def light_sense(self, light_action=None):
         """The sensing point of one substep on its own (kb_light_sense): Light.step with `light_action` (None: the light
         stays) + value_and_gradients at every kilobot's sensor into light_value / light_gx / light_gy -- for kilobots whose

@@ -223,6 +223,24 @@ int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, in
  * No reference counterpart (the reference has no neighbour sensing; nearest: Body.collides_with, body.py:87-90). */
 int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream);
 
+/* Nearest-neighbour lists on the CURRENT poses, without stepping: for every kilobot i the k nearest kilobots j != i of
+ * the same env within IR range, with their offsets in the body frame of i -- what a decentralised policy observes.
+ * No reference counterpart.  Every operation below is one fp32 operation rounded on its own:
+ *   Rw = radius_m * 25, R2 = Rw * Rw (on the host, as kb_sense);  ex = x_j - x_i, ey = y_j - y_i (world units);
+ *   d2 = ex * ex + ey * ey;  j is in range iff !(d2 > R2) (the predicate of kb_sense);
+ *   neighbours are ordered by (d2, j) ascending, ties go to the lower index; the first min(k, count) are written;
+ *   (s, c) = the library's sine and cosine of theta_i (the Cephes algorithm every kernel uses);
+ *   rel[0] = (c * ex + s * ey) / 25   metres ahead         rel[1] = (c * ey - s * ex) / 25   metres to the left
+ *   rel[2] = sqrt(d2) / 25            distance in metres   rel[3] = theta_j - theta_i        (not wrapped)
+ *   with correctly rounded divisions and square root.
+ * d_index [num_envs][num_bots][k] int32: index of the neighbour within its env, -1 in unused slots.
+ * d_rel   [num_envs][num_bots][k][4] float32, 16-byte aligned: rel of each slot, all 0.0f in unused slots.
+ * d_count [num_envs][num_bots] uint32 or NULL: kilobots in range (may exceed k) -- what kb_sense writes for this radius.
+ * 1 <= k <= KB_MAX_NEIGHBORS.  Reads x, y, theta; writes the three outputs only.  Asynchronous on `stream`. */
+#define KB_MAX_NEIGHBORS 16
+int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count,
+                       void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into

@@ -2,6 +2,7 @@
 """Per-kernel register / scratch / spill table of the kernel units (hipcc -Rpass-analysis=kernel-resource-usage).
 
 usage: tools/kernel_resources.py [unit ...]      e.g. tools/kernel_resources.py d0 d0_discs      (default: all kb_inst_* units)
+       tools/kernel_resources.py abi             the kernels of kb_abi.hip (sensing, neighbour lists, reset, read-back)
 Prints one line per kernel: VGPRs, SGPRs, scratch bytes per lane, waves per SIMD, spilled SGPRs / VGPRs, and the number of
 "Folded Spill" stores in the generated code."""
 import glob
@@ -55,15 +56,20 @@ def main():
     units = [s for s in B.sources() if os.path.basename(s).startswith('kb_inst_')]
     if sel:
         units = [u for u in units if any(os.path.basename(u)[:-4] == 'kb_inst_' + s for s in sel)]
+        if 'abi' in sel:
+            units.append(os.path.join(B.CSRC, 'kb_abi.hip'))
     with ThreadPoolExecutor(max_workers=min(8, len(units))) as ex:
         tabs = list(ex.map(unit_table, units))
     print('%-78s %5s %5s %8s %5s %7s %7s %7s' % ('kernel', 'VGPR', 'SGPR', 'scratch', 'w/SIMD', 'sgprSp', 'vgprSp', 'spillSt'))
     for u, rows in zip(units, tabs):
         for r in rows:
-            if 'kb_step_kernel' not in r['name']:
+            abi = os.path.basename(u) == 'kb_abi.hip'
+            if 'kb_step_kernel' not in r['name'] and not abi:
                 continue
             n = demangle(r['name']).replace('void kb::', '').replace('(kb::Params)', '')
-            print('%-78s %5s %5s %8s %5s %7s %7s %7d' % (os.path.basename(u)[8:-4] + ':' + n, r.get('VGPRs'), r.get('TotalSGPRs'), r.get('ScratchSize'),
+            if abi:
+                n = n.replace('void (anonymous namespace)::', '').split('(')[0]
+            print('%-78s %5s %5s %8s %5s %7s %7s %7d' % (('abi' if abi else os.path.basename(u)[8:-4]) + ':' + n, r.get('VGPRs'), r.get('TotalSGPRs'), r.get('ScratchSize'),
                                                       r.get('Occupancy'), r.get('SGPRs Spill'), r.get('VGPRs Spill'), r['folded_spill_stores']))
 
 
