@@ -20,6 +20,7 @@ SHAPE_CIRCLE, SHAPE_BOX, SHAPE_POLYGON = range(3)
 OWS_COLS, OWS_WORDS = 12, 6
 MAX_BOTS = 1024
 MAX_NEIGHBORS = 16     # KB_MAX_NEIGHBORS: slots per kilobot of kb_sense_neighbors
+HIST_MAX_RINGS, HIST_MAX_SECTORS, HIST_MAX_BINS = 8, 16, 64     # KB_HIST_MAX_*: bin grid of kb_sense_histogram
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -76,7 +77,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -131,6 +132,10 @@ def load():
     lib.kb_sense.restype = C.c_int
     lib.kb_sense_neighbors.argtypes = [_P, C.c_float, C.c_int, _P, _P, _P, _P]
     lib.kb_sense_neighbors.restype = C.c_int
+    lib.kb_sense_histogram.argtypes = [_P, C.c_float, C.c_int, C.c_int, _P, _P, _P]
+    lib.kb_sense_histogram.restype = C.c_int
+    lib.kb_histogram_sectors.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.kb_histogram_sectors.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -154,6 +159,28 @@ def check(rc, what):
     if rc != KB_OK:
         msg = load().kb_last_error().decode('utf-8', 'replace')
         raise KilobotsHipError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def check_histogram_grid(n_rings, n_sectors):
+    """The limits of kb_sense_histogram on the bin grid; ValueError where the library would answer KB_EINVAL."""
+    n_rings, n_sectors = int(n_rings), int(n_sectors)
+    if not 1 <= n_rings <= HIST_MAX_RINGS:
+        raise ValueError('n_rings must be in 1..%d' % HIST_MAX_RINGS)
+    if n_sectors != 1 and (n_sectors < 2 or n_sectors > HIST_MAX_SECTORS or n_sectors % 2):
+        raise ValueError('n_sectors must be 1 or an even number in 2..%d' % HIST_MAX_SECTORS)
+    if n_rings * n_sectors > HIST_MAX_BINS:
+        raise ValueError('n_rings * n_sectors must not exceed %d' % HIST_MAX_BINS)
+    return n_rings, n_sectors
+
+
+def histogram_sectors(n_sectors):
+    """The sector boundaries u_m, m = 1 .. n_sectors / 2 - 1, that kb_sense_histogram hands its kernel
+    (kb_histogram_sectors): a list of (x, y) floats; no handle and no device needed."""
+    n = int(n_sectors)
+    rows = max(n // 2 - 1, 0)
+    buf = (C.c_float * (2 * max(rows, 1)))()
+    check(load().kb_histogram_sectors(n, buf), 'kb_histogram_sectors')
+    return [(buf[2 * m], buf[2 * m + 1]) for m in range(rows)]
 
 
 def default_config(num_envs, num_bots, drive_mode=DRIVE_VELOCITY, light_type=LIGHT_NONE, **kw):

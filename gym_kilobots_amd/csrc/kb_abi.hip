@@ -201,6 +201,121 @@ __global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const
     }
 }
 
+// Local neighbour histograms on the current poses (kb_sense_histogram): every kilobot counts ALL kilobots of its env in IR
+// range, binned by ring (distance) and sector (bearing in its own frame).  One workgroup per env, poses and the cell lists
+// of the broadphase grid in LDS, one kilobot per lane over the full stencil.  The walk is the walk of kb_neighbors_kernel,
+// kept local to this kernel: that kernel's register figures stay what they are.  A kilobot's heading is
+// used once, by its own lane, so it is read straight from global memory into a register.
+// Accumulator: the env is processed in tiles of 256 kilobots; lane t owns column t of u16 hist[bin][HIST_STRIDE] in LDS
+// (a count is at most N - 1 <= 1023) and is the only one to update it: no atomics, no per-lane array, no scratch.  After
+// the tile's walk and a barrier the workgroup writes the tile's n * B floats with the flat index f = tid + 256 i
+// (kilobot f / B, bin f % B, both kept incrementally): consecutive lanes store consecutive floats.  HIST_STRIDE = 258
+// halfwords = 129 words: in that read-out the lanes of a wave read bins of one or two kilobots, and the odd word stride
+// puts them on different banks (a stride of 256 would put all 64 on one).  The edge and boundary tables arrive as a kernel
+// argument and go through LDS into per-lane registers, and the ring and sector counts run over the whole tables without
+// branches (unused edges are +inf, unused boundaries (0, 0): they count nothing): with the tables in SGPRs next to Params,
+// or with a uniform early exit per table entry, the kernel spilled SGPRs.
+struct HistArgs {
+    int n_rings, n_sectors;
+    float e2[KB_HIST_MAX_RINGS - 1];            // E2_r of ring edge r + 1
+    float ux[KB_HIST_MAX_SECTORS / 2 - 1];      // u_m of sector boundary m + 1 (kb_histogram_sectors)
+    float uy[KB_HIST_MAX_SECTORS / 2 - 1];
+};
+constexpr int HIST_TILE = 256;
+constexpr int HIST_STRIDE = HIST_TILE + 2;
+constexpr int HIST_TABLE_BYTES = 4 * (KB_HIST_MAX_RINGS + KB_HIST_MAX_SECTORS - 3);
+// the largest image (1024 kilobots, every cell, 64 bins) stays under the default limit for dynamic LDS: no attribute to raise
+static_assert(12 * KB_MAX_BOTS + 2 * MAX_CELLS + 2 * KB_HIST_MAX_BINS * HIST_STRIDE + HIST_TABLE_BYTES <= 64 * 1024, "kb_histogram_kernel: LDS image");
+
+__global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const int s, const float R2, const HistArgs h,
+                                                           float *d_hist, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int W = 8;      // list heads fetched together, as kb_neighbors_kernel
+    constexpr int NE = KB_HIST_MAX_RINGS - 1, NU = KB_HIST_MAX_SECTORS / 2 - 1;
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const int B = h.n_rings * h.n_sectors, H = h.n_sectors >> 1;
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + 8 * p.NP);
+    unsigned short *cellOf = nextb + p.NP;
+    unsigned short *head = cellOf + p.NP;
+    unsigned short *hist = head + ((p.ncell + 1) & ~1);      // (kb_exch16 works on whole words of head)
+    float *tab = reinterpret_cast<float *>(hist + B * HIST_STRIDE);
+    const size_t o = (size_t)e * N;
+    if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < NE; ++r) tab[r] = h.e2[r];
+#pragma unroll
+        for (int m = 0; m < NU; ++m) { tab[NE + m] = h.ux[m]; tab[NE + NU + m] = h.uy[m]; }
+    }
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    float e2[NE], ux[NU], uy[NU];
+#pragma unroll
+    for (int r = 0; r < NE; ++r) e2[r] = tab[r];
+#pragma unroll
+    for (int m = 0; m < NU; ++m) { ux[m] = tab[NE + m]; uy[m] = tab[NE + NU + m]; }
+    const int q256 = HIST_TILE / B, r256 = HIST_TILE % B;
+    for (int t0 = 0; t0 < N; t0 += HIST_TILE) {
+        const int a = t0 + tid;
+        unsigned short *col = hist + tid;
+        for (int b = 0; b < B; ++b) col[b * HIST_STRIDE] = 0;
+        if (a < N) {
+            const int cell = cellOf[a];
+            const int cx = cell % p.gw, cy = cell / p.gw;
+            const float2 pa = pos[a];
+            float sn, cs;
+            kb_sincosf(p.buf.theta[o + a], sn, cs);
+            unsigned cnt = 0;
+            const int y1 = min(cy + s, p.gh - 1), x0 = max(cx - s, 0), x1 = min(cx + s, p.gw - 1);
+            for (int oy = max(cy - s, 0); oy <= y1; ++oy) {
+                for (int xb = x0; xb <= x1; xb += W) {
+                    unsigned cur[W];
+#pragma unroll
+                    for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
+#pragma unroll
+                    for (int i = 0; i < W; ++i) {
+                        for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
+                            const float2 pb = pos[b];
+                            const unsigned nb = nextb[b];
+                            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+                            const float dd = ex * ex + ey * ey;
+                            if ((int)b != a && !(dd > R2)) {
+                                cnt++;
+                                int ring = 0;
+#pragma unroll
+                                for (int r = 0; r < NE; ++r) ring += dd > e2[r] ? 1 : 0;
+                                int sector = 0;
+                                if (H > 0) {
+                                    float ah = cs * ex + sn * ey;
+                                    float lf = cs * ey - sn * ex;
+                                    const bool low = lf < 0.0f;
+                                    if (low) { ah = -ah; lf = -lf; }
+#pragma unroll
+                                    for (int m = 0; m < NU; ++m) sector += ux[m] * lf - uy[m] * ah > 0.0f ? 1 : 0;
+                                    if (low) sector += H;
+                                }
+                                unsigned short *c = col + (ring * h.n_sectors + sector) * HIST_STRIDE;
+                                *c = (unsigned short)(*c + 1u);
+                            }
+                            b = nb;
+                        }
+                    }
+                }
+            }
+            if (d_count) d_count[o + a] = cnt;
+        }
+        __syncthreads();
+        const int total = min(HIST_TILE, N - t0) * B;
+        float *out = d_hist + (o + t0) * (size_t)B;
+        int kb = tid / B, bin = tid % B;
+        for (int f = tid; f < total; f += HIST_TILE) {
+            out[f] = (float)hist[bin * HIST_STRIDE + kb];
+            kb += q256; bin += r256;
+            if (bin >= B) { bin -= B; kb++; }
+        }
+        __syncthreads();
+    }
+}
+
 // The sensing point of a substep on its own (kb_light_sense): light.step + value_and_gradients at every kilobot's sensor
 // (kilobots_env.py:171-180), with the arithmetic of the step kernel (shared functions of kb_common.h), for kilobots whose
 // _loop runs on the host between the sensing and the motor law.  One workgroup per env.
@@ -705,6 +820,49 @@ int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, flo
                        d_index, reinterpret_cast<float4 *>(d_rel), d_count);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_neighbors: %s", hipGetErrorString(err));
+    return KB_OK;
+}
+
+int kb_histogram_sectors(int n_sectors, float *xy) {
+    if (n_sectors != 1 && (n_sectors < 2 || n_sectors > KB_HIST_MAX_SECTORS || (n_sectors & 1)))
+        return fail(KB_EINVAL, "kb_histogram_sectors: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)");
+    const int H = n_sectors / 2;
+    if (H > 1 && !xy) return fail(KB_EINVAL, "kb_histogram_sectors: NULL table");
+    for (int m = 1; m < H; ++m) {
+        const double t = 3.14159265358979323846 * (double)m / (double)H;
+        xy[2 * (m - 1) + 0] = 2 * m == H ? 0.0f : (float)cos(t);
+        xy[2 * (m - 1) + 1] = 2 * m == H ? 1.0f : (float)sin(t);
+    }
+    return KB_OK;
+}
+
+int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, float *d_hist, uint32_t *d_count, void *stream) {
+    if (!sim || !d_hist) return fail(KB_EINVAL, "kb_sense_histogram: NULL argument");
+    if (n_rings < 1 || n_rings > KB_HIST_MAX_RINGS) return fail(KB_EINVAL, "kb_sense_histogram: 1 <= n_rings <= KB_HIST_MAX_RINGS (8) required");
+    if (n_sectors != 1 && (n_sectors < 2 || n_sectors > KB_HIST_MAX_SECTORS || (n_sectors & 1)))
+        return fail(KB_EINVAL, "kb_sense_histogram: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)");
+    if (n_rings * n_sectors > KB_HIST_MAX_BINS) return fail(KB_EINVAL, "kb_sense_histogram: n_rings * n_sectors <= KB_HIST_MAX_BINS (64) required");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_histogram: radius must be positive");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_histogram: kb_bind() first");
+    const Params &p = sim->p;
+    const float Rw = radius_m * WORLD_SCALE;
+    HistArgs h;
+    memset(&h, 0, sizeof(h));
+    h.n_rings = n_rings; h.n_sectors = n_sectors;
+    // the kernel's comparisons are branch-free over the whole tables: an edge at infinity and a zero boundary vector count nothing
+    for (int r = 1; r < KB_HIST_MAX_RINGS; ++r) {
+        const float edge = (Rw * (float)r) / (float)n_rings;
+        h.e2[r - 1] = r < n_rings ? edge * edge : INFINITY;
+    }
+    float u[KB_HIST_MAX_SECTORS / 2 - 1][2];
+    if (kb_histogram_sectors(n_sectors, &u[0][0]) != KB_OK) return KB_EINVAL;
+    for (int m = 1; m < n_sectors / 2; ++m) { h.ux[m - 1] = u[m - 1][0]; h.uy[m - 1] = u[m - 1][1]; }
+    const size_t lds = (size_t)12 * p.NP + 2 * (size_t)((p.ncell + 1) & ~1) + 2 * (size_t)(n_rings * n_sectors) * HIST_STRIDE + HIST_TABLE_BYTES;
+    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
+    const int reach = Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh;
+    hipLaunchKernelGGL(kb_histogram_kernel, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, reach, Rw * Rw, h, d_hist, d_count);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_histogram: %s", hipGetErrorString(err));
     return KB_OK;
 }
 

@@ -16,14 +16,17 @@ class BatchedKilobotsEnv(object):
 
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
-                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, **cfg):
+                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
         reset() and after every status_interval-th step(): 'raise' | 'warn' | 'ignore' (one 4-byte device read each).
         neighbor_obs: (radius_m, k) adds the IR-range observation of a decentralised policy: neighbors() returns the k
         nearest kilobots within radius_m of every kilobot in its own frame (KilobotSim.neighbors), and step() puts them
-        in its info dict under 'neighbors'.  None: reset() and step() are what they were, the info dict stays {}."""
+        in its info dict under 'neighbors'.  None: reset() and step() are what they were, the info dict stays {}.
+        histogram_obs: (radius_m, n_rings, n_sectors) adds the fixed-size local histogram of ALL kilobots in range, binned by
+        distance and bearing in the kilobot's own frame (KilobotSim.neighbor_histogram): neighbor_histogram() returns it,
+        step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -45,6 +48,17 @@ class BatchedKilobotsEnv(object):
             if not float(radius_m) > 0.0 or not 1 <= int(k) <= nat.MAX_NEIGHBORS:
                 raise ValueError('neighbor_obs must be (radius_m > 0, 1 <= k <= %d)' % nat.MAX_NEIGHBORS)
             self.neighbor_obs = (float(radius_m), int(k))
+        self.histogram_obs = None
+        if histogram_obs is not None:
+            try:
+                radius_m, n_rings, n_sectors = histogram_obs
+                radius_m = float(radius_m)
+                n_rings, n_sectors = nat.check_histogram_grid(n_rings, n_sectors)
+            except TypeError as err:
+                raise ValueError('histogram_obs must be (radius_m, n_rings, n_sectors): %s' % err)
+            if not radius_m > 0.0:
+                raise ValueError('histogram_obs: radius_m must be positive')
+            self.histogram_obs = (radius_m, n_rings, n_sectors)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -131,6 +145,8 @@ class BatchedKilobotsEnv(object):
             self._check_status('step()')
         done = torch.zeros(self.num_envs, dtype=torch.bool, device=obs.device)
         info = {} if self.neighbor_obs is None else {'neighbors': self.neighbors()}
+        if self.histogram_obs is not None:
+            info['neighbor_histogram'] = self.neighbor_histogram()
         return obs, reward, done, info
 
     def neighbors(self):
@@ -139,6 +155,13 @@ class BatchedKilobotsEnv(object):
         if self.neighbor_obs is None:
             raise ValueError('create the env with neighbor_obs=(radius_m, k) to observe neighbours')
         return self.sim.neighbors(*self.neighbor_obs)
+
+    def neighbor_histogram(self):
+        """hist [E, N, n_rings, n_sectors] float32 of the current poses for the histogram_obs=(radius_m, n_rings, n_sectors)
+        the env was created with: KilobotSim.neighbor_histogram."""
+        if self.histogram_obs is None:
+            raise ValueError('create the env with histogram_obs=(radius_m, n_rings, n_sectors) to observe neighbour histograms')
+        return self.sim.neighbor_histogram(*self.histogram_obs)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

@@ -266,6 +266,33 @@ class KilobotSim:
                                                    pc, self._stream()), 'kb_sense_neighbors')
         return (out[0], out[1], out[2] if count else None)
 
+    def neighbor_histogram(self, radius_m, n_rings, n_sectors, out=None, count=False):
+        """Local neighbour histograms on the current poses (kb_sense_histogram; no reference counterpart): for every kilobot
+        the number of kilobots of its env within radius_m (centre to centre), binned by distance (n_rings rings of equal
+        width) and by bearing in its own frame (n_sectors sectors, sector 0 starting dead ahead, counter-clockwise).
+        Returns hist [E, N, n_rings, n_sectors] float32, or (hist, count [E, N] int32 = kilobots in range = hist.sum((2, 3)))
+        with count=True.  out: a preallocated contiguous hist tensor to write into (with count=True: the tuple (hist, count))."""
+        E, N = self.num_envs, self.num_bots
+        n_rings, n_sectors = nat.check_histogram_grid(n_rings, n_sectors)
+        if not float(radius_m) > 0.0:
+            raise ValueError('radius_m must be positive')
+        shapes = [((E, N, n_rings, n_sectors), torch.float32, 'hist')] + ([((E, N), torch.int32, 'count')] if count else [])
+        if out is None:
+            out = tuple(torch.empty(*s, dtype=d, device=self.device) for s, d, _ in shapes)
+        out = (out,) if torch.is_tensor(out) else tuple(out)
+        if len(out) != len(shapes):
+            raise ValueError('out must be %s' % ('the tuple (hist, count)' if count else 'the hist tensor'))
+        for t, (s, d, n) in zip(out, shapes):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
+                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
+            if t.device != self.device:
+                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+        pc = C.c_void_p(out[1].data_ptr()) if count else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_histogram(self._h, float(radius_m), n_rings, n_sectors, C.c_void_p(out[0].data_ptr()),
+                                                   pc, self._stream()), 'kb_sense_histogram')
+        return (out[0], out[1]) if count else out[0]
+
     def light_sense(self, light_action=None):
         """The sensing point of one substep on its own (kb_light_sense): Light.step with `light_action` (None: the light
         stays) + value_and_gradients at every kilobot's sensor into light_value / light_gx / light_gy -- for kilobots whose

@@ -241,6 +241,37 @@ int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream);
 int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count,
                        void *stream);
 
+/* Local neighbour histograms on the CURRENT poses, without stepping: for every kilobot i the number of kilobots j != i of
+ * the same env within IR range, binned by distance (n_rings rings of equal width) and by bearing in the body frame of i
+ * (n_sectors sectors of equal angle) -- a fixed-size, permutation-invariant observation that counts ALL neighbours in
+ * range, however many there are.  No reference counterpart.  Every operation below is one fp32 operation rounded on its own:
+ *   Rw = radius_m * 25, R2 = Rw * Rw (on the host, as kb_sense);  ex = x_j - x_i, ey = y_j - y_i (world units);
+ *   d2 = ex * ex + ey * ey;  j is counted iff !(d2 > R2) (the predicate of kb_sense);
+ *   ring: on the host, for r = 1 .. n_rings - 1, edge_r = (Rw * (float)r) / (float)n_rings and E2_r = edge_r * edge_r;
+ *     ring = the number of r with d2 > E2_r (a neighbour exactly on an edge belongs to the inner ring);
+ *   sector: (s, c) = the library's sine and cosine of theta_i (the Cephes algorithm every kernel uses);
+ *     a = c * ex + s * ey (ahead), l = c * ey - s * ex (to the left), world units, NOT divided by 25;
+ *     n_sectors == 1: sector = 0.  Otherwise H = n_sectors / 2, low = (l < 0), (a', l') = low ? (-a, -l) : (a, l),
+ *     q = the number of m in 1 .. H - 1 with u_m.x * l' - u_m.y * a' > 0 (two products, one difference),
+ *     sector = (low ? H : 0) + q: sector 0 starts dead ahead, the sectors run counter-clockwise.  A neighbour exactly on
+ *     a boundary, one with l == +-0 and a coincident one (a = l = 0: sector 0) are decided by these comparisons alone;
+ *   u_m = ((float)cos(pi m / H), (float)sin(pi m / H)) evaluated in double on the host and rounded to fp32, the entry
+ *     with 2 m == H exactly (0, 1).  kb_histogram_sectors writes this very table, the one the kernel is handed, for
+ *     m = 1 .. H - 1 into xy (HOST memory, [n_sectors / 2 - 1][2]); it needs no handle and no device, and returns
+ *     KB_EINVAL for an illegal n_sectors or a NULL xy when the table is not empty.
+ * d_hist  [num_envs][num_bots][n_rings][n_sectors] float32: neighbours in each bin (at most 1023: exact; float because it
+ *         is a network input as it stands).  Every element is written by every call, the zeros included.
+ * d_count [num_envs][num_bots] uint32 or NULL: kilobots in range = the sum of the row -- what kb_sense writes for this radius.
+ * 1 <= n_rings <= KB_HIST_MAX_RINGS; n_sectors 1 or even in 2..KB_HIST_MAX_SECTORS; n_rings * n_sectors <= KB_HIST_MAX_BINS;
+ * radius_m > 0 (a radius beyond the arena is fine).  Argument errors are reported before an unbound handle.
+ * Reads x, y, theta; writes the two outputs only.  Asynchronous on `stream`. */
+#define KB_HIST_MAX_RINGS 8
+#define KB_HIST_MAX_SECTORS 16
+#define KB_HIST_MAX_BINS 64
+int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, float *d_hist, uint32_t *d_count,
+                       void *stream);
+int kb_histogram_sectors(int n_sectors, float *xy /* host, [n_sectors / 2 - 1][2] */);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into

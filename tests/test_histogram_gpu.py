@@ -1,0 +1,237 @@
+"""kb_sense_histogram on the GPU against the brute-force numpy restatement of its definition (tests/histogram_ref.py).
+
+Everything is compared for equality: float32 arrays only, the oracle's sincosf for the frame, the sector table read through
+kb_histogram_sectors, np.bincount for the counts.  No tolerances."""
+import numpy as np
+import pytest
+import torch
+
+from tests import histogram_ref as ref
+from tests import scenes
+from tests.test_parity_gpu import cpu, dev
+
+pytestmark = pytest.mark.gpu
+
+SWEEP = [(8, 64, 0.07), (8, 64, 0.3), (4, 1024, 0.05), (4, 1024, 0.1), (3, 333, 0.034), (2, 7, 0.5), (5, 1, 0.1)]
+GRIDS = [(1, 1), (1, 2), (5, 1), (3, 6), (4, 8), (8, 8), (4, 16)]
+
+
+def make_sim(E, N, xy=None, th=None, **kw):
+    from gym_kilobots_amd.sim import KilobotSim
+    kw.setdefault('allow_sleep', 0)
+    g = KilobotSim(E, N, **kw)
+    if xy is not None:
+        g.set_poses_m(xy, th)
+    return g
+
+
+def sweep_scene(E, N):
+    if N == 1024:
+        return scenes.lattice_spawn(E, N, seed=3)
+    return scenes.gaussian_spawn(E, N, sigma=0.2, seed=4)
+
+
+def wall_scene():
+    """Kilobots in the corners and along the walls, some outside the arena (their cell indices clamp)."""
+    N = 96
+    rng = np.random.RandomState(9)
+    xy = np.zeros((4, N, 2))
+    corners = np.array([[-1.0, -0.75], [1.0, -0.75], [1.0, 0.75], [-1.0, 0.75]])
+    for e in range(4):
+        xy[e, :24] = corners[e] + rng.uniform(-0.03, 0.08, size=(24, 2)) * -np.sign(corners[e])
+        xy[e, 24:48] = np.stack([rng.uniform(-1, 1, 24), np.full(24, 0.75 - 0.0165) + rng.uniform(-0.01, 0.03, 24)], -1)
+        xy[e, 48:72] = np.stack([np.full(24, -1.0 + 0.0165) + rng.uniform(-0.03, 0.01, 24), rng.uniform(-0.75, 0.75, 24)], -1)
+        xy[e, 72:] = rng.uniform(-0.2, 0.2, size=(24, 2))
+    return xy, rng.uniform(-np.pi, np.pi, size=(4, N))
+
+
+def state(g):
+    torch.cuda.synchronize()
+    return cpu(g.x), cpu(g.y), cpu(g.theta)
+
+
+def check(g, R, rings, sectors, what=''):
+    """hist equals the restatement; its rows sum to count, which is what sense(R) gives."""
+    hist, cnt = g.neighbor_histogram(R, rings, sectors, count=True)
+    sensed = g.sense(R)
+    torch.cuda.synchronize()
+    E, N = g.num_envs, g.num_bots
+    assert hist.dtype == torch.float32 and cnt.dtype == torch.int32
+    assert tuple(hist.shape) == (E, N, rings, sectors) and tuple(cnt.shape) == (E, N)
+    hist, cnt = cpu(hist), cpu(cnt).view(np.uint32)
+    want, wcnt = ref.restate(*state(g), R, rings, sectors)
+    print('%s E=%d N=%d R=%g grid=%dx%d: %d of %d bins differ, %d counts differ, max count %d, bins hit %d of %d'
+          % (what, E, N, R, rings, sectors, int((hist != want).sum()), hist.size, int((cnt != wcnt).sum()), int(wcnt.max()),
+             int((want.sum((0, 1)) > 0).sum()), rings * sectors))
+    assert np.array_equal(cnt, wcnt), what
+    assert np.array_equal(cnt, cpu(sensed).view(np.uint32)), what
+    assert np.array_equal(hist, want), (what, np.argwhere(hist != want)[:5])
+    assert np.array_equal(hist.sum((2, 3)), cnt.astype(np.float32)), what
+    return hist, cnt
+
+
+@pytest.mark.parametrize('E,N,R', SWEEP)
+def test_histograms_equal_the_restatement(E, N, R):
+    """N = 1 (all zeros), a partial tile, two tiles with an odd remainder, four full tiles (at 64 bins the largest LDS image),
+    a radius beyond the arena; every grid on each scene."""
+    g = make_sim(E, N, *sweep_scene(E, N))
+    for rings, sectors in GRIDS:
+        hist, cnt = check(g, R, rings, sectors, 'sweep')
+        assert (hist.any() and cnt.any()) if N > 1 else not (hist.any() or cnt.any())
+
+
+@pytest.mark.parametrize('rings,sectors', [(4, 8), (2, 4)])
+def test_boundary_cases_are_decided_by_the_comparisons(rings, sectors):
+    """Kilobot 0 at the origin heading along +x; neighbours on the four axes and the four diagonals at the multiples of R / 4,
+    two kilobots on top of kilobot 0.  R = 0.125 m: Rw = 3.125 and every ring edge are exact in fp32, so the neighbours on
+    the axes sit exactly on the edges, the outermost ones exactly at distance R."""
+    R, steps = 0.125, 4
+    Rw = np.float32(R) * np.float32(25)
+    pts = [(0.0, 0.0)]
+    for k in range(1, steps + 1):
+        d = (Rw * np.float32(k)) / np.float32(steps)
+        t = d * np.float32(0.70710678)
+        pts += [(d, 0), (0, d), (-d, 0), (0, -d), (t, t), (-t, t), (-t, -t), (t, -t)]
+    pts += [(0.0, 0.0), (0.0, 0.0)]
+    N = len(pts)
+    g = make_sim(1, N)
+    xy = np.array(pts, dtype=np.float32)
+    g.x.copy_(dev(xy[None, :, 0])); g.y.copy_(dev(xy[None, :, 1])); g.theta.zero_()
+    x, y, th = state(g)
+    assert np.array_equal(x[0], xy[:, 0]) and np.array_equal(y[0], xy[:, 1]) and not th.any()
+    # the scene really contains the cases (row 0 of the restatement's intermediates: what kilobot 0 sees)
+    v = ref.restate_env(x[0], y[0], th[0], R, rings, sectors)
+    inr, d2 = v['inr'][0], v['d2'][0]
+    assert all((inr & (d2 == e2)).any() for e2 in v['E2']) and len(v['E2']) == rings - 1      # on every ring edge
+    assert (inr & (d2 == v['R2'])).any()                                                       # exactly at distance R
+    assert all((inr & (cr[0] == 0) & ((v['a'][0] != 0) | (v['l'][0] != 0))).any() for cr in v['cross'])   # on every sector boundary
+    assert len(v['cross']) == sectors // 2 - 1
+    assert (inr & (v['l'][0] == 0) & (v['a'][0] < 0)).any()                                    # dead astern
+    assert (inr & (v['l'][0] == 0) & (v['a'][0] > 0)).any()                                    # dead ahead
+    assert (inr & (d2 == 0)).sum() == 2                                                        # coincident
+    assert v['sector'][0][inr & (d2 == 0)].tolist() == [0, 0] and v['ring'][0][inr & (d2 == 0)].tolist() == [0, 0]
+    assert inr.sum() == N - 1
+    hist, cnt = check(g, R, rings, sectors, 'boundaries')
+    assert cnt[0, 0] == N - 1
+
+
+@pytest.mark.parametrize('R', [0.04, 0.15])
+def test_histograms_at_walls_and_corners(R):
+    xy, th = wall_scene()
+    g = make_sim(4, xy.shape[1], xy, th)
+    x, y = state(g)[:2]
+    assert (np.abs(x) > 25.0).any() and (np.abs(y) > 18.75).any()      # some kilobots are outside
+    hist, cnt = check(g, R, 4, 8, 'walls')
+    assert cnt.max() > 0
+
+
+def test_stepped_poses_with_unaligned_headings():
+    E, N, R = 4, 64, 0.07
+    g = make_sim(E, N, *scenes.gaussian_spawn(E, N, sigma=0.12, seed=5, random_theta=False))
+    g.step(20, actions=dev(scenes.random_actions(E, N, seed=81)))
+    th = state(g)[2]
+    assert (th != 0).all() and th.std() > 0.5
+    hist, cnt = check(g, R, 4, 8, 'stepped')
+    assert cnt.max() > 0
+
+
+class Spy(object):
+    """Records the calls that go through a ctypes library."""
+
+    def __init__(self, lib):
+        self.lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+
+        def call(*args):
+            self.calls.append((name, args))
+            return fn(*args)
+        return call
+
+
+def test_outputs_streams_and_untouched_state():
+    E, N, R, rings, sectors = 3, 333, 0.08, 4, 8
+    g = make_sim(E, N, *scenes.gaussian_spawn(E, N, sigma=0.15, seed=5))
+    fields = ('x', 'y', 'theta', 'status')
+    before = {f: getattr(g, f).clone() for f in fields}
+    want, wcnt = ref.restate(*state(g), R, rings, sectors)
+    assert want.any()
+    # a buffer full of NaN comes back fully written, the zeros included
+    out = torch.full((E, N, rings, sectors), float('nan'), device='cuda')
+    got = g.neighbor_histogram(R, rings, sectors, out=out)
+    assert got.data_ptr() == out.data_ptr()
+    assert np.array_equal(cpu(out), want) and (want == 0).any()
+    # reused: the same answer twice
+    got = g.neighbor_histogram(R, rings, sectors, out=out)
+    assert got.data_ptr() == out.data_ptr() and np.array_equal(cpu(out), want)
+    # (hist, count) into preallocated tensors
+    cnt = torch.full((E, N), 77, dtype=torch.int32, device='cuda')
+    h2, c2 = g.neighbor_histogram(R, rings, sectors, out=(out, cnt), count=True)
+    assert h2.data_ptr() == out.data_ptr() and c2.data_ptr() == cnt.data_ptr()
+    assert np.array_equal(cpu(c2).view(np.uint32), wcnt) and np.array_equal(cpu(h2), want)
+    # count=False hands the library NULL for d_count
+    spy = Spy(g._lib)
+    g._lib = spy
+    try:
+        only = g.neighbor_histogram(R, rings, sectors)
+        g.neighbor_histogram(R, rings, sectors, count=True)
+    finally:
+        g._lib = spy.lib
+    calls = [a for n, a in spy.calls if n == 'kb_sense_histogram']
+    assert len(calls) == 2 and calls[0][5] is None and calls[1][5] is not None
+    assert torch.is_tensor(only) and np.array_equal(cpu(only), want)
+    # a side stream gives the default stream's answer
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        hs, cs = g.neighbor_histogram(R, rings, sectors, count=True)
+    side.synchronize()
+    assert np.array_equal(cpu(hs), want) and np.array_equal(cpu(cs).view(np.uint32), wcnt)
+    # the call reads the state and writes its outputs only
+    torch.cuda.synchronize()
+    for f in fields:
+        assert torch.equal(before[f].view(torch.uint8), getattr(g, f).view(torch.uint8)), f
+    # out is checked like neighbors() checks its own; the limits are checked before the call
+    for bad in (out.view(E, N, rings * sectors), out.double(), out.cpu(), out[..., :4], out.transpose(2, 3), (out, cnt)):
+        with pytest.raises(ValueError):
+            g.neighbor_histogram(R, rings, sectors, out=bad)
+    for bad in (out, (out,), (out, cnt.float()), (out, cnt[:, :5])):
+        with pytest.raises(ValueError):
+            g.neighbor_histogram(R, rings, sectors, out=bad, count=True)
+    for grid in ((0, 8), (9, 4), (4, 3), (4, 18), (8, 16)):
+        with pytest.raises(ValueError):
+            g.neighbor_histogram(R, *grid)
+    with pytest.raises(ValueError):
+        g.neighbor_histogram(0.0, rings, sectors)
+
+
+def test_batched_env_histogram_obs():
+    from gym_kilobots_amd.envs import BatchedKilobotsEnv
+    E, N, obs_arg = 4, 64, (0.07, 4, 8)
+    env = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12, histogram_obs=obs_arg)
+    plain = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12)
+    assert torch.equal(env.reset(), plain.reset())
+    for s in range(2):
+        a = dev(scenes.random_actions(E, N, seed=20 + s))
+        obs, rew, done, info = env.step(a)
+        obs_p, _, _, info_p = plain.step(a)
+        assert info_p == {} and set(info) == {'neighbor_histogram'}
+        assert torch.equal(obs, obs_p)
+        assert torch.equal(info['neighbor_histogram'], env.neighbor_histogram())
+    want, wcnt = ref.restate(*state(env.sim), *obs_arg)
+    assert np.array_equal(cpu(info['neighbor_histogram']), want) and wcnt.max() > 0
+    with pytest.raises(ValueError):
+        plain.neighbor_histogram()
+    # independent of neighbor_obs: both keys
+    both = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12, histogram_obs=obs_arg, neighbor_obs=(0.07, 8))
+    both.reset()
+    info_b = both.step(dev(scenes.random_actions(E, N, seed=20)))[3]
+    assert set(info_b) == {'neighbors', 'neighbor_histogram'}
+    assert tuple(info_b['neighbor_histogram'].shape) == (E, N, 4, 8) and len(info_b['neighbors']) == 3
+    # a shard over envs 2..3 reproduces its rows of the unsharded histogram after reset()
+    whole = BatchedKilobotsEnv(E, N, seed=5, spawn_std=0.12, histogram_obs=obs_arg)
+    shard = BatchedKilobotsEnv(2, N, seed=5, spawn_std=0.12, histogram_obs=obs_arg, env_offset=2)
+    whole.reset(); shard.reset()
+    hw, hs = whole.neighbor_histogram(), shard.neighbor_histogram()
+    assert torch.equal(hw[2:4].contiguous().view(torch.uint8), hs.view(torch.uint8)) and bool(hs.any())
