@@ -1,4 +1,7 @@
-// kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h) and two small elementwise kernels.
+// kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h): argument validation and launches of every entry
+// point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
+// kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
+// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram) are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -27,6 +30,7 @@
 
 #include "kb_common.h"
 #include "kb_objects.h"
+#include "kb_sense.h"
 
 using namespace kb;
 
@@ -80,239 +84,6 @@ __global__ void kb_get_state_kernel(const Params p, float *out) {
         row[3 * k + 2] = p.buf.otheta[j];
     } else {
         row[3 * k] = __int_as_float(p.buf.status[e]);
-    }
-}
-
-
-// IR-range neighbour sensing on the current poses (kb_sense): one workgroup per env builds the cell lists of the
-// broadphase grid in LDS and runs the sensing pass of the step kernel on them
-__global__ void __launch_bounds__(256) kb_sense_kernel(const Params p, const int s, const float R2, unsigned *out) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
-    float2 *pos = reinterpret_cast<float2 *>(smem);
-    unsigned *cnt16 = reinterpret_cast<unsigned *>(smem + 8 * p.NP);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + 10 * p.NP);
-    unsigned short *cellOf = nextb + p.NP;
-    unsigned short *head = cellOf + p.NP;
-    const size_t o = (size_t)e * N;
-    for (int b = tid; b < p.NP / 2; b += nt) cnt16[b] = 0;
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
-    kb_sense_pass(pos, head, nextb, cellOf, cnt16, N, nt, tid, p.gw, p.gh, s, R2, 0);
-    __syncthreads();
-    for (int b = tid; b < N; b += nt) out[o + b] = (unsigned)reinterpret_cast<unsigned short *>(cnt16)[b];
-}
-
-// Nearest-neighbour lists with body-frame offsets on the current poses (kb_sense_neighbors): one workgroup per env, poses,
-// headings and the cell lists of the broadphase grid in LDS, one kilobot per lane.  Every kilobot walks the FULL stencil of
-// reach s (it needs its own ordered list, so the half-stencil trick of kb_sense_pass does not apply) and keeps the K best
-// keys (bits of d2) << 32 | j in registers: d2 >= 0, so the unsigned order of the key is the order by (d2, j).  A
-// candidate in range that beats the worst kept key runs down an unrolled compare-exchange chain (best[] stays sorted; every
-// index is a compile-time constant, so best[] never leaves the registers).  K: the requested k rounded up to 4, 8 or 16.
-// Rows are written per lane: slot i of kilobot a is one 16-byte store, its k slots are contiguous.
-template <int K>
-__global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const int s, const float R2, const int k, const int vec,
-                                                           int *d_index, float4 *d_rel, unsigned *d_count) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int W = 8;      // list heads fetched together (one LDS round trip); most cells are empty
-    constexpr unsigned long long NONE = ~0ull;
-    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
-    float2 *pos = reinterpret_cast<float2 *>(smem);
-    float *th = reinterpret_cast<float *>(smem + 8 * p.NP);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + 12 * p.NP);
-    unsigned short *cellOf = nextb + p.NP;
-    unsigned short *head = cellOf + p.NP;
-    const size_t o = (size_t)e * N;
-    for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
-    for (int a = tid; a < N; a += nt) {
-        const int cell = cellOf[a];
-        const int cx = cell % p.gw, cy = cell / p.gw;
-        const float2 pa = pos[a];
-        unsigned long long best[K];
-#pragma unroll
-        for (int i = 0; i < K; ++i) best[i] = NONE;
-        unsigned cnt = 0;
-        const int y1 = min(cy + s, p.gh - 1), x0 = max(cx - s, 0), x1 = min(cx + s, p.gw - 1);
-        for (int oy = max(cy - s, 0); oy <= y1; ++oy) {
-            for (int xb = x0; xb <= x1; xb += W) {
-                unsigned cur[W];
-#pragma unroll
-                for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
-#pragma unroll
-                for (int i = 0; i < W; ++i) {
-                    for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
-                        const float2 pb = pos[b];
-                        const unsigned nb = nextb[b];
-                        const float ex = pb.x - pa.x, ey = pb.y - pa.y;
-                        const float dd = ex * ex + ey * ey;
-                        if ((int)b != a && !(dd > R2)) {
-                            cnt++;
-                            unsigned long long key = ((unsigned long long)__float_as_uint(dd) << 32) | b;
-                            if (key < best[K - 1]) {
-#pragma unroll
-                                for (int q = 0; q < K; ++q) {
-                                    const unsigned long long lo = key < best[q] ? key : best[q];
-                                    key = key < best[q] ? best[q] : key;
-                                    best[q] = lo;
-                                }
-                            }
-                        }
-                        b = nb;
-                    }
-                }
-            }
-        }
-        const float tha = th[a];
-        float sn, cs;
-        kb_sincosf(tha, sn, cs);
-        const size_t row = (o + a) * (size_t)k;
-#pragma unroll
-        for (int i = 0; i < K; ++i) {
-            if (i >= k) break;
-            const bool used = best[i] != NONE;
-            const unsigned j = used ? (unsigned)best[i] : (unsigned)a;
-            const float2 pb = pos[j];
-            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
-            const float d2 = __uint_as_float((unsigned)(best[i] >> 32));
-            float4 r;
-            r.x = (cs * ex + sn * ey) / WORLD_SCALE;
-            r.y = (cs * ey - sn * ex) / WORLD_SCALE;
-            r.z = sqrtf(d2) / WORLD_SCALE;
-            r.w = th[j] - tha;
-            if (!used) r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            d_rel[row + i] = r;
-        }
-        if (vec) {      // k is a multiple of 4 and d_index is 16-byte aligned: four indices per store
-#pragma unroll
-            for (int i = 0; i < K; i += 4) {
-                if (i >= k) break;
-                int4 v;
-                v.x = (int)(unsigned)best[i]; v.y = (int)(unsigned)best[i + 1]; v.z = (int)(unsigned)best[i + 2]; v.w = (int)(unsigned)best[i + 3];
-                reinterpret_cast<int4 *>(d_index + row)[i >> 2] = v;      // (the low word of NONE is -1)
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                if (i >= k) break;
-                d_index[row + i] = (int)(unsigned)best[i];
-            }
-        }
-        if (d_count) d_count[o + a] = cnt;
-    }
-}
-
-// Local neighbour histograms on the current poses (kb_sense_histogram): every kilobot counts ALL kilobots of its env in IR
-// range, binned by ring (distance) and sector (bearing in its own frame).  One workgroup per env, poses and the cell lists
-// of the broadphase grid in LDS, one kilobot per lane over the full stencil.  The walk is the walk of kb_neighbors_kernel,
-// kept local to this kernel: that kernel's register figures stay what they are.  A kilobot's heading is
-// used once, by its own lane, so it is read straight from global memory into a register.
-// Accumulator: the env is processed in tiles of 256 kilobots; lane t owns column t of u16 hist[bin][HIST_STRIDE] in LDS
-// (a count is at most N - 1 <= 1023) and is the only one to update it: no atomics, no per-lane array, no scratch.  After
-// the tile's walk and a barrier the workgroup writes the tile's n * B floats with the flat index f = tid + 256 i
-// (kilobot f / B, bin f % B, both kept incrementally): consecutive lanes store consecutive floats.  HIST_STRIDE = 258
-// halfwords = 129 words: in that read-out the lanes of a wave read bins of one or two kilobots, and the odd word stride
-// puts them on different banks (a stride of 256 would put all 64 on one).  The edge and boundary tables arrive as a kernel
-// argument and go through LDS into per-lane registers, and the ring and sector counts run over the whole tables without
-// branches (unused edges are +inf, unused boundaries (0, 0): they count nothing): with the tables in SGPRs next to Params,
-// or with a uniform early exit per table entry, the kernel spilled SGPRs.
-struct HistArgs {
-    int n_rings, n_sectors;
-    float e2[KB_HIST_MAX_RINGS - 1];            // E2_r of ring edge r + 1
-    float ux[KB_HIST_MAX_SECTORS / 2 - 1];      // u_m of sector boundary m + 1 (kb_histogram_sectors)
-    float uy[KB_HIST_MAX_SECTORS / 2 - 1];
-};
-constexpr int HIST_TILE = 256;
-constexpr int HIST_STRIDE = HIST_TILE + 2;
-constexpr int HIST_TABLE_BYTES = 4 * (KB_HIST_MAX_RINGS + KB_HIST_MAX_SECTORS - 3);
-// the largest image (1024 kilobots, every cell, 64 bins) stays under the default limit for dynamic LDS: no attribute to raise
-static_assert(12 * KB_MAX_BOTS + 2 * MAX_CELLS + 2 * KB_HIST_MAX_BINS * HIST_STRIDE + HIST_TABLE_BYTES <= 64 * 1024, "kb_histogram_kernel: LDS image");
-
-__global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const int s, const float R2, const HistArgs h,
-                                                           float *d_hist, unsigned *d_count) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int W = 8;      // list heads fetched together, as kb_neighbors_kernel
-    constexpr int NE = KB_HIST_MAX_RINGS - 1, NU = KB_HIST_MAX_SECTORS / 2 - 1;
-    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
-    const int B = h.n_rings * h.n_sectors, H = h.n_sectors >> 1;
-    float2 *pos = reinterpret_cast<float2 *>(smem);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + 8 * p.NP);
-    unsigned short *cellOf = nextb + p.NP;
-    unsigned short *head = cellOf + p.NP;
-    unsigned short *hist = head + ((p.ncell + 1) & ~1);      // (kb_exch16 works on whole words of head)
-    float *tab = reinterpret_cast<float *>(hist + B * HIST_STRIDE);
-    const size_t o = (size_t)e * N;
-    if (tid == 0) {
-#pragma unroll
-        for (int r = 0; r < NE; ++r) tab[r] = h.e2[r];
-#pragma unroll
-        for (int m = 0; m < NU; ++m) { tab[NE + m] = h.ux[m]; tab[NE + NU + m] = h.uy[m]; }
-    }
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
-    float e2[NE], ux[NU], uy[NU];
-#pragma unroll
-    for (int r = 0; r < NE; ++r) e2[r] = tab[r];
-#pragma unroll
-    for (int m = 0; m < NU; ++m) { ux[m] = tab[NE + m]; uy[m] = tab[NE + NU + m]; }
-    const int q256 = HIST_TILE / B, r256 = HIST_TILE % B;
-    for (int t0 = 0; t0 < N; t0 += HIST_TILE) {
-        const int a = t0 + tid;
-        unsigned short *col = hist + tid;
-        for (int b = 0; b < B; ++b) col[b * HIST_STRIDE] = 0;
-        if (a < N) {
-            const int cell = cellOf[a];
-            const int cx = cell % p.gw, cy = cell / p.gw;
-            const float2 pa = pos[a];
-            float sn, cs;
-            kb_sincosf(p.buf.theta[o + a], sn, cs);
-            unsigned cnt = 0;
-            const int y1 = min(cy + s, p.gh - 1), x0 = max(cx - s, 0), x1 = min(cx + s, p.gw - 1);
-            for (int oy = max(cy - s, 0); oy <= y1; ++oy) {
-                for (int xb = x0; xb <= x1; xb += W) {
-                    unsigned cur[W];
-#pragma unroll
-                    for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
-#pragma unroll
-                    for (int i = 0; i < W; ++i) {
-                        for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
-                            const float2 pb = pos[b];
-                            const unsigned nb = nextb[b];
-                            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
-                            const float dd = ex * ex + ey * ey;
-                            if ((int)b != a && !(dd > R2)) {
-                                cnt++;
-                                int ring = 0;
-#pragma unroll
-                                for (int r = 0; r < NE; ++r) ring += dd > e2[r] ? 1 : 0;
-                                int sector = 0;
-                                if (H > 0) {
-                                    float ah = cs * ex + sn * ey;
-                                    float lf = cs * ey - sn * ex;
-                                    const bool low = lf < 0.0f;
-                                    if (low) { ah = -ah; lf = -lf; }
-#pragma unroll
-                                    for (int m = 0; m < NU; ++m) sector += ux[m] * lf - uy[m] * ah > 0.0f ? 1 : 0;
-                                    if (low) sector += H;
-                                }
-                                unsigned short *c = col + (ring * h.n_sectors + sector) * HIST_STRIDE;
-                                *c = (unsigned short)(*c + 1u);
-                            }
-                            b = nb;
-                        }
-                    }
-                }
-            }
-            if (d_count) d_count[o + a] = cnt;
-        }
-        __syncthreads();
-        const int total = min(HIST_TILE, N - t0) * B;
-        float *out = d_hist + (o + t0) * (size_t)B;
-        int kb = tid / B, bin = tid % B;
-        for (int f = tid; f < total; f += HIST_TILE) {
-            out[f] = (float)hist[bin * HIST_STRIDE + kb];
-            kb += q256; bin += r256;
-            if (bin >= B) { bin -= B; kb++; }
-        }
-        __syncthreads();
     }
 }
 
@@ -434,6 +205,27 @@ int fail(int code, const char *fmt, const char *detail = "") {
     return code;
 }
 
+// the status of the launch that `entry` has just made
+int launched(const char *entry) {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return KB_OK;
+    snprintf(g_err, sizeof(g_err), "%s: %s", entry, hipGetErrorString(err));
+    return KB_EHIP;
+}
+
+// a sensing radius in metres as the kernels take it: in world units, squared, and as the reach of the stencil in cells
+struct SenseRange { float Rw, R2; int reach; };
+SenseRange sense_range(const Params &p, float radius_m) {
+    const float Rw = radius_m * WORLD_SCALE;
+    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
+    return {Rw, Rw * Rw, Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh};
+}
+
+// n_sectors of the histogram entries, reported under the caller's name
+int check_sectors(const char *entry, int n_sectors) {
+    if (n_sectors == 1 || (n_sectors >= 2 && n_sectors <= KB_HIST_MAX_SECTORS && !(n_sectors & 1))) return KB_OK;
+    return fail(KB_EINVAL, "%s: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)", entry);
+}
 
 }  // namespace
 
@@ -742,9 +534,7 @@ int kb_set_actions(kb_sim *sim, const float *d_actions, void *stream) {
     p.actions = d_actions;
     const size_t T = (size_t)p.E * p.N;
     hipLaunchKernelGGL(kb_set_actions_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_set_actions: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_set_actions");
 }
 
 int kb_resident_envs_per_cu(kb_sim *sim) {
@@ -785,9 +575,7 @@ int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, in
     }
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3((unsigned)sim->threads), (size_t)p.lds_total,
                        (hipStream_t)stream, p);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_step: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_step");
 }
 
 int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream) {
@@ -795,12 +583,9 @@ int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream) {
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense: kb_bind() first");
     if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense: radius must be positive");
     const Params &p = sim->p;
-    const float Rw = radius_m * WORLD_SCALE;
-    const size_t lds = (size_t)14 * p.NP + 2 * (size_t)p.ncell + 16;
-    hipLaunchKernelGGL(kb_sense_kernel, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, sense_reach(Rw, p.inv_cell), Rw * Rw, d_count);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_sense: %s", hipGetErrorString(err));
-    return KB_OK;
+    const SenseRange r = sense_range(p, radius_m);
+    hipLaunchKernelGGL(kb_sense_kernel, dim3((unsigned)p.E), dim3(256), (size_t)SenseLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, d_count);
+    return launched("kb_sense");
 }
 
 int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count, void *stream) {
@@ -810,22 +595,16 @@ int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, flo
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_neighbors: kb_bind() first");
     if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_neighbors: d_rel must be 16-byte aligned");
     const Params &p = sim->p;
-    const float Rw = radius_m * WORLD_SCALE;
-    const size_t lds = (size_t)16 * p.NP + 2 * (size_t)p.ncell + 16;
+    const SenseRange r = sense_range(p, radius_m);
     const int vec = k % 4 == 0 && (reinterpret_cast<uintptr_t>(d_index) & 15u) == 0;
     const auto fn = k <= 4 ? kb_neighbors_kernel<4> : k <= 8 ? kb_neighbors_kernel<8> : kb_neighbors_kernel<16>;
-    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
-    const int reach = Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh;
-    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, reach, Rw * Rw, k, vec,
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)NeighborsLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, k, vec,
                        d_index, reinterpret_cast<float4 *>(d_rel), d_count);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_neighbors: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_sense_neighbors");
 }
 
 int kb_histogram_sectors(int n_sectors, float *xy) {
-    if (n_sectors != 1 && (n_sectors < 2 || n_sectors > KB_HIST_MAX_SECTORS || (n_sectors & 1)))
-        return fail(KB_EINVAL, "kb_histogram_sectors: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)");
+    if (check_sectors("kb_histogram_sectors", n_sectors) != KB_OK) return KB_EINVAL;
     const int H = n_sectors / 2;
     if (H > 1 && !xy) return fail(KB_EINVAL, "kb_histogram_sectors: NULL table");
     for (int m = 1; m < H; ++m) {
@@ -839,31 +618,26 @@ int kb_histogram_sectors(int n_sectors, float *xy) {
 int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, float *d_hist, uint32_t *d_count, void *stream) {
     if (!sim || !d_hist) return fail(KB_EINVAL, "kb_sense_histogram: NULL argument");
     if (n_rings < 1 || n_rings > KB_HIST_MAX_RINGS) return fail(KB_EINVAL, "kb_sense_histogram: 1 <= n_rings <= KB_HIST_MAX_RINGS (8) required");
-    if (n_sectors != 1 && (n_sectors < 2 || n_sectors > KB_HIST_MAX_SECTORS || (n_sectors & 1)))
-        return fail(KB_EINVAL, "kb_sense_histogram: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)");
+    if (check_sectors("kb_sense_histogram", n_sectors) != KB_OK) return KB_EINVAL;
     if (n_rings * n_sectors > KB_HIST_MAX_BINS) return fail(KB_EINVAL, "kb_sense_histogram: n_rings * n_sectors <= KB_HIST_MAX_BINS (64) required");
     if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_histogram: radius must be positive");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_histogram: kb_bind() first");
     const Params &p = sim->p;
-    const float Rw = radius_m * WORLD_SCALE;
+    const SenseRange rg = sense_range(p, radius_m);
     HistArgs h;
     memset(&h, 0, sizeof(h));
     h.n_rings = n_rings; h.n_sectors = n_sectors;
     // the kernel's comparisons are branch-free over the whole tables: an edge at infinity and a zero boundary vector count nothing
     for (int r = 1; r < KB_HIST_MAX_RINGS; ++r) {
-        const float edge = (Rw * (float)r) / (float)n_rings;
+        const float edge = (rg.Rw * (float)r) / (float)n_rings;
         h.e2[r - 1] = r < n_rings ? edge * edge : INFINITY;
     }
     float u[KB_HIST_MAX_SECTORS / 2 - 1][2];
     if (kb_histogram_sectors(n_sectors, &u[0][0]) != KB_OK) return KB_EINVAL;
     for (int m = 1; m < n_sectors / 2; ++m) { h.ux[m - 1] = u[m - 1][0]; h.uy[m - 1] = u[m - 1][1]; }
-    const size_t lds = (size_t)12 * p.NP + 2 * (size_t)((p.ncell + 1) & ~1) + 2 * (size_t)(n_rings * n_sectors) * HIST_STRIDE + HIST_TABLE_BYTES;
-    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
-    const int reach = Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh;
-    hipLaunchKernelGGL(kb_histogram_kernel, dim3((unsigned)p.E), dim3(256), lds, (hipStream_t)stream, p, reach, Rw * Rw, h, d_hist, d_count);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_histogram: %s", hipGetErrorString(err));
-    return KB_OK;
+    hipLaunchKernelGGL(kb_histogram_kernel, dim3((unsigned)p.E), dim3(256), (size_t)HistLds(p.NP, p.ncell, n_rings * n_sectors).bytes, (hipStream_t)stream,
+                       p, rg.reach, rg.R2, h, d_hist, d_count);
+    return launched("kb_sense_histogram");
 }
 
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {
@@ -873,9 +647,7 @@ int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {
     const Params &p = sim->p;
     if (!p.buf.light_value || !p.buf.light_gx || !p.buf.light_gy) return fail(KB_EINVAL, "kb_light_sense: kb_buffers.light_value / light_gx / light_gy are not bound");
     hipLaunchKernelGGL(kb_light_sense_kernel, dim3((unsigned)p.E), dim3(256), 0, (hipStream_t)stream, p, d_light_action);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_light_sense: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_light_sense");
 }
 
 int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream) {
@@ -892,8 +664,8 @@ int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream) {
     a.lo_y = -0.5f * sim->cfg.world_height + 0.02f; a.hi_y = 0.5f * sim->cfg.world_height - 0.02f;
     const size_t T = (size_t)p.E * p.N;
     hipLaunchKernelGGL(kb_reset_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, a);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_reset: %s", hipGetErrorString(err));
+    const int rc = launched("kb_reset");
+    if (rc != KB_OK) return rc;
     if (rp->resolve) return kb_step(sim, nullptr, nullptr, 1, KB_STEP_NO_DRIVE, stream);
     return KB_OK;
 }
@@ -904,9 +676,7 @@ int kb_get_poses(kb_sim *sim, float *d_out, void *stream) {
     const size_t T = (size_t)sim->p.E * sim->p.N;
     hipLaunchKernelGGL(kb_get_poses_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        sim->p.buf.x, sim->p.buf.y, sim->p.buf.theta, d_out, T);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_get_poses: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_get_poses");
 }
 
 int kb_get_state(kb_sim *sim, float *d_out, void *stream) {
@@ -914,9 +684,7 @@ int kb_get_state(kb_sim *sim, float *d_out, void *stream) {
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_get_state: kb_bind() first");
     const size_t T = (size_t)sim->p.E * (size_t)(sim->p.N + sim->p.M + 1);
     hipLaunchKernelGGL(kb_get_state_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sim->p, d_out);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(KB_EHIP, "kb_get_state: %s", hipGetErrorString(err));
-    return KB_OK;
+    return launched("kb_get_state");
 }
 
 int kb_lds_bytes(const kb_sim *sim) { return sim ? sim->p.lds_total : KB_EINVAL; }

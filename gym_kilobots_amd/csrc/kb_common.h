@@ -435,28 +435,6 @@ __device__ __forceinline__ unsigned kb_exch16(unsigned short *base, int idx, uns
     return (old >> sh) & 0xFFFFu;
 }
 
-// The cell lists of the broadphase grid off the poses of one env in global memory, for the kernels that sense on the
-// current poses without stepping (kb_sense, kb_sense_neighbors): pos[b] and cellOf[b] of every kilobot (cell indices
-// clamp to the grid), head[cell] -> nextb chains (plain heads: no hash).  o: index of the env's first kilobot.  The
-// order inside a chain is the order of the exchanges; nothing that reads the lists may depend on it.  Ends on a barrier.
-__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, float2 *pos, unsigned short *head,
-                                                    unsigned short *nextb, unsigned short *cellOf, int tid, int nt) {
-    for (int c = tid; c < p.ncell; c += nt) head[c] = EMPTY16;
-    __syncthreads();
-    for (int b = tid; b < p.N; b += nt) {
-        const float bx = p.buf.x[o + b], by = p.buf.y[o + b];
-        pos[b].x = bx; pos[b].y = by;
-        int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
-        int cy = (int)floorf((by - p.ymin) * p.inv_cell);
-        cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
-        cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-        const int cell = cy * p.gw + cx;
-        cellOf[b] = (unsigned short)cell;
-        nextb[b] = (unsigned short)kb_exch16(head, cell, (unsigned)b);
-    }
-    __syncthreads();
-}
-
 // IR-range neighbour sensing off the cell lists of the broadphase: kilobot a walks the half stencil of reach s
 // (own cell: partners with a higher id; the cells to the east in its row; every cell of the s rows above), so that every
 // pair is met exactly once, and both ends of a pair within range are counted.  cnt16: u16 counters packed in pairs

@@ -1,0 +1,281 @@
+// kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
+// kb_sense_histogram): one workgroup per env, poses and the cell lists of the broadphase grid in LDS.  Each kernel's LDS
+// image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry point (kb_abi.hip)
+// the dynamic-LDS size.  Included by kb_abi.hip only.
+#pragma once
+
+#include "kb_common.h"
+
+namespace kb {
+
+// The cell lists of the broadphase grid off the poses of one env in global memory: pos[b] and cellOf[b] of every kilobot
+// (cell indices clamp to the grid), head[cell] -> nextb chains (plain heads: no hash).  o: index of the env's first kilobot.
+// The order inside a chain is the order of the exchanges; nothing that reads the lists may depend on it.  Ends on a barrier.
+__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, float2 *pos, unsigned short *head,
+                                                    unsigned short *nextb, unsigned short *cellOf, int tid, int nt) {
+    for (int c = tid; c < p.ncell; c += nt) head[c] = EMPTY16;
+    __syncthreads();
+    for (int b = tid; b < p.N; b += nt) {
+        const float bx = p.buf.x[o + b], by = p.buf.y[o + b];
+        pos[b].x = bx; pos[b].y = by;
+        int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
+        int cy = (int)floorf((by - p.ymin) * p.inv_cell);
+        cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
+        cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
+        const int cell = cy * p.gw + cx;
+        cellOf[b] = (unsigned short)cell;
+        nextb[b] = (unsigned short)kb_exch16(head, cell, (unsigned)b);
+    }
+    __syncthreads();
+}
+
+// The full-stencil walk of kilobot a (in `cell`, at pa): every cell within reach s of its own, eight list heads per LDS
+// round trip (most cells are empty), down each chain.  Calls hit(b, ex, ey, dd) for every kilobot b != a with !(dd > R2),
+// (ex, ey) = pos[b] - pa, dd = ex^2 + ey^2, and returns how many there were.  (The half stencil of kb_sense_pass meets every
+// pair once and counts with atomics: a different traversal.)  hit is taken by value: taken by reference, the 16-slot list
+// kernel needed 156 VGPRs instead of 130 and ran 4 % slower.
+template <typename Hit>
+__device__ __forceinline__ unsigned kb_walk_in_range(const Params &p, const float2 *pos, const unsigned short *head,
+                                                     const unsigned short *nextb, const int a, const int cell, const float2 pa,
+                                                     const int s, const float R2, Hit hit) {
+    constexpr int W = 8;
+    const int cx = cell % p.gw, cy = cell / p.gw;
+    unsigned cnt = 0;
+    const int y1 = min(cy + s, p.gh - 1), x0 = max(cx - s, 0), x1 = min(cx + s, p.gw - 1);
+    for (int oy = max(cy - s, 0); oy <= y1; ++oy) {
+        for (int xb = x0; xb <= x1; xb += W) {
+            unsigned cur[W];
+#pragma unroll
+            for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
+                    const float2 pb = pos[b];
+                    const unsigned nb = nextb[b];
+                    const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+                    const float dd = ex * ex + ey * ey;
+                    if ((int)b != a && !(dd > R2)) {
+                        cnt++;
+                        hit(b, ex, ey, dd);
+                    }
+                    b = nb;
+                }
+            }
+        }
+    }
+    return cnt;
+}
+
+// ---- kb_sense: counts --------------------------------------------------------------------------------------------------
+struct SenseLds {       // byte offsets: pos (float2) at 0, the packed u16 counters, nextb, cellOf, head (u16 each)
+    int cnt16, nextb, cellOf, head, bytes;
+    __host__ __device__ constexpr SenseLds(int NP, int ncell)
+        : cnt16(8 * NP), nextb(10 * NP), cellOf(12 * NP), head(14 * NP), bytes(14 * NP + 2 * ncell + 16) {}
+};
+
+// IR-range neighbour sensing on the current poses (kb_sense): the sensing pass of the step kernel on the cell lists
+__global__ void __launch_bounds__(256) kb_sense_kernel(const Params p, const int s, const float R2, unsigned *out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const SenseLds L(p.NP, p.ncell);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned *cnt16 = reinterpret_cast<unsigned *>(smem + L.cnt16);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const size_t o = (size_t)e * N;
+    for (int b = tid; b < p.NP / 2; b += nt) cnt16[b] = 0;
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_sense_pass(pos, head, nextb, cellOf, cnt16, N, nt, tid, p.gw, p.gh, s, R2, 0);
+    __syncthreads();
+    for (int b = tid; b < N; b += nt) out[o + b] = (unsigned)reinterpret_cast<unsigned short *>(cnt16)[b];
+}
+
+// ---- kb_sense_neighbors: the k nearest ---------------------------------------------------------------------------------
+struct NeighborsLds {   // byte offsets: pos (float2) at 0, th (float), nextb, cellOf, head (u16 each)
+    int th, nextb, cellOf, head, bytes;
+    __host__ __device__ constexpr NeighborsLds(int NP, int ncell)
+        : th(8 * NP), nextb(12 * NP), cellOf(14 * NP), head(16 * NP), bytes(16 * NP + 2 * ncell + 16) {}
+};
+
+// Nearest-neighbour lists with body-frame offsets on the current poses (kb_sense_neighbors): poses, headings and the cell
+// lists in LDS, one kilobot per lane.  Every kilobot walks the FULL stencil of reach s (it needs its own ordered list, so the
+// half-stencil trick of kb_sense_pass does not apply) and keeps the K best keys (bits of d2) << 32 | j in registers:
+// d2 >= 0, so the unsigned order of the key is the order by (d2, j).  A candidate in range that beats the worst kept key
+// runs down an unrolled compare-exchange chain (best[] stays sorted; every index is a compile-time constant, so best[]
+// never leaves the registers).  K: the requested k rounded up to 4, 8 or 16.
+// Rows are written per lane: slot i of kilobot a is one 16-byte store, its k slots are contiguous.
+template <int K>
+__global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const int s, const float R2, const int k, const int vec,
+                                                           int *d_index, float4 *d_rel, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr unsigned long long NONE = ~0ull;
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const NeighborsLds L(p.NP, p.ncell);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    float *th = reinterpret_cast<float *>(smem + L.th);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const size_t o = (size_t)e * N;
+    for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    for (int a = tid; a < N; a += nt) {
+        const int cell = cellOf[a];
+        const float2 pa = pos[a];
+        unsigned long long best[K];
+#pragma unroll
+        for (int i = 0; i < K; ++i) best[i] = NONE;
+        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float dd) {
+            unsigned long long key = ((unsigned long long)__float_as_uint(dd) << 32) | b;
+            if (key < best[K - 1]) {
+#pragma unroll
+                for (int q = 0; q < K; ++q) {
+                    const unsigned long long lo = key < best[q] ? key : best[q];
+                    key = key < best[q] ? best[q] : key;
+                    best[q] = lo;
+                }
+            }
+        });
+        const float tha = th[a];
+        float sn, cs;
+        kb_sincosf(tha, sn, cs);
+        const size_t row = (o + a) * (size_t)k;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (i >= k) break;
+            const bool used = best[i] != NONE;
+            const unsigned j = used ? (unsigned)best[i] : (unsigned)a;
+            const float2 pb = pos[j];
+            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+            const float d2 = __uint_as_float((unsigned)(best[i] >> 32));
+            float4 r;
+            r.x = (cs * ex + sn * ey) / WORLD_SCALE;
+            r.y = (cs * ey - sn * ex) / WORLD_SCALE;
+            r.z = sqrtf(d2) / WORLD_SCALE;
+            r.w = th[j] - tha;
+            if (!used) r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            d_rel[row + i] = r;
+        }
+        if (vec) {      // k is a multiple of 4 and d_index is 16-byte aligned: four indices per store
+#pragma unroll
+            for (int i = 0; i < K; i += 4) {
+                if (i >= k) break;
+                int4 v;
+                v.x = (int)(unsigned)best[i]; v.y = (int)(unsigned)best[i + 1]; v.z = (int)(unsigned)best[i + 2]; v.w = (int)(unsigned)best[i + 3];
+                reinterpret_cast<int4 *>(d_index + row)[i >> 2] = v;      // (the low word of NONE is -1)
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                if (i >= k) break;
+                d_index[row + i] = (int)(unsigned)best[i];
+            }
+        }
+        if (d_count) d_count[o + a] = cnt;
+    }
+}
+
+// ---- kb_sense_histogram: ring x sector counts --------------------------------------------------------------------------
+struct HistArgs {
+    int n_rings, n_sectors;
+    float e2[KB_HIST_MAX_RINGS - 1];            // E2_r of ring edge r + 1
+    float ux[KB_HIST_MAX_SECTORS / 2 - 1];      // u_m of sector boundary m + 1 (kb_histogram_sectors)
+    float uy[KB_HIST_MAX_SECTORS / 2 - 1];
+};
+constexpr int HIST_TILE = 256;
+constexpr int HIST_STRIDE = HIST_TILE + 2;
+constexpr int HIST_TABLE_BYTES = 4 * (KB_HIST_MAX_RINGS + KB_HIST_MAX_SECTORS - 3);
+
+struct HistLds {        // byte offsets: pos (float2) at 0, nextb, cellOf, head, hist[bins][HIST_STRIDE] (u16 each), tab (float)
+    int nextb, cellOf, head, hist, tab, bytes;
+    __host__ __device__ constexpr HistLds(int NP, int ncell, int bins)
+        : nextb(8 * NP), cellOf(10 * NP), head(12 * NP),
+          hist(head + 2 * ((ncell + 1) & ~1)),      // (kb_exch16 works on whole words of head)
+          tab(hist + 2 * bins * HIST_STRIDE), bytes(tab + HIST_TABLE_BYTES) {}
+};
+// the largest image (1024 kilobots, every cell, 64 bins) stays under the default limit for dynamic LDS: no attribute to raise
+static_assert(HistLds(KB_MAX_BOTS, MAX_CELLS, KB_HIST_MAX_BINS).bytes <= 64 * 1024, "kb_histogram_kernel: LDS image");
+
+// Local neighbour histograms on the current poses (kb_sense_histogram): every kilobot counts ALL kilobots of its env in IR
+// range, binned by ring (distance) and sector (bearing in its own frame).  Poses and the cell lists in LDS, one kilobot per
+// lane over the full stencil.  A kilobot's heading is used once, by its own lane, so it is read straight from global
+// memory into a register.
+// Accumulator: the env is processed in tiles of 256 kilobots; lane t owns column t of u16 hist[bin][HIST_STRIDE] in LDS
+// (a count is at most N - 1 <= 1023) and is the only one to update it: no atomics, no per-lane array, no scratch.  After
+// the tile's walk and a barrier the workgroup writes the tile's n * B floats with the flat index f = tid + 256 i
+// (kilobot f / B, bin f % B, both kept incrementally): consecutive lanes store consecutive floats.  HIST_STRIDE = 258
+// halfwords = 129 words: in that read-out the lanes of a wave read bins of one or two kilobots, and the odd word stride
+// puts them on different banks (a stride of 256 would put all 64 on one).  The edge and boundary tables arrive as a kernel
+// argument and go through LDS into per-lane registers, and the ring and sector counts run over the whole tables without
+// branches (unused edges are +inf, unused boundaries (0, 0): they count nothing): with the tables in SGPRs next to Params,
+// or with a uniform early exit per table entry, the kernel spilled SGPRs.
+__global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const int s, const float R2, const HistArgs h,
+                                                           float *d_hist, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int NE = KB_HIST_MAX_RINGS - 1, NU = KB_HIST_MAX_SECTORS / 2 - 1;
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const int B = h.n_rings * h.n_sectors, H = h.n_sectors >> 1;
+    const HistLds L(p.NP, p.ncell, B);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    unsigned short *hist = reinterpret_cast<unsigned short *>(smem + L.hist);
+    float *tab = reinterpret_cast<float *>(smem + L.tab);
+    const size_t o = (size_t)e * N;
+    if (tid == 0) {
+#pragma unroll
+        for (int r = 0; r < NE; ++r) tab[r] = h.e2[r];
+#pragma unroll
+        for (int m = 0; m < NU; ++m) { tab[NE + m] = h.ux[m]; tab[NE + NU + m] = h.uy[m]; }
+    }
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    float e2[NE], ux[NU], uy[NU];
+#pragma unroll
+    for (int r = 0; r < NE; ++r) e2[r] = tab[r];
+#pragma unroll
+    for (int m = 0; m < NU; ++m) { ux[m] = tab[NE + m]; uy[m] = tab[NE + NU + m]; }
+    const int q256 = HIST_TILE / B, r256 = HIST_TILE % B;
+    for (int t0 = 0; t0 < N; t0 += HIST_TILE) {
+        const int a = t0 + tid;
+        unsigned short *col = hist + tid;
+        for (int b = 0; b < B; ++b) col[b * HIST_STRIDE] = 0;
+        if (a < N) {
+            const int cell = cellOf[a];
+            const float2 pa = pos[a];
+            float sn, cs;
+            kb_sincosf(p.buf.theta[o + a], sn, cs);
+            const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned, float ex, float ey, float dd) {
+                int ring = 0;
+#pragma unroll
+                for (int r = 0; r < NE; ++r) ring += dd > e2[r] ? 1 : 0;
+                int sector = 0;
+                if (H > 0) {
+                    float ah = cs * ex + sn * ey;
+                    float lf = cs * ey - sn * ex;
+                    const bool low = lf < 0.0f;
+                    if (low) { ah = -ah; lf = -lf; }
+#pragma unroll
+                    for (int m = 0; m < NU; ++m) sector += ux[m] * lf - uy[m] * ah > 0.0f ? 1 : 0;
+                    sector += low ? H : 0;      // (a select: as `if (low)` it became a branch, + 1 % on the launch)
+                }
+                unsigned short *c = col + (ring * h.n_sectors + sector) * HIST_STRIDE;
+                *c = (unsigned short)(*c + 1u);
+            });
+            if (d_count) d_count[o + a] = cnt;
+        }
+        __syncthreads();
+        const int total = min(HIST_TILE, N - t0) * B;
+        float *out = d_hist + (o + t0) * (size_t)B;
+        int kb = tid / B, bin = tid % B;
+        for (int f = tid; f < total; f += HIST_TILE) {
+            out[f] = (float)hist[bin * HIST_STRIDE + kb];
+            kb += q256; bin += r256;
+            if (bin >= B) { bin -= B; kb++; }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace kb

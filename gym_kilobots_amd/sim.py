@@ -231,10 +231,7 @@ class KilobotSim:
     def sense(self, radius_m, out=None):
         """IR-range neighbour sensing on the current poses: [num_envs, num_bots] int32 counts of the kilobots within
         radius_m (centre to centre) of each kilobot (kb_sense; no reference counterpart)."""
-        if out is None:
-            out = torch.empty(self.num_envs, self.num_bots, dtype=torch.int32, device=self.device)
-        if not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (self.num_envs, self.num_bots)):
-            raise ValueError('out must be a contiguous int32 cuda tensor of shape (num_envs, num_bots)')
+        out, = self._outputs(out, [((self.num_envs, self.num_bots), torch.int32, 'count')], 'the count tensor')
         with torch.cuda.device(self.device):
             nat.check(self._lib.kb_sense(self._h, float(radius_m), C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense')
         return out
@@ -250,16 +247,7 @@ class KilobotSim:
         if not 1 <= k <= nat.MAX_NEIGHBORS:
             raise ValueError('k must be in 1..%d' % nat.MAX_NEIGHBORS)
         shapes = [((E, N, k), torch.int32, 'index'), ((E, N, k, 4), torch.float32, 'rel')] + ([((E, N), torch.int32, 'count')] if count else [])
-        if out is None:
-            out = tuple(torch.empty(*s, dtype=d, device=self.device) for s, d, _ in shapes)
-        out = tuple(out)
-        if len(out) != len(shapes):
-            raise ValueError('out must be a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes)))
-        for t, (s, d, n) in zip(out, shapes):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
-                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
-            if t.device != self.device:
-                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+        out = self._outputs(out, shapes, 'a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes)))
         pc = C.c_void_p(out[2].data_ptr()) if count else None
         with torch.cuda.device(self.device):
             nat.check(self._lib.kb_sense_neighbors(self._h, float(radius_m), k, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
@@ -277,21 +265,27 @@ class KilobotSim:
         if not float(radius_m) > 0.0:
             raise ValueError('radius_m must be positive')
         shapes = [((E, N, n_rings, n_sectors), torch.float32, 'hist')] + ([((E, N), torch.int32, 'count')] if count else [])
-        if out is None:
-            out = tuple(torch.empty(*s, dtype=d, device=self.device) for s, d, _ in shapes)
-        out = (out,) if torch.is_tensor(out) else tuple(out)
-        if len(out) != len(shapes):
-            raise ValueError('out must be %s' % ('the tuple (hist, count)' if count else 'the hist tensor'))
-        for t, (s, d, n) in zip(out, shapes):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
-                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
-            if t.device != self.device:
-                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+        out = self._outputs(out, shapes, 'the tuple (hist, count)' if count else 'the hist tensor')
         pc = C.c_void_p(out[1].data_ptr()) if count else None
         with torch.cuda.device(self.device):
             nat.check(self._lib.kb_sense_histogram(self._h, float(radius_m), n_rings, n_sectors, C.c_void_p(out[0].data_ptr()),
                                                    pc, self._stream()), 'kb_sense_histogram')
         return (out[0], out[1]) if count else out[0]
+
+    def _outputs(self, out, shapes, what):
+        """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
+        tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""
+        if out is None:
+            return tuple(torch.empty(*s, dtype=d, device=self.device) for s, d, _ in shapes)
+        out = (out,) if torch.is_tensor(out) else tuple(out)
+        if len(out) != len(shapes):
+            raise ValueError('out must be %s' % what)
+        for t, (s, d, n) in zip(out, shapes):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
+                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
+            if t.device != self.device:
+                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+        return out
 
     def light_sense(self, light_action=None):
         """The sensing point of one substep on its own (kb_light_sense): Light.step with `light_action` (None: the light

@@ -14,6 +14,7 @@ from gym_kilobots_amd import _native as nat
 from gym_kilobots_amd import build as kb_build
 from tests import histogram_ref as ref
 from tests import scenes
+from tests.sensing_common import kernel_metadata
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -125,20 +126,11 @@ def test_kernel_uses_no_scratch_and_spills_nothing(lib):
     """The counters live in LDS columns, never in a per-lane array: every instantiation of the histogram kernel has a zero
     private segment and zero spill counts in the metadata of the code object that was linked (the assembly build() keeps
     next to the object)."""
-    asm = os.path.join(os.path.dirname(kb_build.LIB), '_obj', 'rel', 'kb_abi-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(asm):
-        kb_build.build(force=True)
-    text = open(asm).read()
     seen = 0
-    for doc in re.split(r'\n  - \.agpr_count:', text)[1:]:
-        name = re.search(r'\.name:\s+(\S*kb_histogram_kernel\S*)', doc)
-        if not name:
-            continue
+    for name, fields in kernel_metadata('kb_histogram_kernel'):
         seen += 1
         for key in ('.private_segment_fixed_size', '.sgpr_spill_count', '.vgpr_spill_count'):
-            m = re.search(re.escape(key) + r':\s+(\d+)', doc)
-            assert m, (name.group(1), key)
-            assert int(m.group(1)) == 0, (name.group(1), key, m.group(1))
+            assert fields[key] == 0, (name, key, fields[key])
     assert seen >= 1, 'no kb_histogram_kernel in the code object'
 
 

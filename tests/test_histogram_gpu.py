@@ -8,46 +8,12 @@ import torch
 
 from tests import histogram_ref as ref
 from tests import scenes
+from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
 from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
 
-SWEEP = [(8, 64, 0.07), (8, 64, 0.3), (4, 1024, 0.05), (4, 1024, 0.1), (3, 333, 0.034), (2, 7, 0.5), (5, 1, 0.1)]
 GRIDS = [(1, 1), (1, 2), (5, 1), (3, 6), (4, 8), (8, 8), (4, 16)]
-
-
-def make_sim(E, N, xy=None, th=None, **kw):
-    from gym_kilobots_amd.sim import KilobotSim
-    kw.setdefault('allow_sleep', 0)
-    g = KilobotSim(E, N, **kw)
-    if xy is not None:
-        g.set_poses_m(xy, th)
-    return g
-
-
-def sweep_scene(E, N):
-    if N == 1024:
-        return scenes.lattice_spawn(E, N, seed=3)
-    return scenes.gaussian_spawn(E, N, sigma=0.2, seed=4)
-
-
-def wall_scene():
-    """Kilobots in the corners and along the walls, some outside the arena (their cell indices clamp)."""
-    N = 96
-    rng = np.random.RandomState(9)
-    xy = np.zeros((4, N, 2))
-    corners = np.array([[-1.0, -0.75], [1.0, -0.75], [1.0, 0.75], [-1.0, 0.75]])
-    for e in range(4):
-        xy[e, :24] = corners[e] + rng.uniform(-0.03, 0.08, size=(24, 2)) * -np.sign(corners[e])
-        xy[e, 24:48] = np.stack([rng.uniform(-1, 1, 24), np.full(24, 0.75 - 0.0165) + rng.uniform(-0.01, 0.03, 24)], -1)
-        xy[e, 48:72] = np.stack([np.full(24, -1.0 + 0.0165) + rng.uniform(-0.03, 0.01, 24), rng.uniform(-0.75, 0.75, 24)], -1)
-        xy[e, 72:] = rng.uniform(-0.2, 0.2, size=(24, 2))
-    return xy, rng.uniform(-np.pi, np.pi, size=(4, N))
-
-
-def state(g):
-    torch.cuda.synchronize()
-    return cpu(g.x), cpu(g.y), cpu(g.theta)
 
 
 def check(g, R, rings, sectors, what=''):
@@ -117,7 +83,7 @@ def test_boundary_cases_are_decided_by_the_comparisons(rings, sectors):
 
 @pytest.mark.parametrize('R', [0.04, 0.15])
 def test_histograms_at_walls_and_corners(R):
-    xy, th = wall_scene()
+    xy, th = wall_scene(random_headings=True)
     g = make_sim(4, xy.shape[1], xy, th)
     x, y = state(g)[:2]
     assert (np.abs(x) > 25.0).any() and (np.abs(y) > 18.75).any()      # some kilobots are outside

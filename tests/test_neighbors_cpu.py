@@ -9,6 +9,7 @@ import pytest
 
 from gym_kilobots_amd import _native as nat
 from gym_kilobots_amd import build as kb_build
+from tests.sensing_common import kernel_metadata
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -73,18 +74,9 @@ def test_argument_errors_come_before_the_bound_check(lib, handle):
 def test_kernels_use_no_scratch_and_spill_nothing(lib):
     """The k best (d2, j) keys live in registers: every instantiation of the list kernel has a zero private segment and zero
     spill counts in the metadata of the code object that was linked (the assembly build() keeps next to the object)."""
-    asm = os.path.join(os.path.dirname(kb_build.LIB), '_obj', 'rel', 'kb_abi-hip-amdgcn-amd-amdhsa-gfx950.s')
-    if not os.path.exists(asm):
-        kb_build.build(force=True)
-    text = open(asm).read()
     seen = 0
-    for doc in re.split(r'\n  - \.agpr_count:', text)[1:]:
-        name = re.search(r'\.name:\s+(\S*kb_neighbors_kernel\S*)', doc)
-        if not name:
-            continue
+    for name, fields in kernel_metadata('kb_neighbors_kernel'):
         seen += 1
         for key in ('.private_segment_fixed_size', '.sgpr_spill_count', '.vgpr_spill_count'):
-            m = re.search(re.escape(key) + r':\s+(\d+)', doc)
-            assert m, (name.group(1), key)
-            assert int(m.group(1)) == 0, (name.group(1), key, m.group(1))
+            assert fields[key] == 0, (name, key, fields[key])
     assert seen == 3, 'expected the instantiations for 4, 8 and 16 slots, found %d' % seen

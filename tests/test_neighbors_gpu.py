@@ -9,40 +9,10 @@ import torch
 
 from oracle import oracle as O
 from tests import scenes
+from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
 from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
-
-SWEEP = [(8, 64, 0.07), (8, 64, 0.3), (4, 1024, 0.05), (4, 1024, 0.1), (3, 333, 0.034), (2, 7, 0.5), (5, 1, 0.1)]   # test_sense_equals_brute_force_oracle
-
-
-def make_sim(E, N, xy=None, th=None, **kw):
-    from gym_kilobots_amd.sim import KilobotSim
-    kw.setdefault('allow_sleep', 0)
-    g = KilobotSim(E, N, **kw)
-    if xy is not None:
-        g.set_poses_m(xy, th)
-    return g
-
-
-def sweep_scene(E, N):
-    if N == 1024:
-        return scenes.lattice_spawn(E, N, seed=3)
-    return scenes.gaussian_spawn(E, N, sigma=0.2, seed=4)
-
-
-def wall_scene():
-    """The scene of test_sense_at_walls_and_corners: kilobots in the corners and along the walls, some outside the arena."""
-    N = 96
-    rng = np.random.RandomState(9)
-    xy = np.zeros((4, N, 2))
-    corners = np.array([[-1.0, -0.75], [1.0, -0.75], [1.0, 0.75], [-1.0, 0.75]])
-    for e in range(4):
-        xy[e, :24] = corners[e] + rng.uniform(-0.03, 0.08, size=(24, 2)) * -np.sign(corners[e])
-        xy[e, 24:48] = np.stack([rng.uniform(-1, 1, 24), np.full(24, 0.75 - 0.0165) + rng.uniform(-0.01, 0.03, 24)], -1)
-        xy[e, 48:72] = np.stack([np.full(24, -1.0 + 0.0165) + rng.uniform(-0.03, 0.01, 24), rng.uniform(-0.75, 0.75, 24)], -1)
-        xy[e, 72:] = rng.uniform(-0.2, 0.2, size=(24, 2))
-    return xy, np.zeros((4, N))
 
 
 def restate(x, y, th, R, k):
@@ -78,10 +48,6 @@ def restate(x, y, th, R, k):
             rel[e, i, :m, 2] = np.sqrt(d2[i, js]) / W
             rel[e, i, :m, 3] = th[e, js] - th[e, i]
     return index, rel, count, zeros
-
-
-def state(g):
-    return cpu(g.x), cpu(g.y), cpu(g.theta)
 
 
 def check(g, R, k, what=''):

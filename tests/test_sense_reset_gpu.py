@@ -7,6 +7,7 @@ import torch
 
 from oracle import oracle as O
 from tests import scenes
+from tests.sensing_common import SWEEP
 from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
@@ -17,9 +18,10 @@ def counts(g):
 
 
 # ---------------------------------------------------------------------------------------------- kb_sense
-@pytest.mark.parametrize('E,N,R', [(8, 64, 0.07), (8, 64, 0.3), (4, 1024, 0.05), (4, 1024, 0.1), (3, 333, 0.034), (2, 7, 0.5), (5, 1, 0.1)])
+@pytest.mark.parametrize('E,N,R', SWEEP)
 def test_sense_equals_brute_force_oracle(E, N, R):
-    """cfg2 / cfg3 slices, odd sizes; R from one cell (0.035 m) to R > 2 cells and the whole arena."""
+    """cfg2 / cfg3 slices, odd sizes; R from one cell (0.035 m) to R > 2 cells, the whole arena, and beyond it (the reach is
+    clamped to the grid)."""
     if N == 1024:
         xy, th = scenes.lattice_spawn(E, N, seed=3)
     else:
