@@ -236,6 +236,7 @@ struct kb_sim {
     const void *attr_fn;   // kernel whose dynamic-LDS limit has been raised
     int threads;
     kb_step_fn fn;         // the instantiation that runs the handle (plan_launch), nullptr if the library has none
+    int variant;           // ... and its position in kb_variants, -1 likewise (kb_variant_index)
 };
 
 kb_step_fn kb::kb_kernels[NUM_VARIANTS];
@@ -258,6 +259,7 @@ static void use_plan(kb_sim *s, const Plan &pl) {
     s->threads = pl.threads;
     const int i = variant_index(pl.variant);
     s->fn = i < 0 ? nullptr : kb_kernels[i];
+    s->variant = s->fn ? i : -1;
 }
 
 extern "C" {
@@ -695,6 +697,7 @@ size_t kb_scratch_bytes(const kb_sim *sim) { return sim ? (size_t)sim->p.E * (si
 int kb_contact_capacity(const kb_sim *sim) { return sim ? sim->p.cap : KB_EINVAL; }
 int kb_lds_staging_entries(const kb_sim *sim) { return sim ? sim->p.capL : KB_EINVAL; }
 int kb_block_threads(const kb_sim *sim) { return sim ? sim->threads : KB_EINVAL; }
+int kb_variant_index(const kb_sim *sim) { return sim ? sim->variant : -1; }
 int kb_set_block_threads(kb_sim *sim, int threads) {
     if (!sim || threads == 0) return fail(KB_EINVAL, "kb_set_block_threads: multiple of 64 up to the build maximum");   // (0: plan_launch would choose)
     const Plan pl = plan_launch(plan_input(sim, threads));

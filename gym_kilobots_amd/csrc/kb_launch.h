@@ -45,6 +45,7 @@ constexpr int mc_candidates(int M) { return M * (M - 1) / 2 + 4 * M; }
 // for the whole launch; in the fixed-size instantiations all of this folds to constants.
 namespace lds {
 constexpr int A16(int x) { return (x + 15) & ~15; }
+constexpr int A4(int x) { return (x + 3) & ~3; }
 constexpr int MISC = 0;
 constexpr int WSUM = MISC + A16(4 * 64);
 constexpr int BKSTART = WSUM + A16(4 * 16);
@@ -76,7 +77,9 @@ constexpr int BOT16_COUNT = 4, BOT8_COUNT = 2;
 constexpr int body32(int fx, int NB, int k) { return fx + 4 * NB * k; }
 constexpr int con32(int fx, int NB, int capL, int k) { return body32(fx, NB, BODY32_COUNT) + 4 * capL * k; }
 constexpr int con16(int fx, int NB, int capL, int k) { return con32(fx, NB, capL, CON32_COUNT) + 2 * capL * k; }
-constexpr int bot16(int fx, int NB, int capL, int NP, int k) { return con16(fx, NB, capL, CON16_COUNT) + 2 * NP * k; }
+// (whole words: the fused sensing pass counts into newOff with 32-bit atomics, two u16 counters per word, and an odd capL --
+//  3 N + 64 staging entries of an odd swarm -- leaves the three 16-bit contact arrays in front an odd number of half words long)
+constexpr int bot16(int fx, int NB, int capL, int NP, int k) { return A4(con16(fx, NB, capL, CON16_COUNT)) + 2 * NP * k; }
 constexpr int bot8(int fx, int NB, int capL, int NP, int k) { return bot16(fx, NB, capL, NP, BOT16_COUNT) + NP * k; }
 constexpr int active(int fx, int NB, int capL, int NP) { return bot8(fx, NB, capL, NP, BOT8_COUNT); }
 constexpr int islwave(int fx, int NB, int capL, int NP) { return active(fx, NB, capL, NP) + 2 * NB; }   // u8 per body: wave that sweeps its island

@@ -146,6 +146,12 @@ class KilobotSim:
     def block_threads(self, n):
         nat.check(self._lib.kb_set_block_threads(self._h, int(n)), 'kb_set_block_threads')
 
+    @property
+    def variant_index(self):
+        """Which instantiation of the step kernel runs this sim: its position in the library's list (kb_variant.h), -1 if
+        the library has none.  Follows block_threads."""
+        return self._lib.kb_variant_index(self._h)
+
     # ------------------------------------------------------------------ state
     def set_poses_m(self, xy_m, theta):
         """Body poses in metres / radians; stored as fp32 world units like body.py:32-34 does."""

@@ -324,6 +324,9 @@ int kb_lds_staging_entries(const kb_sim *sim);  /* contacts of one env that are 
                                                    5 num_bots / 2 + 64 (at least 256) with objects or mixed drive laws */
 size_t kb_scratch_bytes(const kb_sim *sim);     /* size of kb_buffers.scratch: 32 B per contact of the capacity (staging record; level-sorted record of the cooperative sweeps) */
 int kb_block_threads(const kb_sim *sim);
+int kb_variant_index(const kb_sim *sim);        /* which instantiation of the step kernel runs the handle: its position in the library's
+                                                   list (kb_variant.h: kb_variants), -1 if the library has none (kb_step then fails).
+                                                   Follows kb_set_block_threads.  For tests that must know which kernel they ran */
 int kb_resident_envs_per_cu(kb_sim *sim);        /* workgroups (= envs) of this handle's kernel that one CU holds at a time (HIP occupancy query; needs a GPU) */
 int kb_set_block_threads(kb_sim *sim, int threads);  /* multiple of 64 in [64, 512], num_bots <= 2 * threads.  kb_create picks
                                                          the measured best (one kilobot per thread, power-of-two wave count,

@@ -24,8 +24,9 @@ int main() {
         const Plan p = plan_launch({v[0], v[1], v[2], v[3] != 0, v[4], v[5], v[6] != 0, v[7] != 0, v[8], v[9], v[10]});
         if (p.status != KB_OK) { printf("%d\n", p.status); continue; }
         const Variant &k = p.variant;
-        printf("%d %d %d %d %d %d %d %d %d %d : %d %d %d %d %d %d %d %d\n", p.status, p.cap, p.capL, p.nhead, p.hmask, p.threads,
-               p.lds_total, p.islmin_off, p.botlaw_off, p.tier, k.drive, k.light, k.obj, k.fn, k.tier, k.poly, k.sense, k.sleep);
+        printf("%d %d %d %d %d %d %d %d %d %d : %d %d %d %d %d %d %d %d # %d\n", p.status, p.cap, p.capL, p.nhead, p.hmask, p.threads,
+               p.lds_total, p.islmin_off, p.botlaw_off, p.tier, k.drive, k.light, k.obj, k.fn, k.tier, k.poly, k.sense, k.sleep,
+               variant_index(p.variant));
     }
     return 0;
 }
@@ -45,8 +46,9 @@ def golden_rows():
     return rows
 
 
-def test_plan_matches_the_recorded_shapes(tmp_path):
-    rows = golden_rows()
+def plan_rows(tmp_path, rows):
+    """plan_launch of the header on the inputs of `rows`: [(result in the format of the golden file, position of the
+    instantiation in kb_variants or None for a refused configuration)]"""
     src = tmp_path / 'launch.cpp'
     src.write_text(PROGRAM)
     exe = str(tmp_path / 'launch')
@@ -55,8 +57,19 @@ def test_plan_matches_the_recorded_shapes(tmp_path):
     stdin = '\n'.join(' '.join(map(str, inputs)) for inputs, _ in rows).encode()
     out = subprocess.run([exe], input=stdin, stdout=subprocess.PIPE, check=True).stdout.decode().split('\n')
     assert len(out) >= len(rows)
-    for (inputs, want), got in zip(rows, out):
+    plans = []
+    for line in out[:len(rows)]:
+        result, _, index = line.partition(' # ')
+        plans.append((result, int(index) if index else None))
+    return plans
+
+
+def test_plan_matches_the_recorded_shapes(tmp_path):
+    rows = golden_rows()
+    for (inputs, want), (got, index) in zip(rows, plan_rows(tmp_path, rows)):
         assert got == want, 'plan input %s: %s, recorded %s' % (inputs, got, want)
+        # every recorded instantiation is one of the library's list
+        assert index is None or 0 <= index < 176, inputs
 
 
 def config(inputs):
@@ -81,9 +94,11 @@ def lib():
     return nat.load()
 
 
-def test_library_matches_the_recorded_shapes(lib):
+def test_library_matches_the_recorded_shapes(lib, tmp_path):
     h = C.c_void_p()
-    for inputs, want in golden_rows():
+    rows = golden_rows()
+    accepted = 0
+    for (inputs, want), (_, index) in zip(rows, plan_rows(tmp_path, rows)):
         threads = inputs[-1]
         cfg = config(inputs)
         rc = lib.kb_create(C.byref(cfg), C.byref(h))
@@ -100,4 +115,43 @@ def test_library_matches_the_recorded_shapes(lib):
             status, cap, capL, _, _, wg, lds = (int(x) for x in fields[:7])
             assert (rc, lib.kb_contact_capacity(h), lib.kb_lds_staging_entries(h), lib.kb_block_threads(h), lib.kb_lds_bytes(h)) == \
                 (status, cap, capL, wg, lds), inputs
+            # ... and runs the instantiation that the header selects for the row (kb_variant_index follows kb_set_block_threads)
+            assert index is not None and lib.kb_variant_index(h) == index, inputs
+            accepted += 1
         lib.kb_destroy(h)
+    assert accepted > 0
+
+
+ALIGNMENT_PROGRAM = r'''
+#include <cstdio>
+#include "kb_launch.h"
+using namespace kb;
+int main() {
+    int bad = 0;
+    for (int mixed = 0; mixed < 2; ++mixed)
+        for (int M = mixed ? 0 : 1; M <= KB_MAX_OBJECTS; ++M)
+            for (int N = 1; N <= 1024; ++N) {
+                const Plan p = plan_launch({N, M, M, false, mixed ? KB_DRIVE_MIXED : KB_DRIVE_VELOCITY, 0, true, true, 2494, 0, 0});
+                if (p.status != KB_OK) continue;
+                const int NP = (N + 3) & ~3, NB = NP + KB_MAX_OBJECTS + 4, fx = lds::fixed(true, p.threads / 64);
+                for (int k = 0; k < lds::BOT16_COUNT; ++k)
+                    if (lds::bot16(fx, NB, p.capL, NP, k) % 4 != 0 && ++bad <= 5) printf("N %d M %d capL %d array %d at %d\n", N, M, p.capL, k, lds::bot16(fx, NB, p.capL, NP, k));
+                if (lds::head(fx, NB, p.capL, NP) % 4 != 0 && ++bad <= 5) printf("N %d M %d capL %d head\n", N, M, p.capL);
+            }
+    printf("%d\n", bad);
+    return 0;
+}
+'''
+
+
+def test_word_atomics_on_the_16_bit_arrays_are_aligned(tmp_path):
+    """The kernels with objects (and mixed laws) run 32-bit LDS atomics on 16-bit arrays: two neighbour counters per word in
+    newOff (fused sensing), compare-and-swap on the cell heads.  An odd number of staging entries (3 N + 64 of an odd swarm,
+    e.g. 129 kilobots with two objects: 451) once left newOff at a half-word offset, and the sensing pass faulted."""
+    src = tmp_path / 'align.cpp'
+    src.write_text(ALIGNMENT_PROGRAM)
+    exe = str(tmp_path / 'align')
+    subprocess.check_call(['g++', '-std=c++17', '-O1', '-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'gym_kilobots_amd', 'csrc'),
+                           str(src), '-o', exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, check=True).stdout.decode().strip().split('\n')
+    assert out[-1] == '0', 'misaligned: ' + '; '.join(out[:-1])

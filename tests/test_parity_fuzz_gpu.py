@@ -97,6 +97,13 @@ def test_random_scene(seed):
         mode = O.DRIVE_MIXED
         kw.update(mode_density=[2.0, 2.0, 1.0, 1.0, 1.0])
     sx, sy = W / 2.0, H / 1.5
+    # fused neighbour sensing (kb_config.sense_radius): in half the scenes, one cell to more than two cells of reach scaled to the
+    # arena; from a third stream of its own (the scenes keep their layout, and sensing does not change the step)
+    rng3 = np.random.default_rng(555000 + seed)
+    sense_radius = 0.0
+    if rng3.random() < 0.5:
+        sense_radius = float(rng3.choice([0.04, 0.07, 0.15])) * min(sx, sy)
+        kw.update(sense_radius=sense_radius)
     with_objects = rng.random() < 0.6
     nobj = 0
     if with_objects:
@@ -139,6 +146,8 @@ def test_random_scene(seed):
                 v = getattr(osim, name)
                 v[off] = 0
                 getattr(gsim, name).copy_(dev(v))
+    if sense_radius > 0.0:
+        fields += ('nbr_count',)
     la_dim = {O.LIGHT_NONE: 0, O.LIGHT_GRADIENT: 1}.get(light, 2)
     for k in range(12):
         la = None if la_dim == 0 or k % 3 == 2 else rng.uniform(-0.02, 0.02, (E, la_dim)).astype(np.float32)

@@ -9,6 +9,7 @@ import torch
 
 from oracle import oracle as O
 from tests import scenes
+from tests.variant_census import stop_and_go_actions as _stop_and_go_actions
 
 
 def _sim(E, N, xy, th=None, **kw):
@@ -140,16 +141,6 @@ def test_a_pushed_disc_comes_to_rest_and_sleeps_with_zero_velocity():
 def _pair(E, N, xy, th, objects=None, **kw):
     from tests.test_parity_gpu import make_pair
     return make_pair(E, N, O.DRIVE_VELOCITY, O.LIGHT_NONE, xy=xy, th=th, objects=objects, allow_sleep=1, **kw)
-
-
-def _stop_and_go_actions(E, N, k, seed):
-    """Velocity commands in which groups of kilobots stop for a while (they fall asleep in their islands) and start again."""
-    rng = np.random.RandomState(seed + k)
-    a = scenes.random_actions(E, N, seed=seed + 100 + k)
-    phase = (np.arange(N)[None, :] // 7 + np.arange(E)[:, None] + k // 9) % 3
-    a[phase == 0] = 0.0                                   # a third of the kilobots rests for 9 substeps at a time
-    a[rng.rand(E, N) < 0.05] = 0.0
-    return a.astype(np.float32)
 
 
 SLEEP_FIELDS = ('x', 'y', 'theta', 'sleep_time')
