@@ -91,7 +91,7 @@ class KilobotsHipError(RuntimeError):
 STATUS_BITS = {
     1: 'contact capacity overflow: contacts were dropped (raise kb_config.contact_capacity or spread the spawn)',
     2: 'warm-start slot overflow: a kilobot touches more partners than kb_config.ws_slots, their impulses are not carried over',
-    4: 'a device staging limit was hit (more than 64 kilobots on one fixture, 255 kilobot-object contacts in one env or 63 partners in one cell pair)',
+    4: 'a device staging limit was hit (more than 64 kilobots on one fixture, 255 kilobot-object contacts in one env, 63 partners in one cell pair or a contact dependency chain deeper than the level table of the cooperative sweep)',
     8: 'continuous step skipped for some kilobots: more kilobots near the walls in one substep than the staging area holds',
 }
 

@@ -234,10 +234,11 @@ __device__ __forceinline__ unsigned lds_load_relaxed(const unsigned *p_) {
     return *reinterpret_cast<const volatile unsigned *>(p_);
 }
 
-// Workgroup barrier for phases that only exchange LDS data: __syncthreads() also drains the vector-memory counter
-// (s_waitcnt vmcnt(0)), i.e. it waits for every global load a thread has in flight -- which is exactly what a sweep that
-// requests its records several rounds ahead must not do.  No memory instruction inside: the compiler's own s_waitcnt
-// bookkeeping for the registers of outstanding loads stays valid.
+// Workgroup barrier for phases that only exchange LDS data: __syncthreads() may also drain the vector-memory counter
+// (s_waitcnt vmcnt(0): whenever the compiler sees accesses in flight that its fence has to order), i.e. wait for every
+// global load a thread has in flight -- which is exactly what a sweep that requests its records several rounds ahead must
+// not do.  Data that changes hands through GLOBAL memory takes __syncthreads() (kb_coopsolve_bins.inc, StoreImpulses).
+// No memory instruction inside: the compiler's own s_waitcnt bookkeeping for the registers of outstanding loads stays valid.
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }

@@ -199,7 +199,15 @@
     KB_ABLATE_EXIT(11);
     // StoreImpulses: back to the staged contacts (their index is the position in the packed list)
     if (accInLds) { for (int si = tid; si < nsorted; si += nt) sAcc_[order_[si]] = accL[si]; }
-    else { for (int si = tid; si < nsorted; si += nt) sAcc_[order_[si]] = sacc2[si]; }
+    else {
+        // (record si was last written by the thread that swept it in the final velocity pass, through GLOBAL memory, and this
+        //  copy hands it to another thread: lds_barrier() orders LDS only, so the hand-over takes the barrier with the
+        //  workgroup-scope release / acquire of the memory model -- block-uniform, once per substep, only with the impulses
+        //  in the records.  On gfx950 it compiles to the same s_waitcnt lgkmcnt(0) + s_barrier: vector memory of one
+        //  workgroup is ordered by the CU's in-order L1, DESIGN.md 3)
+        __syncthreads();
+        for (int si = tid; si < nsorted; si += nt) sAcc_[order_[si]] = sacc2[si];
+    }
     // integrate positions (b2Island::Solve)
 #pragma unroll
     for (int q = 0; q < BPT; ++q) {

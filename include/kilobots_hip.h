@@ -177,7 +177,10 @@ typedef struct kb_buffers {
     float *cmd_vx, *cmd_vy, *cmd_w;     /* optional outputs: body velocity written by the drive law */
     int32_t *status;                    /* required: [num_envs]; bit0 contact capacity overflow,
                                            bit1 warm-start slot overflow, bit2 a device staging limit was hit (more than 64 kilobots
-                                           on one fixture, 255 kilobot-object contacts in one env, or 63 partners in one cell pair),
+                                           on one fixture, 255 kilobot-object contacts in one env, 63 partners in one cell pair, or --
+                                           kernels without objects, an env swept by the whole workgroup -- a chain of contacts that
+                                           depend on each other deeper than the level table: 44 x waves of the workgroup - 2 levels,
+                                           at least 62),
                                            bit3 more kilobots near the walls in one substep than half the LDS contact staging holds
                                            (512 at 1024 kilobots; the continuous step is skipped for the rest) */
     void *scratch;                      /* required: kb_scratch_bytes() bytes; contact staging of envs whose
