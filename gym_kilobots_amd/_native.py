@@ -21,6 +21,8 @@ OWS_COLS, OWS_WORDS = 12, 6
 MAX_BOTS = 1024
 MAX_NEIGHBORS = 16     # KB_MAX_NEIGHBORS: slots per kilobot of kb_sense_neighbors
 HIST_MAX_RINGS, HIST_MAX_SECTORS, HIST_MAX_BINS = 8, 16, 64     # KB_HIST_MAX_*: bin grid of kb_sense_histogram
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)     # kb_reduce_op: how kb_sense_reduce combines the messages heard
+REDUCE_MAX_CHANNELS = 8     # KB_REDUCE_MAX_CHANNELS: floats per message of kb_sense_reduce
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -77,7 +79,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -136,6 +138,8 @@ def load():
     lib.kb_sense_histogram.restype = C.c_int
     lib.kb_histogram_sectors.argtypes = [C.c_int, C.POINTER(C.c_float)]
     lib.kb_histogram_sectors.restype = C.c_int
+    lib.kb_sense_reduce.argtypes = [_P, C.c_float, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]
+    lib.kb_sense_reduce.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -171,6 +175,26 @@ def check_histogram_grid(n_rings, n_sectors):
     if n_rings * n_sectors > HIST_MAX_BINS:
         raise ValueError('n_rings * n_sectors must not exceed %d' % HIST_MAX_BINS)
     return n_rings, n_sectors
+
+
+REDUCE_OPS = {'sum': REDUCE_SUM, 'min': REDUCE_MIN, 'max': REDUCE_MAX}
+
+
+def check_reduce(op, n_channels, scale):
+    """The limits of kb_sense_reduce on op ('sum' | 'min' | 'max' or REDUCE_*), channel count and scale (the sum's only);
+    ValueError where the library would answer KB_EINVAL.  Returns (op as an integer, n_channels, scale)."""
+    if isinstance(op, str):
+        if op not in REDUCE_OPS:
+            raise ValueError("op must be 'sum', 'min' or 'max'")
+        op = REDUCE_OPS[op]
+    op, n_channels, scale = int(op), int(n_channels), float(scale)
+    if op not in (REDUCE_SUM, REDUCE_MIN, REDUCE_MAX):
+        raise ValueError('op must be REDUCE_SUM, REDUCE_MIN or REDUCE_MAX')
+    if not 1 <= n_channels <= REDUCE_MAX_CHANNELS:
+        raise ValueError('n_channels must be in 1..%d' % REDUCE_MAX_CHANNELS)
+    if op == REDUCE_SUM and not 0.0 < scale < float('inf'):
+        raise ValueError('scale must be finite and positive')
+    return op, n_channels, scale
 
 
 def histogram_sectors(n_sectors):

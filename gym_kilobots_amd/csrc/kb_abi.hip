@@ -1,7 +1,7 @@
 // kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h): argument validation and launches of every entry
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
-// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram) are in kb_sense.h.
+// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce) are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -225,6 +225,13 @@ SenseRange sense_range(const Params &p, float radius_m) {
 int check_sectors(const char *entry, int n_sectors) {
     if (n_sectors == 1 || (n_sectors >= 2 && n_sectors <= KB_HIST_MAX_SECTORS && !(n_sectors & 1))) return KB_OK;
     return fail(KB_EINVAL, "%s: n_sectors must be 1 or an even number in 2..KB_HIST_MAX_SECTORS (16)", entry);
+}
+
+// the instantiation of kb_reduce_kernel for an op and a channel count: rows of 1, 2, 4 or 8 words
+using kb_reduce_fn = void (*)(Params, int, float, int, int, float, const float *, float *, unsigned *);
+template <int OP>
+kb_reduce_fn reduce_kernel(int CP) {
+    return CP == 1 ? kb_reduce_kernel<OP, 1> : CP == 2 ? kb_reduce_kernel<OP, 2> : CP == 4 ? kb_reduce_kernel<OP, 4> : kb_reduce_kernel<OP, 8>;
 }
 
 }  // namespace
@@ -640,6 +647,24 @@ int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, 
     hipLaunchKernelGGL(kb_histogram_kernel, dim3((unsigned)p.E), dim3(256), (size_t)HistLds(p.NP, p.ncell, n_rings * n_sectors).bytes, (hipStream_t)stream,
                        p, rg.reach, rg.R2, h, d_hist, d_count);
     return launched("kb_sense_histogram");
+}
+
+int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float scale, const float *d_values, float *d_out,
+                    uint32_t *d_count, void *stream) {
+    if (!sim || !d_values || !d_out) return fail(KB_EINVAL, "kb_sense_reduce: NULL argument");
+    if (op != KB_REDUCE_SUM && op != KB_REDUCE_MIN && op != KB_REDUCE_MAX) return fail(KB_EINVAL, "kb_sense_reduce: op must be KB_REDUCE_SUM, KB_REDUCE_MIN or KB_REDUCE_MAX");
+    if (n_channels < 1 || n_channels > KB_REDUCE_MAX_CHANNELS) return fail(KB_EINVAL, "kb_sense_reduce: 1 <= n_channels <= KB_REDUCE_MAX_CHANNELS (8) required");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_reduce: radius must be positive");
+    if (op == KB_REDUCE_SUM && !(scale > 0.0f && scale < INFINITY)) return fail(KB_EINVAL, "kb_sense_reduce: scale must be finite and positive");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_reduce: kb_bind() first");
+    const Params &p = sim->p;
+    const SenseRange r = sense_range(p, radius_m);
+    const int CP = n_channels <= 2 ? n_channels : n_channels <= 4 ? 4 : 8;
+    const int vec = n_channels % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+    const kb_reduce_fn fn = op == KB_REDUCE_SUM ? reduce_kernel<KB_REDUCE_SUM>(CP) : op == KB_REDUCE_MIN ? reduce_kernel<KB_REDUCE_MIN>(CP) : reduce_kernel<KB_REDUCE_MAX>(CP);
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ReduceLds(p.NP, p.ncell, CP).bytes, (hipStream_t)stream, p, r.reach, r.R2, n_channels, vec,
+                       scale, d_values, d_out, d_count);
+    return launched("kb_sense_reduce");
 }
 
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {

@@ -1,7 +1,7 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram): one workgroup per env, poses and the cell lists of the broadphase grid in LDS.  Each kernel's LDS
-// image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry point (kb_abi.hip)
-// the dynamic-LDS size.  Included by kb_abi.hip only.
+// kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS.
+// Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
+// point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
 
 #include "kb_common.h"
@@ -275,6 +275,105 @@ __global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const
             if (bin >= B) { bin -= B; kb++; }
         }
         __syncthreads();
+    }
+}
+
+// ---- kb_sense_reduce: the messages of the kilobots in range, summed or ordered -----------------------------------------
+struct ReduceLds {      // byte offsets: pos (float2) at 0, nextb, cellOf, head (u16 each), msg[NP][CP] (one 32-bit word per channel)
+    int nextb, cellOf, head, msg, bytes;
+    __host__ __device__ constexpr ReduceLds(int NP, int ncell, int CP)
+        : nextb(8 * NP), cellOf(10 * NP), head(12 * NP),
+          msg((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),      // (rows are read 4, 8 or 16 bytes at a time)
+          bytes(msg + 4 * CP * NP) {}
+};
+// the largest image (1024 kilobots, every cell, 8 channels) stays under the default limit for dynamic LDS: no attribute to raise
+static_assert(ReduceLds(KB_MAX_BOTS, MAX_CELLS, KB_REDUCE_MAX_CHANNELS).bytes <= 64 * 1024, "kb_reduce_kernel: LDS image");
+
+// The total order of the bit patterns as unsigned keys: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN.
+__device__ __forceinline__ unsigned kb_reduce_key(unsigned bits) { return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+__device__ __forceinline__ unsigned kb_reduce_unkey(unsigned key) { return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+// The fixed-point image of a broadcast value: NaN -> 0, otherwise v * scale clamped to +-2^21 and rounded half to even.
+__device__ __forceinline__ int kb_reduce_quant(float v, float scale) {
+    const float t = v * scale;
+    return t != t ? 0 : (int)rintf(fminf(fmaxf(t, -2097152.0f), 2097152.0f));
+}
+
+// IR-range message aggregation on the current poses (kb_sense_reduce): every kilobot combines, channel by channel, what the
+// kilobots of its env in IR range broadcast.  Poses and the cell lists in LDS, one kilobot per lane over the full stencil,
+// like kb_neighbors_kernel.  Every broadcast value is converted ONCE, while the env is staged: to its fixed-point int32 for
+// the sum, to its order key for min / max, so that LDS holds one 32-bit word per (kilobot, channel) in rows of CP words
+// (the channels rounded up to 1, 2, 4 or 8: one LDS read of 4, 8 or 16 bytes, two of 16 for CP = 8, fetches a neighbour's
+// whole message) and the work per pair is an integer add, unsigned min or unsigned max per channel into CP per-lane
+// registers.  No two floats are ever added: the result does not depend on the order of the chains.  The words go back to
+// floats once per kilobot, at write-out: one row of C floats per lane, in 16-byte stores with vec (C a multiple of 4 and
+// d_out 16-byte aligned).  Padding channels hold the identity and are never written.  d_out may be d_values: the env's
+// values are all in LDS before the barrier that ends kb_build_cell_lists, and nothing is written before it.
+template <int OP, int CP>
+__global__ void __launch_bounds__(256) kb_reduce_kernel(const Params p, const int s, const float R2, const int C, const int vec,
+                                                        const float scale, const float *d_values, float *d_out, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr unsigned IDENT = OP == KB_REDUCE_MIN ? 0xFFFFFFFFu : 0u;      // of the words: sum 0, min the top key, max the bottom key
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const ReduceLds L(p.NP, p.ncell, CP);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    unsigned *msg = reinterpret_cast<unsigned *>(smem + L.msg);
+    const size_t o = (size_t)e * N;
+    const float *val = d_values + o * (size_t)C;
+    for (int f = tid; f < N * CP; f += nt) {
+        const int b = f / CP, c = f % CP;
+        unsigned w = IDENT;
+        if (c < C) {
+            const float v = val[b * C + c];
+            w = OP == KB_REDUCE_SUM ? (unsigned)kb_reduce_quant(v, scale) : kb_reduce_key(__float_as_uint(v));
+        }
+        msg[f] = w;
+    }
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    for (int a = tid; a < N; a += nt) {
+        const int cell = cellOf[a];
+        const float2 pa = pos[a];
+        unsigned acc[CP];
+#pragma unroll
+        for (int c = 0; c < CP; ++c) acc[c] = IDENT;
+        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
+            unsigned w[CP];
+            if constexpr (CP == 1) {
+                w[0] = msg[b];
+            } else if constexpr (CP == 2) {
+                const uint2 r = reinterpret_cast<const uint2 *>(msg)[b];
+                w[0] = r.x; w[1] = r.y;
+            } else {
+#pragma unroll
+                for (int q = 0; q < CP / 4; ++q) {
+                    const uint4 r = reinterpret_cast<const uint4 *>(msg)[b * (CP / 4) + q];
+                    w[4 * q] = r.x; w[4 * q + 1] = r.y; w[4 * q + 2] = r.z; w[4 * q + 3] = r.w;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CP; ++c)
+                acc[c] = OP == KB_REDUCE_SUM ? acc[c] + w[c] : OP == KB_REDUCE_MIN ? min(acc[c], w[c]) : max(acc[c], w[c]);
+        });
+        float r[CP];
+#pragma unroll
+        for (int c = 0; c < CP; ++c) {
+            if (OP == KB_REDUCE_SUM) r[c] = (float)(int)acc[c] / scale;
+            else r[c] = __uint_as_float(cnt ? kb_reduce_unkey(acc[c]) : OP == KB_REDUCE_MIN ? 0x7F800000u : 0xFF800000u);   // nothing heard: +inf / -inf
+        }
+        float *row = d_out + (o + a) * (size_t)C;
+        if (CP >= 4 && vec) {       // C == CP and d_out is 16-byte aligned: four channels per store
+#pragma unroll
+            for (int c = 0; c + 3 < CP; c += 4) reinterpret_cast<float4 *>(row)[c >> 2] = make_float4(r[c], r[c + 1], r[c + 2], r[c + 3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < CP; ++c) {
+                if (c >= C) break;
+                row[c] = r[c];
+            }
+        }
+        if (d_count) d_count[o + a] = cnt;
     }
 }
 

@@ -16,7 +16,8 @@ class BatchedKilobotsEnv(object):
 
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
-                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, **cfg):
+                 sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
+                 **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -26,7 +27,9 @@ class BatchedKilobotsEnv(object):
         in its info dict under 'neighbors'.  None: reset() and step() are what they were, the info dict stays {}.
         histogram_obs: (radius_m, n_rings, n_sectors) adds the fixed-size local histogram of ALL kilobots in range, binned by
         distance and bearing in the kilobot's own frame (KilobotSim.neighbor_histogram): neighbor_histogram() returns it,
-        step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing."""
+        step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing.
+        comm_radius: the IR range in metres over which neighbor_reduce(values) aggregates what the kilobots broadcast
+        (KilobotSim.neighbor_reduce).  reset() and step() do not change with it."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -59,6 +62,15 @@ class BatchedKilobotsEnv(object):
             if not radius_m > 0.0:
                 raise ValueError('histogram_obs: radius_m must be positive')
             self.histogram_obs = (radius_m, n_rings, n_sectors)
+        self.comm_radius = None
+        if comm_radius is not None:
+            try:
+                comm_radius = float(comm_radius)
+            except TypeError as err:
+                raise ValueError('comm_radius must be a radius in metres: %s' % err)
+            if not comm_radius > 0.0:
+                raise ValueError('comm_radius must be positive')
+            self.comm_radius = comm_radius
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -162,6 +174,13 @@ class BatchedKilobotsEnv(object):
         if self.histogram_obs is None:
             raise ValueError('create the env with histogram_obs=(radius_m, n_rings, n_sectors) to observe neighbour histograms')
         return self.sim.neighbor_histogram(*self.histogram_obs)
+
+    def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
+        """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env
+        was created with, combined by op ('sum' | 'min' | 'max'): KilobotSim.neighbor_reduce."""
+        if self.comm_radius is None:
+            raise ValueError('create the env with comm_radius=radius_m to aggregate messages')
+        return self.sim.neighbor_reduce(values, self.comm_radius, op=op, scale=scale, count=count)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

@@ -278,6 +278,33 @@ class KilobotSim:
                                                    pc, self._stream()), 'kb_sense_histogram')
         return (out[0], out[1]) if count else out[0]
 
+    def neighbor_reduce(self, values, radius_m, op='sum', scale=65536.0, out=None, count=False):
+        """IR-range message aggregation on the current poses (kb_sense_reduce; no reference counterpart): every kilobot
+        broadcasts its row of `values` ([E, N] or [E, N, C] contiguous float32 on the sim's device, C <= 8) and hears, channel
+        by channel, the op ('sum' | 'min' | 'max') over ALL kilobots of its env within radius_m (centre to centre).  The sum
+        is a fixed-point sum of rint(values * scale) (clamped to +-2^21, NaN dropped) divided by scale: exact on the quantised
+        values and independent of the order; the default scale resolves 1.5e-5 over +-32 per message.  min / max order the
+        bit patterns (-0 < +0, NaNs outside the infinities) and return the value heard unchanged; scale is ignored.  Nothing
+        heard: +0.0 / +inf / -inf.  Returns a tensor of the shape of values, or (result, count [E, N] int32 = kilobots
+        heard) with count=True; the mean is result / count.  out: a preallocated tensor to write into, which may be values
+        itself (with count=True: the tuple (result, count))."""
+        E, N = self.num_envs, self.num_bots
+        if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.is_contiguous()
+                and values.dim() in (2, 3) and tuple(values.shape[:2]) == (E, N)):
+            raise ValueError('values must be a contiguous float32 cuda tensor of shape %s or %s' % ((E, N), (E, N, 'C')))
+        if values.device != self.device:
+            raise ValueError('values lives on %s, the simulator on %s' % (values.device, self.device))
+        op, n_channels, scale = nat.check_reduce(op, values.shape[2] if values.dim() == 3 else 1, scale)
+        if not float(radius_m) > 0.0:
+            raise ValueError('radius_m must be positive')
+        shapes = [(tuple(values.shape), torch.float32, 'result')] + ([((E, N), torch.int32, 'count')] if count else [])
+        out = self._outputs(out, shapes, 'the tuple (result, count)' if count else 'the result tensor')
+        pc = C.c_void_p(out[1].data_ptr()) if count else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_reduce(self._h, float(radius_m), op, n_channels, scale, C.c_void_p(values.data_ptr()),
+                                                C.c_void_p(out[0].data_ptr()), pc, self._stream()), 'kb_sense_reduce')
+        return (out[0], out[1]) if count else out[0]
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

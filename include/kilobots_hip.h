@@ -275,6 +275,36 @@ int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, 
                        void *stream);
 int kb_histogram_sectors(int n_sectors, float *xy /* host, [n_sectors / 2 - 1][2] */);
 
+/* IR-range message aggregation on the CURRENT poses, without stepping: every kilobot broadcasts a message of n_channels
+ * floats, and every kilobot i combines, channel by channel, the messages of the kilobots j != i of the same env within IR
+ * range -- the reduction behind gradient (hop-count) formation (min + 1), consensus (mean), leader election (max) and the
+ * sum of a message-passing layer.  ALL kilobots in range take part, however many there are.  No reference counterpart.
+ * Every reduction is independent of the order in which the neighbours are met: no two floats are ever added, so the
+ * result is the same bit for bit in a shard.  Every operation below is one fp32 operation rounded on its own:
+ *   Rw = radius_m * 25, R2 = Rw * Rw (on the host, as kb_sense);  ex = x_j - x_i, ey = y_j - y_i (world units);
+ *   d2 = ex * ex + ey * ey;  j is heard by i iff !(d2 > R2) (the predicate of kb_sense);
+ *   KB_REDUCE_SUM, a fixed-point sum: per broadcast value v, t = v * scale;  q = 0 if t is NaN, otherwise
+ *     q = (int32) rint(clamp(t, -2^21, 2^21)), round half to even (+-inf become +-2^21);  acc = the sum of q_j over the
+ *     kilobots heard, in int32 (1023 * 2^21 < 2^31: no overflow);  out = (float)acc / scale: int -> float to nearest even,
+ *     then one correctly rounded division.  scale must be finite and > 0; with a power of two the quantisation is the only
+ *     rounding.  The sum is exact on the quantised values; the mean is out / count, taken by the caller;
+ *   KB_REDUCE_MIN / KB_REDUCE_MAX, in the total order of the bit patterns: key = bits ^ (bits >> 31 ? 0xFFFFFFFF :
+ *     0x80000000) compared unsigned, so -0 < +0, NaNs with the sign bit clear sort above +inf and those with it set below
+ *     -inf;  out = the value heard whose key is smallest / largest, bit pattern preserved.  scale is ignored;
+ *   nothing heard: SUM gives +0.0, MIN +inf, MAX -inf (the identities: h = min(h, reduce_min(h) + 1) needs no special case).
+ * d_values [num_envs][num_bots][n_channels] float32: what every kilobot broadcasts.
+ * d_out    [num_envs][num_bots][n_channels] float32: what every kilobot has heard.  d_out == d_values (the same pointer)
+ *          is allowed: every env is read whole before any of it is written.  Any other overlap is undefined.
+ * d_count  [num_envs][num_bots] uint32 or NULL: kilobots heard -- what kb_sense writes for this radius.
+ * 1 <= n_channels <= KB_REDUCE_MAX_CHANNELS; op is one of kb_reduce_op; radius_m > 0 (a radius beyond the arena is fine).
+ * Argument errors (NULL sim / d_values / d_out, then op, n_channels, radius_m and, for KB_REDUCE_SUM, scale) are reported
+ * before an unbound handle.  Reads x, y and d_values; writes d_out and d_count only, every element on every call.
+ * Asynchronous on `stream`. */
+enum kb_reduce_op { KB_REDUCE_SUM = 0, KB_REDUCE_MIN = 1, KB_REDUCE_MAX = 2 };
+#define KB_REDUCE_MAX_CHANNELS 8
+int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float scale, const float *d_values, float *d_out,
+                    uint32_t *d_count, void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into
