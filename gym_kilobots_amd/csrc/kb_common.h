@@ -230,6 +230,10 @@ __device__ __forceinline__ void wave_sync() {
 // access through an LDS-qualified pointer, the same via the low half of the address): each made hipcc 7.2 fail in some OTHER
 // instantiation with "Illegal instruction detected: Operand has incorrect register class. V_CMP_NE_U32_e32 0, $src_shared_base",
 // so the flat form stays; it was worth ~ 0.5 % of a cfg3 launch.
+// A fourth form, a plain load between two compiler barriers (`asm volatile("" ::: "memory"); unsigned v = *p_;
+// asm volatile("" : "+v"(v) :: "memory");`), gives the ds_read_b32 in the fixed-size kernels of kb_inst_d0, and fails in
+// kb_inst_d2.hip with the same message: "error: Illegal instruction detected: Operand has incorrect register class.
+// V_CMP_NE_U32_e32 0, $src_shared_base, implicit-def $vcc, implicit $exec".
 __device__ __forceinline__ unsigned lds_load_relaxed(const unsigned *p_) {
     return *reinterpret_cast<const volatile unsigned *>(p_);
 }

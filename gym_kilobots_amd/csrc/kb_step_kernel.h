@@ -629,8 +629,11 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 unsigned cnt = 0, nbb = 0, l0 = 0u, l1 = 0u;
                 for_partners(sa, SC_CX(scell[q]), SC_CY(scell[q]), [&](int sl, int k) __attribute__((always_inline)) {
                     const unsigned e16 = (unsigned)sl | ((unsigned)k << 12);
-                    if (nbb < 2u) l0 |= e16 << (16u * nbb);
-                    else if (nbb < 4u) l1 |= e16 << (16u * (nbb - 2u));
+                    // (selects on the value, not `if (nbb < 2u) l0 |= ...; else l1 |= ...`: the branchy form becomes a store through
+                    //  a selected pointer, which keeps l0 / l1 in scratch memory with a load, a full wait and a store per batch)
+                    const unsigned sh = e16 << (16u * (nbb & 1u));
+                    l0 |= nbb < 2u ? sh : 0u;
+                    l1 |= (nbb >= 2u && nbb < 4u) ? sh : 0u;
                     nbb++;
                     if (((cnt >> (6 * k)) & 63u) == 63u) atomicOr(&misc[M_STATUS], 4u);
                     else cnt += 1u << (6 * k);
@@ -1160,12 +1163,16 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         KB_RETID();
         KB_ABLATE_EXIT(7);     // roots flattened
         // per contact: island size (giant islands force the cooperative sweep) and contacts per wave
+        // (Sorted bins, several waves, solver_mode 0: nobody reads the contacts per wave of the default placement -- the
+        //  placement by size below zeroes and recounts them, and with a giant island or the global staging slice `reg` is false
+        //  whatever they say -- so the eight hot counters are left alone.)
+        const bool wcntDead = BINS && nw > 1 && p.solver_mode == 0;
         auto census = [&](const unsigned *sPair) __attribute__((always_inline)) {
             for (int c = tid; c < ncon; c += nt) {
                 const unsigned root = parent[sPair[c] >> 16];
                 const unsigned n = atomicAdd(&islCnt[root], 1u) + 1u;
                 if (n > (unsigned)GIANT_ISLAND) atomicMax(&misc[M_MAXISL], n);
-                atomicAdd(&misc[M_WCNT + islWave[root]], 1u);
+                if (!wcntDead) atomicAdd(&misc[M_WCNT + islWave[root]], 1u);
             }
         };
         if (big) census(gPair); else census(lPair);
