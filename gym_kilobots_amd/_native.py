@@ -59,6 +59,13 @@ class KbConfig(C.Structure):
     ]
 
 
+class KbOutline(C.Structure):
+    """kb_outline: the geometry kb_sense_objects reads, fixtures grouped by body in stable order (kb_get_outline)."""
+    _fields_ = [('num_objects', C.c_int32), ('num_fixtures', C.c_int32), ('arena', C.c_float * 4),
+                ('body', C.c_int32 * MAX_OBJECTS), ('kind', C.c_int32 * MAX_OBJECTS), ('nverts', C.c_int32 * MAX_OBJECTS),
+                ('radius', C.c_float * MAX_OBJECTS), ('verts', ((C.c_float * 2) * MAX_POLY_VERTS) * MAX_OBJECTS)]
+
+
 class KbResetParams(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('env_offset', C.c_int32), ('mean', C.c_float * 2), ('std', C.c_float),
                 ('random_theta', C.c_int32), ('random_velocity', C.c_int32), ('resolve', C.c_int32)]
@@ -79,7 +86,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -140,6 +147,10 @@ def load():
     lib.kb_histogram_sectors.restype = C.c_int
     lib.kb_sense_reduce.argtypes = [_P, C.c_float, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]
     lib.kb_sense_reduce.restype = C.c_int
+    lib.kb_get_outline.argtypes = [_P, C.POINTER(KbOutline)]
+    lib.kb_get_outline.restype = C.c_int
+    lib.kb_sense_objects.argtypes = [_P, _P, _P, _P]
+    lib.kb_sense_objects.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -205,6 +216,14 @@ def histogram_sectors(n_sectors):
     buf = (C.c_float * (2 * max(rows, 1)))()
     check(load().kb_histogram_sectors(n, buf), 'kb_histogram_sectors')
     return [(buf[2 * m], buf[2 * m + 1]) for m in range(rows)]
+
+
+def outline(handle):
+    """The geometry kb_sense_objects reads for a handle (kb_get_outline) as a KbOutline: the arena bounds and the fixtures
+    grouped by body in stable order, world units; no device and no bound buffers needed."""
+    o = KbOutline()
+    check(load().kb_get_outline(handle, C.byref(o)), 'kb_get_outline')
+    return o
 
 
 def default_config(num_envs, num_bots, drive_mode=DRIVE_VELOCITY, light_type=LIGHT_NONE, **kw):

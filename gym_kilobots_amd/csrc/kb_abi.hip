@@ -1,7 +1,8 @@
 // kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h): argument validation and launches of every entry
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
-// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce) are in kb_sense.h.
+// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects)
+// are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -665,6 +666,45 @@ int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float s
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ReduceLds(p.NP, p.ncell, CP).bytes, (hipStream_t)stream, p, r.reach, r.R2, n_channels, vec,
                        scale, d_values, d_out, d_count);
     return launched("kb_sense_reduce");
+}
+
+int kb_get_outline(const kb_sim *sim, kb_outline *out) {
+    if (!sim || !out) return fail(KB_EINVAL, "kb_get_outline: NULL argument");
+    const Params &p = sim->p;
+    memset(out, 0, sizeof(*out));
+    out->num_objects = p.M;
+    out->arena[0] = p.xmin; out->arena[1] = p.xmax; out->arena[2] = p.ymin; out->arena[3] = p.ymax;
+    int g = 0;
+    for (int b = 0; b < p.M; ++b) {             // grouped by body; within a body the kb_config order
+        for (int f = 0; f < p.F; ++f) {
+            const float *T = p.otab[f];
+            if (ot_body(T) != b) continue;
+            const bool circle = ot_kind(T) == KB_SHAPE_CIRCLE;
+            out->body[g] = b; out->kind[g] = ot_kind(T); out->nverts[g] = circle ? 0 : ot_n(T);
+            out->radius[g] = circle ? T[OT_RADIUS] : 0.0f;
+            for (int i = 0; i < out->nverts[g]; ++i) { out->verts[g][i][0] = T[OT_VERTS + 2 * i]; out->verts[g][i][1] = T[OT_VERTS + 2 * i + 1]; }
+            ++g;
+        }
+    }
+    out->num_fixtures = g;
+    return KB_OK;
+}
+
+int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream) {
+    if (!sim) return fail(KB_EINVAL, "kb_sense_objects: NULL handle");
+    if (!d_obj && !d_wall) return fail(KB_EINVAL, "kb_sense_objects: d_obj and d_wall are both NULL");
+    if (d_obj && sim->cfg.num_objects == 0) return fail(KB_EINVAL, "kb_sense_objects: d_obj given, but the handle has no objects");
+    if ((reinterpret_cast<uintptr_t>(d_obj) | reinterpret_cast<uintptr_t>(d_wall)) & 15u) return fail(KB_EINVAL, "kb_sense_objects: d_obj and d_wall must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_objects: kb_bind() first");
+    const Params &p = sim->p;
+    kb_outline ol;
+    kb_get_outline(sim, &ol);
+    const int threads = p.N < OBJ_TILE ? (p.N + 63) & ~63 : OBJ_TILE;      // one kilobot per lane: no idle waves in a small env
+    const int tiles = (p.N + threads - 1) / threads;
+    hipLaunchKernelGGL(kb_objects_kernel, dim3((unsigned)p.E * (unsigned)tiles), dim3((unsigned)threads), (size_t)ObjectsLds().bytes, (hipStream_t)stream,
+                       ol, p.N, tiles, p.buf.x, p.buf.y, p.buf.theta, p.buf.ox, p.buf.oy, p.buf.otheta,
+                       reinterpret_cast<float4 *>(d_obj), reinterpret_cast<float4 *>(d_wall));
+    return launched("kb_sense_objects");
 }
 
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {

@@ -1,5 +1,6 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS.
+// kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
+// and kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -374,6 +375,127 @@ __global__ void __launch_bounds__(256) kb_reduce_kernel(const Params p, const in
             }
         }
         if (d_count) d_count[o + a] = cnt;
+    }
+}
+
+// ---- kb_sense_objects: the nearest point of every object and of the walls ------------------------------------------------
+#ifndef KB_OBJECTS_TILE
+#define KB_OBJECTS_TILE 256             // kilobots (= lanes) per workgroup of kb_objects_kernel: a multiple of 64 up to 256 (A/B knob)
+#endif
+constexpr int OBJ_TILE = KB_OBJECTS_TILE;
+static_assert(OBJ_TILE % 64 == 0 && OBJ_TILE >= 64 && OBJ_TILE <= 256, "kb_objects_kernel: tile");
+constexpr int OBJ_EDGES = KB_MAX_OBJECTS * KB_MAX_POLY_VERTS;
+struct ObjectsLds {     // byte offsets: frame[M] (float4: ox, oy, sin, cos) at 0, edge[F][4][2] (float4 pairs), fix[F] (nverts, radius), first[M + 1]
+    int edge, fix, first, bytes;
+    __host__ __device__ constexpr ObjectsLds()
+        : edge(16 * KB_MAX_OBJECTS), fix(edge + 32 * OBJ_EDGES), first(fix + 8 * KB_MAX_OBJECTS), bytes(first + 16 * ((KB_MAX_OBJECTS + 4) / 4)) {}
+};
+
+// Object and wall points on the current poses (kb_sense_objects): one kilobot per lane, workgroups over (env, tile of
+// kilobots); no stencil and no cell lists, every kilobot meets every fixture of its env.  Once per workgroup the env's
+// object frames (ox, oy, sin, cos: one kb_sincosf in each of the first M lanes) and the fixture table go to LDS.  The table
+// (kb_outline, fixtures grouped by body on the host) arrives as a kernel argument and is staged edge by edge: lane 4 f + k
+// stores a, e = b - a and e . e of edge k of fixture f -- values every lane would otherwise compute for itself, each a
+// single fp32 operation and therefore the same bits whoever evaluates it.  Lane m stores first[m], the number of fixtures of
+// lower bodies: object m's fixtures are first[m] .. first[m + 1] - 1.  Then every lane runs objects -> fixtures -> edges with
+// the running best (d2, rx, ry) and the inside flag in scalars and all table reads from LDS at addresses that are the same
+// in every lane (broadcasts): no per-object register array is ever indexed by a run-time number, nothing goes to scratch.
+// The loop bounds are the same in all lanes and are made scalar with readfirstlane.  A lane writes the M consecutive rows of
+// its own kilobot, one 16-byte store each (the layout kb_neighbors_kernel uses for its slots), then the wall row.
+__global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline ol, const int N, const int tiles, const float *x, const float *y,
+                                                         const float *theta, const float *ox, const float *oy, const float *otheta,
+                                                         float4 *d_obj, float4 *d_wall) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr ObjectsLds L;
+    float4 *frame = reinterpret_cast<float4 *>(smem);
+    float4 *edge = reinterpret_cast<float4 *>(smem + L.edge);
+    float2 *fix = reinterpret_cast<float2 *>(smem + L.fix);
+    int *first = reinterpret_cast<int *>(smem + L.first);
+    const int tid = threadIdx.x, e = blockIdx.x / tiles, a = (blockIdx.x % tiles) * blockDim.x + tid;
+    const int M = ol.num_objects, F = ol.num_fixtures;
+    if (d_obj) {
+        if (tid < M) {
+            const size_t j = (size_t)e * M + tid;
+            float so, co;
+            kb_sincosf(otheta[j], so, co);
+            frame[tid] = make_float4(ox[j], oy[j], so, co);
+        }
+        if (tid < OBJ_EDGES) {
+            const int f = tid / KB_MAX_POLY_VERTS, k = tid % KB_MAX_POLY_VERTS;
+            const int n = f < F ? ol.nverts[f] : 0;
+            if (k < n) {
+                const int k1 = k + 1 == n ? 0 : k + 1;
+                const float ax = ol.verts[f][k][0], ay = ol.verts[f][k][1], bx = ol.verts[f][k1][0], by = ol.verts[f][k1][1];
+                const float ex = bx - ax, ey = by - ay;
+                edge[2 * tid] = make_float4(ax, ay, ex, ey);
+                edge[2 * tid + 1] = make_float4(bx, by, ex * ex + ey * ey, 0.0f);
+            }
+            if (k == 0 && f < F) fix[f] = make_float2(__int_as_float(n), ol.radius[f]);
+        }
+        if (tid <= M) {
+            int c = 0;
+            for (int f = 0; f < F; ++f) c += ol.body[f] < tid ? 1 : 0;
+            first[tid] = c;
+        }
+        __syncthreads();
+    }
+    if (a >= N) return;
+    const size_t i = (size_t)e * N + a;
+    const float xi = x[i], yi = y[i];
+    float si, ci;
+    kb_sincosf(theta[i], si, ci);
+    if (d_obj) {
+        float4 *row = d_obj + i * (size_t)M;
+        for (int m = 0; m < M; ++m) {
+            const float4 fr = frame[m];
+            const float so = fr.z, co = fr.w;
+            const float dx = xi - fr.x, dy = yi - fr.y;
+            const float px = co * dx + so * dy, py = co * dy - so * dx;
+            float best = INFINITY, brx = 0.0f, bry = 0.0f;
+            bool inside = false;
+            const int f0 = __builtin_amdgcn_readfirstlane(first[m]), f1 = __builtin_amdgcn_readfirstlane(first[m + 1]);
+            for (int f = f0; f < f1; ++f) {
+                const float2 fx = fix[f];
+                const int n = __builtin_amdgcn_readfirstlane(__float_as_int(fx.x));
+                if (n == 0) {
+                    const float r = fx.y;
+                    const float n2 = px * px + py * py;
+                    const float nn = sqrtf(n2);
+                    const float g = nn - r;
+                    float rx = r, ry = 0.0f;
+                    if (nn > 0.0f) { rx = -(g * (px / nn)); ry = -(g * (py / nn)); }
+                    const float d2 = g * g;
+                    if (d2 < best) { best = d2; brx = rx; bry = ry; }
+                    inside = inside || !(g > 0.0f);
+                } else {
+                    bool in_f = true;
+                    for (int k = 0; k < n; ++k) {
+                        const float4 ea = edge[2 * (KB_MAX_POLY_VERTS * f + k)], eb = edge[2 * (KB_MAX_POLY_VERTS * f + k) + 1];
+                        const float ex = ea.z, ey = ea.w;
+                        const float wx = px - ea.x, wy = py - ea.y;
+                        const float t = (wx * ex + wy * ey) / eb.z;
+                        float qx = ea.x + t * ex, qy = ea.y + t * ey;
+                        if (t >= 1.0f) { qx = eb.x; qy = eb.y; }
+                        if (!(t > 0.0f)) { qx = ea.x; qy = ea.y; }
+                        const float rx = qx - px, ry = qy - py;
+                        const float d2 = rx * rx + ry * ry;
+                        if (d2 < best) { best = d2; brx = rx; bry = ry; }
+                        in_f = in_f && ex * wy - ey * wx >= 0.0f;
+                    }
+                    inside = inside || in_f;
+                }
+            }
+            const float gx = co * brx - so * bry, gy = so * brx + co * bry;
+            row[m] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, sqrtf(best) / WORLD_SCALE, inside ? 1.0f : 0.0f);
+        }
+    }
+    if (d_wall) {
+        const float g0 = xi - ol.arena[0], g1 = ol.arena[1] - xi, g2 = yi - ol.arena[2], g3 = ol.arena[3] - yi;
+        float g = g0, gx = -g0, gy = 0.0f, w = 0.0f;
+        if (g1 < g) { g = g1; gx = g1; w = 1.0f; }
+        if (g2 < g) { g = g2; gx = 0.0f; gy = -g2; w = 2.0f; }
+        if (g3 < g) { g = g3; gx = 0.0f; gy = g3; w = 3.0f; }
+        d_wall[i] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, g / WORLD_SCALE, w);
     }
 }
 

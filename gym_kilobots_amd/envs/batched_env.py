@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 **cfg):
+                 object_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -29,7 +29,10 @@ class BatchedKilobotsEnv(object):
         distance and bearing in the kilobot's own frame (KilobotSim.neighbor_histogram): neighbor_histogram() returns it,
         step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing.
         comm_radius: the IR range in metres over which neighbor_reduce(values) aggregates what the kilobots broadcast
-        (KilobotSim.neighbor_reduce).  reset() and step() do not change with it."""
+        (KilobotSim.neighbor_reduce).  reset() and step() do not change with it.
+        object_obs: True adds what a kilobot sees of the objects and the walls: object_points() returns the nearest point of
+        every object and of the arena walls in every kilobot's own frame (KilobotSim.object_points), and step() puts them in
+        its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -71,6 +74,9 @@ class BatchedKilobotsEnv(object):
             if not comm_radius > 0.0:
                 raise ValueError('comm_radius must be positive')
             self.comm_radius = comm_radius
+        if object_obs not in (None, False, True):
+            raise ValueError('object_obs must be True, False or None')
+        self.object_obs = bool(object_obs)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -159,6 +165,12 @@ class BatchedKilobotsEnv(object):
         info = {} if self.neighbor_obs is None else {'neighbors': self.neighbors()}
         if self.histogram_obs is not None:
             info['neighbor_histogram'] = self.neighbor_histogram()
+        if self.object_obs:
+            points = self.object_points()
+            if torch.is_tensor(points):
+                info['walls'] = points
+            else:
+                info['objects'], info['walls'] = points
         return obs, reward, done, info
 
     def neighbors(self):
@@ -174,6 +186,13 @@ class BatchedKilobotsEnv(object):
         if self.histogram_obs is None:
             raise ValueError('create the env with histogram_obs=(radius_m, n_rings, n_sectors) to observe neighbour histograms')
         return self.sim.neighbor_histogram(*self.histogram_obs)
+
+    def object_points(self):
+        """(obj [E, N, M, 4], wall [E, N, 4]) float32 of the current poses -- wall alone in an env without objects -- for
+        an env created with object_obs=True: KilobotSim.object_points."""
+        if not self.object_obs:
+            raise ValueError('create the env with object_obs=True to observe objects and walls')
+        return self.sim.object_points()
 
     def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
         """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env

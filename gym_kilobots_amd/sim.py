@@ -305,6 +305,33 @@ class KilobotSim:
                                                 C.c_void_p(out[0].data_ptr()), pc, self._stream()), 'kb_sense_reduce')
         return (out[0], out[1]) if count else out[0]
 
+    def outline(self):
+        """The geometry object_points() reads (kb_get_outline) as a KbOutline: the arena bounds and the fixtures grouped by
+        body in stable order -- the order that decides ties -- in world units."""
+        return nat.outline(self._h)
+
+    def object_points(self, out=None, walls=True):
+        """Object and wall points on the current poses (kb_sense_objects; no reference counterpart): for every kilobot the
+        nearest point of every object of its env and of the arena walls, in its own frame.  Returns (obj [E, N, M, 4], wall
+        [E, N, 4]) float32: obj = (metres ahead, metres to the left, distance in metres, 1.0 if the kilobot's centre is inside
+        the object else 0.0), one row per object in object order, no range cut; wall = (metres ahead, metres to the left,
+        signed distance in metres -- negative outside the arena --, index of the wall: 0 = xmin, 1 = xmax, 2 = ymin, 3 = ymax).
+        With the centre inside an object the point is the nearest fixture edge, which on an LForm / TForm / CForm may be an
+        interior edge.  walls=False returns obj alone; a sim without objects returns wall alone, and raises ValueError with
+        walls=False.  out: the preallocated contiguous tensor(s) to write into, in the shape of the result."""
+        E, N, M = self.num_envs, self.num_bots, self.num_objects
+        if M == 0 and not walls:
+            raise ValueError('object_points(walls=False) asks for object points, but the sim has no objects')
+        shapes = ([((E, N, M, 4), torch.float32, 'obj')] if M > 0 else []) + ([((E, N, 4), torch.float32, 'wall')] if walls else [])
+        out = self._outputs(out, shapes, 'the tuple (obj, wall)' if len(shapes) == 2 else 'the %s tensor' % shapes[0][2])
+        if any(t.data_ptr() % 16 for t in out):
+            raise ValueError('out: the tensors must be 16-byte aligned')
+        po = C.c_void_p(out[0].data_ptr()) if M > 0 else None
+        pw = C.c_void_p(out[-1].data_ptr()) if walls else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_objects(self._h, po, pw, self._stream()), 'kb_sense_objects')
+        return out if len(out) == 2 else out[0]
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

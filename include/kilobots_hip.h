@@ -305,6 +305,53 @@ enum kb_reduce_op { KB_REDUCE_SUM = 0, KB_REDUCE_MIN = 1, KB_REDUCE_MAX = 2 };
 int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float scale, const float *d_values, float *d_out,
                     uint32_t *d_count, void *stream);
 
+/* Object and wall points on the CURRENT poses, without stepping: for every kilobot i and every pushable object m of its env
+ * the nearest point of the object's outline in the body frame of i, and the nearest point of the arena walls -- what a
+ * decentralised policy sees of the thing it pushes and of what confines it.  Rows are fixed-size, one per object, in object
+ * order; there is no range cut.  No reference counterpart.  Every operation below is one fp32 operation rounded on its own,
+ * with correctly rounded divisions and square roots; all lengths are world units until the final / 25:
+ *   (si, ci) = the library's sine and cosine of theta_i (the Cephes algorithm every kernel uses).
+ *   Per object m, (so, co) = sine and cosine of otheta_m:  dx = x_i - ox_m, dy = y_i - oy_m;  the kilobot in the object's
+ *     frame is px = co * dx + so * dy, py = co * dy - so * dx.
+ *   Candidates come from the fixtures of object m in the order of kb_get_outline:
+ *     polygon (and box) fixture, edge k from a = v[k] to b = v[(k + 1) % n]:  ex = b.x - a.x, ey = b.y - a.y;
+ *       wx = px - a.x, wy = py - a.y;  t = (wx * ex + wy * ey) / (ex * ex + ey * ey);
+ *       q = a if !(t > 0) (NaN included), q = b if t >= 1, otherwise q = (a.x + t * ex, a.y + t * ey);
+ *       rx = q.x - px, ry = q.y - py;  d2 = rx * rx + ry * ry;  cr = ex * wy - ey * wx: the centre is inside the fixture
+ *       iff cr >= 0 on all of its edges;
+ *     circle fixture of radius r (centred on the body origin):  n2 = px * px + py * py, n = sqrt(n2), g = n - r;
+ *       n > 0: rx = -(g * (px / n)), ry = -(g * (py / n));  otherwise (rx, ry) = (r, 0);  d2 = g * g;  inside iff !(g > 0).
+ *   The candidate with the smallest d2 wins (d2 < the best so far, starting from +inf with r = (0, 0)); ties go to the
+ *     earlier candidate: the lower fixture in outline order, then the lower edge.
+ *   gx = co * rx - so * ry, gy = so * rx + co * ry (world frame);
+ *   obj = ((ci * gx + si * gy) / 25 metres ahead, (ci * gy - si * gx) / 25 metres to the left, sqrt(d2) / 25 distance in metres,
+ *          1.0f if the centre is inside ANY fixture of the object, else 0.0f).
+ *   With the centre inside, the point is the nearest fixture EDGE; on a body with several fixtures (LForm, TForm, CForm)
+ *   that may be an interior edge, where two fixtures meet, and not a point of the body's outer outline.
+ *   Walls: g0 = x_i - xmin, g1 = xmax - x_i, g2 = y_i - ymin, g3 = ymax - y_i; the smallest gap g wins, ties go to the lower
+ *     index; a kilobot outside the arena has a negative gap, and that gap wins.  The world vector to the wall point is
+ *     (-g0, 0), (g1, 0), (0, -g2) or (0, g3), rotated like (gx, gy):
+ *   wall = (ahead / 25, left / 25, g / 25 (signed), (float)index).
+ * d_obj  [num_envs][num_bots][num_objects][4] float32, 16-byte aligned, or NULL.
+ * d_wall [num_envs][num_bots][4] float32, 16-byte aligned, or NULL.  Both NULL is KB_EINVAL, and so is a non-NULL d_obj on a
+ * handle with num_objects == 0.  Argument errors are reported before an unbound handle.
+ * Reads x, y, theta, ox, oy, otheta; writes the two outputs only, every element on every call.  Asynchronous on `stream`.
+ *
+ * kb_get_outline: the geometry kb_sense_objects reads, exactly as its kernel is handed it -- the fixture tables kb_create
+ * derived and the arena bounds.  Fixtures are grouped by body in stable order (body 0's fixtures first; within a body they
+ * keep their kb_config order): the order the kernel walks and the order that decides ties.  Host only: needs no device and
+ * no bound buffers. */
+typedef struct kb_outline {
+    int32_t num_objects, num_fixtures;          /* num_fixtures: the fixtures of the handle (>= num_objects) */
+    float arena[4];                             /* xmin, xmax, ymin, ymax in fp32 world units */
+    int32_t body[KB_MAX_OBJECTS], kind[KB_MAX_OBJECTS], nverts[KB_MAX_OBJECTS];  /* per fixture, in the order the kernel visits
+                                                   them: its object, enum kb_shape, vertices (circles: 0, boxes: 4) */
+    float radius[KB_MAX_OBJECTS];               /* circles: world units; polygons and boxes: 0 */
+    float verts[KB_MAX_OBJECTS][KB_MAX_POLY_VERTS][2];  /* body frame (origin), world units; boxes as their 4 SetAsBox vertices */
+} kb_outline;
+int kb_get_outline(const kb_sim *sim, kb_outline *out);
+int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into

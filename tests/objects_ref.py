@@ -1,0 +1,195 @@
+"""Numpy restatement of kb_sense_objects' definition (include/kilobots_hip.h), shared by the object-point tests.
+
+With ft = float32 every operation is its own float32 expression on float32 arrays, so each rounds on its own like the
+kernel's (-ffp-contract=off), and sine and cosine are the oracle library's sincosf: comparisons with the device are by
+equality of the bit patterns.  With ft = float64 the same formulas are evaluated on the same inputs in double (numpy's sine
+and cosine): the quantity the float32 evaluation approximates.  The geometry comes ONLY from kb_get_outline
+(tables(outline)): fixtures in the order the kernel visits them, which is the order that decides ties."""
+import numpy as np
+
+from oracle import oracle as O
+
+
+def tables(ol):
+    """A KbOutline as plain numpy: {'M', 'arena' float32[4], 'fixtures': [{'body', 'kind', 'n', 'radius', 'verts' float32[n, 2]}]}
+    in outline order."""
+    fixtures = []
+    for f in range(ol.num_fixtures):
+        n = int(ol.nverts[f])
+        verts = np.array([[ol.verts[f][i][0], ol.verts[f][i][1]] for i in range(n)], dtype=np.float32).reshape(n, 2)
+        fixtures.append(dict(body=int(ol.body[f]), kind=int(ol.kind[f]), n=n, radius=np.float32(ol.radius[f]), verts=verts))
+    return dict(M=int(ol.num_objects), arena=np.array(list(ol.arena), dtype=np.float32), fixtures=fixtures)
+
+
+def sincos(th, ft):
+    """(sin, cos) of float32 angles: the oracle library's sincosf for ft = float32, numpy's in double otherwise."""
+    th = np.asarray(th, dtype=np.float32)
+    if ft is np.float32:
+        sc = np.array([O.sincosf(float(t)) for t in th.ravel()], dtype=np.float32).reshape(th.shape + (2,))
+        return sc[..., 0], sc[..., 1]
+    return np.sin(th.astype(ft)), np.cos(th.astype(ft))
+
+
+def restate_env(tab, x, y, th, ox, oy, oth, ft=np.float32):
+    """One env: x, y, th [N], ox, oy, oth [M] float32 (world units, radians).  Returns (obj [N, M, 4], wall [N, 4]) of dtype ft
+    and aux = {'winner' [N, M]: ordinal of the winning candidate among the object's candidates; 'ties' [N, M]: candidates
+    whose d2 equals the winner's; 'lo', 'hi' [N, M]: the winner is a polygon edge with t clamped at a (!(t > 0)) / at b
+    (t >= 1); 'second' [N, M]: the distance (world units) of the best candidate that did not win; 'walltie' [N]: walls whose gap equals the winner's}."""
+    for v in (x, y, th, ox, oy, oth):
+        assert v.dtype == np.float32
+    N, M = x.shape[0], tab['M']
+    S = ft(25)
+    xi, yi = x.astype(ft), y.astype(ft)
+    si, ci = sincos(th, ft)
+    so_all, co_all = sincos(oth, ft)
+    obj = np.zeros((N, M, 4), dtype=ft)
+    aux = dict(winner=np.full((N, M), -1), ties=np.zeros((N, M), dtype=int), lo=np.zeros((N, M), dtype=bool), hi=np.zeros((N, M), dtype=bool),
+               second=np.zeros((N, M), dtype=ft))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for m in range(M):
+            so, co = so_all[m], co_all[m]
+            dx = xi - ft(ox[m])
+            dy = yi - ft(oy[m])
+            px = co * dx + so * dy
+            py = co * dy - so * dx
+            best, second = np.full(N, np.inf, dtype=ft), np.full(N, np.inf, dtype=ft)
+            brx, bry = np.zeros(N, dtype=ft), np.zeros(N, dtype=ft)
+            inside = np.zeros(N, dtype=bool)
+            win, ties = np.full(N, -1), np.zeros(N, dtype=int)
+            lo, hi = np.zeros(N, dtype=bool), np.zeros(N, dtype=bool)
+            cand = 0
+
+            def take(d2, rx, ry, clo, chi):
+                nonlocal best, second, brx, bry, win, ties, lo, hi, cand
+                better = d2 < best
+                second = np.where(better, best, np.minimum(second, d2))
+                ties = np.where(better, 1, ties + (d2 == best))
+                brx, bry = np.where(better, rx, brx), np.where(better, ry, bry)
+                win, lo, hi = np.where(better, cand, win), np.where(better, clo, lo), np.where(better, chi, hi)
+                best = np.where(better, d2, best)
+                cand += 1
+
+            for fx in tab['fixtures']:
+                if fx['body'] != m:
+                    continue
+                if fx['n'] == 0:
+                    r = ft(fx['radius'])
+                    n2 = px * px + py * py
+                    nn = np.sqrt(n2)
+                    g = nn - r
+                    pos = nn > 0
+                    rx = np.where(pos, -(g * (px / nn)), r)
+                    ry = np.where(pos, -(g * (py / nn)), ft(0))
+                    d2 = g * g
+                    take(d2, rx, ry, False, False)
+                    inside |= ~(g > 0)
+                    continue
+                v = fx['verts'].astype(ft)
+                in_f = np.ones(N, dtype=bool)
+                for k in range(fx['n']):
+                    a, b = v[k], v[(k + 1) % fx['n']]
+                    ex = b[0] - a[0]
+                    ey = b[1] - a[1]
+                    wx = px - a[0]
+                    wy = py - a[1]
+                    t = (wx * ex + wy * ey) / (ex * ex + ey * ey)
+                    clo, chi = ~(t > 0), t >= 1
+                    qx = np.where(clo, a[0], np.where(chi, b[0], a[0] + t * ex))
+                    qy = np.where(clo, a[1], np.where(chi, b[1], a[1] + t * ey))
+                    rx = qx - px
+                    ry = qy - py
+                    d2 = rx * rx + ry * ry
+                    take(d2, rx, ry, clo, chi)
+                    cr = ex * wy - ey * wx
+                    in_f &= cr >= 0
+                inside |= in_f
+            gx = co * brx - so * bry
+            gy = so * brx + co * bry
+            obj[:, m, 0] = (ci * gx + si * gy) / S
+            obj[:, m, 1] = (ci * gy - si * gx) / S
+            obj[:, m, 2] = np.sqrt(best) / S
+            obj[:, m, 3] = np.where(inside, ft(1), ft(0))
+            aux['winner'][:, m], aux['ties'][:, m], aux['lo'][:, m], aux['hi'][:, m] = win, ties, lo, hi
+            aux['second'][:, m] = np.sqrt(second)
+    ar = tab['arena'].astype(ft)
+    g0 = xi - ar[0]
+    g1 = ar[1] - xi
+    g2 = yi - ar[2]
+    g3 = ar[3] - yi
+    zero = np.zeros(N, dtype=ft)
+    g, gx, gy, w = g0, -g0, zero, np.zeros(N, dtype=ft)
+    for idx, (gk, vx, vy) in enumerate(((g1, g1, zero), (g2, zero, -g2), (g3, zero, g3)), start=1):
+        less = gk < g
+        g, gx, gy, w = np.where(less, gk, g), np.where(less, vx, gx), np.where(less, vy, gy), np.where(less, ft(idx), w)
+    wall = np.stack([(ci * gx + si * gy) / S, (ci * gy - si * gx) / S, g / S, w], -1)
+    aux['walltie'] = sum((gk == g).astype(int) for gk in (g0, g1, g2, g3))
+    assert obj.dtype == ft and wall.dtype == ft
+    return obj, wall, aux
+
+
+def restate(tab, x, y, th, ox=None, oy=None, oth=None, ft=np.float32):
+    """x, y, th [E, N], ox, oy, oth [E, M] float32 (None without objects) -> (obj [E, N, M, 4], wall [E, N, 4], [aux per env])."""
+    E = x.shape[0]
+    none = np.zeros((E, 0), dtype=np.float32)
+    ox, oy, oth = (none if v is None else v for v in (ox, oy, oth))
+    envs = [restate_env(tab, x[e], y[e], th[e], ox[e], oy[e], oth[e], ft) for e in range(E)]
+    return np.stack([o for o, _, _ in envs]), np.stack([w for _, w, _ in envs]), [a for _, _, a in envs]
+
+
+# ---- the object sets of the tests, as kb_config keywords -------------------------------------------------------------------
+def fixtures_kw(num_objects, fixtures):
+    """kb_config keywords for fixtures = [(kb_shape, vertices in world units or None, body, radius in metres)] in declaration
+    order (tests/test_parity_gpu.py::_compound_kw)."""
+    return dict(num_objects=num_objects, num_fixtures=len(fixtures), obj_fixture_body=[f[2] for f in fixtures],
+                obj_shape=[f[0] for f in fixtures], obj_nverts=[0 if f[1] is None or f[0] == 1 else len(f[1]) for f in fixtures],
+                obj_radius=[f[3] for f in fixtures], obj_verts=[[[0.0, 0.0]] if f[1] is None else f[1] for f in fixtures])
+
+
+def box(w_m, h_m):
+    return [[w_m / 2 * 25.0, h_m / 2 * 25.0]]
+
+
+TRIANGLE = [[-1.5, -1.0], [1.5, -1.0], [0.0, 2.0]]
+QUAD = [[-2.0, -1.25], [2.0, -1.5], [1.5, 1.5], [-1.5, 1.25]]
+
+
+def forms_kw():
+    """The reference's LForm (object 0), TForm (1), CForm (2) and a disc (3): 7 + 1 fixtures declared interleaved."""
+    from gym_kilobots_amd.lib.body import TForm
+    from tests.test_parity_gpu import CFORM, LFORM, _reference_polygon_fixtures
+    lf, cf = _reference_polygon_fixtures(LFORM), _reference_polygon_fixtures(CFORM)
+    tf = _reference_polygon_fixtures(TForm._shape_vertices().tolist())
+    return fixtures_kw(4, [(2, cf[0], 2, 0.0), (2, lf[0], 0, 0.0), (2, tf[0], 1, 0.0), (0, None, 3, 0.05), (2, cf[1], 2, 0.0),
+                           (2, tf[1], 1, 0.0), (2, lf[1], 0, 0.0), (2, cf[2], 2, 0.0)])
+
+
+FORMS_ORDER = [1, 6, 2, 5, 0, 4, 7, 3]      # declaration indices of forms_kw grouped by body in stable order
+
+
+def object_sets():
+    """{name: (kb_config keywords, object positions [M, 2] in metres)}: the sets of the sweep."""
+    grid8 = np.array([[x, y] for y in (-0.3, 0.3) for x in (-0.6, -0.2, 0.2, 0.6)])
+    cfg4 = np.array([[0.5, 0.35], [-0.5, 0.35], [-0.5, -0.35], [0.5, -0.35]])
+    mixed = [(0, None, 0, 0.075), (1, box(0.15, 0.1), 1, 0.0), (2, TRIANGLE, 2, 0.0), (2, QUAD, 3, 0.0),
+             (1, box(0.05, 0.2), 4, 0.0), (0, None, 5, 0.04), (2, QUAD, 6, 0.0), (2, TRIANGLE, 7, 0.0)]
+    return {
+        'disc': (dict(num_objects=1, obj_radius=[0.075]), np.array([[0.1, -0.05]])),
+        'boxes': (dict(num_objects=4, obj_shape=[1] * 4, obj_verts=[box(0.15, 0.1)] * 4), cfg4),
+        'mixed': (fixtures_kw(8, mixed), grid8),
+        'forms': (forms_kw(), cfg4),
+    }
+
+
+def spawn_over_objects(E, N, centres_m, seed, sigma=0.06):
+    """Kilobots drawn around the objects (a Gaussian about a randomly chosen centre, so that some are inside), random
+    headings; random object headings.  Returns (xy [E, N, 2] m, th [E, N], objects [E, M, 2] m, oth [E, M])."""
+    rng = np.random.RandomState(seed)
+    M = len(centres_m)
+    objs = np.tile(np.asarray(centres_m, dtype=np.float64)[None], (E, 1, 1)) + rng.uniform(-0.02, 0.02, size=(E, M, 2))
+    pick = rng.randint(0, M, size=(E, N))
+    xy = np.take_along_axis(objs, pick[..., None].repeat(2, -1), 1) + rng.normal(scale=sigma, size=(E, N, 2))
+    return xy, rng.uniform(-np.pi, np.pi, size=(E, N)), objs, rng.uniform(-np.pi, np.pi, size=(E, M))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
