@@ -23,6 +23,8 @@ MAX_NEIGHBORS = 16     # KB_MAX_NEIGHBORS: slots per kilobot of kb_sense_neighbo
 HIST_MAX_RINGS, HIST_MAX_SECTORS, HIST_MAX_BINS = 8, 16, 64     # KB_HIST_MAX_*: bin grid of kb_sense_histogram
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)     # kb_reduce_op: how kb_sense_reduce combines the messages heard
 REDUCE_MAX_CHANNELS = 8     # KB_REDUCE_MAX_CHANNELS: floats per message of kb_sense_reduce
+GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_sense_grid, a bit each
+GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -86,7 +88,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -151,6 +153,10 @@ def load():
     lib.kb_get_outline.restype = C.c_int
     lib.kb_sense_objects.argtypes = [_P, _P, _P, _P]
     lib.kb_sense_objects.restype = C.c_int
+    lib.kb_grid_channels.argtypes = [_P, C.c_int]
+    lib.kb_grid_channels.restype = C.c_int
+    lib.kb_sense_grid.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P]
+    lib.kb_sense_grid.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -206,6 +212,30 @@ def check_reduce(op, n_channels, scale):
     if op == REDUCE_SUM and not 0.0 < scale < float('inf'):
         raise ValueError('scale must be finite and positive')
     return op, n_channels, scale
+
+
+GRID_PLANES = {'count': GRID_COUNT, 'flow': GRID_FLOW, 'objects': GRID_OBJECTS}
+
+
+def check_grid(width, height, planes):
+    """The limits of kb_sense_grid on the grid and the planes (a GRID_* mask or an iterable of 'count' | 'flow' | 'objects');
+    ValueError where the library would answer KB_EINVAL -- but for 'objects' on a handle without objects, which only the
+    handle knows.  Returns (width, height, planes as an integer mask)."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
+        raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
+    if isinstance(planes, str):
+        planes = (planes,)
+    if not isinstance(planes, int):
+        mask = 0
+        for name in planes:
+            if name not in GRID_PLANES:
+                raise ValueError("planes must be a GRID_* mask or made of 'count', 'flow' and 'objects'")
+            mask |= GRID_PLANES[name]
+        planes = mask
+    if isinstance(planes, bool) or planes <= 0 or planes & ~(GRID_COUNT | GRID_FLOW | GRID_OBJECTS):
+        raise ValueError('planes must be a non-empty subset of GRID_COUNT | GRID_FLOW | GRID_OBJECTS')
+    return width, height, planes
 
 
 def histogram_sectors(n_sectors):

@@ -707,6 +707,56 @@ int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream) {
     return launched("kb_sense_objects");
 }
 
+// planes of the grid entries, reported under the caller's name: a non-empty subset of the three bits ...
+static int check_grid_planes(const char *entry, int planes) {
+    if (planes > 0 && !(planes & ~(KB_GRID_COUNT | KB_GRID_FLOW | KB_GRID_OBJECTS))) return KB_OK;
+    return fail(KB_EINVAL, "%s: planes must be a non-empty subset of KB_GRID_COUNT | KB_GRID_FLOW | KB_GRID_OBJECTS", entry);
+}
+// ... and the objects only of a handle that has some
+static int check_grid_objects(const char *entry, const kb_sim *sim, int planes) {
+    if (!(planes & KB_GRID_OBJECTS) || sim->cfg.num_objects > 0) return KB_OK;
+    return fail(KB_EINVAL, "%s: KB_GRID_OBJECTS asked for, but the handle has no objects", entry);
+}
+
+int kb_grid_channels(const kb_sim *sim, int planes) {
+    if (!sim) return fail(KB_EINVAL, "kb_grid_channels: NULL handle");
+    if (check_grid_planes("kb_grid_channels", planes) != KB_OK || check_grid_objects("kb_grid_channels", sim, planes) != KB_OK) return KB_EINVAL;
+    return (planes & KB_GRID_COUNT ? 1 : 0) + (planes & KB_GRID_FLOW ? 2 : 0) + (planes & KB_GRID_OBJECTS ? sim->cfg.num_objects : 0);
+}
+
+int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *stream) {
+    if (!sim || !d_out) return fail(KB_EINVAL, "kb_sense_grid: NULL argument");
+    if (check_grid_planes("kb_sense_grid", planes) != KB_OK) return KB_EINVAL;
+    if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_sense_grid: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
+    if (check_grid_objects("kb_sense_grid", sim, planes) != KB_OK) return KB_EINVAL;
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_grid: kb_bind() first");
+    const Params &p = sim->p;
+    const int C = kb_grid_channels(sim, planes), bots = planes & (KB_GRID_COUNT | KB_GRID_FLOW);
+    const int words = (bots & KB_GRID_COUNT ? 1 : 0) + (bots & KB_GRID_FLOW ? 2 : 0);
+    const float wx = p.xmax - p.xmin, wy = p.ymax - p.ymin;        // (kb_outline.arena is these four)
+    if (bots) {
+        const GridLds L(gw, gh, words);
+        const int vec = gw % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+        const auto fn = bots == KB_GRID_COUNT ? kb_grid_bots_kernel<KB_GRID_COUNT> : bots == KB_GRID_FLOW ? kb_grid_bots_kernel<KB_GRID_FLOW>
+                                                                                   : kb_grid_bots_kernel<KB_GRID_COUNT | KB_GRID_FLOW>;
+        hipLaunchKernelGGL(fn, dim3((unsigned)p.E * (unsigned)L.bands), dim3(256), (size_t)L.bytes, (hipStream_t)stream, p.N, gw, gh, L.bands, L.rows, C, vec,
+                           p.xmin, p.ymin, (float)gw / wx, (float)gh / wy, p.buf.x, p.buf.y, p.buf.theta, d_out);
+        const int rc = launched("kb_sense_grid");
+        if (rc != KB_OK) return rc;
+    }
+    if (planes & KB_GRID_OBJECTS) {
+        kb_outline ol;
+        kb_get_outline(sim, &ol);
+        const int cells = gw * gh;
+        const int threads = cells < 256 ? (cells + 63) & ~63 : 256;        // one cell per lane: no idle waves in a small grid
+        const int tiles = (cells + threads - 1) / threads;
+        hipLaunchKernelGGL(kb_grid_objects_kernel, dim3((unsigned)p.E * (unsigned)tiles), dim3((unsigned)threads), (size_t)ObjectsLds().bytes, (hipStream_t)stream,
+                           ol, gw, gh, tiles, C, words, wx / (float)gw, wy / (float)gh, p.buf.ox, p.buf.oy, p.buf.otheta, d_out);
+        return launched("kb_sense_grid");
+    }
+    return KB_OK;
+}
+
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {
     if (!sim) return fail(KB_EINVAL, "kb_light_sense: NULL handle");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_light_sense: kb_bind() first");

@@ -1,6 +1,7 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
 // kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
-// and kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists.
+// kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; and kb_sense_grid, which bins
+// a whole env into an image of the table for an observer outside it.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -391,54 +392,117 @@ struct ObjectsLds {     // byte offsets: frame[M] (float4: ox, oy, sin, cos) at 
         : edge(16 * KB_MAX_OBJECTS), fix(edge + 32 * OBJ_EDGES), first(fix + 8 * KB_MAX_OBJECTS), bytes(first + 16 * ((KB_MAX_OBJECTS + 4) / 4)) {}
 };
 
+// Pointers into the LDS image of ObjectsLds
+struct ObjectsImage {
+    float4 *frame, *edge;
+    float2 *fix;
+    int *first;
+    __device__ __forceinline__ explicit ObjectsImage(unsigned char *smem) {
+        constexpr ObjectsLds L;
+        frame = reinterpret_cast<float4 *>(smem);
+        edge = reinterpret_cast<float4 *>(smem + L.edge);
+        fix = reinterpret_cast<float2 *>(smem + L.fix);
+        first = reinterpret_cast<int *>(smem + L.first);
+    }
+};
+
+// Once per workgroup (of at least 64 lanes) the object frames of env e (ox, oy, sin, cos: one kb_sincosf in each of the
+// first M lanes) and the fixture table go to LDS.  The table (kb_outline, fixtures grouped by body on the host) arrives as a
+// kernel argument and is staged edge by edge: lane 4 f + k stores a, e = b - a and e . e of edge k of fixture f -- values
+// every lane would otherwise compute for itself, each a single fp32 operation and therefore the same bits whoever evaluates
+// it.  Lane m stores first[m], the number of fixtures of lower bodies: object m's fixtures are first[m] .. first[m + 1] - 1.
+// Ends on a barrier.
+__device__ __forceinline__ void kb_stage_objects(const kb_outline &ol, const ObjectsImage &I, const int e, const int tid,
+                                                 const float *ox, const float *oy, const float *otheta) {
+    const int M = ol.num_objects, F = ol.num_fixtures;
+    if (tid < M) {
+        const size_t j = (size_t)e * M + tid;
+        float so, co;
+        kb_sincosf(otheta[j], so, co);
+        I.frame[tid] = make_float4(ox[j], oy[j], so, co);
+    }
+    if (tid < OBJ_EDGES) {
+        const int f = tid / KB_MAX_POLY_VERTS, k = tid % KB_MAX_POLY_VERTS;
+        const int n = f < F ? ol.nverts[f] : 0;
+        if (k < n) {
+            const int k1 = k + 1 == n ? 0 : k + 1;
+            const float ax = ol.verts[f][k][0], ay = ol.verts[f][k][1], bx = ol.verts[f][k1][0], by = ol.verts[f][k1][1];
+            const float ex = bx - ax, ey = by - ay;
+            I.edge[2 * tid] = make_float4(ax, ay, ex, ey);
+            I.edge[2 * tid + 1] = make_float4(bx, by, ex * ex + ey * ey, 0.0f);
+        }
+        if (k == 0 && f < F) I.fix[f] = make_float2(__int_as_float(n), ol.radius[f]);
+    }
+    if (tid <= M) {
+        int c = 0;
+        for (int f = 0; f < F; ++f) c += ol.body[f] < tid ? 1 : 0;
+        I.first[tid] = c;
+    }
+    __syncthreads();
+}
+
+// The point (xi, yi) against object m of the staged env, fixtures -> edges with the running best candidate in scalars and
+// all table reads from LDS at addresses that are the same in every lane (broadcasts): returns the inside flag (the point is
+// covered by ANY fixture of the object: cr >= 0 on all edges of a polygon, !(g > 0) for a circle) and leaves the nearest
+// candidate in best (d2) and (brx, bry) (object frame).  The ONE definition of the predicate, for kb_objects_kernel and
+// kb_grid_objects_kernel; a caller that drops best, brx and bry leaves their arithmetic to dead-code elimination.  The loop
+// bounds are the same in all lanes and are made scalar with readfirstlane.
+__device__ __forceinline__ bool kb_object_walk(const ObjectsImage &I, const int m, const float4 fr, const float xi, const float yi,
+                                               float &best, float &brx, float &bry) {
+    const float so = fr.z, co = fr.w;
+    const float dx = xi - fr.x, dy = yi - fr.y;
+    const float px = co * dx + so * dy, py = co * dy - so * dx;
+    best = INFINITY; brx = 0.0f; bry = 0.0f;
+    bool inside = false;
+    const int f0 = __builtin_amdgcn_readfirstlane(I.first[m]), f1 = __builtin_amdgcn_readfirstlane(I.first[m + 1]);
+    for (int f = f0; f < f1; ++f) {
+        const float2 fx = I.fix[f];
+        const int n = __builtin_amdgcn_readfirstlane(__float_as_int(fx.x));
+        if (n == 0) {
+            const float r = fx.y;
+            const float n2 = px * px + py * py;
+            const float nn = sqrtf(n2);
+            const float g = nn - r;
+            float rx = r, ry = 0.0f;
+            if (nn > 0.0f) { rx = -(g * (px / nn)); ry = -(g * (py / nn)); }
+            const float d2 = g * g;
+            if (d2 < best) { best = d2; brx = rx; bry = ry; }
+            inside = inside || !(g > 0.0f);
+        } else {
+            bool in_f = true;
+            for (int k = 0; k < n; ++k) {
+                const float4 ea = I.edge[2 * (KB_MAX_POLY_VERTS * f + k)], eb = I.edge[2 * (KB_MAX_POLY_VERTS * f + k) + 1];
+                const float ex = ea.z, ey = ea.w;
+                const float wx = px - ea.x, wy = py - ea.y;
+                const float t = (wx * ex + wy * ey) / eb.z;
+                float qx = ea.x + t * ex, qy = ea.y + t * ey;
+                if (t >= 1.0f) { qx = eb.x; qy = eb.y; }
+                if (!(t > 0.0f)) { qx = ea.x; qy = ea.y; }
+                const float rx = qx - px, ry = qy - py;
+                const float d2 = rx * rx + ry * ry;
+                if (d2 < best) { best = d2; brx = rx; bry = ry; }
+                in_f = in_f && ex * wy - ey * wx >= 0.0f;
+            }
+            inside = inside || in_f;
+        }
+    }
+    return inside;
+}
+
 // Object and wall points on the current poses (kb_sense_objects): one kilobot per lane, workgroups over (env, tile of
 // kilobots); no stencil and no cell lists, every kilobot meets every fixture of its env.  Once per workgroup the env's
-// object frames (ox, oy, sin, cos: one kb_sincosf in each of the first M lanes) and the fixture table go to LDS.  The table
-// (kb_outline, fixtures grouped by body on the host) arrives as a kernel argument and is staged edge by edge: lane 4 f + k
-// stores a, e = b - a and e . e of edge k of fixture f -- values every lane would otherwise compute for itself, each a
-// single fp32 operation and therefore the same bits whoever evaluates it.  Lane m stores first[m], the number of fixtures of
-// lower bodies: object m's fixtures are first[m] .. first[m + 1] - 1.  Then every lane runs objects -> fixtures -> edges with
-// the running best (d2, rx, ry) and the inside flag in scalars and all table reads from LDS at addresses that are the same
-// in every lane (broadcasts): no per-object register array is ever indexed by a run-time number, nothing goes to scratch.
-// The loop bounds are the same in all lanes and are made scalar with readfirstlane.  A lane writes the M consecutive rows of
-// its own kilobot, one 16-byte store each (the layout kb_neighbors_kernel uses for its slots), then the wall row.
+// object frames and the fixture table go to LDS (kb_stage_objects); then every lane runs objects -> fixtures -> edges
+// (kb_object_walk): no per-object register array is ever indexed by a run-time number, nothing goes to scratch.  A lane
+// writes the M consecutive rows of its own kilobot, one 16-byte store each (the layout kb_neighbors_kernel uses for its
+// slots), then the wall row.
 __global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline ol, const int N, const int tiles, const float *x, const float *y,
                                                          const float *theta, const float *ox, const float *oy, const float *otheta,
                                                          float4 *d_obj, float4 *d_wall) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr ObjectsLds L;
-    float4 *frame = reinterpret_cast<float4 *>(smem);
-    float4 *edge = reinterpret_cast<float4 *>(smem + L.edge);
-    float2 *fix = reinterpret_cast<float2 *>(smem + L.fix);
-    int *first = reinterpret_cast<int *>(smem + L.first);
+    const ObjectsImage I(smem);
     const int tid = threadIdx.x, e = blockIdx.x / tiles, a = (blockIdx.x % tiles) * blockDim.x + tid;
-    const int M = ol.num_objects, F = ol.num_fixtures;
-    if (d_obj) {
-        if (tid < M) {
-            const size_t j = (size_t)e * M + tid;
-            float so, co;
-            kb_sincosf(otheta[j], so, co);
-            frame[tid] = make_float4(ox[j], oy[j], so, co);
-        }
-        if (tid < OBJ_EDGES) {
-            const int f = tid / KB_MAX_POLY_VERTS, k = tid % KB_MAX_POLY_VERTS;
-            const int n = f < F ? ol.nverts[f] : 0;
-            if (k < n) {
-                const int k1 = k + 1 == n ? 0 : k + 1;
-                const float ax = ol.verts[f][k][0], ay = ol.verts[f][k][1], bx = ol.verts[f][k1][0], by = ol.verts[f][k1][1];
-                const float ex = bx - ax, ey = by - ay;
-                edge[2 * tid] = make_float4(ax, ay, ex, ey);
-                edge[2 * tid + 1] = make_float4(bx, by, ex * ex + ey * ey, 0.0f);
-            }
-            if (k == 0 && f < F) fix[f] = make_float2(__int_as_float(n), ol.radius[f]);
-        }
-        if (tid <= M) {
-            int c = 0;
-            for (int f = 0; f < F; ++f) c += ol.body[f] < tid ? 1 : 0;
-            first[tid] = c;
-        }
-        __syncthreads();
-    }
+    const int M = ol.num_objects;
+    if (d_obj) kb_stage_objects(ol, I, e, tid, ox, oy, otheta);
     if (a >= N) return;
     const size_t i = (size_t)e * N + a;
     const float xi = x[i], yi = y[i];
@@ -447,44 +511,10 @@ __global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline o
     if (d_obj) {
         float4 *row = d_obj + i * (size_t)M;
         for (int m = 0; m < M; ++m) {
-            const float4 fr = frame[m];
+            const float4 fr = I.frame[m];
             const float so = fr.z, co = fr.w;
-            const float dx = xi - fr.x, dy = yi - fr.y;
-            const float px = co * dx + so * dy, py = co * dy - so * dx;
-            float best = INFINITY, brx = 0.0f, bry = 0.0f;
-            bool inside = false;
-            const int f0 = __builtin_amdgcn_readfirstlane(first[m]), f1 = __builtin_amdgcn_readfirstlane(first[m + 1]);
-            for (int f = f0; f < f1; ++f) {
-                const float2 fx = fix[f];
-                const int n = __builtin_amdgcn_readfirstlane(__float_as_int(fx.x));
-                if (n == 0) {
-                    const float r = fx.y;
-                    const float n2 = px * px + py * py;
-                    const float nn = sqrtf(n2);
-                    const float g = nn - r;
-                    float rx = r, ry = 0.0f;
-                    if (nn > 0.0f) { rx = -(g * (px / nn)); ry = -(g * (py / nn)); }
-                    const float d2 = g * g;
-                    if (d2 < best) { best = d2; brx = rx; bry = ry; }
-                    inside = inside || !(g > 0.0f);
-                } else {
-                    bool in_f = true;
-                    for (int k = 0; k < n; ++k) {
-                        const float4 ea = edge[2 * (KB_MAX_POLY_VERTS * f + k)], eb = edge[2 * (KB_MAX_POLY_VERTS * f + k) + 1];
-                        const float ex = ea.z, ey = ea.w;
-                        const float wx = px - ea.x, wy = py - ea.y;
-                        const float t = (wx * ex + wy * ey) / eb.z;
-                        float qx = ea.x + t * ex, qy = ea.y + t * ey;
-                        if (t >= 1.0f) { qx = eb.x; qy = eb.y; }
-                        if (!(t > 0.0f)) { qx = ea.x; qy = ea.y; }
-                        const float rx = qx - px, ry = qy - py;
-                        const float d2 = rx * rx + ry * ry;
-                        if (d2 < best) { best = d2; brx = rx; bry = ry; }
-                        in_f = in_f && ex * wy - ey * wx >= 0.0f;
-                    }
-                    inside = inside || in_f;
-                }
-            }
+            float best, brx, bry;
+            const bool inside = kb_object_walk(I, m, fr, xi, yi, best, brx, bry);
             const float gx = co * brx - so * bry, gy = so * brx + co * bry;
             row[m] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, sqrtf(best) / WORLD_SCALE, inside ? 1.0f : 0.0f);
         }
@@ -496,6 +526,103 @@ __global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline o
         if (g2 < g) { g = g2; gx = 0.0f; gy = -g2; w = 2.0f; }
         if (g3 < g) { g = g3; gx = 0.0f; gy = g3; w = 3.0f; }
         d_wall[i] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, g / WORLD_SCALE, w);
+    }
+}
+
+// ---- kb_sense_grid: top-down occupancy grids of every env ----------------------------------------------------------------
+constexpr int GRID_LDS_LIMIT = 64 * 1024;       // the default limit for dynamic LDS: no attribute to raise
+struct GridLds {        // the int32 counters of one band of rows, plane by plane: acc[words][rows][gw] (count, sum of qc, sum of qs)
+    int bands, rows, plane, bytes;      // bands per env; rows per band (the last band may hold fewer); words per plane; the image
+    static constexpr int max_rows(int gw, int words) { return GRID_LDS_LIMIT / (4 * words * gw); }
+    // the fewest bands whose image stays within the limit, then rows spread evenly over them
+    __host__ __device__ constexpr GridLds(int gw, int gh, int words)
+        : bands((gh + max_rows(gw, words) - 1) / max_rows(gw, words)), rows((gh + bands - 1) / bands), plane(rows * gw), bytes(4 * words * plane) {}
+};
+static_assert(GridLds(64, 48, 3).bands == 1 && GridLds(64, 48, 3).bytes == 36 * 1024, "kb_grid_bots_kernel: one band of 36 KiB");
+static_assert(GridLds(KB_GRID_MAX_SIDE, KB_GRID_MAX_SIDE, 3).bytes <= GRID_LDS_LIMIT && GridLds(KB_GRID_MAX_SIDE, KB_GRID_MAX_SIDE, 1).bytes <= GRID_LDS_LIMIT,
+              "kb_grid_bots_kernel: LDS image");
+
+// The kilobot planes of kb_sense_grid: one workgroup per (env, band of rows), the band's counters as int32 words in LDS.  The
+// workgroup zeroes them, reads the env's x, y once (coalesced, up to four kilobots per lane; theta only with the flow and only
+// of the kilobots of its band), bins every kilobot and adds those of its band into LDS with atomics whose result is not
+// used (ds_add_u32: nothing comes back); all 1024 kilobots in one cell serialise on one word and stay correct.  After one
+// barrier the planes go out as floats, consecutive lanes to consecutive words (the rows of a band are contiguous in a
+// channel), 16 bytes per lane with vec (gw a multiple of 4 and d_out 16-byte aligned: every band of every channel then starts
+// on 16 bytes, in LDS and in d_out).  Every output word is written exactly once, by a plain store: no global atomics, no
+// cleared buffer.  No two floats are ever added: the flow is the integer sum of the fixed-point images of kb_reduce_quant.
+// PL: KB_GRID_COUNT | KB_GRID_FLOW, the planes asked for; their channels are the first of the env's C.  bands, band_rows: of GridLds.
+template <int PL>
+__global__ void __launch_bounds__(256) kb_grid_bots_kernel(const int N, const int gw, const int gh, const int bands, const int band_rows, const int C,
+                                                           const int vec, const float xmin, const float ymin, const float icw, const float ich,
+                                                           const float *x, const float *y, const float *theta, float *d_out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr bool COUNT = (PL & KB_GRID_COUNT) != 0, FLOW = (PL & KB_GRID_FLOW) != 0;
+    constexpr int W = (COUNT ? 1 : 0) + (FLOW ? 2 : 0);
+    static_assert(W > 0, "kb_grid_bots_kernel: no plane");
+    const int tid = threadIdx.x, nt = blockDim.x, e = blockIdx.x / bands, row0 = (blockIdx.x % bands) * band_rows;
+    const int rows = min(band_rows, gh - row0), plane = band_rows * gw;      // (GridLds: sized on the host)
+    int *acc = reinterpret_cast<int *>(smem);
+    for (int f = tid; f < W * plane; f += nt) acc[f] = 0;
+    __syncthreads();
+    const size_t o = (size_t)e * N;
+    for (int b = tid; b < N; b += nt) {
+        const float tx = (x[o + b] - xmin) * icw, ty = (y[o + b] - ymin) * ich;
+        const int ix = !(tx > 0.0f) ? 0 : tx >= (float)gw ? gw - 1 : (int)tx;
+        const int iy = !(ty > 0.0f) ? 0 : ty >= (float)gh ? gh - 1 : (int)ty;
+        const int r = iy - row0;
+        if (r < 0 || r >= rows) continue;
+        int *c = acc + r * gw + ix;
+        if (COUNT) {
+            atomicAdd(c, 1);
+            c += plane;
+        }
+        if (FLOW) {
+            float sn, cs;
+            kb_sincosf(theta[o + b], sn, cs);
+            atomicAdd(c, kb_reduce_quant(cs, 65536.0f));
+            atomicAdd(c + plane, kb_reduce_quant(sn, 65536.0f));
+        }
+    }
+    __syncthreads();
+    const size_t chan = (size_t)gh * gw;
+    float *band = d_out + ((size_t)e * C * gh + row0) * gw;     // the band's first row in channel 0 of the env
+    const int n = rows * gw;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const float div = COUNT && w == 0 ? 1.0f : 65536.0f;        // (a division by 1 is exact: the count is the float of the integer)
+        const int *src = acc + w * plane;
+        float *dst = band + w * chan;
+        if (vec) {
+            for (int f = tid; f < n / 4; f += nt) {
+                const int4 v = reinterpret_cast<const int4 *>(src)[f];
+                reinterpret_cast<float4 *>(dst)[f] = make_float4((float)v.x / div, (float)v.y / div, (float)v.z / div, (float)v.w / div);
+            }
+        } else {
+            for (int f = tid; f < n; f += nt) dst[f] = (float)src[f] / div;
+        }
+    }
+}
+
+// The object planes of kb_sense_grid: one lane per cell, workgroups over (env, tile of cells); the env's object frames and the
+// fixture table are staged as in kb_objects_kernel and every lane asks kb_object_walk whether its cell centre is covered,
+// object by object.  Lanes of a wave hold consecutive cells: each object's store is one run of consecutive words.
+// ch0: the first object channel among the env's C.
+__global__ void __launch_bounds__(256) kb_grid_objects_kernel(const kb_outline ol, const int gw, const int gh, const int tiles, const int C, const int ch0,
+                                                              const float cw, const float ch, const float *ox, const float *oy, const float *otheta,
+                                                              float *d_out) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const ObjectsImage I(smem);
+    const int tid = threadIdx.x, e = blockIdx.x / tiles, cell = (blockIdx.x % tiles) * blockDim.x + tid;
+    const int M = ol.num_objects;
+    kb_stage_objects(ol, I, e, tid, ox, oy, otheta);
+    if (cell >= gw * gh) return;
+    const int iy = cell / gw, ix = cell - iy * gw;
+    const float cx = ol.arena[0] + ((float)ix + 0.5f) * cw, cy = ol.arena[2] + ((float)iy + 0.5f) * ch;
+    const size_t chan = (size_t)gh * gw;
+    float *out = d_out + ((size_t)e * C + ch0) * chan + cell;
+    for (int m = 0; m < M; ++m) {
+        float best, brx, bry;
+        out[m * chan] = kb_object_walk(I, m, I.frame[m], cx, cy, best, brx, bry) ? 1.0f : 0.0f;
     }
 }
 

@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, **cfg):
+                 object_obs=None, grid_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -32,7 +32,10 @@ class BatchedKilobotsEnv(object):
         (KilobotSim.neighbor_reduce).  reset() and step() do not change with it.
         object_obs: True adds what a kilobot sees of the objects and the walls: object_points() returns the nearest point of
         every object and of the arena walls in every kilobot's own frame (KilobotSim.object_points), and step() puts them in
-        its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added."""
+        its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added.
+        grid_obs: (width, height) or (width, height, planes) adds what a CENTRAL policy is fed, a fixed-size image of the
+        whole table: occupancy_grid() returns [E, C, height, width] (KilobotSim.occupancy_grid; planes made of 'count',
+        'flow' and 'objects', default ('count',)), and step() puts it in its info dict under 'grid'.  None adds nothing."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -77,6 +80,15 @@ class BatchedKilobotsEnv(object):
         if object_obs not in (None, False, True):
             raise ValueError('object_obs must be True, False or None')
         self.object_obs = bool(object_obs)
+        self.grid_obs = None
+        if grid_obs is not None:
+            try:
+                width, height, planes = tuple(grid_obs) if len(grid_obs) == 3 else tuple(grid_obs) + (('count',),)
+                self.grid_obs = nat.check_grid(width, height, planes)
+            except TypeError as err:
+                raise ValueError('grid_obs must be (width, height) or (width, height, planes): %s' % err)
+            if self.grid_obs[2] & nat.GRID_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
+                raise ValueError("grid_obs: 'objects' asked for, but the env has no objects")
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -171,6 +183,8 @@ class BatchedKilobotsEnv(object):
                 info['walls'] = points
             else:
                 info['objects'], info['walls'] = points
+        if self.grid_obs is not None:
+            info['grid'] = self.occupancy_grid()
         return obs, reward, done, info
 
     def neighbors(self):
@@ -193,6 +207,13 @@ class BatchedKilobotsEnv(object):
         if not self.object_obs:
             raise ValueError('create the env with object_obs=True to observe objects and walls')
         return self.sim.object_points()
+
+    def occupancy_grid(self):
+        """grid [E, C, height, width] float32 of the current poses for the grid_obs=(width, height[, planes]) the env was
+        created with: KilobotSim.occupancy_grid."""
+        if self.grid_obs is None:
+            raise ValueError('create the env with grid_obs=(width, height[, planes]) to observe occupancy grids')
+        return self.sim.occupancy_grid(*self.grid_obs)
 
     def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
         """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env

@@ -332,6 +332,32 @@ class KilobotSim:
             nat.check(self._lib.kb_sense_objects(self._h, po, pw, self._stream()), 'kb_sense_objects')
         return out if len(out) == 2 else out[0]
 
+    def grid_channels(self, planes=('count',)):
+        """The channels of occupancy_grid() for these planes (kb_grid_channels): 1 for 'count', 2 for 'flow', one per object
+        for 'objects'.  ValueError for 'objects' on a sim without objects."""
+        planes = nat.check_grid(1, 1, planes)[2]
+        if planes & nat.GRID_OBJECTS and self.num_objects == 0:
+            raise ValueError("planes: 'objects' asked for, but the sim has no objects")
+        n = self._lib.kb_grid_channels(self._h, planes)
+        if n < 0:
+            nat.check(n, 'kb_grid_channels')
+        return n
+
+    def occupancy_grid(self, width, height, planes=('count',), out=None):
+        """Top-down occupancy grids on the current poses (kb_sense_grid; no reference counterpart): the arena of every env cut
+        into width x height equal cells, row 0 at ymin and column 0 at xmin -- the fixed-size image of the table a central
+        policy is fed.  planes: a GRID_* mask or an iterable of 'count' (1 channel: kilobots in the cell), 'flow' (2 channels:
+        the sums of cos(theta) and of sin(theta) over the kilobots in the cell, fixed-point sums at 2^-16 that do not depend on
+        the order) and 'objects' (one channel per object: 1.0 where the cell centre is inside the object); the channels come in
+        that order.  A kilobot outside the arena counts in the nearest edge cell.  Returns [E, C, height, width] float32 on the
+        sim's device.  out: a preallocated contiguous tensor of that shape to write into; every element is written."""
+        width, height, planes = nat.check_grid(width, height, planes)
+        channels = self.grid_channels(planes)
+        out, = self._outputs(out, [((self.num_envs, channels, height, width), torch.float32, 'grid')], 'the grid tensor')
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_grid(self._h, width, height, planes, C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense_grid')
+        return out
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

@@ -352,6 +352,46 @@ typedef struct kb_outline {
 int kb_get_outline(const kb_sim *sim, kb_outline *out);
 int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream);
 
+/* Top-down occupancy grids on the CURRENT poses, without stepping: a fixed-size image of the table of every env -- where the
+ * kilobots are, which way they face, where each object lies -- for a CENTRAL observer that watches the whole table and moves
+ * the light (KilobotsEnv.get_observation, yaml_kilobots_env.py:149-192).  No reference counterpart.  The arena is cut into
+ * gw x gh equal cells; row iy = 0 is the ymin edge, column ix = 0 the xmin edge.  Every operation below is one fp32 operation
+ * rounded on its own, with correctly rounded divisions:
+ *   Host constants: (xmin, xmax, ymin, ymax) = kb_outline.arena;  cw = (xmax - xmin) / (float)gw, icw = (float)gw / (xmax - xmin);
+ *     ch = (ymax - ymin) / (float)gh, ich = (float)gh / (ymax - ymin): one subtraction and one division each.
+ *   Cell of kilobot i:  tx = (x_i - xmin) * icw;  ix = 0 if !(tx > 0) (NaN included), gw - 1 if tx >= (float)gw, otherwise
+ *     (int)tx (truncation);  iy likewise from y_i, ymin, ich and gh.  A kilobot outside the arena lands in the nearest edge
+ *     cell, so the count plane of an env always sums to exactly num_bots.
+ *   KB_GRID_COUNT, 1 channel: the number of kilobots of the env in the cell, as (float) of the integer (at most 1024: exact).
+ *   KB_GRID_FLOW, 2 channels: with (s, c) = the library's sine and cosine of theta_i (the Cephes algorithm every kernel
+ *     uses), qc and qs = the fixed-point images of c and s at scale 65536 exactly as KB_REDUCE_SUM quantises a broadcast value
+ *     (t = v * 65536; q = 0 if t is NaN, otherwise (int32) rint(clamp(t, -2^21, 2^21)), round half to even);  acc = the int32
+ *     sum of qc (first channel), of qs (second channel) over the kilobots of the cell (1024 * 2^16 = 2^26: no overflow);
+ *     out = (float)acc / 65536.0f: int -> float to nearest even, then one division.  No two floats are ever added: the result
+ *     does not depend on the order of the kilobots.  A heading that is not finite contributes whatever the library's sine and
+ *     cosine give for it, and a NaN among them counts as 0.
+ *   KB_GRID_OBJECTS, num_objects channels: channel m is 1.0f at cell (iy, ix) if the cell centre
+ *     cx = xmin + ((float)ix + 0.5f) * cw, cy = ymin + ((float)iy + 0.5f) * ch  is inside ANY fixture of object m, else 0.0f.
+ *     The predicate is the inside flag of kb_sense_objects, taken over unchanged: in the frame (so, co) of otheta_m a polygon
+ *     or box fixture covers the centre iff cr >= 0 on all of its edges, a circle iff !(g > 0); the fixtures are those of
+ *     kb_get_outline.  It is the fourth word of kb_sense_objects' row for a kilobot whose centre is the cell centre.
+ * d_out [num_envs][C][gh][gw] float32, float aligned; C = kb_grid_channels: the channels of the selected planes in the order
+ *       count, flow-cos, flow-sin, object 0 .. num_objects - 1.
+ * planes: a non-empty subset of KB_GRID_COUNT | KB_GRID_FLOW | KB_GRID_OBJECTS;  1 <= gw, gh <= KB_GRID_MAX_SIDE.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_out;  planes;  gw, gh;  KB_GRID_OBJECTS on
+ * a handle with num_objects == 0.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, theta, ox, oy, otheta; writes d_out only: every element on every call, zeros included (d_out need not be
+ * cleared).  At most two launches, none for planes that were not asked for.  Asynchronous on `stream`.
+ *
+ * kb_grid_channels: C for this handle and these planes, or KB_EINVAL (NULL sim, planes not such a subset, KB_GRID_OBJECTS
+ * without objects).  Host only: needs no device and no bound buffers. */
+#define KB_GRID_COUNT   1   /* 1 channel: kilobots per cell */
+#define KB_GRID_FLOW    2   /* 2 channels: per cell the sum of cos(theta), then of sin(theta) */
+#define KB_GRID_OBJECTS 4   /* num_objects channels: cell centre covered by object m */
+#define KB_GRID_MAX_SIDE 128
+int kb_grid_channels(const kb_sim *sim, int planes);
+int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into
