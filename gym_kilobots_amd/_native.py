@@ -24,6 +24,7 @@ HIST_MAX_RINGS, HIST_MAX_SECTORS, HIST_MAX_BINS = 8, 16, 64     # KB_HIST_MAX_*:
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)     # kb_reduce_op: how kb_sense_reduce combines the messages heard
 REDUCE_MAX_CHANNELS = 8     # KB_REDUCE_MAX_CHANNELS: floats per message of kb_sense_reduce
 GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_sense_grid, a bit each
+MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense_contacts
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
@@ -88,7 +89,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads',
            'kb_last_error', 'kb_version']
 
@@ -157,6 +158,8 @@ def load():
     lib.kb_grid_channels.restype = C.c_int
     lib.kb_sense_grid.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P]
     lib.kb_sense_grid.restype = C.c_int
+    lib.kb_sense_contacts.argtypes = [_P, C.c_int, C.c_float, _P, _P, _P, _P, _P]
+    lib.kb_sense_contacts.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]

@@ -1,8 +1,8 @@
 // kb_abi.hip -- the C ABI of libkilobots_hip.so (include/kilobots_hip.h): argument validation and launches of every entry
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
-// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects)
-// are in kb_sense.h.
+// kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
+// kb_sense_grid, kb_sense_contacts) are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -755,6 +755,28 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
         return launched("kb_sense_grid");
     }
     return KB_OK;
+}
+
+int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float *d_impulse, float *d_touch, float *d_obj, void *stream) {
+    if (!sim) return fail(KB_EINVAL, "kb_sense_contacts: NULL handle");
+    if (!d_partner != !d_impulse) return fail(KB_EINVAL, "kb_sense_contacts: d_partner and d_impulse go together: both or neither");
+    if (d_partner && (k < 1 || k > KB_MAX_CONTACT_SLOTS)) return fail(KB_EINVAL, "kb_sense_contacts: 1 <= k <= KB_MAX_CONTACT_SLOTS (16) required");
+    if (!(scale > 0.0f && scale < INFINITY)) return fail(KB_EINVAL, "kb_sense_contacts: scale must be finite and positive");
+    if (!d_partner && !d_touch && !d_obj) return fail(KB_EINVAL, "kb_sense_contacts: all outputs are NULL");
+    if (d_obj && sim->cfg.num_objects == 0) return fail(KB_EINVAL, "kb_sense_contacts: d_obj given, but the handle has no objects");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_contacts: kb_bind() first");
+    const Params &p = sim->p;
+    ContactsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = p.N; a.M = p.M; a.F = p.F; a.cap = p.cap;
+    for (int f = 0; f < p.F; ++f) a.body[f] = ot_body(p.otab[f]);       // (kb_create checked 0 <= body < M)
+    const int lists = d_partner != nullptr;
+    const int vec = (lists && k % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_partner) | reinterpret_cast<uintptr_t>(d_impulse)) & 15u) == 0 ? 1 : 0)
+                  | ((reinterpret_cast<uintptr_t>(d_touch) & 15u) == 0 ? 2 : 0);
+    const auto fn = !lists ? kb_contacts_kernel<0> : k <= 4 ? kb_contacts_kernel<4> : k <= 8 ? kb_contacts_kernel<8> : kb_contacts_kernel<16>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ContactsLds(p.N).bytes, (hipStream_t)stream, a, k, vec, scale,
+                       p.buf.ws_key, p.buf.ws_acc, p.buf.ws_cnt, reinterpret_cast<uint2 *>(p.buf.scratch), d_partner, d_impulse, d_touch, d_obj);
+    return launched("kb_sense_contacts");
 }
 
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {

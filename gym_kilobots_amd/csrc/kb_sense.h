@@ -1,7 +1,8 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
 // kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
-// kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; and kb_sense_grid, which bins
-// a whole env into an image of the table for an observer outside it.
+// kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
+// a whole env into an image of the table for an observer outside it; and kb_sense_contacts, which reads no poses at all but
+// the contact store the last step left.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -623,6 +624,206 @@ __global__ void __launch_bounds__(256) kb_grid_objects_kernel(const kb_outline o
     for (int m = 0; m < M; ++m) {
         float best, brx, bry;
         out[m * chan] = kb_object_walk(I, m, I.frame[m], cx, cy, best, brx, bry) ? 1.0f : 0.0f;
+    }
+}
+
+// ---- kb_sense_contacts: touch and push sensing from the warm-start store ---------------------------------------------------
+constexpr unsigned WS_WALL = 0x10000u, WS_OBJ = 0x20000u;      // the key classes the step writes into ws_key
+struct ContactsArgs {       // the handle's fixture -> body table (kb_config numbering) and what the kernel needs of Params
+    int N, M, F, cap;
+    int body[KB_MAX_OBJECTS];
+};
+struct ContactsLds {        // byte offsets of u32 arrays: off[NP4 + 1] at 0, ioff[NP4 + 1], icnt[NP4], qin[NP4], own[NP4], oacc[2 M], fb[F], wsum[4]
+    int NP4, ioff, icnt, qin, own, oacc, fb, wsum, bytes;
+    __host__ __device__ constexpr ContactsLds(int N)
+        : NP4((N + 3) & ~3), ioff(4 * (NP4 + 4)), icnt(2 * ioff), qin(icnt + 4 * NP4), own(qin + 4 * NP4), oacc(own + 4 * NP4),
+          fb(oacc + 8 * KB_MAX_OBJECTS), wsum(fb + 4 * KB_MAX_OBJECTS), bytes(wsum + 16) {}
+};
+static_assert(ContactsLds(KB_MAX_BOTS).bytes <= 64 * 1024, "kb_contacts_kernel: LDS image");
+
+// Exclusive scan in place of the NP4 (a multiple of 4, <= 4 * blockDim.x) u32 words of v, which start on 16 bytes; v[NP4]
+// receives the total.  All threads must call; two workgroup barriers inside, the second behind the last store.
+__device__ __forceinline__ void kb_block_scan_u32(unsigned *v, const int NP4, unsigned *wsum, const int tid) {
+    const int lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const bool in = 4 * tid < NP4;
+    const uint4 c = in ? reinterpret_cast<const uint4 *>(v)[tid] : make_uint4(0u, 0u, 0u, 0u);
+    const unsigned sum = c.x + c.y + c.z + c.w;
+    const unsigned incl = wave_incl_scan(sum);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    unsigned base = incl - sum;
+    for (int w = 0; w < nw; ++w) { const unsigned s = wsum[w]; if (w < wave) base += s; }
+    if (in) {
+        uint4 r;
+        r.x = base; r.y = r.x + c.x; r.z = r.y + c.y; r.w = r.z + c.z;
+        reinterpret_cast<uint4 *>(v)[tid] = r;
+        if (4 * tid + 4 == NP4) v[NP4] = r.w + c.w;
+    }
+    __syncthreads();
+}
+
+// What entry `key` of kilobot a is: 0 nothing (a key of no class, the kilobot itself), 1 a kilobot, 2 a wall, 3 a fixture;
+// code: the public partner code (kilobot; N + wall in the order of kb_sense_objects; N + 4 + object), sub: the fixture.
+__device__ __forceinline__ int kb_contact_class(const unsigned key, const int a, const int N, const int F, const unsigned *fb,
+                                                unsigned &code, unsigned &sub) {
+    sub = 0u;
+    if (key < (unsigned)N) { code = key; return key != (unsigned)a ? 1 : 0; }
+    const unsigned w = key - WS_WALL;
+    if (w < 4u) { code = (unsigned)N + ((w & 1u) << 1 | w >> 1); return 2; }      // store: xmin ymin xmax ymax; public: xmin xmax ymin ymax
+    const unsigned f = key - WS_OBJ;
+    if (key >= WS_OBJ && f < (unsigned)F) { code = (unsigned)N + 4u + fb[f]; sub = f; return 3; }
+    code = 0u;
+    return 0;
+}
+
+// Touch and push sensing from the contact store of the last step (kb_sense_contacts): one workgroup per env, one kilobot per
+// lane and pass.  The store lists a kilobot-kilobot contact under one of its two kilobots only; every kilobot reports it.
+//   1. ws_cnt -> off (u32: a store past its capacity may count more than 65535 entries), exclusive scan (kb_block_scan_u32).
+//   2. Owner pass: every kilobot walks its own entries (those behind the capacity were never stored).  Wall and fixture
+//      entries count in its registers; a kilobot entry counts there and adds 1 to icnt[partner] and the fixed-point image of
+//      its impulse (kb_reduce_quant) to qin[partner] with LDS atomics whose result is not used -- integer adds, so the sums
+//      do not depend on the order.  Fixture entries add likewise to the 2 M words of the object rows.
+//   3. K > 0: icnt -> ioff, scan, and every owner hands each kilobot entry to its partner as (owner, impulse bits), 8 bytes,
+//      at ioff[partner] + a cursor (icnt, counted down) in the env's slice of kb_buffers.scratch: at most one record per
+//      stored entry, cap * 8 of the slice's cap * 32 bytes.  The records change hands through global memory: __syncthreads().
+//   4. Gather: every kilobot runs its own and its incoming entries down the compare-exchange chain of kb_neighbors_kernel on
+//      ((code * 8 + fixture) << 32) | impulse bits -- best[] is indexed by constants only and stays in registers -- so
+//      neither the order of the store nor that of the cursors shows.  Rows go out per lane, 16 bytes per store with vec.
+// K: the requested k rounded up to 4, 8 or 16; 0: no lists (steps 3 and the chain are not compiled).
+template <int K>
+__global__ void __launch_bounds__(256) kb_contacts_kernel(const ContactsArgs A, const int k, const int vec, const float scale, const unsigned *ws_key,
+                                                          const float *ws_acc, const unsigned char *ws_cnt, uint2 *slice, int *d_partner,
+                                                          float *d_impulse, float *d_touch, float *d_obj) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr unsigned long long NONE = ~0ull;
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = A.N, M = A.M, F = A.F, cap = A.cap;
+    const ContactsLds L(N);
+    unsigned *off = reinterpret_cast<unsigned *>(smem);
+    unsigned *ioff = reinterpret_cast<unsigned *>(smem + L.ioff);
+    unsigned *icnt = reinterpret_cast<unsigned *>(smem + L.icnt);
+    unsigned *qin = reinterpret_cast<unsigned *>(smem + L.qin);
+    unsigned *own = reinterpret_cast<unsigned *>(smem + L.own);
+    unsigned *oacc = reinterpret_cast<unsigned *>(smem + L.oacc);
+    unsigned *fb = reinterpret_cast<unsigned *>(smem + L.fb);
+    unsigned *wsum = reinterpret_cast<unsigned *>(smem + L.wsum);
+    const size_t o = (size_t)e * N;
+    const unsigned *wk = ws_key + (size_t)e * cap;
+    const float *wa = ws_acc + (size_t)e * cap;
+    uint2 *tr = slice + (size_t)e * cap * 4;        // (the env's slice: 32 bytes per contact of the capacity)
+    for (int b = tid; b < L.NP4; b += nt) {
+        off[b] = b < N ? (unsigned)ws_cnt[o + b] : 0u;
+        icnt[b] = 0u; qin[b] = 0u;
+    }
+    if (tid < 2 * KB_MAX_OBJECTS) oacc[tid] = 0u;
+#pragma unroll
+    for (int f = 0; f < KB_MAX_OBJECTS; ++f) if (tid == f) fb[f] = (unsigned)A.body[f];
+    __syncthreads();
+    kb_block_scan_u32(off, L.NP4, wsum, tid);
+    for (int a = tid; a < N; a += nt) {
+        const unsigned p1 = min(off[a + 1], (unsigned)cap);
+        unsigned nk = 0, nw = 0, no = 0, q = 0;
+        for (unsigned pos = off[a]; pos < p1; ++pos) {
+            const unsigned key = wk[pos];
+            const unsigned qi = (unsigned)kb_reduce_quant(wa[pos], scale);
+            unsigned code, sub;
+            const int cls = kb_contact_class(key, a, N, F, fb, code, sub);
+            if (cls) q += qi;
+            if (cls == 1) {
+                nk++;
+                atomicAdd(&icnt[key], 1u);
+                atomicAdd(&qin[key], qi);
+            } else if (cls == 2) {
+                nw++;
+            } else if (cls == 3) {
+                no++;
+                const unsigned m = code - (unsigned)N - 4u;
+                atomicAdd(&oacc[2 * m], 1u);
+                atomicAdd(&oacc[2 * m + 1], qi);
+            }
+        }
+        own[a] = nk | nw << 10 | no << 20;      // (each at most 255)
+        if (q) atomicAdd(&qin[a], q);
+    }
+    __syncthreads();
+    if (d_obj && tid < M) {
+        float *row = d_obj + ((size_t)e * M + tid) * 2;
+        row[0] = (float)oacc[2 * tid];
+        row[1] = (float)(int)oacc[2 * tid + 1] / scale;
+    }
+    if constexpr (K > 0) {
+        for (int b = tid; b < L.NP4; b += nt) ioff[b] = icnt[b];
+        __syncthreads();
+        kb_block_scan_u32(ioff, L.NP4, wsum, tid);
+        for (int a = tid; a < N; a += nt) {
+            const unsigned p1 = min(off[a + 1], (unsigned)cap);
+            for (unsigned pos = off[a]; pos < p1; ++pos) {
+                const unsigned key = wk[pos];
+                if (key < (unsigned)N && key != (unsigned)a) {
+                    const unsigned slot = ioff[key] + atomicSub(&icnt[key], 1u) - 1u;
+                    if (slot < (unsigned)cap) tr[slot] = make_uint2((unsigned)a, __float_as_uint(wa[pos]));
+                }
+            }
+        }
+        __syncthreads();        // the records are read by other lanes, from global memory
+    }
+    for (int a = tid; a < N; a += nt) {
+        const unsigned ow = own[a];
+        const unsigned i0 = K > 0 ? ioff[a] : 0u, i1 = K > 0 ? min(ioff[a + 1], (unsigned)cap) : 0u;
+        if (d_touch) {
+            const unsigned nin = K > 0 ? ioff[a + 1] - i0 : icnt[a];
+            const float4 t = make_float4((float)((ow & 1023u) + nin), (float)((ow >> 10) & 1023u), (float)(ow >> 20), (float)(int)qin[a] / scale);
+            float *row = d_touch + (o + a) * 4;
+            if (vec & 2) *reinterpret_cast<float4 *>(row) = t;
+            else { row[0] = t.x; row[1] = t.y; row[2] = t.z; row[3] = t.w; }
+        }
+        if constexpr (K > 0) {
+            unsigned long long best[K];
+#pragma unroll
+            for (int i = 0; i < K; ++i) best[i] = NONE;
+            const auto insert = [&](unsigned long long key) {
+                if (key < best[K - 1]) {
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+                        const unsigned long long lo = key < best[j] ? key : best[j];
+                        key = key < best[j] ? best[j] : key;
+                        best[j] = lo;
+                    }
+                }
+            };
+            const unsigned p1 = min(off[a + 1], (unsigned)cap);
+            for (unsigned pos = off[a]; pos < p1; ++pos) {
+                unsigned code, sub;
+                if (kb_contact_class(wk[pos], a, N, F, fb, code, sub))
+                    insert(((unsigned long long)(code * 8u + sub) << 32) | __float_as_uint(wa[pos]));
+            }
+            for (unsigned i = i0; i < i1; ++i) {
+                const uint2 r = tr[i];
+                insert(((unsigned long long)(r.x * 8u) << 32) | r.y);
+            }
+            const size_t row = (o + a) * (size_t)k;
+            if (vec & 1) {      // k is a multiple of 4, d_partner and d_impulse are 16-byte aligned: four slots per store
+#pragma unroll
+                for (int i = 0; i < K; i += 4) {
+                    if (i >= k) break;
+                    int4 c;
+                    uint4 b;
+                    c.x = best[i] != NONE ? (int)(best[i] >> 35) : -1; b.x = best[i] != NONE ? (unsigned)best[i] : 0u;
+                    c.y = best[i + 1] != NONE ? (int)(best[i + 1] >> 35) : -1; b.y = best[i + 1] != NONE ? (unsigned)best[i + 1] : 0u;
+                    c.z = best[i + 2] != NONE ? (int)(best[i + 2] >> 35) : -1; b.z = best[i + 2] != NONE ? (unsigned)best[i + 2] : 0u;
+                    c.w = best[i + 3] != NONE ? (int)(best[i + 3] >> 35) : -1; b.w = best[i + 3] != NONE ? (unsigned)best[i + 3] : 0u;
+                    reinterpret_cast<int4 *>(d_partner + row)[i >> 2] = c;
+                    reinterpret_cast<uint4 *>(d_impulse + row)[i >> 2] = b;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+                    if (i >= k) break;
+                    const bool used = best[i] != NONE;
+                    d_partner[row + i] = used ? (int)(best[i] >> 35) : -1;
+                    reinterpret_cast<unsigned *>(d_impulse)[row + i] = used ? (unsigned)best[i] : 0u;
+                }
+            }
+        }
     }
 }
 

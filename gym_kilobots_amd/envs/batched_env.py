@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, **cfg):
+                 object_obs=None, grid_obs=None, contact_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -35,7 +35,11 @@ class BatchedKilobotsEnv(object):
         its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added.
         grid_obs: (width, height) or (width, height, planes) adds what a CENTRAL policy is fed, a fixed-size image of the
         whole table: occupancy_grid() returns [E, C, height, width] (KilobotSim.occupancy_grid; planes made of 'count',
-        'flow' and 'objects', default ('count',)), and step() puts it in its info dict under 'grid'.  None adds nothing."""
+        'flow' and 'objects', default ('count',)), and step() puts it in its info dict under 'grid'.  None adds nothing.
+        contact_obs: k, an int in 0..16, adds touch and push sensing from the contacts the solver acted on in the last world
+        step: contacts() returns (partner [E, N, k], impulse [E, N, k], touch [E, N, 4], obj [E, M, 2] or None)
+        (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
+        'contacts'.  None adds nothing."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -89,6 +93,11 @@ class BatchedKilobotsEnv(object):
                 raise ValueError('grid_obs must be (width, height) or (width, height, planes): %s' % err)
             if self.grid_obs[2] & nat.GRID_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
                 raise ValueError("grid_obs: 'objects' asked for, but the env has no objects")
+        self.contact_obs = None
+        if contact_obs is not None:
+            if isinstance(contact_obs, bool) or not isinstance(contact_obs, (int, np.integer)) or not 0 <= contact_obs <= nat.MAX_CONTACT_SLOTS:
+                raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
+            self.contact_obs = int(contact_obs)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -185,6 +194,8 @@ class BatchedKilobotsEnv(object):
                 info['objects'], info['walls'] = points
         if self.grid_obs is not None:
             info['grid'] = self.occupancy_grid()
+        if self.contact_obs is not None:
+            info['contacts'] = self.contacts()
         return obs, reward, done, info
 
     def neighbors(self):
@@ -214,6 +225,13 @@ class BatchedKilobotsEnv(object):
         if self.grid_obs is None:
             raise ValueError('create the env with grid_obs=(width, height[, planes]) to observe occupancy grids')
         return self.sim.occupancy_grid(*self.grid_obs)
+
+    def contacts(self):
+        """(partner [E, N, k] int32, impulse [E, N, k] float32, touch [E, N, 4] float32, obj [E, M, 2] float32 or None) of the
+        contacts of the last world step for the contact_obs=k the env was created with: KilobotSim.contacts."""
+        if self.contact_obs is None:
+            raise ValueError('create the env with contact_obs=k to observe contacts')
+        return self.sim.contacts(self.contact_obs)
 
     def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
         """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env

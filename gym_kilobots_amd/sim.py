@@ -358,6 +358,35 @@ class KilobotSim:
             nat.check(self._lib.kb_sense_grid(self._h, width, height, planes, C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense_grid')
         return out
 
+    def contacts(self, k=8, scale=65536.0, out=None):
+        """Touch and push sensing from the contact store of the last step (kb_sense_contacts; Body.collides_with of every
+        kilobot at once, with the impulses the solver applied): returns (partner, impulse, touch, obj).  partner [E, N, k]
+        int32 and impulse [E, N, k] float32: the first k contacts of every kilobot -- a kilobot j < N, wall N + w (w: 0 = xmin,
+        1 = xmax, 2 = ymin, 3 = ymax as in object_points) or object N + 4 + m, in that order, one entry per fixture of an
+        object -- with the accumulated normal impulse in Box2D world units; -1 and 0.0 in unused slots.  touch [E, N, 4]
+        float32: kilobot contacts, wall contacts, fixture contacts and the impulse sum over ALL contacts of the kilobot,
+        whatever k.  obj [E, M, 2] float32: the kilobot contacts on every object and their impulse sum; None without objects.
+        The sums are fixed-point sums of rint(impulse * scale) divided by scale, as in neighbor_reduce: independent of the
+        order.  k=0 skips the lists: partner and impulse are None.  The contacts are those the last world step found (on
+        the poses before its integration); forget_contacts() empties them.  out: a tuple of the preallocated contiguous
+        tensors that are returned (None left out) to write into."""
+        E, N, M, k = self.num_envs, self.num_bots, self.num_objects, int(k)
+        if not 0 <= k <= nat.MAX_CONTACT_SLOTS:
+            raise ValueError('k must be in 0..%d' % nat.MAX_CONTACT_SLOTS)
+        scale = float(scale)
+        if not 0.0 < scale < float('inf'):
+            raise ValueError('scale must be finite and positive')
+        shapes = ([((E, N, k), torch.int32, 'partner'), ((E, N, k), torch.float32, 'impulse')] if k else []) \
+            + [((E, N, 4), torch.float32, 'touch')] + ([((E, M, 2), torch.float32, 'obj')] if M > 0 else [])
+        out = list(self._outputs(out, shapes, 'a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes))))
+        partner, impulse = (out.pop(0), out.pop(0)) if k else (None, None)
+        touch, obj = out[0], out[1] if M > 0 else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_contacts(self._h, k, scale, ptr(partner), ptr(impulse), ptr(touch), ptr(obj), self._stream()),
+                      'kb_sense_contacts')
+        return partner, impulse, touch, obj
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

@@ -392,6 +392,44 @@ int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream);
 int kb_grid_channels(const kb_sim *sim, int planes);
 int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *stream);
 
+/* Touch and push sensing from the contact store, without stepping: who touches whom, and how hard -- what the solver alone
+ * knows (Body.collides_with, body.py:87-90, walks b2Body.contacts; the impulses have no reference counterpart).  A pure
+ * function of ws_key / ws_acc / ws_cnt as the last kb_step left them: the Box2D contact list of the last world step.
+ *   Store reading, env e, N = num_bots, M = num_objects, cap = kb_contact_capacity():  off[a] = sum of ws_cnt[e][b], b < a;
+ *     entry (a, s), s < ws_cnt[e][a], sits at pos = off[a] + s and is skipped when pos >= cap (never stored);
+ *     key = ws_key[e][pos], acc = ws_acc[e][pos].
+ *   Meaning of an entry of owner a, by key:
+ *     key < N, key != a: a kilobot-kilobot contact.  It is stored under ONE of its two kilobots (not always the lower) and is
+ *       reported in the list of a with code key and in the list of key with code a.
+ *     0x10000 <= key < 0x10004: a wall.  The store numbers walls 0 xmin, 1 ymin, 2 xmax, 3 ymax; the public index is that of
+ *       kb_sense_objects (0 xmin, 1 xmax, 2 ymin, 3 ymax): W = (0, 2, 1, 3)[key - 0x10000], code N + W.
+ *     key >= 0x20000, f = key - 0x20000 < fixtures of the handle: fixture f in the kb_config numbering (NOT the body-grouped
+ *       order of kb_outline), of object m = obj_fixture_body[f] (f when num_fixtures == 0): code N + 4 + m, sub-order f.
+ *     Every other key is ignored.
+ *   Order of a kilobot's list: ascending by the 64-bit key ((code * 8 + f) << 32) | bits(acc), f = 0 unless a fixture:
+ *     kilobots first, then walls, then objects with fixtures ascending -- whatever order the store holds.
+ * d_partner [num_envs][num_bots][k] int32 and d_impulse [num_envs][num_bots][k] float32, both or neither, 1 <= k <=
+ *       KB_MAX_CONTACT_SLOTS: the first min(k, count) entries of the list, the code and acc with unchanged bits; unused slots
+ *       hold -1 and +0.0.
+ * d_touch [num_envs][num_bots][4] float32 or NULL: kilobot contacts, wall contacts, fixture contacts, impulse sum -- over ALL
+ *       entries of the kilobot, never truncated by k.  The sum is the fixed-point sum of kb_sense_reduce:
+ *       (float)(int32)(sum of q(acc)) / scale with q the quantisation of KB_REDUCE_SUM, accumulated modulo 2^32: exact on the
+ *       quantised values and independent of the order.
+ * d_obj [num_envs][num_objects][2] float32 or NULL: the kilobot-fixture contacts on object m and the same fixed-point sum of
+ *       their impulses.  KB_EINVAL on a handle without objects.
+ * scale: finite and > 0; 65536 resolves 1.5e-5 over +-32 (impulses are in Box2D world units: b2ManifoldPoint::normalImpulse
+ *       after the velocity iterations of the last substep).
+ * Meaningful when the env's status has bit 0 clear; the list is that of the contacts the last world step found on the poses
+ * BEFORE its integration (as after b2World::Step); stale after poses were set without a step; empty once ws_cnt is zeroed;
+ * after the resolve step of a reset it lists the overlaps with impulse 0 (count and flags still report them).
+ * Argument errors are reported before an unbound handle, in this order: NULL sim;  exactly one of d_partner / d_impulse;  k
+ * (when the lists are asked for);  scale;  all outputs NULL;  d_obj without objects.  Only then comes KB_ENOTBOUND.
+ * Reads ws_key, ws_acc, ws_cnt; may use the env's slice of kb_buffers.scratch (transient by contract); writes the outputs
+ * only, every element of every output given on every call.  One launch.  Asynchronous on `stream`. */
+#define KB_MAX_CONTACT_SLOTS 16
+int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float *d_impulse, float *d_touch, float *d_obj,
+                      void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into
