@@ -90,7 +90,7 @@ class KbBuffers(C.Structure):
 
 
 EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_light_sense', 'kb_reset',
-           'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads',
+           'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
 _lib = None
@@ -164,11 +164,13 @@ def load():
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
     lib.kb_reset.restype = C.c_int
-    for name in ('kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_block_threads', 'kb_variant_index', 'kb_light_action_dim', 'kb_light_count'):
+    for name in ('kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_block_threads', 'kb_variant_index', 'kb_light_action_dim', 'kb_light_count', 'kb_exact_division'):
         getattr(lib, name).argtypes = [_P]
         getattr(lib, name).restype = C.c_int
     lib.kb_scratch_bytes.argtypes = [_P]
     lib.kb_scratch_bytes.restype = C.c_size_t
+    lib.kb_exact_selftest.argtypes = [_P, _P, _P]
+    lib.kb_exact_selftest.restype = C.c_int
     lib.kb_set_block_threads.argtypes = [_P, C.c_int]
     lib.kb_set_block_threads.restype = C.c_int
     lib.kb_last_error.argtypes = []

@@ -27,7 +27,10 @@
 //
 // Arithmetic: fp32, compiled with -ffp-contract=off; every expression is written in the operation order of the
 // specification so results do not depend on launch fusion, workgroup size or sharding.
+#include <mutex>
 #include <new>
+#include <utility>
+#include <vector>
 
 #include "kb_common.h"
 #include "kb_objects.h"
@@ -194,12 +197,81 @@ __global__ void kb_reset_kernel(const Params p, const ResetArgs a) {
     }
 }
 
+// Test entry kb_exact_selftest: the short forms of kb_exact.h with THIS chip's seeds (v_sqrt_f32, v_rsq_f32, v_rcp_f32) against
+// the compiler's sqrtf(x), 1.0f / x and a / K over all 2^32 bit patterns, each form on the operands the position sweep gives it.
+// counts[2 f] = operands checked, counts[2 f + 1] = results that differ in a bit; f = 0 square root, 1 reciprocal, 2 division.
+__global__ void __launch_bounds__(256) kb_exact_selftest_kernel(float kbb, float kwb, unsigned long long *counts) {
+    __shared__ unsigned sh[6];
+    if (threadIdx.x < 6) sh[threadIdx.x] = 0u;
+    __syncthreads();
+    const float ybb = 1.0f / kbb, ywb = 1.0f / kwb;
+    unsigned n[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+    const unsigned low = blockIdx.x * 256u + threadIdx.x;      // 2^16 blocks: the low 24 bits; the loop: the high 8
+    for (unsigned k = 0; k < 256u; ++k) {
+        const unsigned u = (k << 24) | low;
+        const float x = __uint_as_float(u);
+        if (kb_exact_guard(x)) {
+            const float f = kb_sqrt_refine(x, __builtin_amdgcn_sqrtf(x), __builtin_amdgcn_rsqf(x));
+            n[0]++; n[1] += __float_as_uint(f) != __float_as_uint(sqrtf(x));
+        }
+        if (kb_exact_len_guard(x)) {
+            const float f = kb_rcp_refine(x, __builtin_amdgcn_rcpf(x));
+            n[2]++; n[3] += __float_as_uint(f) != __float_as_uint(1.0f / x);
+        }
+        const int ex = (int)((u >> 23) & 255u) - 127;
+        if ((u << 1) == 0u || (ex >= KB_EXACT_C_EXP_MIN && ex <= KB_EXACT_C_EXP_MAX)) {
+            n[4] += 2u;
+            n[5] += __float_as_uint(kb_div_const(x, kbb, ybb)) != __float_as_uint(x / kbb);
+            n[5] += __float_as_uint(kb_div_const(x, kwb, ywb)) != __float_as_uint(x / kwb);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) if (n[i]) atomicAdd(&sh[i], n[i]);
+    __syncthreads();
+    if (threadIdx.x < 6 && sh[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)sh[threadIdx.x]);
+}
+
 thread_local char g_err[512] = "";
 
 float kb_clampf_host(float a, float lo, float hi) { return fmaxf(lo, fminf(a, hi)); }
 // reach of the sensing stencil in cells: cell indices are monotone in the coordinate, and two kilobots within Rw differ
 // by at most floor(Rw / cell) + 1 cells (the small margin covers the rounding of the cell computation)
 int sense_reach(float Rw, float inv_cell) { return (int)floorf(Rw * inv_cell + 1e-3f) + 1; }
+
+// kb_div_const (kb_exact.h) against a / K for one divisor of the position sweep, a = -C: every mantissa of the binade of the
+// largest |C| (0.2), a stride through the mantissas of every smaller binade that |C| can reach (the form is invariant under
+// scaling by a power of two while nothing leaves the normal range; the stride looks for exactly that), and both zeros.
+// About 1.7e7 quotients per divisor, once per process and divisor.
+bool div_form_exact(float K) {
+    static std::mutex mtx;
+    static std::vector<std::pair<unsigned, bool>> seen;
+    unsigned kbits;
+    memcpy(&kbits, &K, 4);
+    std::lock_guard<std::mutex> lock(mtx);
+    for (const auto &e : seen) if (e.first == kbits) return e.second;
+    bool ok = K > 0.0f && std::isfinite(K);
+    if (ok) {
+        const float y = 1.0f / K;
+        auto same = [&](float a) {
+            const float f = kb_div_const(a, K, y), d = a / K;
+            return memcmp(&f, &d, 4) == 0;
+        };
+        ok = same(0.0f) && same(-0.0f);
+        for (int ex = KB_EXACT_C_EXP_MIN; ok && ex <= KB_EXACT_C_EXP_MAX; ++ex) {
+            const unsigned step = ex == KB_EXACT_C_EXP_MAX ? 1u : 1021u;
+            unsigned bad = 0;
+            for (unsigned m = 0; m < (1u << 23); m += step) {
+                const unsigned u = ((unsigned)(ex + 127) << 23) | m;
+                float a;
+                memcpy(&a, &u, 4);
+                bad += !same(a);
+            }
+            ok = bad == 0;
+        }
+    }
+    seen.emplace_back(kbits, ok);
+    return ok;
+}
 
 int fail(int code, const char *fmt, const char *detail = "") {
     snprintf(g_err, sizeof(g_err), fmt, detail);
@@ -371,6 +443,9 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
         p.rr2 = rr * rr; p.rw2 = rw * rw; p.rw_tot = p.r_bot + B2_POLYGON_RADIUS;
         const float kbb = p.im_bot + p.im_bot, kwb = 0.0f + p.im_bot;
         p.nm_bb = kbb > 0.0f ? 1.0f / kbb : 0.0f; p.nm_wb = kwb > 0.0f ? 1.0f / kwb : 0.0f;
+        // the position sweep divides -C by these two: by multiplying, if the short form gives the quotient's bits for them
+        p.exact_div = div_form_exact(kbb) && div_form_exact(kwb);
+        p.y_bb = p.exact_div ? 1.0f / kbb : 0.0f; p.y_wb = p.exact_div ? 1.0f / kwb : 0.0f;
     }
     for (int k = 0; k < 5; ++k) {       // KB_DRIVE_MIXED: the classes have different fixture densities (kilobot.py:25 / :214)
         p.im_mode[k] = p.im_bot;
@@ -831,6 +906,16 @@ int kb_light_action_dim(const kb_sim *sim) { return sim ? sim->p.ladim : KB_EINV
 int kb_light_count(const kb_sim *sim) { return sim ? (sim->cfg.light_type == KB_LIGHT_NONE ? 0 : sim->p.lcount) : KB_EINVAL; }
 // per contact: the 16-byte staging record + the 16-byte level-sorted record (pair, normal, impulse) of the cooperative sweeps (kernels with objects: normal and effective mass, 12 B)
 size_t kb_scratch_bytes(const kb_sim *sim) { return sim ? (size_t)sim->p.E * (size_t)sim->p.cap * 32u : 0; }
+int kb_exact_division(const kb_sim *sim) { return sim ? sim->p.exact_div : KB_EINVAL; }
+
+int kb_exact_selftest(const kb_sim *sim, unsigned long long *d_counts, void *stream) {
+    if (!sim || !d_counts) return fail(KB_EINVAL, "kb_exact_selftest: NULL argument");
+    const float kbb = sim->p.im_bot + sim->p.im_bot, kwb = 0.0f + sim->p.im_bot;
+    if (hipMemsetAsync(d_counts, 0, 6 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return launched("kb_exact_selftest");
+    hipLaunchKernelGGL(kb_exact_selftest_kernel, dim3(1u << 16), dim3(256), 0, (hipStream_t)stream, kbb, kwb, d_counts);
+    return launched("kb_exact_selftest");
+}
+
 int kb_contact_capacity(const kb_sim *sim) { return sim ? sim->p.cap : KB_EINVAL; }
 int kb_lds_staging_entries(const kb_sim *sim) { return sim ? sim->p.capL : KB_EINVAL; }
 int kb_block_threads(const kb_sim *sim) { return sim ? sim->threads : KB_EINVAL; }

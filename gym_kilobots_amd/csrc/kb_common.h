@@ -9,6 +9,7 @@
 
 #include "kilobots_hip.h"
 #include "kb_launch.h"
+#include "kb_exact.h"
 
 namespace kb {
 
@@ -86,6 +87,8 @@ struct Params {
     // arguments they live in scalar registers -- computed in the kernel they would hold a vector register each
     float rr2, rw2, rw_tot;                   // (r + r)^2;  (polygonRadius + r)^2;  r + polygonRadius
     float nm_bb, nm_wb;                       // effective mass of a kilobot-kilobot and of a wall-kilobot contact
+    float y_bb, y_wb;                         // RN(1 / (im_bot + im_bot)), RN(1 / im_bot): the position sweep divides by multiplying (kb_exact.h) ...
+    int exact_div;                            // ... once kb_create has checked kb_div_const against a / K for these two K; 0: the sweep divides
 };
 
 

@@ -319,15 +319,25 @@
                         const float2 pa = RB_POS(ra[j]);
                         axx = pa.x; ayy = pa.y;
                         const float dx = bx - axx, dy = by - ayy;
-                        const float len = sqrtf(dx * dx + dy * dy);
-                        nx = dx; ny = dy;
-                        if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
+                        const float dd = dx * dx + dy * dy;
+                        // The round is a chain of dependent instructions, and most of them were the IEEE sequences of sqrtf and
+                        // the division.  With every pair of the round inside the proven range (wave-uniform test; it also
+                        // rules out len < B2_EPSILON) one correction step on the hardware seeds gives the same bits (kb_exact.h).
+                        if (__builtin_expect(__builtin_amdgcn_ballot_w64(!kb_exact_guard(dd)) == 0ull, 1)) {
+                            const float len = kb_sqrt_refine(dd, __builtin_amdgcn_sqrtf(dd), __builtin_amdgcn_rsqf(dd));
+                            const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
+                            nx = dx * inv; ny = dy * inv;
+                        } else {
+                            const float len = sqrtf(dd);
+                            nx = dx; ny = dy;
+                            if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
+                        }
                         sep = (dx * nx + dy * ny) - p.r_bot - p.r_bot;
                     }
                     if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
                     const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                     const float K = ima + imb;
-                    const float imp = K > 0.0f ? -C / K : 0.0f;
+                    const float imp = __builtin_expect(p.exact_div, 1) ? kb_div_const(-C, K, wallA ? p.y_wb : p.y_bb) : (K > 0.0f ? -C / K : 0.0f);
                     const float Px = imp * nx, Py = imp * ny;
                     if (!wallA) RB_POS(ra[j]) = make_float2(axx - ima * Px, ayy - ima * Py);
                     RB_POS(rb[j]) = make_float2(bx + imb * Px, by + imb * Py);

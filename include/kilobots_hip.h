@@ -485,6 +485,15 @@ int kb_block_threads(const kb_sim *sim);
 int kb_variant_index(const kb_sim *sim);        /* which instantiation of the step kernel runs the handle: its position in the library's
                                                    list (kb_variant.h: kb_variants), -1 if the library has none (kb_step then fails).
                                                    Follows kb_set_block_threads.  For tests that must know which kernel they ran */
+int kb_exact_division(const kb_sim *sim);       /* 1: the position sweep of the register solver takes -C / K by multiplying with RN(1 / K) (one
+                                                   correction step, same bits): kb_create compared the form with the division for this handle's
+                                                   two K, over every mantissa of the dividend in the binade of the largest |C| (0.2), every
+                                                   1021st mantissa in each smaller binade down to 2^-34, and both zeros.  0: it divides */
+int kb_exact_selftest(const kb_sim *sim, unsigned long long *d_counts, void *stream);
+                                                /* for tests: the short forms of the position sweep (square root, reciprocal, division by this
+                                                   handle's two K) with the device's own seed instructions against the compiler's IEEE sequences
+                                                   over all 2^32 bit patterns.  d_counts (device, 6 words): per form the operands inside its
+                                                   guard and the results that differ in a bit */
 int kb_resident_envs_per_cu(kb_sim *sim);        /* workgroups (= envs) of this handle's kernel that one CU holds at a time (HIP occupancy query; needs a GPU) */
 int kb_set_block_threads(kb_sim *sim, int threads);  /* multiple of 64 in [64, 512], num_bots <= 2 * threads.  kb_create picks
                                                          the measured best (one kilobot per thread, power-of-two wave count,
