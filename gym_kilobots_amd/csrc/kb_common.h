@@ -237,8 +237,15 @@ __device__ __forceinline__ void wave_sync() {
 // asm volatile("" : "+v"(v) :: "memory");`), gives the ds_read_b32 in the fixed-size kernels of kb_inst_d0, and fails in
 // kb_inst_d2.hip with the same message: "error: Illegal instruction detected: Operand has incorrect register class.
 // V_CMP_NE_U32_e32 0, $src_shared_base, implicit-def $vcc, implicit $exec".
+// A fifth form, DS_ATOMIC = true: a returning LDS atomic that changes nothing, `atomicOr(p, 0u)`.  The compiler turns it into
+// ds_read_b32 + s_waitcnt lgkmcnt(0) -- no FLAT instruction, nothing on the vector-memory counter, and two of them to different
+// words go out back to back under one wait.  Used everywhere it fails like the others (kb_inst_d2.hip, same message), so the
+// caller selects it per instantiation: the step kernel takes it in the fixed-size sorted-bin kernels only (FN != 0 && BINS,
+// all of them in kb_inst_d0.hip, where it compiles); every other instantiation keeps the volatile form.
+template <bool DS_ATOMIC = false>
 __device__ __forceinline__ unsigned lds_load_relaxed(const unsigned *p_) {
-    return *reinterpret_cast<const volatile unsigned *>(p_);
+    if constexpr (DS_ATOMIC) return atomicOr(const_cast<unsigned *>(p_), 0u);
+    else return *reinterpret_cast<const volatile unsigned *>(p_);
 }
 
 // Workgroup barrier for phases that only exchange LDS data: __syncthreads() may also drain the vector-memory counter

@@ -36,6 +36,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     constexpr bool WIDE = TIER == 1 || TIER == 3;       // (256 VGPRs: no register spills)
     constexpr bool BINS = !OBJ;          // sorted-bin broadphase, bodies in slot order, contacts at their warm-start position (namespace ldsb)
     constexpr int KRX = BINS ? KB_KREG_BINS : KREG;      // contacts per lane of the register-resident solver
+    // union-find parents read with an LDS instruction (kb_common.h: lds_load_relaxed, the fifth form) where that form compiles
+    constexpr bool PAR_DS = FN != 0 && BINS;
     static_assert(!SLEEP || FN == 0 || !OBJ, "the fixed-size instantiations with objects do not carry the sleep state");
     extern __shared__ __align__(16) unsigned char smem[];
     int e = blockIdx.x;
@@ -752,13 +754,86 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             KB_ABLATE_EXIT(5);     // contacts staged
             // ---- narrowphase, pass 3 (thread per contact): class and rank in the canonical order, impulse of the same pair in
             //      the previous substep, key of the new packed list (bits 16.. of the info word), island hooking ----
-            auto label_pass_bins = [&](unsigned *sPair, unsigned *sInfo, float *sAcc) __attribute__((always_inline)) {
+            // (STAGED_LDS with the previous list in LDS, the regime of a settled swarm: every step of the chain below is ONE batch of
+            //  independent LDS reads under one wait -- pair and raw record; ids and parents of both slots; count and offset of both
+            //  owners' lists; the first four keys of BOTH lists; the impulse of the entry that matched; then the two root walks
+            //  side by side.  The global list and the global staging slice keep the plain chain behind it.)
+            auto label_pass_bins = [&](unsigned *sPair, unsigned *sInfo, float *sAcc, auto stagedInLds) __attribute__((always_inline)) {
+            constexpr bool STAGED_LDS = decltype(stagedInLds)::value;
             for (int c = tid; c < ncon; c += nt) {
                 const unsigned pr = sPair[c], raw = sInfo[c];
                 const unsigned a = pr & 0xFFFFu, b = pr >> 16;
                 unsigned key16, cls, r = (raw >> 4) & 0xFFu;
                 float acc;
-                if (a >= (unsigned)WALL_CODE) {
+                if (STAGED_LDS && oldInLds) {
+                    const bool wall = a >= (unsigned)WALL_CODE;
+                    const unsigned sa_ = wall ? b : a;      // the owner's slot (a wall contact: the kilobot's, and only its list)
+                    const unsigned ida = idOf[sa_], idb = idOf[b];
+                    unsigned ta = lds_load_relaxed<PAR_DS>(&parent[sa_]), tb = lds_load_relaxed<PAR_DS>(&parent[b]);
+                    const int k = wall ? 0 : (int)(raw & 15u);
+                    const unsigned keyA = wall ? a : idb;
+                    const int cntA = wsCnt[ida], offA = wsOff[ida];
+                    const int cntB = wall ? 0 : (int)wsCnt[idb], offB = wsOff[idb];
+                    // keys are unique inside an owner's list: the first match is the match
+                    unsigned kA[4], kB[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        kA[u] = oldKey[offA + min(u, max(cntA, 1) - 1)];
+                        kB[u] = oldKey[offB + min(u, max(cntB, 1) - 1)];
+                    }
+                    int hitA = -1, hitB = -1;
+#pragma unroll
+                    for (int u = 3; u >= 0; --u) {
+                        if (u < cntA && kA[u] == keyA) hitA = u;
+                        if (u < cntB && kB[u] == ida) hitB = u;
+                    }
+                    if (hitA < 0)
+                        for (int s = 4; s < cntA; ++s) if ((unsigned)oldKey[offA + s] == keyA) { hitA = s; break; }
+                    if (hitA < 0 && hitB < 0)
+                        for (int s = 4; s < cntB; ++s) if ((unsigned)oldKey[offB + s] == ida) { hitB = s; break; }
+                    // the owner's list wins, the partner's counts only where the owner's missed; only the entry that is used is marked
+                    const int ent = hitA >= 0 ? offA + hitA : (hitB >= 0 ? offB + hitB : -1);
+                    acc = -1.0f;
+                    if (ent >= 0) {
+                        acc = oldAcc[ent];
+                        if (SLEEP) oldAcc[ent] = -1.0f - acc;      // (matched: b2Contact::Update "was touching and still is"; impulses are >= 0)
+                    }
+                    key16 = keyA;
+                    if (wall) cls = (unsigned)CLS_WALL | ((raw >> 15) ? 0x80u : 0u);
+                    else {
+                        const unsigned px = (raw >> 12) & 1u, py = (raw >> 13) & 1u;
+                        cls = k == 0 ? (unsigned)CLS_SAME : (k == 1 ? CLS_E + px : (k == 2 ? CLS_N + py : (k == 3 ? CLS_NE + px : CLS_NW + px)));
+                        if ((raw >> 14) & 1u) {
+                            // rank base of the (cell, direction) group: its contacts owned by the kilobots of the cell in front of the owner
+                            const float2 pa = pos[a];
+                            int cx = (int)floorf((pa.x - p.xmin) * p.inv_cell);
+                            int cy = (int)floorf((pa.y - p.ymin) * p.inv_cell);
+                            cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
+                            cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
+                            const int cell = cy * p.gw + cx;
+                            for (int s_ = (int)E1[hashed ? (cell & p.hmask) : cell]; s_ < (int)a; ++s_) {
+                                if (hashed && (int)cellOfSlot[s_] != cell) continue;
+                                r += (dirCnt[s_] >> (6 * k)) & 63u;
+                            }
+                            if (r > 255u) { r = 255u; atomicOr(&misc[M_STATUS], 4u); }
+                        }
+                        // island hooking: larger root goes under the smaller one.  Both walks go on from the parents in hand, a step of
+                        // each in one round trip (a parent that is no root never changes in this pass; one that was a root and has been
+                        // hooked since fails the exchange, which hands back its new parent)
+                        unsigned ra = a, rb = b;
+                        for (;;) {
+                            while (ta != ra || tb != rb) {
+                                ra = ta; rb = tb;
+                                ta = lds_load_relaxed<PAR_DS>(&parent[ra]); tb = lds_load_relaxed<PAR_DS>(&parent[rb]);
+                            }
+                            if (ra == rb) break;
+                            if (ra < rb) { unsigned t = ra; ra = rb; rb = t; }
+                            const unsigned seen = atomicCAS(&parent[ra], ra, rb);
+                            if (seen == ra) break;
+                            ta = seen; tb = rb;
+                        }
+                    }
+                } else if (a >= (unsigned)WALL_CODE) {
                     key16 = a;
                     cls = (unsigned)CLS_WALL | ((raw >> 15) ? 0x80u : 0u);
                     acc = ws_find((int)idOf[b], key16);
@@ -787,8 +862,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     // island hooking: larger root goes under the smaller one
                     unsigned ra = a, rb = b;
                     for (;;) {
-                        while (true) { unsigned t = lds_load_relaxed(&parent[ra]); if (t == ra) break; ra = t; }
-                        while (true) { unsigned t = lds_load_relaxed(&parent[rb]); if (t == rb) break; rb = t; }
+                        while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[ra]); if (t == ra) break; ra = t; }
+                        while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[rb]); if (t == rb) break; rb = t; }
                         if (ra == rb) break;
                         if (ra < rb) { unsigned t = ra; ra = rb; rb = t; }
                         if (atomicCAS(&parent[ra], ra, rb) == ra) break;
@@ -799,7 +874,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 sAcc[c] = acc;
             }
             };
-            if (big) label_pass_bins(gPair, gInfo, gAcc); else label_pass_bins(lPair, lInfo, lAcc);
+            if (big) label_pass_bins(gPair, gInfo, gAcc, std::false_type()); else label_pass_bins(lPair, lInfo, lAcc, std::true_type());
             KB_STAMP_PRE(18);
             __syncthreads();
             KB_STAMP(2);
@@ -959,8 +1034,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 if (OBJ && wave == 0 && lane < NMC && mcTouch && mci(ox, MC_A, lane) < WALL_CODE) {   // object - object: one island
                     unsigned ra = (unsigned)mci(ox, MC_A, lane), rb = (unsigned)mci(ox, MC_B, lane);
                     for (;;) {
-                        while (true) { unsigned t = lds_load_relaxed(&parent[ra]); if (t == ra) break; ra = t; }
-                        while (true) { unsigned t = lds_load_relaxed(&parent[rb]); if (t == rb) break; rb = t; }
+                        while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[ra]); if (t == ra) break; ra = t; }
+                        while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[rb]); if (t == rb) break; rb = t; }
                         if (ra == rb) break;
                         if (ra < rb) { unsigned t = ra; ra = rb; rb = t; }
                         if (atomicCAS(&parent[ra], ra, rb) == ra) break;
@@ -995,8 +1070,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         fixbits = (unsigned)m << 24;      // the fixture travels with the contact (bits 24..27)
                         unsigned ra = a, rb = pr >> 16;        // the object the fixture belongs to
                         for (;;) {
-                            while (true) { unsigned t = lds_load_relaxed(&parent[ra]); if (t == ra) break; ra = t; }
-                            while (true) { unsigned t = lds_load_relaxed(&parent[rb]); if (t == rb) break; rb = t; }
+                            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[ra]); if (t == ra) break; ra = t; }
+                            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[rb]); if (t == rb) break; rb = t; }
                             if (ra == rb) break;
                             if (ra < rb) { unsigned t = ra; ra = rb; rb = t; }
                             if (atomicCAS(&parent[ra], ra, rb) == ra) break;
@@ -1055,8 +1130,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         // island hooking: larger root goes under the smaller one
                         unsigned ra = a, rb = b;
                         for (;;) {
-                            while (true) { unsigned t = lds_load_relaxed(&parent[ra]); if (t == ra) break; ra = t; }
-                            while (true) { unsigned t = lds_load_relaxed(&parent[rb]); if (t == rb) break; rb = t; }
+                            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[ra]); if (t == ra) break; ra = t; }
+                            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[rb]); if (t == rb) break; rb = t; }
                             if (ra == rb) break;
                             if (ra < rb) { unsigned t = ra; ra = rb; rb = t; }
                             if (atomicCAS(&parent[ra], ra, rb) == ra) break;
@@ -1110,7 +1185,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // ---- islands: flatten roots; empty the grid for the next substep; offsets of the new ws list ----
         for (int b = tid; b < N; b += nt) {
             unsigned r = b;
-            while (true) { unsigned t = lds_load_relaxed(&parent[r]); if (t == r) break; r = t; }
+            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[r]); if (t == r) break; r = t; }
             parent[b] = r;   // only ever replaces an ancestor by an older ancestor: concurrent walks stay valid
             islCnt[b] = 0;
             islWave[b] = (unsigned char)((unsigned)b % (unsigned)nsolve);
@@ -1124,7 +1199,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         if (tid < M) {
             const int b = N + tid;
             unsigned r = b;
-            while (true) { unsigned t = lds_load_relaxed(&parent[r]); if (t == r) break; r = t; }
+            while (true) { unsigned t = lds_load_relaxed<PAR_DS>(&parent[r]); if (t == r) break; r = t; }
             parent[b] = r;
             islCnt[b] = 0;
             islWave[b] = (unsigned char)((unsigned)b % (unsigned)nw);
