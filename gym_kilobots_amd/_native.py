@@ -26,6 +26,8 @@ REDUCE_MAX_CHANNELS = 8     # KB_REDUCE_MAX_CHANNELS: floats per message of kb_s
 GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_sense_grid, a bit each
 MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense_contacts
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
+RENDER_OBJECTS, RENDER_BOTS, RENDER_LIGHT = 1, 2, 4     # KB_RENDER_*: the layers of kb_render, a bit each
+RENDER_MAX_SIDE = 2048     # KB_RENDER_MAX_SIDE: pixels along either side of a frame of kb_render
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -69,6 +71,12 @@ class KbOutline(C.Structure):
                 ('radius', C.c_float * MAX_OBJECTS), ('verts', ((C.c_float * 2) * MAX_POLY_VERTS) * MAX_OBJECTS)]
 
 
+class KbRenderStyle(C.Structure):
+    """kb_render_style: the colours of kb_render as (R, G, B) bytes; kb_render_default_style fills in the reference's."""
+    _fields_ = [('table', C.c_uint8 * 3), ('body', C.c_uint8 * 3), ('ring', C.c_uint8 * 3), ('mark', C.c_uint8 * 3), ('light', C.c_uint8 * 3),
+                ('light_alpha', C.c_uint8), ('obj', (C.c_uint8 * 3) * MAX_OBJECTS)]
+
+
 class KbResetParams(C.Structure):
     _fields_ = [('seed', C.c_uint64), ('env_offset', C.c_int32), ('mean', C.c_float * 2), ('std', C.c_float),
                 ('random_theta', C.c_int32), ('random_velocity', C.c_int32), ('resolve', C.c_int32)]
@@ -89,7 +97,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
@@ -160,6 +168,10 @@ def load():
     lib.kb_sense_grid.restype = C.c_int
     lib.kb_sense_contacts.argtypes = [_P, C.c_int, C.c_float, _P, _P, _P, _P, _P]
     lib.kb_sense_contacts.restype = C.c_int
+    lib.kb_render_default_style.argtypes = [C.POINTER(KbRenderStyle)]
+    lib.kb_render_default_style.restype = C.c_int
+    lib.kb_render.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(KbRenderStyle), _P, _P, _P, _P]
+    lib.kb_render.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -241,6 +253,89 @@ def check_grid(width, height, planes):
     if isinstance(planes, bool) or planes <= 0 or planes & ~(GRID_COUNT | GRID_FLOW | GRID_OBJECTS):
         raise ValueError('planes must be a non-empty subset of GRID_COUNT | GRID_FLOW | GRID_OBJECTS')
     return width, height, planes
+
+
+RENDER_LAYERS = {'objects': RENDER_OBJECTS, 'bots': RENDER_BOTS, 'light': RENDER_LIGHT}
+RENDER_STYLE_FIELDS = ('table', 'body', 'ring', 'mark', 'light', 'light_alpha', 'obj')
+
+
+def check_render(width, height, layers):
+    """The limits of kb_render on the frame and the layers (a RENDER_* mask or an iterable of 'objects' | 'bots' | 'light');
+    ValueError where the library would answer KB_EINVAL.  Returns (width, height, layers as an integer mask)."""
+    width, height = int(width), int(height)
+    if not (1 <= width <= RENDER_MAX_SIDE and 1 <= height <= RENDER_MAX_SIDE):
+        raise ValueError('width and height must be in 1..%d' % RENDER_MAX_SIDE)
+    if isinstance(layers, str):
+        layers = (layers,)
+    if not isinstance(layers, int):
+        mask = 0
+        for name in layers:
+            if name not in RENDER_LAYERS:
+                raise ValueError("layers must be a RENDER_* mask or made of 'objects', 'bots' and 'light'")
+            mask |= RENDER_LAYERS[name]
+        layers = mask
+    if isinstance(layers, bool) or layers <= 0 or layers & ~(RENDER_OBJECTS | RENDER_BOTS | RENDER_LIGHT):
+        raise ValueError('layers must be a non-empty subset of RENDER_OBJECTS | RENDER_BOTS | RENDER_LIGHT')
+    return width, height, layers
+
+
+def render_style(style=None):
+    """A KbRenderStyle: the defaults (kb_render_default_style) with the keys of the dict `style` written over them.  Colours
+    are (R, G, B) in 0..255, 'light_alpha' one such number, 'obj' a list of up to MAX_OBJECTS colours (the rest keep the
+    default).  ValueError for an unknown key or a value outside a byte."""
+    st = KbRenderStyle()
+    check(load().kb_render_default_style(C.byref(st)), 'kb_render_default_style')
+
+    def colour(dst, v, key):
+        v = [int(c) for c in v]
+        if len(v) != 3 or not all(0 <= c <= 255 for c in v):
+            raise ValueError('style[%r] must be (R, G, B) in 0..255' % key)
+        for i in range(3):
+            dst[i] = v[i]
+    for key, v in dict(style or {}).items():
+        if key not in RENDER_STYLE_FIELDS:
+            raise ValueError('style: unknown key %r (the keys are %s)' % (key, ', '.join(RENDER_STYLE_FIELDS)))
+        if key == 'light_alpha':
+            if not 0 <= int(v) <= 255:
+                raise ValueError("style['light_alpha'] must be in 0..255")
+            st.light_alpha = int(v)
+        elif key == 'obj':
+            v = list(v)
+            if len(v) > MAX_OBJECTS:
+                raise ValueError("style['obj'] holds at most %d colours" % MAX_OBJECTS)
+            for m, c in enumerate(v):
+                colour(st.obj[m], c, 'obj')
+        else:
+            colour(getattr(st, key), v, key)
+    return st
+
+
+def _f32(v):
+    return C.c_float(v).value
+
+
+def render_bands(num_bots, world_width, world_height, bot_radius, width, height):
+    """(bands, rows per band) of kb_render for a handle of this shape and a frame of this size: the host rule of RenderLds
+    (csrc/kb_sense.h) restated, with the broadphase grid of kb_create.  A band's bytes are staged in what the
+    64 KiB of dynamic LDS leave behind the cell lists (3 width bytes per row, 32 kept back for alignment), a band holds at
+    most 8192 pixels and at least one row; the fewest such bands, rows spread evenly."""
+    cell = 0.875
+    while cell < _f32(_f32(2.0 * _f32(bot_radius)) * 25.0):
+        cell *= 2.0
+    W, H = _f32(_f32(world_width) * 25.0), _f32(_f32(world_height) * 25.0)
+    while True:
+        inv = _f32(1.0 / cell)
+        gw, gh = max(1, int(-(-_f32(W * inv) // 1))), max(1, int(-(-_f32(H * inv) // 1)))
+        if gw * gh <= 8192:
+            break
+        cell *= 2.0
+    NP = (int(num_bots) + 3) & ~3
+    objects_image = 16 * MAX_OBJECTS + 32 * MAX_OBJECTS * MAX_POLY_VERTS + 8 * MAX_OBJECTS + 16 * ((MAX_OBJECTS + 4) // 4)
+    stage = (objects_image + 4 * MAX_OBJECTS + 16 * MAX_LIGHTS + 16 + 20 * NP + 2 * ((gw * gh + 1) & ~1) + 15) & ~15
+    room = 64 * 1024 - stage
+    max_rows = max(1, min((room - 32) // (3 * width), 8192 // width))
+    bands = (height + max_rows - 1) // max_rows
+    return bands, (height + bands - 1) // bands
 
 
 def histogram_sectors(n_sectors):

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts) are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -830,6 +830,53 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
         return launched("kb_sense_grid");
     }
     return KB_OK;
+}
+
+int kb_render_default_style(kb_render_style *out) {
+    if (!out) return fail(KB_EINVAL, "kb_render_default_style: NULL argument");
+    const uint8_t table[3] = {255, 255, 255}, body[3] = {150, 150, 150}, ring[3] = {100, 100, 100}, mark[3] = {255, 255, 255};
+    const uint8_t light[3] = {255, 255, 30}, obj[3] = {93, 133, 195};
+    for (int c = 0; c < 3; ++c) {
+        out->table[c] = table[c]; out->body[c] = body[c]; out->ring[c] = ring[c]; out->mark[c] = mark[c]; out->light[c] = light[c];
+        for (int m = 0; m < KB_MAX_OBJECTS; ++m) out->obj[m][c] = obj[c];
+    }
+    out->light_alpha = 150;
+    return KB_OK;
+}
+
+int kb_render(kb_sim *sim, int width, int height, int layers, const kb_render_style *style, const uint32_t *d_body_rgb,
+              const uint32_t *d_mark_rgb, uint8_t *d_rgb, void *stream) {
+    if (!sim || !d_rgb) return fail(KB_EINVAL, "kb_render: NULL argument");
+    if (layers <= 0 || (layers & ~(KB_RENDER_OBJECTS | KB_RENDER_BOTS | KB_RENDER_LIGHT)))
+        return fail(KB_EINVAL, "kb_render: layers must be a non-empty subset of KB_RENDER_OBJECTS | KB_RENDER_BOTS | KB_RENDER_LIGHT");
+    if (width < 1 || width > KB_RENDER_MAX_SIDE || height < 1 || height > KB_RENDER_MAX_SIDE)
+        return fail(KB_EINVAL, "kb_render: 1 <= width, height <= KB_RENDER_MAX_SIDE (2048) required");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_render: kb_bind() first");
+    const Params &p = sim->p;
+    kb_render_style st;
+    if (style) st = *style;
+    else kb_render_default_style(&st);
+    const auto rgb = [](const uint8_t *c) { return (unsigned)c[0] << 16 | (unsigned)c[1] << 8 | (unsigned)c[2]; };
+    RenderArgs a;
+    memset(&a, 0, sizeof(a));
+    const RenderLds L(p.NP, p.ncell, width, height);
+    a.width = width; a.height = height; a.layers = layers; a.bands = L.bands; a.band_rows = L.rows;
+    a.cw = (p.xmax - p.xmin) / (float)width; a.ch = (p.ymax - p.ymin) / (float)height;       // (kb_outline.arena is these four)
+    const float r = sim->cfg.bot_radius, ro = r + 0.002f, Ro = ro * WORLD_SCALE;
+    a.Ro2 = Ro * Ro;
+    a.Ri = (ro - 0.005f) * WORLD_SCALE; a.Ri2 = a.Ri * a.Ri;
+    a.Lf = (r - 0.005f) * WORLD_SCALE; a.Hw = 0.0025f * WORLD_SCALE;
+    const bool positional = sim->cfg.light_type == KB_LIGHT_CIRCULAR || sim->cfg.light_type == KB_LIGHT_MOMENTUM || sim->cfg.light_type == KB_LIGHT_COMPOSITE;
+    a.nlights = (layers & KB_RENDER_LIGHT) && positional ? p.lcount : 0;
+    for (int l = 0; l < a.nlights; ++l) { const float Rl = p.lradius[l] * WORLD_SCALE; a.Rl2[l] = Rl * Rl; }
+    a.table = rgb(st.table); a.body = rgb(st.body); a.ring = rgb(st.ring); a.mark = rgb(st.mark); a.light = rgb(st.light); a.alpha = st.light_alpha;
+    for (int m = 0; m < KB_MAX_OBJECTS; ++m) a.obj[m] = rgb(st.obj[m]);
+    kb_outline ol;
+    kb_get_outline(sim, &ol);
+    const int reach = Ro * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Ro, p.inv_cell) : p.gw + p.gh;
+    hipLaunchKernelGGL(kb_render_kernel, dim3((unsigned)p.E * (unsigned)L.bands), dim3(256), (size_t)L.bytes, (hipStream_t)stream, p, ol, a, reach,
+                       d_body_rgb, d_mark_rgb, d_rgb);
+    return launched("kb_render");
 }
 
 int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float *d_impulse, float *d_touch, float *d_obj, void *stream) {

@@ -1,8 +1,8 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
 // kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
-// a whole env into an image of the table for an observer outside it; and kb_sense_contacts, which reads no poses at all but
-// the contact store the last step left.
+// a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
+// the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -624,6 +624,160 @@ __global__ void __launch_bounds__(256) kb_grid_objects_kernel(const kb_outline o
     for (int m = 0; m < M; ++m) {
         float best, brx, bry;
         out[m * chan] = kb_object_walk(I, m, I.frame[m], cx, cy, best, brx, bry) ? 1.0f : 0.0f;
+    }
+}
+
+// ---- kb_render: RGB frames of every env ------------------------------------------------------------------------------------
+#ifndef KB_RENDER_SINCOS
+#define KB_RENDER_SINCOS 1              // sine and cosine of the winning kilobot: 1 once per kilobot into LDS before the walk, 0 per covered pixel (A/B knob)
+#endif
+constexpr int RENDER_LDS_LIMIT = 64 * 1024;     // the default limit for dynamic LDS: no attribute to raise
+constexpr int RENDER_BAND_PIXELS = 8192;        // at most 32 pixels per lane and band: a large frame of a single env still fills the chip
+struct RenderArgs {         // the host constants of the definition (include/kilobots_hip.h) and the style, colours as 0x00RRGGBB
+    int width, height, layers, bands, band_rows, nlights;
+    float cw, ch, Ro2, Ri, Ri2, Lf, Hw, Rl2[KB_MAX_LIGHTS];
+    unsigned table, body, ring, mark, light, alpha, obj[KB_MAX_OBJECTS];
+};
+struct RenderLds {      // byte offsets: the ObjectsLds image at 0, ocol[8] (u32), lit[4] (float4: x, y, Rl2), lcol (uint4: the light's share of the blend and 255 - alpha) --
+                        // constants, which cost no register --, then pos (float2), sc (float2: sin, cos), nextb, cellOf, head (u16 each), stage (bytes)
+    static constexpr int ocol = ObjectsLds().bytes, lit = ocol + 4 * KB_MAX_OBJECTS, lcol = lit + 16 * KB_MAX_LIGHTS, pos = lcol + 16;
+    int sc, nextb, cellOf, head, stage, bands, rows, bytes;
+    // the rows of a band: what fits behind the fixed part (3 width bytes each; up to 15 bytes of misalignment of the band in
+    // d_rgb in front and the rounding to 16 behind), at most RENDER_BAND_PIXELS pixels, at least one; then the fewest such
+    // bands, rows spread evenly over them
+    static constexpr int max_rows(int room, int width) {
+        const int fit = (room - 32) / (3 * width), cap = RENDER_BAND_PIXELS / width;
+        return fit < cap ? (fit > 1 ? fit : 1) : (cap > 1 ? cap : 1);
+    }
+    __host__ __device__ constexpr RenderLds(int NP, int ncell, int width, int height)
+        : sc(pos + 8 * NP), nextb(sc + (KB_RENDER_SINCOS ? 8 * NP : 0)), cellOf(nextb + 2 * NP), head(cellOf + 2 * NP),
+          stage((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),
+          bands((height + max_rows(RENDER_LDS_LIMIT - stage, width) - 1) / max_rows(RENDER_LDS_LIMIT - stage, width)),
+          rows((height + bands - 1) / bands), bytes(stage + ((3 * rows * width + 15 + 15) & ~15)) {}
+};
+static_assert(ObjectsLds().bytes % 16 == 0, "kb_render_kernel: lit, lcol and pos start on 16 bytes");
+static_assert(RenderLds(KB_MAX_BOTS, MAX_CELLS, KB_RENDER_MAX_SIDE, KB_RENDER_MAX_SIDE).bytes <= RENDER_LDS_LIMIT &&
+              RenderLds(KB_MAX_BOTS, MAX_CELLS, 64, 48).bands == 1, "kb_render_kernel: LDS image");
+
+// RGB frames (kb_render): one workgroup per (env, band of rows), one pixel per lane and pass.  GATHER: the workgroup builds the
+// env's cell lists (kb_build_cell_lists) and every pixel walks the cells within reach of its own (kb_walk_in_range with a = -1:
+// no kilobot is excluded), its cell computed from (px, py) as a kilobot's is.  It keeps the highest index among the hits with
+// dd <= Ro2 -- the walk lets a NaN through -- so nothing depends on the order of the chains and no pixel is ever updated by
+// two lanes.  The walk finds every covering kilobot, those outside the arena too: the cell index along an axis is
+// clamp(floor(fl(fl(v - min) * inv_cell))), monotone in v, and two coordinates within Ro of each other give unclamped indices
+// at most sense_reach(Ro, inv_cell) apart (the argument of sense_reach); the clamp to the grid maps both monotonically and moves
+// no two indices further apart, and a pixel centre's own index is clamped like any other.
+// Then the winner's frame (sine and cosine from LDS, one kb_sincosf per kilobot ahead of the walk, or per covered pixel:
+// KB_RENDER_SINCOS), the objects for pixels no kilobot covers (kb_stage_objects + kb_object_walk, as kb_grid_objects_kernel;
+// every lane of a wave asks about the same object m, so the walk's scalar loop bounds hold), the light discs, and three bytes
+// into the band's staging area in LDS: 64 lanes write 192 consecutive bytes, at most two lanes to a word, which costs a store
+// nothing.  After one barrier the band leaves as 16-byte stores: its bytes are staged at the offset `mis` that
+// its first byte has from a 16-byte boundary of d_rgb, so that every aligned chunk of LDS is an aligned chunk of memory,
+// whatever the width; the (at most two) chunks the band only partly owns are written byte by byte.
+__global__ void __launch_bounds__(256) kb_render_kernel(const Params p, const kb_outline ol, const RenderArgs A, const int s,
+                                                        const unsigned *body_rgb, const unsigned *mark_rgb, unsigned char *d_rgb) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, nt = blockDim.x, N = p.N, W = A.width, H = A.height;
+    const int e = blockIdx.x / A.bands, row0 = (blockIdx.x % A.bands) * A.band_rows, rows = min(A.band_rows, H - row0);
+    const RenderLds L(p.NP, p.ncell, W, H);
+    const ObjectsImage I(smem);
+    unsigned *ocol = reinterpret_cast<unsigned *>(smem + L.ocol);
+    float4 *lit = reinterpret_cast<float4 *>(smem + L.lit);
+    uint4 *lcol = reinterpret_cast<uint4 *>(smem + L.lcol);
+    float2 *pos = reinterpret_cast<float2 *>(smem + L.pos);
+    float2 *sc = reinterpret_cast<float2 *>(smem + L.sc);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    unsigned char *stage = smem + L.stage;
+    const size_t o = (size_t)e * N;
+    const bool bots = (A.layers & KB_RENDER_BOTS) != 0;
+    const int M = (A.layers & KB_RENDER_OBJECTS) ? ol.num_objects : 0, nlights = A.nlights;
+    // the tables a pixel indexes by a run-time number go through LDS (they arrive in scalar registers, which cannot be indexed)
+#pragma unroll
+    for (int m = 0; m < KB_MAX_OBJECTS; ++m) if (tid == 64 + m) ocol[m] = A.obj[m];
+#pragma unroll
+    for (int l = 0; l < KB_MAX_LIGHTS; ++l) {
+        if (tid == 96 + l && l < nlights)
+            lit[l] = make_float4(p.buf.light_x[(size_t)e * nlights + l] * WORLD_SCALE, p.buf.light_y[(size_t)e * nlights + l] * WORLD_SCALE, A.Rl2[l], 0.0f);
+    }
+    if (tid == 100) lcol[0] = make_uint4(((A.light >> 16) & 255u) * A.alpha + 127u, ((A.light >> 8) & 255u) * A.alpha + 127u, (A.light & 255u) * A.alpha + 127u, 255u - A.alpha);
+    if (M > 0) kb_stage_objects(ol, I, e, tid, p.buf.ox, p.buf.oy, p.buf.otheta);
+    if (bots) {
+        if (KB_RENDER_SINCOS) {
+            for (int b = tid; b < N; b += nt) {
+                float sn, cs;
+                kb_sincosf(p.buf.theta[o + b], sn, cs);
+                sc[b] = make_float2(sn, cs);
+            }
+        }
+        kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    } else {
+        __syncthreads();
+    }
+    // (the low bits of the address of the band's first byte: 32-bit arithmetic, which may wrap, gives them)
+    const int mis = (int)(((unsigned)reinterpret_cast<uintptr_t>(d_rgb) + ((unsigned)e * (unsigned)H + (unsigned)row0) * (unsigned)W * 3u) & 15u);
+    const int npix = rows * W;
+    const int q256 = nt / W, r256 = nt % W;
+    int r = tid / W, i = tid % W;
+    for (int f = tid; f < npix; f += nt) {
+        const float px = p.xmin + ((float)i + 0.5f) * A.cw;
+        const float py = p.ymin + ((float)(H - 1 - (row0 + r)) + 0.5f) * A.ch;
+        unsigned col = A.table;
+        int win = -1;
+        if (bots) {
+            int cx = (int)floorf((px - p.xmin) * p.inv_cell);
+            int cy = (int)floorf((py - p.ymin) * p.inv_cell);
+            cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
+            cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
+            kb_walk_in_range(p, pos, head, nextb, -1, cy * p.gw + cx, make_float2(px, py), s, A.Ro2, [&](unsigned b, float, float, float dd) {
+                if (dd <= A.Ro2) win = max(win, (int)b);
+            });
+        }
+        if (win >= 0) {
+            const float2 pb = pos[win];
+            const float qx = px - pb.x, qy = py - pb.y;
+            const float dd = qx * qx + qy * qy;
+            float sn, cs;
+            if (KB_RENDER_SINCOS) { const float2 t = sc[win]; sn = t.x; cs = t.y; }
+            else kb_sincosf(p.buf.theta[o + win], sn, cs);
+            const float a = cs * qx + sn * qy, l = cs * qy - sn * qx;
+            if (A.Lf > 0.0f && a >= 0.0f && a <= A.Lf && fabsf(l) <= A.Hw) col = mark_rgb ? mark_rgb[o + win] : A.mark;
+            else if (!(A.Ri > 0.0f) || dd > A.Ri2) col = A.ring;
+            else col = body_rgb ? body_rgb[o + win] : A.body;
+        } else {
+            for (int m = 0; m < M; ++m) {
+                float best, brx, bry;
+                if (kb_object_walk(I, m, I.frame[m], px, py, best, brx, bry)) col = ocol[m];
+            }
+        }
+        unsigned cr = (col >> 16) & 255u, cg = (col >> 8) & 255u, cb = col & 255u;
+        for (int l = 0; l < nlights; ++l) {
+            const float4 lt = lit[l];
+            const float fx = lt.x - px, fy = lt.y - py;
+            if (fx * fx + fy * fy <= lt.z) {
+                const uint4 lc = lcol[0];       // (light_c * A + 127 per channel, 255 - A)
+                cr = (lc.x + cr * lc.w) / 255u;
+                cg = (lc.y + cg * lc.w) / 255u;
+                cb = (lc.z + cb * lc.w) / 255u;
+            }
+        }
+        unsigned char *dst = stage + mis + 3 * f;
+        dst[0] = (unsigned char)cr; dst[1] = (unsigned char)cg; dst[2] = (unsigned char)cb;
+        r += q256; i += r256;
+        if (i >= W) { i -= W; r++; }
+    }
+    __syncthreads();
+    const int end = mis + 3 * npix;         // the band's bytes are stage[mis .. end)
+    const size_t first = ((size_t)e * H + row0) * (size_t)W * 3;        // the band's first byte in d_rgb
+    unsigned char *base = d_rgb + first - mis;      // 16-byte aligned; nothing before base + mis or from base + end on is touched
+    for (int c = tid; 16 * c < end; c += nt) {
+        const int lo = 16 * c;
+        if (lo >= mis && lo + 16 <= end) {
+            reinterpret_cast<uint4 *>(base)[c] = reinterpret_cast<const uint4 *>(stage)[c];
+        } else {
+            for (int k = max(lo, mis); k < min(lo + 16, end); ++k) base[k] = stage[k];
+        }
     }
 }
 

@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, contact_obs=None, **cfg):
+                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -39,7 +39,9 @@ class BatchedKilobotsEnv(object):
         contact_obs: k, an int in 0..16, adds touch and push sensing from the contacts the solver acted on in the last world
         step: contacts() returns (partner [E, N, k], impulse [E, N, k], touch [E, N, 4], obj [E, M, 2] or None)
         (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
-        'contacts'.  None adds nothing."""
+        'contacts'.  None adds nothing.
+        render_size: (width, height) in pixels lets render('rgb_array') return the frames of every env, [E, height, width, 3]
+        uint8 on the device (KilobotSim.render).  reset(), step() and the info dict do not change with it."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -98,6 +100,13 @@ class BatchedKilobotsEnv(object):
             if isinstance(contact_obs, bool) or not isinstance(contact_obs, (int, np.integer)) or not 0 <= contact_obs <= nat.MAX_CONTACT_SLOTS:
                 raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
             self.contact_obs = int(contact_obs)
+        self.render_size = None
+        if render_size is not None:
+            try:
+                width, height = render_size
+                self.render_size = nat.check_render(width, height, nat.RENDER_BOTS)[:2]
+            except TypeError as err:
+                raise ValueError('render_size must be (width, height): %s' % err)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -232,6 +241,15 @@ class BatchedKilobotsEnv(object):
         if self.contact_obs is None:
             raise ValueError('create the env with contact_obs=k to observe contacts')
         return self.sim.contacts(self.contact_obs)
+
+    def render(self, mode='rgb_array'):
+        """frames [E, height, width, 3] uint8 of the current state for the render_size=(width, height) the env was created
+        with: KilobotSim.render.  Only mode 'rgb_array' exists: there is no window."""
+        if mode != 'rgb_array':
+            raise NotImplementedError("BatchedKilobotsEnv.render: only mode 'rgb_array' (got %r)" % (mode,))
+        if self.render_size is None:
+            raise ValueError('create the env with render_size=(width, height) to render frames')
+        return self.sim.render(*self.render_size)
 
     def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
         """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env

@@ -38,7 +38,7 @@ def _default_sim_factory(*args, **kwargs):
 
 
 class KilobotsEnv(object):
-    metadata = {'render.modes': ['human']}
+    metadata = {'render.modes': ['human', 'rgb_array']}
 
     world_size = world_width, world_height = 2., 1.5
     screen_size = screen_width, screen_height = 1200, 900
@@ -477,8 +477,26 @@ class KilobotsEnv(object):
             sim.step(1)
 
     def render(self, mode=None):
-        raise NotImplementedError('rendering (pygame viewer) is outside the accelerated hot path; '
-                                  'see SURVEY.md section 2, component 8')
+        """mode 'rgb_array': the frame of the env as a numpy array [screen_height, screen_width, 3] uint8 ([num_envs, ...]
+        with num_envs > 1), rasterised on the device (kb_render) with every kilobot's _body_color / _highlight_color and
+        every object's color.  mode None takes self.render_mode, which is 'human' as in the reference: there is no window,
+        so that mode raises.  _draw_on_table / _draw_on_top take a pygame viewer and are not called."""
+        mode = self.render_mode if mode is None else mode
+        if mode != 'rgb_array':
+            raise NotImplementedError('rendering (pygame viewer) is outside the accelerated hot path; '
+                                      "render('rgb_array') returns the frame as an array")
+        if self._sim is None:
+            raise RuntimeError('call reset() before render()')
+        if not hasattr(self._sim, 'render'):
+            raise NotImplementedError("render('rgb_array') needs the device simulator (this backend has no render)")
+        dev = self._sim.x.device
+        word = lambda c: (int(c[0]) & 255) << 16 | (int(c[1]) & 255) << 8 | (int(c[2]) & 255)
+        rows = [[word(k._body_color) for k in self._kilobots], [word(k._highlight_color) for k in self._kilobots]]
+        cols = torch.tensor(rows, dtype=torch.int32).unsqueeze(1).expand(2, self.num_envs, len(self._kilobots)).contiguous().to(dev)
+        style = {'obj': [[int(v) for v in ob.color] for ob in self._objects]} if self._objects else None
+        rgb = self._sim.render(self.screen_width, self.screen_height, style=style, body_rgb=cols[0], mark_rgb=cols[1])
+        frame = rgb.cpu().numpy()
+        return frame[0] if self.num_envs == 1 else frame
 
     def get_objects(self):
         return self._objects

@@ -387,6 +387,34 @@ class KilobotSim:
                       'kb_sense_contacts')
         return partner, impulse, touch, obj
 
+    def render(self, width, height, layers=('objects', 'bots', 'light'), style=None, body_rgb=None, mark_rgb=None, out=None):
+        """RGB frames of every env on the current state (kb_render; KilobotsEnv.render of the reference as a point-sampled
+        image, include/kilobots_hip.h): [E, height, width, 3] uint8 on the sim's device, row 0 at ymax, column 0 at xmin.
+        layers: a RENDER_* mask or an iterable of 'objects', 'bots' and 'light', painted in that order; 'objects' on a sim
+        without objects and 'light' on a sim without a positional light draw nothing.  style: a dict of the fields of
+        kb_render_style ('table', 'body', 'ring', 'mark', 'light': (R, G, B); 'light_alpha'; 'obj': a list of colours, one per
+        object); missing keys take the reference's colours.  body_rgb, mark_rgb: contiguous int32 / uint32 tensors [E, N] of
+        0x00RRGGBB words on the sim's device, the body colour and the colour of the heading mark of every kilobot; None: the
+        style's.  out: a preallocated contiguous uint8 tensor of the result's shape to write into; every byte is written."""
+        width, height, layers = nat.check_render(width, height, layers)
+        st = style if isinstance(style, nat.KbRenderStyle) else nat.render_style(style)
+        out, = self._outputs(out, [((self.num_envs, height, width, 3), torch.uint8, 'rgb')], 'the rgb tensor')
+        ptrs = []
+        for name, t in (('body_rgb', body_rgb), ('mark_rgb', mark_rgb)):
+            if t is None:
+                ptrs.append(None)
+                continue
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.int32, getattr(torch, 'uint32', torch.int32)) and t.is_contiguous()
+                    and tuple(t.shape) == (self.num_envs, self.num_bots)):
+                raise ValueError('%s must be a contiguous int32 or uint32 cuda tensor of shape %s' % (name, (self.num_envs, self.num_bots)))
+            if t.device != self.device:
+                raise ValueError('%s lives on %s, the simulator on %s' % (name, t.device, self.device))
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_render(self._h, width, height, layers, C.byref(st), ptrs[0], ptrs[1], C.c_void_p(out.data_ptr()), self._stream()),
+                      'kb_render')
+        return out
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

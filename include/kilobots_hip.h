@@ -430,6 +430,58 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
 int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float *d_impulse, float *d_touch, float *d_obj,
                       void *stream);
 
+/* RGB frames of every env, rasterised on the device: what KilobotsEnv.render draws (kilobots_env.py:221-275 with
+ * Kilobot.draw, kilobot.py:129-145, Body.draw, body.py:156-281, and Light.draw, light.py:95-96,194-195) as a point-sampled
+ * image with every operation stated.  No pixel parity with pygame is claimed: its integer circle and line rasterisers are
+ * not restated.  A pure function of the poses, the object poses and the light positions; no range cut, no state.
+ * d_rgb [num_envs][height][width][3] uint8, R, G, B; row 0 is the ymax edge (the viewer flips y), column 0 the xmin edge;
+ *       byte aligned.  Every byte is written on every call, exactly once, by a plain store.
+ * d_body_rgb, d_mark_rgb [num_envs][num_bots] uint32 words 0x00RRGGBB (the top byte is ignored) or NULL: the body colour and
+ *       the colour of the heading mark (the LED) of every kilobot (Kilobot._body_color, _highlight_color; set_color,
+ *       kilobot.py:83-84,262-263).  NULL: style->body / style->mark for every kilobot.
+ * style NULL: the defaults of kb_render_default_style, the reference's colours: table (255, 255, 255) kilobots_env.py:252-253,
+ *       body (150, 150, 150) kilobot.py:42,132, ring (100, 100, 100) kilobot.py:133, mark (255, 255, 255) kilobot.py:43,145,
+ *       light (255, 255, 30) with light_alpha 150 light.py:195, every obj[m] (93, 133, 195) body.py:21.
+ * Host constants, all fp32, every step one operation rounded on its own:  (xmin, xmax, ymin, ymax) = kb_outline.arena;
+ *   cw = (xmax - xmin) / (float)width, ch = (ymax - ymin) / (float)height;  with r = bot_radius:  ro = r + 0.002f,
+ *   Ro = ro * 25.0f, Ro2 = Ro * Ro, Ri = (ro - 0.005f) * 25.0f, Ri2 = Ri * Ri, Lf = (r - 0.005f) * 25.0f, Hw = 0.0025f * 25.0f;
+ *   per positional light component l:  Rl = radius_l * 25.0f, Rl2 = Rl * Rl  (radius_l: light_radius, or lightc_radius[l]
+ *   of a composite light).
+ * Pixel (row j, column i); every multiplication, addition and comparison is its own fp32 operation, nothing is contracted:
+ *   px = xmin + ((float)i + 0.5f) * cw,  py = ymin + ((float)(height - 1 - j) + 0.5f) * ch;  the colour starts as table.
+ *   KB_RENDER_OBJECTS: obj[m] of the HIGHEST m whose inside flag holds for the point (px, py) (painter's order,
+ *     kilobots_env.py:261-262); the flag is the predicate of kb_sense_objects / KB_GRID_OBJECTS, unchanged.  The highlight
+ *     triangle of a CornerQuad (body.py:174) is not drawn: the handle does not know a CornerQuad from a Quad.
+ *   KB_RENDER_BOTS: for kilobot b  qx = px - x_b, qy = py - y_b, dd = qx * qx + qy * qy;  b covers the pixel iff dd <= Ro2 (a NaN
+ *     or infinite coordinate never covers).  The HIGHEST covering b wins (painter's order, kilobots_env.py:265-266); no other
+ *     kilobot matters.  With (s, c) the library's sine and cosine of theta_b, a = c * qx + s * qy, l = c * qy - s * qx:
+ *       mark_b  if Lf > 0 && a >= 0 && a <= Lf && fabsf(l) <= Hw  (the line from the centre to the front, kilobot.py:137-145),
+ *       ring    otherwise if !(Ri > 0) || dd > Ri2  (the 5 mm outline, kilobot.py:133-134),
+ *       body_b  otherwise.  A kilobot pixel replaces the object colour.
+ *   KB_RENDER_LIGHT: last, for every positional component l in component order (KB_LIGHT_CIRCULAR and KB_LIGHT_MOMENTUM, alone
+ *     or inside a KB_LIGHT_COMPOSITE):  fx = light_x[e][l] * 25.0f - px, fy likewise;  inside iff fx * fx + fy * fy <= Rl2.  An
+ *     inside pixel is blended per channel in integers, v = (light_c * A + v * (255 - A) + 127) / 255 with A = light_alpha; later
+ *     components blend over earlier ones.  A handle with no light or a KB_LIGHT_GRADIENT light draws nothing for this layer:
+ *     not an error.
+ *   The arena border line (kilobots_env.py:254-255, 3 mm wide, centred on the edge) is not drawn.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_rgb;  layers not a non-empty subset of
+ * the three bits;  width or height outside 1..KB_RENDER_MAX_SIDE.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, theta; ox, oy, otheta when the handle has objects and the layer is on; light_x, light_y when it has positional
+ * lights and the layer is on; the two colour arrays when given.  Writes d_rgb only.  One launch.  Asynchronous on `stream`.
+ *
+ * kb_render_default_style: the defaults into *out; KB_EINVAL for NULL.  Host only. */
+#define KB_RENDER_OBJECTS 1
+#define KB_RENDER_BOTS    2
+#define KB_RENDER_LIGHT   4
+#define KB_RENDER_MAX_SIDE 2048
+typedef struct kb_render_style {
+    uint8_t table[3], body[3], ring[3], mark[3], light[3], light_alpha;
+    uint8_t obj[KB_MAX_OBJECTS][3];
+} kb_render_style;
+int kb_render_default_style(kb_render_style *out);
+int kb_render(kb_sim *sim, int width, int height, int layers, const kb_render_style *style,
+              const uint32_t *d_body_rgb, const uint32_t *d_mark_rgb, uint8_t *d_rgb, void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into
