@@ -36,41 +36,68 @@
     int maxD = 0;
     unsigned mycnt = 0;
     const float nm_bb = p.nm_bb, nm_wb = p.nm_wb;
-    const int DUMMY = NB - 1;       // scratch body of the lanes that are not part of a round of the depth pass
 #ifdef KB_SOLVER_PRIO
     __builtin_amdgcn_s_setprio(KB_SOLVER_PRIO);     // the serial chain of the substep: ahead of the other envs' throughput phases
 #endif
     if (solving) {
-        unsigned mybase = 0;
-        for (int w = 0; w < wave; ++w) mybase += misc[M_WCNT + w];
+        // ---- light load: bodies and key of the contacts of this wave, in arrival order.  The grouping pass left the wave's fill
+        // pointer at the end of its stretch of lOrder, so the stretch is two words read side by side. ----
         mycnt = misc[M_WCNT + wave];
-        // ---- light load: bodies and key of the contacts of this wave, in arrival order ----
+        const unsigned mybase = misc[M_WFILL + wave] - mycnt;
         unsigned lk[KRB];           // key (6) | rank (8) << 8 | staging index << 16 | valid << 31;  key 63: contact of a sleeping island
         unsigned lp[KRB];           // a | b << 16 (body indices; a wall is WALL_CODE + w)
         int rdepth[KRB];
+        unsigned klo[KRB], khi[KRB];    // the slot's key as a bit (none: no contact, or one of a sleeping island)
 #define RB_A(j) ((int)(lp[j] & 0xFFFFu))
 #define RB_B(j) ((int)(lp[j] >> 16))
-        unsigned mlo = 0, mhi = 0;
+        // Both slots go through every trip together: the lanes without a contact read entry 0 and drop what they get, so no
+        // slot waits under a branch of its own for the slot in front of it (as in label_pass_bins).
+        {
+            unsigned c_[KRB], inf_[KRB];
+            bool v_[KRB], awake_[KRB];
 #pragma unroll
-        for (int j = 0; j < KRB; ++j) {
-            const unsigned idx = lane + 64u * j;
-            lk[j] = 0u; lp[j] = 0u; rdepth[j] = 0;
-            if (idx < mycnt) {
-                const unsigned c = lOrder[mybase + idx];
-                const unsigned pr = lPair[c], inf = lInfo[c];
-                const unsigned cls = inf & 0x7Fu, r = (inf >> 8) & 0xFFu;
-                lp[j] = pr;
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned idx = lane + 64u * j;
+                v_[j] = idx < mycnt;
+                c_[j] = lOrder[v_[j] ? mybase + idx : 0u];
+            }
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                c_[j] = v_[j] ? c_[j] : 0u;
+                lp[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) { lp[j] = v_[j] ? lp[j] : 0u; awake_[j] = true; }
+            if (SLEEP) {
+                unsigned root_[KRB];
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) root_[j] = parent[lp[j] >> 16];
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) awake_[j] = active[root_[j]] != 0;
+            }
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned cls = inf_[j] & 0x7Fu, r = (inf_[j] >> 8) & 0xFFu;
                 unsigned key = cls * RK + (r < RK - 1 ? r : RK - 1);
-                if (SLEEP && !active[parent[pr >> 16]]) key = 63u;      // in no round (depth 0), its impulse is carried over
-                else {
-                    if (key < 32u) mlo |= 1u << key; else mhi |= 1u << (key - 32u);
-                    if (r >= RK - 1) atomicMax(&bkMaxRank[wave * NUM_CLS + cls], r);
-                }
-                lk[j] = key | (r << 8) | (c << 16) | 0x80000000u;
+                const bool on = v_[j] && awake_[j];
+                if (!on) key = 63u;     // in no round (depth 0), its impulse is carried over
+                const unsigned bit = on ? 1u << (key & 31u) : 0u;
+                klo[j] = key < 32u ? bit : 0u; khi[j] = key < 32u ? 0u : bit;
+                if (on && r >= RK - 1) atomicMax(&bkMaxRank[wave * NUM_CLS + cls], r);
+                lk[j] = v_[j] ? (key | (r << 8) | (c_[j] << 16) | 0x80000000u) : 0u;
+                rdepth[j] = 0;
             }
         }
-        mlo = wave_or(mlo); mhi = wave_or(mhi);
-        const unsigned long long keymask = ((unsigned long long)mhi << 32) | mlo;
+        // keys present in the wave, and those of them that the slots behind slot 0 hold as well (wave-uniform)
+        unsigned long long keymask = 0ull, restmask = 0ull;
+        {
+            unsigned mlo = 0, mhi = 0, rlo = 0, rhi = 0;
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) { mlo |= klo[j]; mhi |= khi[j]; if (j > 0) { rlo |= klo[j]; rhi |= khi[j]; } }
+            mlo = wave_or(mlo); mhi = wave_or(mhi);
+            keymask = ((unsigned long long)mhi << 32) | mlo;
+            if (mycnt > 64u) { rlo = wave_or(rlo); rhi = wave_or(rhi); restmask = ((unsigned long long)rhi << 32) | rlo; }
+        }
         wave_sync();   // bkMaxRank of this wave
 #ifdef KB_PROFILE
         if (tid == 0) { atomicAdd(&KB_PROF(8), (unsigned)__popcll(keymask)); atomicAdd(&KB_PROF(11), 1u); }
@@ -81,36 +108,48 @@
         // order of any two contacts that do -- so depth rounds give exactly the result of the key-by-key sweep. ----
         unsigned *bodyDepth = islCnt;   // zeroed before the contacts were grouped
         {
-            auto depth_round = [&](unsigned key_, int r_) __attribute__((always_inline)) {
-                int ia[KRB], ib[KRB];
-                unsigned da[KRB], db[KRB];
-                bool on[KRB];
+            // A round is one LDS trip under the EXEC mask of the lanes whose contact is of the round: the round a contact
+            // belongs to (its key; in the open-ended rank bucket its key and rank) and the addresses of its two bodies are
+            // made once, a wall contact names its kilobot twice (max(d, d) + 1: the wall has no depth), a slot without a
+            // contact of the key is left out by a scalar test, and the highest ranks of the wave's open-ended buckets are
+            // fetched once, one class per lane.
+            char *const bdB = reinterpret_cast<char *>(bodyDepth);
+#define RB_BD(off) (*reinterpret_cast<unsigned *>(bdB + (off)))
+            unsigned rc[KRB], ia4[KRB], ib4[KRB];
 #pragma unroll
-                for (int j = 0; j < KRB; ++j) {
-                    on[j] = (lk[j] >> 31) && (lk[j] & 63u) == key_ && (r_ < 0 || (int)((lk[j] >> 8) & 0xFFu) == r_);
-                    ia[j] = (on[j] && RB_A(j) < WALL_CODE) ? RB_A(j) : DUMMY;
-                    ib[j] = on[j] ? RB_B(j) : DUMMY;
-                    da[j] = bodyDepth[ia[j]]; db[j] = bodyDepth[ib[j]];
-                }
-#pragma unroll
-                for (int j = 0; j < KRB; ++j) {
-                    const unsigned d = max((on[j] && RB_A(j) < WALL_CODE) ? da[j] : 0u, db[j]) + 1u;
-                    if (on[j]) {
-                        rdepth[j] = (int)d;
-                        bodyDepth[ib[j]] = d;
-                        if (RB_A(j) < WALL_CODE) bodyDepth[ia[j]] = d;
-                    }
-                }
-                wave_sync();
-            };
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned key = lk[j] & 63u, r = (lk[j] >> 8) & 0xFFu;
+                const bool on = (lk[j] >> 31) != 0u && key != 63u;
+                rc[j] = on ? ((key % RK) == RK - 1 ? (key | (r << 6)) : key) : 0xFFFFFFFFu;
+                ib4[j] = 4u * (unsigned)RB_B(j);
+                ia4[j] = RB_A(j) < WALL_CODE ? 4u * (unsigned)RB_A(j) : ib4[j];
+            }
+            const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
             for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
                 const unsigned key_ = (unsigned)__builtin_ctzll(m_);
-                if ((key_ % RK) < RK - 1) depth_round(key_, -1);
+                const bool rest_ = ((restmask >> key_) & 1ull) != 0ull;
+                auto depth_round = [&](unsigned code_) __attribute__((always_inline)) {
+                    // (the contacts of a round share no body: the slots may go one after the other)
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) {
+                        if (j == 0 || rest_) {
+                            if (rc[j] == code_) {
+                                const unsigned d = max(RB_BD(ia4[j]), RB_BD(ib4[j])) + 1u;
+                                rdepth[j] = (int)d;
+                                RB_BD(ib4[j]) = d;
+                                RB_BD(ia4[j]) = d;
+                            }
+                        }
+                    }
+                    wave_sync();
+                };
+                if ((key_ % RK) < RK - 1) depth_round(key_);
                 else {
-                    const int maxr_ = (int)bkMaxRank[wave * NUM_CLS + key_ / RK];
-                    for (int r_ = RK - 1; r_ <= maxr_; ++r_) depth_round(key_, r_);
+                    const unsigned maxr_ = (unsigned)__builtin_amdgcn_readlane((int)mrow, (int)(key_ / RK));
+                    for (unsigned r_ = RK - 1; r_ <= maxr_; ++r_) depth_round(key_ | (r_ << 6));
                 }
             }
+#undef RB_BD
         }
 #pragma unroll
         for (int j = 0; j < KRB; ++j) maxD = max(maxD, rdepth[j]);
@@ -120,24 +159,41 @@
         // A depth level then lives in one slot (two at a boundary), and a round only pays for the slots that hold contacts
         // of its level. ----
         if (mycnt > 64u) {
+            // the place of every contact first (ballots and lane counts, nothing waits for memory), then one write per slot,
+            // and both slots read back side by side
+            unsigned at[KRB];
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) at[j] = 0u;
             unsigned base_ = 0;
             for (int d_ = SLEEP ? 0 : 1; d_ <= maxD; ++d_) {      // (depth 0: contacts of sleeping islands)
 #pragma unroll
                 for (int j = 0; j < KRB; ++j) {
                     const bool is = (lk[j] >> 31) && rdepth[j] == d_;
                     const unsigned long long m_ = __ballot(is);
-                    if (is) {
-                        const unsigned at = mybase + base_ + (unsigned)__popcll(m_ & ((1ull << lane) - 1ull));
-                        lOrder[at] = (unsigned short)((lk[j] >> 16) & 0xFFFu);
-                        lCbk[at] = (unsigned short)d_;
-                    }
+                    const unsigned mine = __builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_, base_));
+                    at[j] = is ? mine : at[j];
                     base_ += (unsigned)__popcll(m_);
                 }
             }
-            wave_sync();
 #pragma unroll
             for (int j = 0; j < KRB; ++j)
-                if (lk[j] >> 31) { lk[j] = (lk[j] & 0x8000FFFFu) | ((unsigned)lOrder[mybase + lane + 64u * j] << 16); rdepth[j] = lCbk[mybase + lane + 64u * j]; }
+                if (lk[j] >> 31) {
+                    lOrder[mybase + at[j]] = (unsigned short)((lk[j] >> 16) & 0xFFFu);
+                    lCbk[mybase + at[j]] = (unsigned short)rdepth[j];
+                }
+            wave_sync();
+            unsigned short o_[KRB], l_[KRB];
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned i_ = mybase + ((lk[j] >> 31) ? lane + 64u * j : 0u);
+                o_[j] = lOrder[i_]; l_[j] = lCbk[i_];
+            }
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const bool v_ = (lk[j] >> 31) != 0u;
+                lk[j] = v_ ? ((lk[j] & 0x8000FFFFu) | ((unsigned)o_[j] << 16)) : lk[j];
+                rdepth[j] = v_ ? (int)l_[j] : rdepth[j];
+            }
         }
         KB_STAMP_PRE(21);    // ... + dealing
         // depth levels present in every slot (bit min(depth, 63)), wave-uniform
@@ -154,32 +210,61 @@
             dhi[j] = lv ? ((lv >> 62) ? maxD : 64 - (int)__builtin_clzll(lv)) : 0;
         }
         // ---- full load of the contacts ----
+        // Two trips for both slots together: the contact's words, then its bodies.  The lanes without a contact load
+        // contact 0 and body 0 and keep the idle record (no bodies, no impulse, normal (1, 0)).
+        {
+            unsigned c_[KRB], pr_[KRB], inf_[KRB], root_[KRB];
+            float acc_[KRB];
+            float2 pa_[KRB], pb_[KRB];
+            bool v_[KRB];
 #pragma unroll
-        for (int j = 0; j < KRB; ++j) {
-            ra[j] = 0u; rb[j] = 0u; rm[j] = 0u;
-            if (lk[j] >> 31) {
-                const unsigned c = (lk[j] >> 16) & 0xFFFu;
-                const unsigned pr = lPair[c], inf = lInfo[c];
-                const int a = (int)(pr & 0xFFFFu), b = (int)(pr >> 16);
-                const bool flip = (inf & 0x80u) != 0u;
-                ra[j] = a >= WALL_CODE ? WOFF + 8u * (unsigned)(a - WALL_CODE) : 8u * (unsigned)a;
+            for (int j = 0; j < KRB; ++j) {
+                v_[j] = (lk[j] >> 31) != 0u;
+                c_[j] = v_[j] ? (lk[j] >> 16) & 0xFFFu : 0u;
+                pr_[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]]; acc_[j] = lAcc[c_[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                pr_[j] = v_[j] ? pr_[j] : 0u;
+                const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
+                pa_[j] = pos[a >= WALL_CODE ? b : a]; pb_[j] = pos[b]; root_[j] = parent[b];
+            }
+            bool pairOn[KRB];
+            float dx[KRB], dy[KRB], dd[KRB], wnx[KRB], wny[KRB];
+            bool ieee = false;
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
+                const bool wallA = a >= WALL_CODE, flip = (inf_[j] & 0x80u) != 0u;
+                ra[j] = wallA ? WOFF + 8u * (unsigned)(a - WALL_CODE) : 8u * (unsigned)a;
                 rb[j] = 8u * (unsigned)b;
-                racc[j] = lAcc[c];
-                rm[j] = c | ((unsigned)rdepth[j] << 12) | (flip ? 1u << 21 : 0u) | (parent[b] << 22);
+                racc[j] = v_[j] ? acc_[j] : 0.0f;
+                rm[j] = v_[j] ? (c_[j] | ((unsigned)rdepth[j] << 12) | (flip ? 1u << 21 : 0u) | (root_[j] << 22)) : 0u;
                 // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
-                if (a >= WALL_CODE) {
-                    float dist, nx, ny;
-                    wall_geom(p, a - WALL_CODE, pos[b].x, pos[b].y, dist, nx, ny);
-                    if (flip) { nx = -nx; ny = -ny; }
-                    rnx[j] = nx; rny[j] = ny;
-                } else {
-                    const float dx = pos[b].x - pos[a].x, dy = pos[b].y - pos[a].y;
-                    const float dd = dx * dx + dy * dy;
-                    if (dd > B2_EPSILON * B2_EPSILON) {
-                        const float len = sqrtf(dd);
-                        const float inv = 1.0f / len;
-                        rnx[j] = dx * inv; rny[j] = dy * inv;
-                    }
+                float dist;
+                wall_geom(p, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
+                if (flip) { wnx[j] = -wnx[j]; wny[j] = -wny[j]; }
+                dx[j] = pb_[j].x - pa_[j].x; dy[j] = pb_[j].y - pa_[j].y;
+                dd[j] = dx[j] * dx[j] + dy[j] * dy[j];
+                pairOn[j] = v_[j] && !wallA && dd[j] > B2_EPSILON * B2_EPSILON;
+                ieee = ieee || (pairOn[j] && !kb_exact_guard(dd[j]));
+                if (wallA) { rnx[j] = wnx[j]; rny[j] = wny[j]; } else { rnx[j] = 1.0f; rny[j] = 0.0f; }
+            }
+            // the IEEE sequences of sqrtf and the division are two dozen dependent instructions; with every pair of the wave
+            // inside the proven range one correction step on the hardware seeds gives the same bits (kb_exact.h)
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(ieee) == 0ull, 1)) {
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    const float len = kb_sqrt_refine(dd[j], __builtin_amdgcn_sqrtf(dd[j]), __builtin_amdgcn_rsqf(dd[j]));
+                    const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
+                    if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    const float len = sqrtf(dd[j]);
+                    const float inv = 1.0f / len;
+                    if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
                 }
             }
         }

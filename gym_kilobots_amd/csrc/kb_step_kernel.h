@@ -1451,11 +1451,26 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             // register solver: it only needs each wave's contacts grouped together (any order inside a wave)
             for (int b = tid; b < N + M; b += nt) islCnt[b] = 0;   // reused as per-body dependency depth
             if (tid < nw * NUM_CLS) bkMaxRank[tid] = 0;
-            for (int c = tid; c < ncon; c += nt) {
-                const unsigned w = islWave[parent[lPair[c] >> 16]];
-                unsigned base = 0;
-                for (unsigned w2 = 0; w2 < w; ++w2) base += misc[M_WCNT + w2];
-                lOrder[base + atomicAdd(&misc[M_WFILL + w], 1u)] = (unsigned short)c;
+            if constexpr (BINS) {
+                // the fill pointer of every wave starts at the base of its stretch (exclusive prefix of the contacts per wave)
+                // and ends at the base of the next one: kb_regsolve_bins.inc takes its stretch from there
+                if (wave_s == 0) {
+                    const unsigned v_ = lane < nw ? misc[M_WCNT + lane] : 0u;
+                    const unsigned incl = wave_incl_scan(v_);
+                    if (lane < nw) misc[M_WFILL + lane] = incl - v_;
+                }
+                __syncthreads();
+                for (int c = tid; c < ncon; c += nt) {
+                    const unsigned w = islWave[parent[lPair[c] >> 16]];
+                    lOrder[atomicAdd(&misc[M_WFILL + w], 1u)] = (unsigned short)c;
+                }
+            } else {
+                for (int c = tid; c < ncon; c += nt) {
+                    const unsigned w = islWave[parent[lPair[c] >> 16]];
+                    unsigned base = 0;
+                    for (unsigned w2 = 0; w2 < w; ++w2) base += misc[M_WCNT + w2];
+                    lOrder[base + atomicAdd(&misc[M_WFILL + w], 1u)] = (unsigned short)c;
+                }
             }
             __syncthreads();
         } else if (big) bucket_sort(gPair, gInfo, gCbk, gOrder);
