@@ -441,6 +441,7 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
     {
         const float rr = p.r_bot + p.r_bot, rw = B2_POLYGON_RADIUS + p.r_bot;
         p.rr2 = rr * rr; p.rw2 = rw * rw; p.rw_tot = p.r_bot + B2_POLYGON_RADIUS;
+        p.toi_tt = fmaxf(B2_LINEAR_SLOP, p.rw_tot - 3.0f * B2_LINEAR_SLOP) + 0.25f * B2_LINEAR_SLOP;      // kb_toi_wall: target + tol
         const float kbb = p.im_bot + p.im_bot, kwb = 0.0f + p.im_bot;
         p.nm_bb = kbb > 0.0f ? 1.0f / kbb : 0.0f; p.nm_wb = kwb > 0.0f ? 1.0f / kwb : 0.0f;
         // the position sweep divides -C by these two: by multiplying, if the short form gives the quotient's bits for them

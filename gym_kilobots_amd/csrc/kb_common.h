@@ -85,7 +85,8 @@ struct Params {
     float sense_r2;                           // ... and the squared radius in world units
     // uniform constants of the contact search and the solver, evaluated once on the host (same fp32 expressions): as kernel
     // arguments they live in scalar registers -- computed in the kernel they would hold a vector register each
-    float rr2, rw2, rw_tot;                   // (r + r)^2;  (polygonRadius + r)^2;  r + polygonRadius
+    float rr2, rw2, rw_tot;                   // (r + r)^2;  (polygonRadius + r)^2;  r + polygonRadius (no kernel reads it: kb_create makes toi_tt of it)
+    float toi_tt;                             // target + tolerance of kb_toi_wall for a kilobot, by its operations (kb_toi_no_event)
     float nm_bb, nm_wb;                       // effective mass of a kilobot-kilobot and of a wall-kilobot contact
     float y_bb, y_wb;                         // RN(1 / (im_bot + im_bot)), RN(1 / im_bot): the position sweep divides by multiplying (kb_exact.h) ...
     int exact_div;                            // ... once kb_create has checked kb_div_const against a / K for these two K; 0: the sweep divides
@@ -350,6 +351,21 @@ __device__ __forceinline__ bool kb_toi_wall(const AR &p, int wl, float R, float 
         }
     }
     return false;                                                     // failed (iteration cap)
+}
+
+// The first iteration of kb_toi_wall for the sweep (x0,y0) -> (x1,y1) against wall wl and nothing more: d0 = dist_at(0) and
+// d1 = dist_at(1) by the same expressions, tt = target + tol by the same operations (Params::toi_tt for a kilobot).
+// True: kb_toi_wall returns false for this sweep.  It returns true along two ways only -- |d0| < tt (touching at the start),
+// or from inside the push loop, which it leaves with false at once when d1 > tt -- and d0 == 0 is "overlapped", false.
+// The negation stays as written: an unordered compare keeps the body a candidate.
+// A body for which this holds on all four walls goes through kb_toi_walls_body unchanged: minAlpha stays 1 and the event
+// loop breaks in front of its first change; later events need a first one, whose sweep is this one.
+template <class AR>
+__device__ __forceinline__ bool kb_toi_no_event(const AR &p, int wl, float tt, float x0, float y0, float x1, float y1) {
+    float d0, d1, nx, ny;
+    wall_geom(p, wl, (1.0f - 0.0f) * x0 + 0.0f * x1, (1.0f - 0.0f) * y0 + 0.0f * y1, d0, nx, ny);
+    wall_geom(p, wl, (1.0f - 1.0f) * x0 + 1.0f * x1, (1.0f - 1.0f) * y0 + 1.0f * y1, d1, nx, ny);
+    return fabsf(d0) <= 0.0f || (!(fabsf(d0) < tt) && d1 > tt);
 }
 
 // b2World::SolveTOI + b2Island::SolveTOI for one circular body against the arena walls (the only TOI events Box2D

@@ -2418,9 +2418,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             __syncthreads();       // islMin is read; the continuous step reuses the staging area
         }
         // ---- b2World::SolveTOI: continuous step of every dynamic body against the static walls ----
-        // Only bodies that come within their contact radius of a wall can have a TOI event.  They are collected in
+        // Only bodies for which kb_toi_wall's first iteration does not already say "no event" on every wall (kb_toi_no_event:
+        // exact, so a kilobot that rests on a wall inside its contact radius is none) are collected in
         // a candidate list (in the staging area, idle after the solve) and processed one per thread, so that
-        // the event logic exists once in the kernel instead of once per unrolled bot slot.
+        // the event logic exists once in the kernel instead of once per unrolled bot slot.  In a settled swarm that is one
+        // kilobot in a hundred env-substeps: without a candidate the kernels without objects go on behind the barrier of the
+        // collection -- no processing loop, no barrier behind it, no read-back, no barrier in front of the list image.
+        bool toiRecords = false;     // block-uniform: candidate records were written (or the objects ran their continuous step)
         if (p.toi_walls) {
             // candidate records (body, angle at the start of the substep, angle, angular velocity) in arrays that are idle by now;
             // sorted-bin image: the staged impulses and keys must survive to the end of the substep (they are the packed list)
@@ -2442,11 +2446,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 if (b_ >= N) continue;
                 const int b = KB_SLOT(q, b_);
                 if (SLEEP && slp[q] < 0.0f) continue;           // b2World::SolveTOI skips contacts without an awake dynamic body
-                const float total = p.rw_tot;       // r + polygonRadius
                 const float xa = BINS ? startX[b] : start[b].x, ya = BINS ? startY[b] : start[b].y, xb = pos[b].x, yb = pos[b].y;
-                const float m0 = fminf(fminf(xa - p.xmin, p.xmax - xa), fminf(ya - p.ymin, p.ymax - ya));
-                const float m1 = fminf(fminf(xb - p.xmin, p.xmax - xb), fminf(yb - p.ymin, p.ymax - yb));
-                if (m0 > total && m1 > total) continue;          // stays clear of every wall: no event possible
+                // (the cheap reject on `total` in front of the exact test, so that a wave with nobody near a wall skips it, was
+                //  measured: it gives the whole gain back, DESIGN.md "Continuous step")
+                bool none = true;
+#pragma unroll
+                for (int wl = 0; wl < 4; ++wl) none &= kb_toi_no_event(p, wl, p.toi_tt, xa, ya, xb, yb);
+                if (none) continue;          // no wall can have an event: the body would leave kb_toi_walls_body as it came
                 const int i = (int)atomicAdd(&misc[M_NCON], 1u);
                 if (i >= candMax) { atomicOr(&misc[M_STATUS], 8u); continue; }
                 cand[q] = i;
@@ -2456,26 +2462,29 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             __syncthreads();
             KB_STAMP_PRE(26);    // ... + candidates of the continuous step collected
             const int ncand = min((int)misc[M_NCON], candMax);
-            for (int i = tid; i < ncand; i += nt) {
-                const int b = BINS ? (int)cSlot[i] : (int)lPair[i];
-                float R = p.r_bot, im = KB_IM_BOT(b);
-                asm volatile("" : "+v"(R), "+v"(im));   // per-lane copies: keeps the two constants out of the scalar file over the event loop
-                float x_ = pos[b].x, y_ = pos[b].y, a_ = cTh[i], vx_ = vel[b].x, vy_ = vel[b].y, w_ = cW[i];
-                kb_toi_walls_body(p, R, im, BINS ? startX[b] : start[b].x, BINS ? startY[b] : start[b].y, cTh0[i], x_, y_, a_, vx_, vy_, w_);
-                pos[b].x = x_; pos[b].y = y_; vel[b].x = vx_; vel[b].y = vy_; cTh[i] = a_; cW[i] = w_;
-            }
-            if (OBJ && tid < M && !(SLEEP && objSlp[tid] < 0.0f)) {   // objects: the TOI sub-solve runs on the manifold-constraint records of their wall contacts
-                Arena ar;
-                ar.xmin = p.xmin; ar.ymin = p.ymin; ar.xmax = p.xmax; ar.ymax = p.ymax;
-                toi_walls_object(ox, ar, F, tid, start[N + tid].x, start[N + tid].y, objA0[tid], p.h, p.vel_iters,
-                                 g.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS));
-            }
-            KB_STAMP_PRE(27);    // ... + wave 0's own candidates processed
-            __syncthreads();
-            KB_STAMP_PRE(28);    // ... + every wave's
+            toiRecords = OBJ || ncand > 0;      // (nothing writes misc[M_NCON] before the barrier at the end of the substep)
+            if (toiRecords) {
+                for (int i = tid; i < ncand; i += nt) {
+                    const int b = BINS ? (int)cSlot[i] : (int)lPair[i];
+                    float R = p.r_bot, im = KB_IM_BOT(b);
+                    asm volatile("" : "+v"(R), "+v"(im));   // per-lane copies: keeps the two constants out of the scalar file over the event loop
+                    float x_ = pos[b].x, y_ = pos[b].y, a_ = cTh[i], vx_ = vel[b].x, vy_ = vel[b].y, w_ = cW[i];
+                    kb_toi_walls_body(p, R, im, BINS ? startX[b] : start[b].x, BINS ? startY[b] : start[b].y, cTh0[i], x_, y_, a_, vx_, vy_, w_);
+                    pos[b].x = x_; pos[b].y = y_; vel[b].x = vx_; vel[b].y = vy_; cTh[i] = a_; cW[i] = w_;
+                }
+                if (OBJ && tid < M && !(SLEEP && objSlp[tid] < 0.0f)) {   // objects: the TOI sub-solve runs on the manifold-constraint records of their wall contacts
+                    Arena ar;
+                    ar.xmin = p.xmin; ar.ymin = p.ymin; ar.xmax = p.xmax; ar.ymax = p.ymax;
+                    toi_walls_object(ox, ar, F, tid, start[N + tid].x, start[N + tid].y, objA0[tid], p.h, p.vel_iters,
+                                     g.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS));
+                }
+                KB_STAMP_PRE(27);    // ... + wave 0's own candidates processed
+                __syncthreads();
+                KB_STAMP_PRE(28);    // ... + every wave's
 #pragma unroll
-            for (int q = 0; q < BPT; ++q)
-                if (cand[q] >= 0) { th[q] = cTh[cand[q]]; bw[q] = cW[cand[q]]; }
+                for (int q = 0; q < BPT; ++q)
+                    if (cand[q] >= 0) { th[q] = cTh[cand[q]]; bw[q] = cW[cand[q]]; }
+            } else { KB_STAMP_PRE(27); KB_STAMP_PRE(28); }
         }
         KB_ABLATE_EXIT(14);    // continuous step
         // The state of an object between substeps is its body origin (what one-substep launches store and load, and
@@ -2499,7 +2508,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         }
         if (!lastSub) for (int b = tid; b < NP; b += nt) { wsCnt[b] = wsCntNew[b]; wsOff[b] = newOff[b]; }
         if (BINS) {
-            if (p.toi_walls && !lastSub) __syncthreads();      // (the candidate records of the continuous step lie where the image goes)
+            if (toiRecords && !lastSub) __syncthreads();      // (the candidate records of the continuous step lie where the image goes)
             // sorted-bin image: the staged contacts 0 .. newTotal - 1 are the packed list (key = bits 16.. of the info word).
             // It becomes the LDS image of the next substep's lookups, or goes out to the global list (last substep of the
             // launch; always when the contacts were staged in the global scratch slice).
