@@ -28,6 +28,8 @@ MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
 RENDER_OBJECTS, RENDER_BOTS, RENDER_LIGHT = 1, 2, 4     # KB_RENDER_*: the layers of kb_render, a bit each
 RENDER_MAX_SIDE = 2048     # KB_RENDER_MAX_SIDE: pixels along either side of a frame of kb_render
+RAY_BOTS, RAY_OBJECTS, RAY_WALLS = 1, 2, 4     # KB_RAY_*: what the rays of kb_sense_rays can hit, a bit each
+MAX_RAYS = 32     # KB_MAX_RAYS: rays per kilobot of kb_sense_rays
 DAMPING_PADE, DAMPING_LINEAR = 0, 1
 WORLD_SCALE = 25.0    # reference gym_kilobots/lib/body.py:7
 
@@ -97,7 +99,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
@@ -172,6 +174,10 @@ def load():
     lib.kb_render_default_style.restype = C.c_int
     lib.kb_render.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(KbRenderStyle), _P, _P, _P, _P]
     lib.kb_render.restype = C.c_int
+    lib.kb_ray_directions.argtypes = [C.c_int, C.POINTER(C.c_float)]
+    lib.kb_ray_directions.restype = C.c_int
+    lib.kb_sense_rays.argtypes = [_P, C.c_float, C.c_int, C.c_int, _P, _P, _P]
+    lib.kb_sense_rays.restype = C.c_int
     lib.kb_light_sense.argtypes = [_P, _P, _P]
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
@@ -308,6 +314,41 @@ def render_style(style=None):
         else:
             colour(getattr(st, key), v, key)
     return st
+
+
+RAY_TARGETS = {'bots': RAY_BOTS, 'objects': RAY_OBJECTS, 'walls': RAY_WALLS}
+
+
+def check_rays(radius_m, n_rays, targets):
+    """The limits of kb_sense_rays on the radius, the ray count and the targets (a RAY_* mask or an iterable of 'bots' |
+    'objects' | 'walls'); ValueError where the library would answer KB_EINVAL -- but for 'objects' on a handle without
+    objects, which only the handle knows.  Returns (radius_m, n_rays, targets as an integer mask)."""
+    radius_m, n_rays = float(radius_m), int(n_rays)
+    if not radius_m > 0.0:
+        raise ValueError('radius_m must be positive')
+    if not 1 <= n_rays <= MAX_RAYS:
+        raise ValueError('n_rays must be in 1..%d' % MAX_RAYS)
+    if isinstance(targets, str):
+        targets = (targets,)
+    if not isinstance(targets, int):
+        mask = 0
+        for name in targets:
+            if name not in RAY_TARGETS:
+                raise ValueError("targets must be a RAY_* mask or made of 'bots', 'objects' and 'walls'")
+            mask |= RAY_TARGETS[name]
+        targets = mask
+    if isinstance(targets, bool) or targets <= 0 or targets & ~(RAY_BOTS | RAY_OBJECTS | RAY_WALLS):
+        raise ValueError('targets must be a non-empty subset of RAY_BOTS | RAY_OBJECTS | RAY_WALLS')
+    return radius_m, n_rays, targets
+
+
+def ray_directions(n_rays):
+    """The directions u_k, k = 0 .. n_rays - 1, that kb_sense_rays hands its kernel (kb_ray_directions): a list of (x, y)
+    floats in the kilobot's frame, ray 0 dead ahead, counter-clockwise; no handle and no device needed."""
+    n = int(n_rays)
+    buf = (C.c_float * (2 * max(min(n, MAX_RAYS), 1)))()
+    check(load().kb_ray_directions(n, buf), 'kb_ray_directions')
+    return [(buf[2 * k], buf[2 * k + 1]) for k in range(n)]
 
 
 def _f32(v):

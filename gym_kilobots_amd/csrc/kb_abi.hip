@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -742,6 +742,49 @@ int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float s
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ReduceLds(p.NP, p.ncell, CP).bytes, (hipStream_t)stream, p, r.reach, r.R2, n_channels, vec,
                        scale, d_values, d_out, d_count);
     return launched("kb_sense_reduce");
+}
+
+int kb_ray_directions(int n_rays, float *xy) {
+    if (n_rays < 1 || n_rays > KB_MAX_RAYS) return fail(KB_EINVAL, "kb_ray_directions: 1 <= n_rays <= KB_MAX_RAYS (32) required");
+    if (!xy) return fail(KB_EINVAL, "kb_ray_directions: NULL table");
+    static const float quarter[4][2] = {{1.0f, 0.0f}, {0.0f, 1.0f}, {-1.0f, 0.0f}, {0.0f, -1.0f}};
+    for (int k = 0; k < n_rays; ++k) {
+        const double t = 2.0 * 3.14159265358979323846 * (double)k / (double)n_rays;
+        const bool whole = (4 * k) % n_rays == 0;       // a whole number of quarter turns
+        xy[2 * k + 0] = whole ? quarter[4 * k / n_rays][0] : (float)cos(t);
+        xy[2 * k + 1] = whole ? quarter[4 * k / n_rays][1] : (float)sin(t);
+    }
+    return KB_OK;
+}
+
+int kb_sense_rays(kb_sim *sim, float radius_m, int n_rays, int targets, float *d_dist, int32_t *d_hit, void *stream) {
+    if (!sim || !d_dist) return fail(KB_EINVAL, "kb_sense_rays: NULL argument");
+    if (targets <= 0 || (targets & ~(KB_RAY_BOTS | KB_RAY_OBJECTS | KB_RAY_WALLS)))
+        return fail(KB_EINVAL, "kb_sense_rays: targets must be a non-empty subset of KB_RAY_BOTS | KB_RAY_OBJECTS | KB_RAY_WALLS");
+    if (n_rays < 1 || n_rays > KB_MAX_RAYS) return fail(KB_EINVAL, "kb_sense_rays: 1 <= n_rays <= KB_MAX_RAYS (32) required");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_rays: radius must be positive");
+    if ((targets & KB_RAY_OBJECTS) && sim->cfg.num_objects == 0) return fail(KB_EINVAL, "kb_sense_rays: KB_RAY_OBJECTS asked for, but the handle has no objects");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_rays: kb_bind() first");
+    const Params &p = sim->p;
+    RayArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_rays = n_rays; a.targets = targets;
+    a.Rw = radius_m * WORLD_SCALE;
+    a.rb2 = p.r_bot * p.r_bot;
+    const float Rc = a.Rw + p.r_bot;
+    a.Rc2 = Rc * Rc;
+    float u[KB_MAX_RAYS][2];
+    if (kb_ray_directions(n_rays, &u[0][0]) != KB_OK) return KB_EINVAL;
+    for (int k = 0; k < n_rays; ++k) { a.ux[k] = u[k][0]; a.uy[k] = u[k][1]; }
+    kb_outline ol;
+    kb_get_outline(sim, &ol);
+    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
+    const int reach = Rc * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rc, p.inv_cell) : p.gw + p.gh;
+    const int vec = n_rays % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_dist) | reinterpret_cast<uintptr_t>(d_hit)) & 15u) == 0;
+    // the rays a lane holds at a time: the count rounded up to 4, 8 or 16; more than that go in passes (17 to 32 rays: two of 16)
+    const auto fn = n_rays <= 4 ? kb_rays_kernel<4> : n_rays <= 8 ? kb_rays_kernel<8> : kb_rays_kernel<KB_RAYS_PER_PASS>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)RaysLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, ol, a, reach, vec, d_dist, d_hit);
+    return launched("kb_sense_rays");
 }
 
 int kb_get_outline(const kb_sim *sim, kb_outline *out) {

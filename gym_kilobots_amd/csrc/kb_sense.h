@@ -1,5 +1,5 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram, kb_sense_reduce): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
+// kb_sense_histogram, kb_sense_reduce, kb_sense_rays): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
@@ -777,6 +777,217 @@ __global__ void __launch_bounds__(256) kb_render_kernel(const Params p, const kb
             reinterpret_cast<uint4 *>(base)[c] = reinterpret_cast<const uint4 *>(stage)[c];
         } else {
             for (int k = max(lo, mis); k < min(lo + 16, end); ++k) base[k] = stage[k];
+        }
+    }
+}
+
+// ---- kb_sense_rays: first-hit range scans in every kilobot's frame -----------------------------------------------------------
+struct RayArgs {            // the host constants of the definition (include/kilobots_hip.h) and the direction table of kb_ray_directions
+    int n_rays, targets;
+    float Rw, Rc2, rb2;
+    float ux[KB_MAX_RAYS], uy[KB_MAX_RAYS];     // (0, 0) behind n_rays: such a ray is computed like any other and never stored
+};
+struct RaysLds {        // byte offsets: pos (float2) at 0, nextb, cellOf, head (u16 each), dir[32] (float2), vert[F][4] (float2: world frame), wall[4][2] (float2), fix[F] (float4)
+    int nextb, cellOf, head, dir, vert, wall, fix, bytes;
+    __host__ __device__ constexpr RaysLds(int NP, int ncell)
+        : nextb(8 * NP), cellOf(10 * NP), head(12 * NP), dir((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),
+          vert(dir + 8 * KB_MAX_RAYS), wall(vert + 8 * OBJ_EDGES), fix(wall + 8 * 8), bytes(fix + 16 * KB_MAX_OBJECTS) {}
+};
+// the largest image (1024 kilobots, every cell) stays under the default limit for dynamic LDS: no attribute to raise
+static_assert(RaysLds(KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024, "kb_rays_kernel: LDS image");
+
+// The world vector (dx, dy) from a kilobot with heading (sn, cs) along and across each of the R rays of u: b[k], q[k].
+template <int R>
+__device__ __forceinline__ void kb_ray_project(const float2 *u, const float sn, const float cs, const float dx, const float dy,
+                                               float *b, float *q) {
+    const float a = cs * dx + sn * dy, l = cs * dy - sn * dx;
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const float2 d = u[k];      // (the same address in every lane: a broadcast)
+        b[k] = a * d.x + l * d.y;
+        q[k] = a * d.y - l * d.x;
+    }
+}
+
+// The best key of one ray against candidate `code` at parameter t: (bits(t + 0) << 32) | code, compared unsigned.  The key
+// starts as (bits(Rw) << 32) | 0xFFFFFFFF, so whatever undercuts it has +0 <= t <= Rw: a negative t and a NaN (a miss of the
+// formulas above it) have larger bits than any Rw, "t <= Rw" and "nothing hit" need no flag, and t + 0 is t except that it
+// turns -0 into the +0 the definition asks for.  One comparison per ray and candidate: with a flag per rule of the
+// definition the 16-ray code held more lane masks than there are scalar registers.
+__device__ __forceinline__ void kb_ray_take(unsigned long long &best, const unsigned tbits, const unsigned code) {
+    const unsigned long long key = ((unsigned long long)tbits << 32) | code;
+    best = key < best ? key : best;
+}
+
+// A disc of squared radius r2 whose centre projects to (b, q), ray by ray.  h2 < 0 makes sq, t1, t2 and t NaN; t2 < 0 makes
+// t = t2 negative: both miss.
+template <int R>
+__device__ __forceinline__ void kb_ray_disc(const float *b, const float *q, const float r2, const unsigned code, unsigned long long *best) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const float h2 = r2 - q[k] * q[k];
+        const float sq = sqrtf(h2);
+        const float t1 = b[k] - sq, t2 = b[k] + sq;
+        const float t = t1 >= 0.0f ? t1 : t2;
+        kb_ray_take(best[k], __float_as_uint(t + 0.0f), code);
+    }
+}
+
+// The segment from the vertex that projects to (bA, qA) to the one that projects to (bB, qB), ray by ray.  It straddles the
+// ray iff min(qA, qB) <= 0 <= max(qA, qB), i.e. iff w = max(min(qA, qB), min(-qA, -qB)) <= 0; a straddling segment with
+// den == 0 has qA = qB = 0, sg = 0 / 0 and t NaN, and a NaN among the q makes t NaN: both miss.
+template <int R>
+__device__ __forceinline__ void kb_ray_segment(const float *bA, const float *qA, const float *bB, const float *qB, const unsigned code,
+                                               unsigned long long *best) {
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const float w = fmaxf(fminf(qA[k], qB[k]), fminf(-qA[k], -qB[k]));
+        const float den = qA[k] - qB[k];
+        const float sg = qA[k] / den;
+        const float t = bA[k] + sg * (bB[k] - bA[k]);
+        kb_ray_take(best[k], w <= 0.0f ? __float_as_uint(t + 0.0f) : 0xFFFFFFFFu, code);
+    }
+}
+
+// The fixtures and the walls of the staged env against G rays of one kilobot at (xi, yi) with heading (sn, cs): fixtures ->
+// vertices with (b, q) of the previous vertex carried in registers, so that a vertex is projected once per ray for both its
+// edges (vertex 0 a second time, to close the outline: the same operations, the same bits); the NW walls, a segment each.
+// All table reads are from LDS at addresses that are the same in every lane (broadcasts); the loop bounds are the same in
+// all lanes and are made scalar with readfirstlane, as in kb_object_walk.  The loops over the edges and the walls are kept
+// rolled and the kernel calls this for four rays at a time: the G correctly rounded divisions of an edge are scheduled
+// side by side, and with 16 rays, or with the walls unrolled, that took all 256 VGPRs.
+template <int G>
+__device__ __forceinline__ void kb_ray_outlines(const float2 *u, const float sn, const float cs, const float xi, const float yi, const float2 *vert,
+                                                const float2 *wall, const float4 *fix, const int F, const int NW, const int N, unsigned long long *best) {
+    for (int f = 0; f < F; ++f) {
+        const float4 fx = fix[f];
+        const int n = __builtin_amdgcn_readfirstlane(__float_as_int(fx.x));
+        const unsigned code = (unsigned)__builtin_amdgcn_readfirstlane(__float_as_int(fx.y));
+        const float2 v0 = vert[KB_MAX_POLY_VERTS * f];
+        float bp[G], qp[G];
+        kb_ray_project<G>(u, sn, cs, v0.x - xi, v0.y - yi, bp, qp);
+        if (n == 0) {
+            kb_ray_disc<G>(bp, qp, fx.z, code, best);
+        } else {
+#pragma unroll 1
+            for (int k = 1; k <= n; ++k) {
+                const float2 v = vert[KB_MAX_POLY_VERTS * f + (k == n ? 0 : k)];
+                float bc[G], qc[G];
+                kb_ray_project<G>(u, sn, cs, v.x - xi, v.y - yi, bc, qc);
+                kb_ray_segment<G>(bp, qp, bc, qc, code, best);
+#pragma unroll
+                for (int i = 0; i < G; ++i) { bp[i] = bc[i]; qp[i] = qc[i]; }
+            }
+        }
+    }
+#pragma unroll 1
+    for (int w = 0; w < NW; ++w) {
+        const float2 va = wall[2 * w], vb = wall[2 * w + 1];
+        float bA[G], qA[G], bB[G], qB[G];
+        kb_ray_project<G>(u, sn, cs, va.x - xi, va.y - yi, bA, qA);
+        kb_ray_project<G>(u, sn, cs, vb.x - xi, vb.y - yi, bB, qB);
+        kb_ray_segment<G>(bA, qA, bB, qB, (unsigned)(N + w), best);
+    }
+}
+
+constexpr int RAY_GROUP = 4;
+#ifndef KB_RAYS_PER_PASS
+#define KB_RAYS_PER_PASS 16             // the most rays kb_rays_kernel keeps in registers at a time: 8 or 16 (A/B knob)
+#endif
+static_assert(KB_RAYS_PER_PASS == 8 || KB_RAYS_PER_PASS == 16, "kb_rays_kernel: rays per pass");
+
+// Range scans on the current poses (kb_sense_rays): one workgroup per env, one kilobot per lane, like kb_neighbors_kernel.
+// Poses and the cell lists in LDS (kb_build_cell_lists); a kilobot's own pose and heading are used by its own lane only and are
+// read straight from global memory into registers, as in kb_histogram_kernel.  Once per workgroup the direction table, the
+// env's fixture vertices in the WORLD frame (lane 64 + 4 f + k rotates vertex k of fixture f by its body's frame; a circle's
+// centre takes the place of vertex 0), per fixture (vertex count, code N + 4 + body, r * r) and the two ends of every wall go
+// to LDS -- values every lane would otherwise compute for itself, each a single fp32 operation and therefore the same bits
+// whoever evaluates it.  A lane then reads them at addresses that are the same in every lane (broadcasts).
+// Candidates: the kilobots through kb_walk_in_range at the reach of Rc = Rw + r_bot, then the fixtures and the walls, four
+// rays at a time (kb_ray_outlines).
+// The best key of every ray stays in registers: RP rays are processed at a time -- the ray count rounded up to 4, 8 or 16,
+// and 17 to 32 rays in two passes of 16 over the candidates (KB_RAYS_PER_PASS) -- and every index into best[], b[] and q[] is
+// a compile-time constant.  The winner of a ray does not depend on the order of the candidates, and no ray on another ray:
+// the passes give what one pass would.  Rays behind n_rays have the direction (0, 0), are computed and never stored.
+// Each lane stores its own rows: 16 bytes per store with vec (n_rays a multiple of 4, d_dist and d_hit 16-byte aligned).
+template <int RP>
+__global__ void __launch_bounds__(256) kb_rays_kernel(const Params p, const kb_outline ol, const RayArgs A, const int s, const int vec,
+                                                      float *d_dist, int *d_hit) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N, n_rays = A.n_rays;
+    const RaysLds L(p.NP, p.ncell);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    float2 *dir = reinterpret_cast<float2 *>(smem + L.dir);
+    float2 *vert = reinterpret_cast<float2 *>(smem + L.vert);
+    float2 *wall = reinterpret_cast<float2 *>(smem + L.wall);
+    float4 *fix = reinterpret_cast<float4 *>(smem + L.fix);
+    const size_t o = (size_t)e * N;
+    const bool bots = (A.targets & KB_RAY_BOTS) != 0;
+    const int F = (A.targets & KB_RAY_OBJECTS) ? ol.num_fixtures : 0, NW = (A.targets & KB_RAY_WALLS) ? 4 : 0;
+    if (tid < KB_MAX_RAYS) dir[tid] = make_float2(A.ux[tid], A.uy[tid]);
+    if (tid >= 64 && tid < 64 + OBJ_EDGES) {
+        const int f = (tid - 64) / KB_MAX_POLY_VERTS, k = (tid - 64) % KB_MAX_POLY_VERTS;
+        if (f < F) {
+            const int n = ol.nverts[f], m = ol.body[f];
+            const size_t j = (size_t)e * ol.num_objects + m;
+            const float ox = p.buf.ox[j], oy = p.buf.oy[j];
+            float so, co;
+            kb_sincosf(p.buf.otheta[j], so, co);
+            const float vx = ol.verts[f][k][0], vy = ol.verts[f][k][1];
+            if (k < n) vert[tid - 64] = make_float2(ox + (co * vx - so * vy), oy + (so * vx + co * vy));
+            if (k == 0) {
+                if (n == 0) vert[tid - 64] = make_float2(ox, oy);
+                const float r = ol.radius[f];
+                fix[f] = make_float4(__int_as_float(n), __int_as_float(N + 4 + m), r * r, 0.0f);
+            }
+        }
+    }
+    if (tid >= 128 && tid < 136) {      // wall w from wall[2 w] to wall[2 w + 1]: W0, W1 run up the xmin and the xmax side, W2, W3 along ymin and ymax
+        const int w = (tid - 128) >> 1, far = (tid - 128) & 1;
+        wall[tid - 128] = make_float2(w == 1 || (w >= 2 && far) ? ol.arena[1] : ol.arena[0], (w < 2 ? far : w == 3) ? ol.arena[3] : ol.arena[2]);
+    }
+    if (bots) kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    else __syncthreads();
+    for (int a = tid; a < N; a += nt) {
+        const float xi = p.buf.x[o + a], yi = p.buf.y[o + a];
+        float sn, cs;
+        kb_sincosf(p.buf.theta[o + a], sn, cs);
+        const size_t row = (o + a) * (size_t)n_rays;
+        for (int k0 = 0; k0 < n_rays; k0 += RP) {
+            const float2 *u = dir + k0;
+            unsigned long long best[RP];
+#pragma unroll
+            for (int k = 0; k < RP; ++k) best[k] = ((unsigned long long)__float_as_uint(A.Rw) << 32) | 0xFFFFFFFFull;
+            if (bots) {
+                kb_walk_in_range(p, pos, head, nextb, a, (int)cellOf[a], make_float2(xi, yi), s, A.Rc2, [&](unsigned j, float ex, float ey, float) {
+                    float b[RP], q[RP];
+                    kb_ray_project<RP>(u, sn, cs, ex, ey, b, q);
+                    kb_ray_disc<RP>(b, q, A.rb2, j, best);
+                });
+            }
+#pragma unroll
+            for (int g = 0; g < RP; g += RAY_GROUP) kb_ray_outlines<RAY_GROUP>(u + g, sn, cs, xi, yi, vert, wall, fix, F, NW, N, best + g);
+            float *dist = d_dist + row + k0;
+            int *hit = d_hit ? d_hit + row + k0 : nullptr;
+            if (vec) {
+#pragma unroll
+                for (int i = 0; i < RP; i += 4) {
+                    if (k0 + i >= n_rays) continue;
+                    reinterpret_cast<float4 *>(dist)[i >> 2] = make_float4(__uint_as_float((unsigned)(best[i] >> 32)) / WORLD_SCALE, __uint_as_float((unsigned)(best[i + 1] >> 32)) / WORLD_SCALE,
+                                                                           __uint_as_float((unsigned)(best[i + 2] >> 32)) / WORLD_SCALE, __uint_as_float((unsigned)(best[i + 3] >> 32)) / WORLD_SCALE);
+                    if (hit) reinterpret_cast<int4 *>(hit)[i >> 2] = make_int4((int)(unsigned)best[i], (int)(unsigned)best[i + 1], (int)(unsigned)best[i + 2], (int)(unsigned)best[i + 3]);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < RP; ++i) {
+                    if (k0 + i >= n_rays) continue;
+                    dist[i] = __uint_as_float((unsigned)(best[i] >> 32)) / WORLD_SCALE;
+                    if (hit) hit[i] = (int)(unsigned)best[i];       // (the low word of a ray that hit nothing is -1)
+                }
+            }
         }
     }
 }

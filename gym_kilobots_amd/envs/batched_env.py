@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, **cfg):
+                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -41,7 +41,11 @@ class BatchedKilobotsEnv(object):
         (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
         'contacts'.  None adds nothing.
         render_size: (width, height) in pixels lets render('rgb_array') return the frames of every env, [E, height, width, 3]
-        uint8 on the device (KilobotSim.render).  reset(), step() and the info dict do not change with it."""
+        uint8 on the device (KilobotSim.render).  reset(), step() and the info dict do not change with it.
+        ray_obs: (radius_m, n_rays) or (radius_m, n_rays, targets) adds the range scan of a decentralised policy: rays() returns
+        (dist [E, N, n_rays], hit [E, N, n_rays]), how far the first kilobot, object or wall along each of n_rays bearings in
+        every kilobot's own frame is and what it is (KilobotSim.rays; targets made of 'bots', 'objects' and 'walls', default:
+        everything the env has), and step() puts the tuple in its info dict under 'rays'.  None adds nothing."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -107,6 +111,17 @@ class BatchedKilobotsEnv(object):
                 self.render_size = nat.check_render(width, height, nat.RENDER_BOTS)[:2]
             except TypeError as err:
                 raise ValueError('render_size must be (width, height): %s' % err)
+        self.ray_obs = None
+        if ray_obs is not None:
+            try:
+                radius_m, n_rays, targets = tuple(ray_obs) if len(ray_obs) == 3 else tuple(ray_obs) + (None,)
+                if targets is None:
+                    targets = nat.RAY_BOTS | nat.RAY_WALLS | (nat.RAY_OBJECTS if int(cfg.get('num_objects', 0)) > 0 else 0)
+                self.ray_obs = nat.check_rays(radius_m, n_rays, targets)
+            except TypeError as err:
+                raise ValueError('ray_obs must be (radius_m, n_rays) or (radius_m, n_rays, targets): %s' % err)
+            if self.ray_obs[2] & nat.RAY_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
+                raise ValueError("ray_obs: 'objects' asked for, but the env has no objects")
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -205,6 +220,8 @@ class BatchedKilobotsEnv(object):
             info['grid'] = self.occupancy_grid()
         if self.contact_obs is not None:
             info['contacts'] = self.contacts()
+        if self.ray_obs is not None:
+            info['rays'] = self.rays()
         return obs, reward, done, info
 
     def neighbors(self):
@@ -241,6 +258,13 @@ class BatchedKilobotsEnv(object):
         if self.contact_obs is None:
             raise ValueError('create the env with contact_obs=k to observe contacts')
         return self.sim.contacts(self.contact_obs)
+
+    def rays(self):
+        """(dist [E, N, n_rays] float32, hit [E, N, n_rays] int32) of the current poses for the ray_obs=(radius_m, n_rays[,
+        targets]) the env was created with: KilobotSim.rays."""
+        if self.ray_obs is None:
+            raise ValueError('create the env with ray_obs=(radius_m, n_rays[, targets]) to observe range scans')
+        return self.sim.rays(*self.ray_obs)
 
     def render(self, mode='rgb_array'):
         """frames [E, height, width, 3] uint8 of the current state for the render_size=(width, height) the env was created

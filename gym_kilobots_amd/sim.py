@@ -415,6 +415,29 @@ class KilobotSim:
                       'kb_render')
         return out
 
+    def rays(self, radius_m, n_rays, targets=None, out=None, hit=True):
+        """Range scans on the current poses (kb_sense_rays; no reference counterpart): for every kilobot and each of n_rays
+        bearings in its own frame (ray 0 dead ahead, counter-clockwise, nat.ray_directions) how far the first thing in that
+        direction is, up to radius_m, and what it is.  Returns (dist [E, N, n_rays] float32: metres, radius_m where nothing was
+        hit; hit [E, N, n_rays] int32: a kilobot j < N, wall N + w (w: 0 = xmin, 1 = xmax, 2 = ymin, 3 = ymax as in
+        object_points) or object N + 4 + m -- the codes of contacts() --, -1 where nothing was hit; None with hit=False).  A
+        body hidden behind another is not seen; a kilobot inside a body sees the way out.  targets: a RAY_* mask or an
+        iterable of 'bots', 'objects' and 'walls'; None: everything the sim has ('objects' only with objects).  out: the
+        preallocated contiguous tensors to write into, the tuple (dist, hit), or dist alone with hit=False; every element is
+        written."""
+        E, N = self.num_envs, self.num_bots
+        if targets is None:
+            targets = nat.RAY_BOTS | nat.RAY_WALLS | (nat.RAY_OBJECTS if self.num_objects > 0 else 0)
+        radius_m, n_rays, targets = nat.check_rays(radius_m, n_rays, targets)
+        if targets & nat.RAY_OBJECTS and self.num_objects == 0:
+            raise ValueError("targets: 'objects' asked for, but the sim has no objects")
+        shapes = [((E, N, n_rays), torch.float32, 'dist')] + ([((E, N, n_rays), torch.int32, 'hit')] if hit else [])
+        out = self._outputs(out, shapes, 'the tuple (dist, hit)' if hit else 'the dist tensor')
+        ph = C.c_void_p(out[1].data_ptr()) if hit else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_rays(self._h, radius_m, n_rays, targets, C.c_void_p(out[0].data_ptr()), ph, self._stream()), 'kb_sense_rays')
+        return out[0], out[1] if hit else None
+
     def _outputs(self, out, shapes, what):
         """The outputs of a sensing call as a tuple: `out` checked against shapes = [(shape, dtype, name), ...] (a lone
         tensor counts as a tuple of one), or freshly allocated if out is None.  what: how a message names the whole."""

@@ -482,6 +482,55 @@ int kb_render_default_style(kb_render_style *out);
 int kb_render(kb_sim *sim, int width, int height, int layers, const kb_render_style *style,
               const uint32_t *d_body_rgb, const uint32_t *d_mark_rgb, uint8_t *d_rgb, void *stream);
 
+/* Range scans on the CURRENT poses, without stepping: for every kilobot i and each of n_rays bearings in its own frame, how
+ * far the first thing in that direction is and what it is -- another kilobot, a pushable object or a wall: the occlusion-aware,
+ * fixed-size observation of decentralised navigation and pushing policies.  A body hidden behind another is not seen.  The
+ * result of an env does not depend on the other envs of the batch.  No reference counterpart.  Every operation below is one
+ * fp32 operation rounded on its own, nothing is contracted, divisions and square roots are correctly rounded; all lengths
+ * are world units until the final / 25:
+ *   Host constants:  Rw = radius_m * 25;  rb = bot_radius * 25, rb2 = rb * rb;  Rc = Rw + rb, Rc2 = Rc * Rc.
+ *   Directions:  u_k = ((float)cos(2 pi k / n_rays), (float)sin(2 pi k / n_rays)), k = 0 .. n_rays - 1, evaluated in double and
+ *     rounded to fp32; the entries at whole quarter turns (4 k a multiple of n_rays) are exactly (+-1, 0) and (0, +-1).  Ray 0
+ *     points dead ahead, the rays run counter-clockwise.  kb_ray_directions writes this very table, the one the kernel is
+ *     handed, into xy (HOST memory, [n_rays][2]); it needs no handle and no device, and returns KB_EINVAL for an n_rays outside
+ *     1..KB_MAX_RAYS or a NULL xy.
+ *   Body frame of kilobot i:  (s, c) = the library's sine and cosine of theta_i (the Cephes algorithm every kernel uses).  A
+ *     world point P becomes  dx = P.x - x_i, dy = P.y - y_i;  a = c * dx + s * dy (ahead), l = c * dy - s * dx (to the left).
+ *     For the point (a, l) and ray k:  b = a * u.x + l * u.y (along the ray),  q = a * u.y - l * u.x (across it).
+ *   Disc of radius r, r2 = r * r, with its centre as the point:  h2 = r2 - q * q;  a miss if !(h2 >= 0);  sq = sqrt(h2),
+ *     t1 = b - sq, t2 = b + sq;  a miss if !(t2 >= 0);  t = t1 >= 0 ? t1 : t2 -- the first crossing of the outline at t >= 0:
+ *     from inside a disc that is the way out.
+ *   Segment from vertex A to vertex B, with (bA, qA) and (bB, qB):  it straddles the ray iff (qA <= 0 && qB >= 0) ||
+ *     (qA >= 0 && qB <= 0);  den = qA - qB;  a miss if den == 0;  sg = qA / den,  t = bA + sg * (bB - bA);  a miss if !(t >= 0).
+ *   Every candidate is a hit iff t <= Rw;  then t = t > 0 ? t : +0.0f.
+ *   Candidates:
+ *     KB_RAY_BOTS: the kilobots j != i of the env with !(dd > Rc2), ex = x_j - x_i, ey = y_j - y_i, dd = ex * ex + ey * ey (the
+ *       predicate of kb_sense at the radius Rw + rb); each a disc with r2 = rb2 at (x_j, y_j), code j.
+ *     KB_RAY_OBJECTS: every fixture of every object of kb_get_outline, no range cut.  With (so, co) the sine and cosine of
+ *       otheta_m, a circle fixture is a disc of radius[f] (r2 = radius[f] * radius[f]) at (ox_m, oy_m); a polygon or box
+ *       fixture gives the segments v[k] -> v[(k + 1) % n] between its world vertices  wx = ox_m + (co * vx - so * vy),
+ *       wy = oy_m + (so * vx + co * vy).  Code num_bots + 4 + m.  On a body with several fixtures (LForm, TForm, CForm) a
+ *       kilobot whose centre is inside the body may report an interior edge, where two fixtures meet -- the caveat of
+ *       kb_sense_objects.
+ *     KB_RAY_WALLS: the four segments of kb_outline.arena, in this vertex order:  W0 (xmin, ymin) -> (xmin, ymax),
+ *       W1 (xmax, ymin) -> (xmax, ymax),  W2 (xmin, ymin) -> (xmax, ymin),  W3 (xmin, ymax) -> (xmax, ymax).  Code num_bots + W:
+ *       the wall numbering of kb_sense_objects.  A kilobot outside the arena sees the walls from behind.
+ *   Per ray the hit with the smallest (t, code) wins: bits(t) compared as unsigned, then the code -- whatever order the
+ *     candidates are met in.  A ray through a shared vertex hits both edges at the same t up to rounding.
+ * d_dist [num_envs][num_bots][n_rays] float32: t / 25, metres; Rw / 25 where nothing was hit.
+ * d_hit  [num_envs][num_bots][n_rays] int32 or NULL: the winner's code (the codes of kb_sense_contacts), -1 where nothing was hit.
+ * targets: a non-empty subset of KB_RAY_BOTS | KB_RAY_OBJECTS | KB_RAY_WALLS;  1 <= n_rays <= KB_MAX_RAYS;  radius_m > 0 (a
+ * radius beyond the arena is fine).  Argument errors are reported before an unbound handle, in this order: NULL sim / d_dist;
+ * targets;  n_rays;  radius_m;  KB_RAY_OBJECTS on a handle with num_objects == 0.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, theta, and ox, oy, otheta with KB_RAY_OBJECTS; writes the two outputs only, every element on every call, by
+ * plain stores.  One launch.  Asynchronous on `stream`. */
+#define KB_RAY_BOTS    1
+#define KB_RAY_OBJECTS 2
+#define KB_RAY_WALLS   4
+#define KB_MAX_RAYS    32
+int kb_ray_directions(int n_rays, float *xy /* host, [n_rays][2] */);
+int kb_sense_rays(kb_sim *sim, float radius_m, int n_rays, int targets, float *d_dist, int32_t *d_hit, void *stream);
+
 /* The sensing point of ONE substep on its own, for kilobots that are programmed on the host (a Kilobot subclass with its
  * own _loop, kilobot.py:86-88,164-168): Light.step with d_light_action ([num_envs][kb_light_action_dim()], NULL = action None:
  * the light stays) and value_and_gradients at every kilobot's light sensor (kilobots_env.py:171-180) into
