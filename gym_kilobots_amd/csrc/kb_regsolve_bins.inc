@@ -324,18 +324,19 @@
                 }
             }
         }
-        KB_STAMP_PRE(30);    // ... + its 10 velocity sweeps, before the barrier
+        KB_STAMP_PRE(30);    // ... + its 10 velocity sweeps
     }
-#ifdef KB_SOLVER_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-    __syncthreads();
-    KB_STAMP(4);
+    // From here to the end of the position sweeps a wave runs through in its own instruction stream (wave_sync() only): it
+    // touches nothing but the bodies of its own islands, so the env no longer pays the slowest wave of the velocity sweeps, then
+    // the integration, then the slowest wave of the position sweeps -- which are usually different waves -- but the slowest
+    // wave of both together.  What made the two workgroup barriers necessary was the integration by the thread that owns a
+    // kilobot by id; a kilobot with a swept contact is now integrated by the lane that holds its LAST contact in canonical
+    // order (the one whose depth is bodyDepth[x] after the depth pass; a wall contact names its kilobot once), every other one
+    // (no contact, or contacts of a sleeping island only) by its owner thread, which learns it from one bit per slot that the
+    // grouping pass left in intMark in front of the set-up barrier.  The owner thread keeps the angle in either case.
+    KB_STAMP(4);           // (profile build) wave 0: warm start and its ten sweeps done -- wave-local
     KB_RETID();
     KB_ABLATE_EXIT(11);    // velocity sweeps
-#ifdef KB_PROFILE
-    if (tid == 0) atomicAdd(&KB_PROF(9), misc[M_PROF]);   // deepest wave of the env
-#endif
     // StoreImpulses: the contact is staged at its position in the packed list, which goes out as a whole at the end of the substep
     if (solving) {
 #pragma unroll
@@ -343,40 +344,91 @@
             if (lane + 64u * j < mycnt) lAcc[RB_C(j)] = racc[j];
     }
     // integrate positions (b2Island::Solve)
-#pragma unroll
-    for (int q = 0; q < BPT; ++q) {
-        const int b_ = tid + q * nt;
-        if (b_ >= N) continue;
-        const int b = ms[q];
-        float vxx = vel[b].x, vyy = vel[b].y, ww = bw[q];
-        startX[b] = pos[b].x; startY[b] = pos[b].y;     // pose at the start of the substep (continuous step)
-        const float tx = h * vxx, ty = h * vyy;
-        if (tx * tx + ty * ty > B2_MAX_TRANSLATION_SQ) {
-            const float ratio = B2_MAX_TRANSLATION / sqrtf(tx * tx + ty * ty);
-            vxx *= ratio; vyy *= ratio;
-        }
-        const float rot = h * ww;
-        if (rot * rot > B2_MAX_ROTATION_SQ) {
-            const float ratio = B2_MAX_ROTATION / fabsf(rot);
-            ww *= ratio;
-        }
-        pos[b].x += h * vxx; pos[b].y += h * vyy;
-        th[q] += h * ww;
-        vel[b].x = vxx; vel[b].y = vyy; bw[q] = ww;
+    {
         // (islWave is idle from here on) island state for the sleep bookkeeping: bit 1 = has an awake body,
         // bit 0 = position constraints not solved (set by the last position sweep; always without sweeps)
-        if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+        const unsigned char unsolved = (unsigned char)(p.pos_iters <= 0 ? 1 : 0);
+        char *const sxB = reinterpret_cast<char *>(startX), *const syB = reinterpret_cast<char *>(startY);
+        // one body: the pose at the start of the substep (continuous step), the clamped velocity and the new position;
+        // off8 = byte offset of the body inside the float2 arrays
+        auto integrate_xy = [&](const unsigned off8, const float2 v0, const float2 p0) __attribute__((always_inline)) {
+            float vxx = v0.x, vyy = v0.y;
+            *reinterpret_cast<float *>(sxB + (off8 >> 1)) = p0.x; *reinterpret_cast<float *>(syB + (off8 >> 1)) = p0.y;
+            const float tx = h * vxx, ty = h * vyy;
+            if (tx * tx + ty * ty > B2_MAX_TRANSLATION_SQ) {
+                const float ratio = B2_MAX_TRANSLATION / sqrtf(tx * tx + ty * ty);
+                vxx *= ratio; vyy *= ratio;
+            }
+            RB_POS(off8) = make_float2(p0.x + h * vxx, p0.y + h * vyy);
+            RB_VEL(off8) = make_float2(vxx, vyy);
+        };
+        // Who integrates: the depths of both bodies of both slots and the owner thread's marker bits are read before anything
+        // is written -- startY lies over bodyDepth, and a lane may look at a body whose last contact another lane holds.
+        // Then one trip per register slot, with the owner thread's kilobot of the same place beside it: what a lane reads
+        // and uses there is a body that nobody else writes.
+        bool intA[KRB], intB[KRB], own[BPT];
+        {
+            unsigned dA[KRB], dB[KRB], mk[BPT];
+            const char *const bdB = reinterpret_cast<const char *>(islCnt);     // bodyDepth
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                dA[j] = *reinterpret_cast<const unsigned *>(bdB + ((RB_WALL(j) ? rb[j] : ra[j]) >> 1));
+                dB[j] = *reinterpret_cast<const unsigned *>(bdB + (rb[j] >> 1));
+            }
+#pragma unroll
+            for (int q = 0; q < BPT; ++q) mk[q] = intMark[(unsigned)ms[q] & 31u];
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned d = (unsigned)RB_DEPTH(j);       // (0: no contact, or one of a sleeping island -- in no round)
+                intA[j] = solving && d != 0u && !RB_WALL(j) && dA[j] == d;
+                intB[j] = solving && d != 0u && dB[j] == d;
+            }
+#pragma unroll
+            for (int q = 0; q < BPT; ++q) {
+                own[q] = tid + q * nt < N && ((mk[q] >> ((unsigned)ms[q] >> 5)) & 1u) == 0u;
+            }
+        }
+        wave_sync();
+        static_assert(KRB == BPT, "a register slot and a kilobot of the owner thread share a trip");
+#pragma unroll
+        for (int j = 0; j < KRB; ++j) {
+            const unsigned oo = 8u * (unsigned)ms[j];
+            const float2 vO = RB_VEL(oo), pO = RB_POS(oo);
+            const unsigned char aO = SLEEP ? active[ms[j]] : (unsigned char)1;
+            if (j == 0 || mycnt > 64u) {        // (wave-uniform: most waves hold nothing in the slots behind slot 0)
+                const float2 vA = RB_VEL(ra[j]), vB = RB_VEL(rb[j]), pA = RB_POS(ra[j]), pB = RB_POS(rb[j]);
+                if (intA[j]) {
+                    integrate_xy(ra[j], vA, pA);
+                    // (the island is awake; only the root's entry is ever read)
+                    if (SLEEP) islWave[ra[j] >> 3] = (unsigned char)(2 | unsolved);
+                }
+                if (intB[j]) {
+                    integrate_xy(rb[j], vB, pB);
+                    if (SLEEP) islWave[rb[j] >> 3] = (unsigned char)(2 | unsolved);
+                }
+            }
+            if (own[j]) {
+                integrate_xy(oo, vO, pO);
+                if (SLEEP) islWave[ms[j]] = (unsigned char)((aO ? 2 : 0) | unsolved);
+            }
+            // the angle never leaves the registers of the owner thread (a thread without a kilobot in this place turns a zero
+            // that nobody stores)
+            float ww = bw[j];
+            const float rot = h * ww;
+            if (rot * rot > B2_MAX_ROTATION_SQ) {
+                const float ratio = B2_MAX_ROTATION / fabsf(rot);
+                ww *= ratio;
+            }
+            th[j] += h * ww;
+            bw[j] = ww;
+        }
     }
-    __syncthreads();
-    KB_STAMP(5);
-    KB_RETID();
+    wave_sync();
+    KB_STAMP(5);           // (profile build) ... + impulses stored, its kilobots integrated -- wave-local
     KB_ABLATE_EXIT(12);    // impulses stored, positions integrated
     // SolvePositionConstraints; an island stops once its minSeparation >= -3 slop.  The island flags are read once per
     // iteration; depth levels without an active contact in this wave are skipped altogether.
     if (solving) {
-#ifdef KB_SOLVER_PRIO
-        __builtin_amdgcn_s_setprio(KB_SOLVER_PRIO);
-#endif
         for (int it = 0; it < p.pos_iters; ++it) {
             unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;
             bool viol = false;
@@ -440,10 +492,10 @@
             wave_sync();
         }
         KB_STAMP_PRE(24);    // (profile build) wave 0's own position sweeps, before it waits for the slowest wave
-#ifdef KB_SOLVER_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     }
+#ifdef KB_SOLVER_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
 #undef RB_WALL
 #undef RB_WALLIDX
 #undef RB_VEL

@@ -94,6 +94,11 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     unsigned *bkMaxRank = (unsigned *)(smem + tb_ + lds::bkmaxrank(nw));
     unsigned short *bkList = (unsigned short *)(smem + tb_ + lds::bklist(nw));
     unsigned char *nList = smem + tb_ + lds::nlist(nw);
+    // register solver of the kernels without objects: one bit per slot, "a solver lane integrates this kilobot" (word slot & 31,
+    // bit slot >> 5: neighbouring slots fall into different words).  bkList holds at least 64 half words and is idle on that
+    // path from the island placement to the next substep.
+    unsigned *intMark = reinterpret_cast<unsigned *>(bkList);
+    static_assert(BPT * 64 * KB_MAX_WAVES <= 1024 && lds::nbk(1) >= 64, "32 words of intMark hold a bit for every slot");
     float *objTab = (float *)(smem + ot_);                       // fixture table (kb_objects.h: OT_*)
     float *objBody = (float *)(smem + ot_ + lds::OBJBODY);                     // body table (kb_objects.h: BT_*)
     unsigned *objCnt = (unsigned *)(smem + ot_ + lds::OBJCNT);                 // kilobots touching object m
@@ -1452,6 +1457,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             for (int b = tid; b < N + M; b += nt) islCnt[b] = 0;   // reused as per-body dependency depth
             if (tid < nw * NUM_CLS) bkMaxRank[tid] = 0;
             if constexpr (BINS) {
+                if (tid < 32) intMark[tid] = 0;
                 // the fill pointer of every wave starts at the base of its stretch (exclusive prefix of the contacts per wave)
                 // and ends at the base of the next one: kb_regsolve_bins.inc takes its stretch from there
                 if (wave_s == 0) {
@@ -1460,9 +1466,17 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     if (lane < nw) misc[M_WFILL + lane] = incl - v_;
                 }
                 __syncthreads();
+                // ... and both kilobots of a contact that will be swept are marked: the lane of a kilobot's last contact integrates
+                // it (kb_regsolve_bins.inc), and its owner thread must know without a barrier behind this one
                 for (int c = tid; c < ncon; c += nt) {
-                    const unsigned w = islWave[parent[lPair[c] >> 16]];
+                    const unsigned pr = lPair[c], a = pr & 0xFFFFu, b = pr >> 16;
+                    const unsigned root = parent[b];
+                    const unsigned w = islWave[root];
                     lOrder[atomicAdd(&misc[M_WFILL + w], 1u)] = (unsigned short)c;
+                    if (!SLEEP || active[root] != 0) {      // (a sleeping island is never swept: its kilobots stay with their owners)
+                        atomicOr(&intMark[b & 31u], 1u << (b >> 5));
+                        if (a < (unsigned)WALL_CODE) atomicOr(&intMark[a & 31u], 1u << (a >> 5));
+                    }
                 }
             } else {
                 for (int c = tid; c < ncon; c += nt) {
@@ -2356,6 +2370,9 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         }
         __syncthreads();
         KB_STAMP_PRE(25);        // ... + waiting for the wave with the most position sweeps
+#ifdef KB_PROFILE
+        if (BINS && reg && tid == 0) atomicAdd(&KB_PROF(9), misc[M_PROF]);   // deepest wave of the env (kb_regsolve_bins.inc: no barrier in front of this one)
+#endif
         KB_RETID();
         KB_ABLATE_EXIT(13);    // position sweeps
         if (SLEEP) {

@@ -1,0 +1,50 @@
+"""The stretch of the register solver that a wave runs through on its own (kb_regsolve_bins.inc: warm start, velocity sweeps,
+StoreImpulses, integration by the lane of a kilobot's last contact or by its owner thread, position sweeps -- wave_sync()
+only) on the device against the oracle, on the scenes of tests/wave_solve_scenes.py (tests/test_wave_solve_cpu.py shows on the
+oracle that every scene has what it is there for).  Per scene and sleep setting: twelve single-substep launches, each compared
+bit for bit -- poses, the sleep times where they are carried, the packed warm-start list (ws_cnt, ws_key, ws_acc) and the
+status --, then one fused launch of ten substeps.  The scenes of 1024 kilobots must run a fixed-size kernel, those of 200 a
+generic sorted-bin kernel of two waves, those of 64 a one-wave workgroup."""
+import pytest
+
+from tests import solver_regimes as SR
+from tests import variant_census as VC
+from tests import wave_solve_scenes as WS
+from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def variants(tmp_path_factory):
+    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
+    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
+    return listed
+
+
+@pytest.mark.parametrize('case', WS.cases(), ids=WS.case_id)
+def test_wave_local_solve_is_bit_exact(case, variants):
+    s, allow_sleep = case
+    E = len(s.envs)
+    osim, gsim = make_pair(E, s.N, allow_sleep=allow_sleep)
+    drive, light, obj, fn, tier, poly, sense, sleep = variants[gsim.variant_index]
+    assert (obj, sleep) == (0, allow_sleep), variants[gsim.variant_index]
+    assert fn == (1024 if s.N == 1024 else 0), 'the handle runs instantiation %s' % (variants[gsim.variant_index],)
+    assert gsim.block_threads == {1024: 512, 200: 128, 64: 64}[s.N], 'workgroup of %d threads' % gsim.block_threads
+    fields = ('x', 'y', 'theta', 'status') + (('sleep_time',) if allow_sleep else ())
+    xy, th, st, role, ids = WS.plant(s)
+    osim.set_poses_m(xy, th)
+    gsim.set_poses_m(xy, th)
+    if allow_sleep:
+        osim.sleep_time[...] = st
+        gsim.sleep_time.copy_(dev(st))
+    for k in range(WS.SINGLE_LAUNCHES + 1):
+        n = 1 if k < WS.SINGLE_LAUNCHES else WS.FUSED_SUBSTEPS
+        a = WS.actions(s, k, role)
+        osim.set_actions(a)
+        osim.step(n)
+        gsim.step(n, actions=dev(a))
+        what = '%s sleep %d launch %d (%d substeps)' % (s.name, allow_sleep, k, n)
+        assert_same(osim, gsim, what, fields)
+        assert_ws_same(osim, gsim, what)
+    assert int(osim.status.max()) == 0 and int(cpu(gsim.status).max()) == 0, (osim.status, cpu(gsim.status))

@@ -17,7 +17,12 @@ sys.path.insert(0, ROOT)
 from gym_kilobots_amd.sim import KilobotSim  # noqa: E402
 from tests import scenes  # noqa: E402
 
-PHASES = ['drive+grid', 'count pass', 'emit pass', 'islands+buckets', 'warm+velocity', 'store+integrate', 'position', 'reg load+depth (part of warm+velocity)']
+# Register solver of the kernels without objects (kb_regsolve_bins.inc): no workgroup barrier stands between the register set-up
+# and the end of the position sweeps, so 'warm+velocity' and 'store+integrate' are wave 0's OWN time (wave-local stamps behind its
+# tenth sweep and behind its integration), and 'position' is its own sweeps, the wait for the slowest wave of the env at the one
+# barrier behind them, and everything up to the end of the substep.  The other solver flows close both at barriers as before.
+PHASES = ['drive+grid', 'count pass', 'emit pass', 'islands+buckets', 'warm+velocity (wave 0 alone)', 'store+integrate (wave 0 alone)',
+          'position .. end of substep', 'reg load+depth (in front of warm+velocity)']
 
 
 def main():
@@ -83,8 +88,11 @@ def main():
     sub_ = raw[:, 19:22].mean(0) * 16
     print('  wave 0 inside the register set-up, cumulative since the sort barrier: light load %.0f, + depth pass %.0f, + dealing %.0f' % tuple(sub_))
     fine = raw[:, 24:31].mean(0) * 16
-    print('  since the register set-up: warm start %.0f, + 10 velocity sweeps of wave 0 %.0f (then the barrier)' % (fine[5], fine[6]))
-    print('  since the integration: own position sweeps %.0f, + waiting for the slowest wave %.0f, + continuous-step candidates collected %.0f, '
+    print('  since the register set-up: warm start %.0f, + 10 velocity sweeps of wave 0 %.0f (then its impulses and its integration, no barrier)' % (fine[5], fine[6]))
+    print('  velocity + integrate + position of the env-substep (wave 0\'s warm start to the barrier behind the position sweeps) %.0f'
+          % (mean[4] + mean[5] + fine[1]))
+    print('  since wave 0\'s own integration: own position sweeps %.0f, + the barrier behind them (the env\'s slowest wave through velocity, '
+          'integration and position) %.0f, + continuous-step candidates collected %.0f, '
           '+ own candidates processed %.0f, + every wave\'s %.0f (then copies, cell heads cleared, barrier)' % tuple(fine[:5]))
     b_ = raw[:, 31:36].mean(0) * 16
     print('  sorted bins, wave 0, cumulative since the drive barrier: boundary scan %.0f, + scatter and barrier %.0f, + slots settled %.0f; since the offset scan: contacts staged %.0f, + barrier %.0f' % tuple(b_))
