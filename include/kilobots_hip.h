@@ -181,8 +181,11 @@ typedef struct kb_buffers {
                                            kernels without objects, an env swept by the whole workgroup -- a chain of contacts that
                                            depend on each other deeper than the level table: 44 x waves of the workgroup - 2 levels,
                                            at least 62),
-                                           bit3 more kilobots near the walls in one substep than half the LDS contact staging holds
-                                           (512 at 1024 kilobots; the continuous step is skipped for the rest) */
+                                           bit3 more kilobots that may meet a wall in the continuous step of one substep than the
+                                           kernel keeps candidates for: min(kb_lds_staging_entries(), num_bots) in the kernels without
+                                           objects (688 at 1024 kilobots; a staging area of num_bots entries or more cannot run out),
+                                           half of kb_lds_staging_entries() in the kernels with objects or mixed drive laws (the
+                                           continuous step is skipped for the rest) */
     void *scratch;                      /* required: kb_scratch_bytes() bytes; contact staging of envs whose
                                            contacts do not fit the LDS staging area (contents are transient) */
     float *ows_acc;                     /* objects: [num_envs][8][KB_OWS_COLS][KB_OWS_WORDS] manifold impulses of the

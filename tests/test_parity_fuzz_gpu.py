@@ -14,14 +14,15 @@ pytestmark = pytest.mark.gpu
 
 # how many scenes of a sweep leave at the capacity early-return (the overflow region must be measurable): counted
 # per process, written behind the last scene to gpurun_out/fuzz_summary.txt (and printed with `pytest -s`)
-COUNTS = {'scenes': 0, 'capacity_flag': 0, 'device_limit_flag': 0}
+COUNTS = {'scenes': 0, 'capacity_flag': 0, 'device_limit_flag': 0, 'slot_flag': 0}
 
 
 @pytest.fixture(scope='module', autouse=True)
 def _fuzz_summary():
     yield
     line = ('fuzz sweep: %(scenes)d scenes, %(capacity_flag)d left at the contact-capacity flag (status bit 0, oracle and device agree on it), '
-            '%(device_limit_flag)d at a device-only staging limit (status bit 2)' % COUNTS)
+            '%(device_limit_flag)d at a device-only staging limit (status bit 2), '
+            '%(slot_flag)d compared to the end with the warm-start slot flag set (status bit 1)' % COUNTS)
     print(line)
     try:
         os.makedirs('gpurun_out', exist_ok=True)
@@ -104,6 +105,12 @@ def test_random_scene(seed):
     if rng3.random() < 0.5:
         sense_radius = float(rng3.choice([0.04, 0.07, 0.15])) * min(sx, sy)
         kw.update(sense_radius=sense_radius)
+    # few warm-start slots (kb_config.ws_slots): in a third of the scenes, from a fourth stream of its own.  A kilobot with more
+    # contacts than slots sets status bit 1 on both sides and ends nothing: the oracle says which entries are kept
+    # (tests/overflow_scenes.py), so these scenes are compared for all twelve steps
+    rng4 = np.random.default_rng(333000 + seed)
+    if rng4.random() < 1.0 / 3.0:
+        kw.update(ws_slots=int(rng4.choice([1, 2, 4, 8])))
     with_objects = rng.random() < 0.6
     nobj = 0
     if with_objects:
@@ -181,3 +188,5 @@ def test_random_scene(seed):
         assert_same(osim, gsim, 'seed %d (N=%d E=%d mode=%d light=%d objects=%d %s) step %d' % (seed, N, E, mode, light, nobj, kw.get('solver_mode'), k), fields)
         assert_ws_same(osim, gsim, 'seed %d step %d' % (seed, k))
     assert np.array_equal(osim.status & 3, cpu(gsim.status) & 3)     # (bits 2, 3 are limits of the device staging only)
+    if (osim.status & 2).any():
+        COUNTS['slot_flag'] += 1
