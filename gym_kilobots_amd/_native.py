@@ -99,7 +99,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
@@ -154,6 +154,8 @@ def load():
     lib.kb_sense.restype = C.c_int
     lib.kb_sense_neighbors.argtypes = [_P, C.c_float, C.c_int, _P, _P, _P, _P]
     lib.kb_sense_neighbors.restype = C.c_int
+    lib.kb_sense_edges.argtypes = [_P, C.c_float, _P, C.c_int64, _P, _P, _P, _P, _P]
+    lib.kb_sense_edges.restype = C.c_int
     lib.kb_sense_histogram.argtypes = [_P, C.c_float, C.c_int, C.c_int, _P, _P, _P]
     lib.kb_sense_histogram.restype = C.c_int
     lib.kb_histogram_sectors.argtypes = [C.c_int, C.POINTER(C.c_float)]
@@ -349,6 +351,21 @@ def ray_directions(n_rays):
     buf = (C.c_float * (2 * max(min(n, MAX_RAYS), 1)))()
     check(load().kb_ray_directions(n, buf), 'kb_ray_directions')
     return [(buf[2 * k], buf[2 * k + 1]) for k in range(n)]
+
+
+def check_edges(radius_m, capacity=None):
+    """The limits of kb_sense_edges on the radius and the capacity (None: the caller sizes the outputs from the counts);
+    ValueError where the library would answer KB_EINVAL.  Returns (radius_m, capacity)."""
+    radius_m = float(radius_m)
+    if not radius_m > 0.0:
+        raise ValueError('radius_m must be positive')
+    if capacity is not None:
+        if isinstance(capacity, bool) or int(capacity) != capacity:
+            raise ValueError('capacity must be an integer or None')
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError('capacity must not be negative')
+    return radius_m, capacity
 
 
 def _f32(v):

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -687,6 +687,23 @@ int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, flo
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)NeighborsLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, k, vec,
                        d_index, reinterpret_cast<float4 *>(d_rel), d_count);
     return launched("kb_sense_neighbors");
+}
+
+int kb_sense_edges(kb_sim *sim, float radius_m, const int64_t *d_offsets, int64_t capacity, int32_t *d_src, int32_t *d_dst, float *d_rel,
+                   uint32_t *d_count, void *stream) {
+    if (!sim || !d_offsets) return fail(KB_EINVAL, "kb_sense_edges: NULL argument");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_edges: radius must be positive");
+    if (capacity < 0) return fail(KB_EINVAL, "kb_sense_edges: capacity must not be negative");
+    if (capacity > 0 && !d_dst) return fail(KB_EINVAL, "kb_sense_edges: NULL d_dst with a capacity");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_edges: kb_bind() first");
+    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_edges: d_rel must be 16-byte aligned");
+    const Params &p = sim->p;
+    if ((long long)p.E * p.N >= (1ll << 31)) return fail(KB_EINVAL, "kb_sense_edges: num_envs * num_bots must be below 2^31 (int32 node ids)");
+    if (capacity == 0 && !d_count) return KB_OK;        // nothing to write: nothing is launched
+    const SenseRange r = sense_range(p, radius_m);
+    hipLaunchKernelGGL(kb_edges_kernel, dim3((unsigned)p.E), dim3(256), (size_t)EdgesLds(p.N, p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2,
+                       reinterpret_cast<const long long *>(d_offsets), (long long)capacity, d_src, d_dst, reinterpret_cast<float4 *>(d_rel), d_count);
+    return launched("kb_sense_edges");
 }
 
 int kb_histogram_sectors(int n_sectors, float *xy) {

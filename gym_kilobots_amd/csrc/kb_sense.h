@@ -1,5 +1,5 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram, kb_sense_reduce, kb_sense_rays): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
+// kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
@@ -988,6 +988,94 @@ __global__ void __launch_bounds__(256) kb_rays_kernel(const Params p, const kb_o
                     if (hit) hit[i] = (int)(unsigned)best[i];       // (the low word of a ray that hit nothing is -1)
                 }
             }
+        }
+    }
+}
+
+// ---- kb_sense_edges: the whole IR-range graph as a CSR edge list --------------------------------------------------------------
+constexpr int EDGE_TILE = 256;          // rows (= lanes) per tile of kb_edges_kernel
+struct EdgesLds {       // byte offsets: pos (float2) at 0, th (float), nextb, head (u16 each), mask[EDGE_TILE][stride] (u32); cellOf (u16) lies over mask
+    int th, nextb, head, mask, words, stride, bytes;
+    // words: of a row's bitmask, one bit per kilobot of the env; stride: the next odd number, so that word w of the rows of
+    // consecutive lanes lies in consecutive banks.  cellOf is read once, before the first mask is cleared, and needs no room of its own.
+    __host__ __device__ constexpr EdgesLds(int N, int NP, int ncell)
+        : th(8 * NP), nextb(12 * NP), head(14 * NP), mask(head + 2 * ((ncell + 1) & ~1)), words((N + 31) >> 5), stride(words | 1),
+          bytes(mask + (4 * EDGE_TILE * stride > 2 * NP ? 4 * EDGE_TILE * stride : 2 * NP)) {}
+};
+// the largest image (1024 kilobots, every cell) stays under the default limit for dynamic LDS: no attribute to raise
+static_assert(EdgesLds(KB_MAX_BOTS, KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024, "kb_edges_kernel: LDS image");
+static_assert(KB_MAX_BOTS <= 4 * EDGE_TILE, "kb_edges_kernel: a lane keeps the cells of at most four rows");
+
+// The IR-range graph on the current poses (kb_sense_edges): every pair of kilobots in range, both directions, as rows of a
+// CSR list whose row pointer the caller supplies.  Poses, headings and the cell lists in LDS, one kilobot (= row) per lane
+// over the full stencil, like kb_neighbors_kernel, in tiles of EDGE_TILE rows.  The chains of the cell lists are in exchange
+// order, so the order of a row is MADE: the lane owns a bitmask of one bit per kilobot of the env in LDS, clears it, sets bit
+// j for every hit of the walk (plain read-modify-write: nobody else touches the row, no atomics, no barrier inside the tile
+// loop) and then scans the words upwards, lowest set bit first -- ascending j by construction, whatever the walk's order.
+// An edge's attributes are recomputed from pos[j] and th[j] with the operations of kb_neighbors_kernel (d2 is the walk's dd:
+// the same operations on the same operands, the same bits).
+// Memory contract: row r owns the slots [lo, hi) of d_offsets[r], d_offsets[r + 1], both clipped to [0, capacity]; the lane
+// writes the first min(count, hi - lo) neighbours there and -1 / +0.0 into what is left of the row, and stores nowhere else.
+// Emission is per lane: 4 + 4 + 16 bytes per edge at the lane's own cursor.
+__global__ void __launch_bounds__(256) kb_edges_kernel(const Params p, const int s, const float R2, const long long *d_offsets, const long long capacity,
+                                                       int *d_src, int *d_dst, float4 *d_rel, unsigned *d_count) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const EdgesLds L(N, p.NP, p.ncell);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    float *th = reinterpret_cast<float *>(smem + L.th);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.mask);
+    unsigned *row = reinterpret_cast<unsigned *>(smem + L.mask) + tid * L.stride;
+    const size_t o = (size_t)e * N;
+    for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
+    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    // the cells of the lane's (at most four) rows, two to a register, before the masks take cellOf's place
+    unsigned c01 = 0, c23 = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int a = tid + t * EDGE_TILE;
+        const unsigned c = a < N ? (unsigned)cellOf[a] : 0u;
+        if (t < 2) c01 |= c << (16 * t);
+        else c23 |= c << (16 * (t - 2));
+    }
+    __syncthreads();
+    const int W = L.words;
+    for (int t = 0; t * EDGE_TILE < N; ++t) {
+        const int a = t * EDGE_TILE + tid;
+        if (a >= N) break;      // (no barrier follows)
+        const int cell = (int)(((t < 2 ? c01 : c23) >> (16 * (t & 1))) & 0xFFFFu);
+        const float2 pa = pos[a];
+        for (int w = 0; w < W; ++w) row[w] = 0u;
+        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
+            row[b >> 5] |= 1u << (b & 31u);
+        });
+        if (d_count) d_count[o + a] = cnt;
+        if (capacity <= 0) continue;
+        const long long o0 = d_offsets[o + a], o1 = d_offsets[o + a + 1];
+        const long long lo = o0 < 0 ? 0 : (o0 > capacity ? capacity : o0), hi = o1 < 0 ? 0 : (o1 > capacity ? capacity : o1);
+        if (hi <= lo) continue;
+        const float tha = th[a];
+        float sn, cs;
+        kb_sincosf(tha, sn, cs);
+        const int node0 = (int)o, src = node0 + a;
+        long long slot = lo;
+        for (int w = 0; w < W && slot < hi; ++w) {
+            for (unsigned bits = row[w]; bits != 0u && slot < hi; bits &= bits - 1u, ++slot) {
+                const int j = 32 * w + __builtin_ctz(bits);
+                const float2 pb = pos[j];
+                const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+                const float d2 = ex * ex + ey * ey;
+                d_dst[slot] = node0 + j;
+                if (d_src) d_src[slot] = src;
+                if (d_rel) d_rel[slot] = make_float4((cs * ex + sn * ey) / WORLD_SCALE, (cs * ey - sn * ex) / WORLD_SCALE, sqrtf(d2) / WORLD_SCALE, th[j] - tha);
+            }
+        }
+        for (; slot < hi; ++slot) {     // offsets that give the row more than it has
+            d_dst[slot] = -1;
+            if (d_src) d_src[slot] = -1;
+            if (d_rel) d_rel[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
     }
 }

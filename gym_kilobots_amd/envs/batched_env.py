@@ -17,7 +17,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, **cfg):
+                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -45,7 +45,12 @@ class BatchedKilobotsEnv(object):
         ray_obs: (radius_m, n_rays) or (radius_m, n_rays, targets) adds the range scan of a decentralised policy: rays() returns
         (dist [E, N, n_rays], hit [E, N, n_rays]), how far the first kilobot, object or wall along each of n_rays bearings in
         every kilobot's own frame is and what it is (KilobotSim.rays; targets made of 'bots', 'objects' and 'walls', default:
-        everything the env has), and step() puts the tuple in its info dict under 'rays'.  None adds nothing."""
+        everything the env has), and step() puts the tuple in its info dict under 'rays'.  None adds nothing.
+        edge_obs: radius_m or (radius_m, capacity) adds the whole IR-range graph, for graph-network policies: edges() returns
+        the named tuple (src, dst, rel, offsets, count, nnz) of KilobotSim.edges -- every pair of kilobots in range as a
+        CSR / COO edge list over the batch, node e * N + i for kilobot i of env e; with a capacity the lists have that fixed
+        length and nothing is read back from the device, without one they have nnz entries at the price of one read -- and
+        step() puts the tuple in its info dict under 'edges'.  None adds nothing."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -122,6 +127,13 @@ class BatchedKilobotsEnv(object):
                 raise ValueError('ray_obs must be (radius_m, n_rays) or (radius_m, n_rays, targets): %s' % err)
             if self.ray_obs[2] & nat.RAY_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
                 raise ValueError("ray_obs: 'objects' asked for, but the env has no objects")
+        self.edge_obs = None
+        if edge_obs is not None:
+            try:
+                radius_m, capacity = tuple(edge_obs) if hasattr(edge_obs, '__len__') else (edge_obs, None)
+                self.edge_obs = nat.check_edges(radius_m, capacity)
+            except TypeError as err:
+                raise ValueError('edge_obs must be radius_m or (radius_m, capacity): %s' % err)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -222,6 +234,8 @@ class BatchedKilobotsEnv(object):
             info['contacts'] = self.contacts()
         if self.ray_obs is not None:
             info['rays'] = self.rays()
+        if self.edge_obs is not None:
+            info['edges'] = self.edges()
         return obs, reward, done, info
 
     def neighbors(self):
@@ -265,6 +279,13 @@ class BatchedKilobotsEnv(object):
         if self.ray_obs is None:
             raise ValueError('create the env with ray_obs=(radius_m, n_rays[, targets]) to observe range scans')
         return self.sim.rays(*self.ray_obs)
+
+    def edges(self):
+        """The named tuple (src, dst, rel, offsets, count, nnz) of the current poses for the edge_obs=radius_m or
+        (radius_m, capacity) the env was created with: KilobotSim.edges."""
+        if self.edge_obs is None:
+            raise ValueError('create the env with edge_obs=radius_m or (radius_m, capacity) to observe the IR-range graph')
+        return self.sim.edges(*self.edge_obs)
 
     def render(self, mode='rgb_array'):
         """frames [E, height, width, 3] uint8 of the current state for the render_size=(width, height) the env was created

@@ -3,6 +3,7 @@
 This is the host side of the hot path only.  torch is used for device memory and streams; all
 simulation arithmetic happens inside libkilobots_hip.so (gym_kilobots_amd/csrc/).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,9 @@ from . import _native as nat
 from ._native import STATUS_BITS, KilobotsStatusError, describe_status  # noqa: F401
 from ._native import (DRIVE_VELOCITY, DRIVE_ACCEL, DRIVE_MOTORS, DRIVE_SIMPLE_PHOTOTAXIS,  # noqa: F401
                       DRIVE_PHOTOTAXIS, LIGHT_NONE, LIGHT_CIRCULAR, STEP_NO_DRIVE, WORLD_SCALE)
+
+# what KilobotSim.edges returns
+Edges = collections.namedtuple('Edges', ('src', 'dst', 'rel', 'offsets', 'count', 'nnz'))
 
 
 class KilobotSim:
@@ -259,6 +263,54 @@ class KilobotSim:
             nat.check(self._lib.kb_sense_neighbors(self._h, float(radius_m), k, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
                                                    pc, self._stream()), 'kb_sense_neighbors')
         return (out[0], out[1], out[2] if count else None)
+
+    def edges(self, radius_m, capacity=None, rel=True, src=True, out=None):
+        """The whole IR-range graph on the current poses (kb_sense_edges; no reference counterpart): every pair of kilobots of
+        an env within radius_m (centre to centre), both directions, as a CSR / COO edge list over the whole batch.  Kilobot i
+        of env e is node e * num_bots + i; the row of a node holds its neighbours in ascending order.  Returns the named
+        tuple Edges(src, dst, rel, offsets, count, nnz): src, dst [n] int32 node ids (src None with src=False), rel [n, 4]
+        float32 as in neighbors() (None with rel=False), offsets [E * N + 1] int64 the CSR row pointer (the cumulative sum
+        of count), count [E, N] int32 = sense(radius_m), nnz = offsets[-1], the number of edges.
+        capacity=None: n = nnz, an int -- read from the device, the ONE synchronising read of this path; nnz == 0 gives
+        empty tensors and still a valid offsets.  capacity=int: n = capacity, nothing is read back, nnz is a 0-dim int64
+        tensor on the device for the caller to compare with capacity when it likes; edges behind the capacity are dropped
+        from the end of the list, freshly allocated outputs hold -1 (src, dst) and 0 (rel) behind nnz.
+        out: the preallocated contiguous tensors to write into, (src, dst, rel) without those switched off; slots behind
+        nnz are left alone.  For an int64 edge_index [2, nnz] stack and cast in torch: torch.stack((src, dst)).long()."""
+        E, N = self.num_envs, self.num_bots
+        radius_m, capacity = nat.check_edges(radius_m, capacity)
+        count = self.sense(radius_m)
+        offsets = torch.zeros(E * N + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(count.view(-1), 0, dtype=torch.int64, out=offsets[1:])
+        nnz = offsets[-1]
+        if capacity is None:
+            nnz = int(nnz)          # the device read
+        n = nnz if capacity is None else capacity
+        shapes = ([((n,), torch.int32, 'src')] if src else []) + [((n,), torch.int32, 'dst')] + ([((n, 4), torch.float32, 'rel')] if rel else [])
+        fresh = out is None
+        out = list(self._outputs(out, shapes, 'a tuple of %d tensors (%s)' % (len(shapes), ', '.join(name for _, _, name in shapes))))
+        if fresh and capacity is not None:
+            for t, (_, _, name) in zip(out, shapes):
+                t.fill_(0 if name == 'rel' else -1)
+        t_src = out.pop(0) if src else None
+        t_dst = out.pop(0)
+        t_rel = out.pop(0) if rel else None
+        self._sense_edges(radius_m, offsets, n, t_src, t_dst, t_rel, None)
+        return Edges(t_src, t_dst, t_rel, offsets, count, nnz)
+
+    def _sense_edges(self, radius_m, offsets, capacity, src, dst, rel, count):
+        """The raw call of kb_sense_edges: offsets [E * N + 1] int64 as they are (the library clips what they say to the
+        capacity), src / dst / rel / count contiguous tensors or None.  The sizes are checked here, because the library cannot:
+        src, dst and rel hold at least `capacity` entries, offsets and count one per row."""
+        rows, capacity = self.num_envs * self.num_bots, int(capacity)
+        for t, dtype, least, name in ((offsets, torch.int64, rows + 1, 'offsets'), (src, torch.int32, capacity, 'src'), (dst, torch.int32, capacity, 'dst'),
+                                      (rel, torch.float32, 4 * capacity, 'rel'), (count, torch.int32, rows, 'count')):
+            if t is not None and not (t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous() and t.numel() >= least):
+                raise ValueError('%s must be a contiguous %s tensor of at least %d elements on %s' % (name, str(dtype).replace('torch.', ''), least, self.device))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_edges(self._h, float(radius_m), ptr(offsets), int(capacity), ptr(src), ptr(dst), ptr(rel), ptr(count),
+                                               self._stream()), 'kb_sense_edges')
 
     def neighbor_histogram(self, radius_m, n_rings, n_sectors, out=None, count=False):
         """Local neighbour histograms on the current poses (kb_sense_histogram; no reference counterpart): for every kilobot

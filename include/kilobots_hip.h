@@ -247,6 +247,39 @@ int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream);
 int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count,
                        void *stream);
 
+/* The whole IR-range graph on the CURRENT poses, without stepping: every pair of kilobots of an env in IR range, as a CSR /
+ * COO edge list over the whole batch -- the ragged output that graph networks, learned message passing and connectivity
+ * metrics consume, and that the fixed-size rows of kb_sense_neighbors truncate at 16.  No reference counterpart.  Every
+ * operation is one fp32 operation rounded on its own.
+ *   Nodes: node ids are local to the handle; kilobot i of env e is node r = e * num_bots + i.  num_envs * num_bots < 2^31
+ *     (KB_EINVAL otherwise).
+ *   Predicate: as kb_sense -- Rw = radius_m * 25, R2 = Rw * Rw (on the host);  ex = x_j - x_i, ey = y_j - y_i,
+ *     d2 = ex * ex + ey * ey;  j is a neighbour of i iff j != i && !(d2 > R2).
+ *   Row of i: its neighbours in ASCENDING j; nothing else decides the order.  Both directions of a pair are present, (i, j)
+ *     in the row of i and (j, i) in the row of j, each with the attributes of its own frame.
+ *   rel[4] of an edge: as kb_sense_neighbors.
+ * d_offsets [num_envs * num_bots + 1] int64: the CSR row pointer, supplied by the caller -- the exclusive prefix sum of the
+ *   counts kb_sense gives at the same radius on the same poses (the library allocates nothing and does not scan).
+ * d_dst   [capacity] int32: node id of j.
+ * d_src   [capacity] int32 or NULL: node id of i.
+ * d_rel   [capacity][4] float32, 16-byte aligned, or NULL.
+ * d_count [num_envs][num_bots] uint32 or NULL: the true number of neighbours of every kilobot, whatever d_offsets says --
+ *   what kb_sense writes for this radius.
+ * Memory contract (d_offsets may be stale; it cannot make the call write out of bounds): row r owns the slots [lo, hi) with
+ *   lo = d_offsets[r], hi = d_offsets[r + 1], both clipped to [0, capacity]; the row is empty if hi <= lo.  The first
+ *   min(count_r, hi - lo) neighbours in ascending j are written there; the slots of the row beyond count_r receive dst = src
+ *   = -1 and rel = +0.0 x 4.  Nothing is stored outside [0, capacity) and nothing in a slot that no row owns.  With consistent
+ *   offsets every slot in [0, d_offsets[num_envs * num_bots]) is written exactly once, by plain stores.  (Offsets that do
+ *   not ascend may make rows overlap; such a slot receives the value of one of its rows.)
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_offsets;  radius_m not > 0;
+ * capacity < 0;  capacity > 0 with NULL d_dst.  Then KB_ENOTBOUND;  then a d_rel that is not 16-byte aligned;  then the node
+ * count.  capacity == 0 is legal: with d_count it is the counting call; without it nothing is launched and the call returns
+ * KB_OK -- after the checks above, so on an unbound handle it answers KB_ENOTBOUND like every other valid call.
+ * Reads x, y, theta and d_offsets; writes the outputs only.  The result of an env does not depend on the other envs, apart
+ * from where its rows start.  One launch.  Asynchronous on `stream`. */
+int kb_sense_edges(kb_sim *sim, float radius_m, const int64_t *d_offsets, int64_t capacity, int32_t *d_src, int32_t *d_dst,
+                   float *d_rel, uint32_t *d_count, void *stream);
+
 /* Local neighbour histograms on the CURRENT poses, without stepping: for every kilobot i the number of kilobots j != i of
  * the same env within IR range, binned by distance (n_rings rings of equal width) and by bearing in the body frame of i
  * (n_sectors sectors of equal angle) -- a fixed-size, permutation-invariant observation that counts ALL neighbours in
