@@ -86,6 +86,11 @@ class KbResetParams(C.Structure):
 
 _P = C.c_void_p
 
+
+class KbEpisodeInit(C.Structure):
+    """kb_episode_init: what kb_reset_envs puts the selected envs at besides the spawn; device pointers, every one optional."""
+    _fields_ = [('d_episode', _P), ('d_obj_pose', _P), ('d_light_pos', _P), ('d_light_vel', _P)]
+
 BUFFER_FIELDS = ['x', 'y', 'theta', 'v', 'w', 'acc_v', 'acc_w', 'motor_l', 'motor_r',
                  'pt_threshold', 'pt_update', 'pt_nochange', 'pt_dir',
                  'light_x', 'light_y', 'light_vx', 'light_vy',
@@ -99,7 +104,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset', 'kb_step_envs', 'kb_reset_envs',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
@@ -184,6 +189,13 @@ def load():
     lib.kb_light_sense.restype = C.c_int
     lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
     lib.kb_reset.restype = C.c_int
+    # (an older build of the library that KB_HIP_LIB selects for an A/B, tools/ab_bench.py, has not got these two: it loads, and
+    #  calling one of them on it raises AttributeError)
+    if hasattr(lib, 'kb_step_envs') or LIB_PATH == os.path.join(HERE, 'libkilobots_hip.so'):
+        lib.kb_step_envs.argtypes = [_P, _P, _P, _P, C.c_int, C.c_int, _P]
+        lib.kb_step_envs.restype = C.c_int
+        lib.kb_reset_envs.argtypes = [_P, C.POINTER(KbResetParams), _P, C.POINTER(KbEpisodeInit), _P]
+        lib.kb_reset_envs.restype = C.c_int
     for name in ('kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_block_threads', 'kb_variant_index', 'kb_light_action_dim', 'kb_light_count', 'kb_exact_division'):
         getattr(lib, name).argtypes = [_P]
         getattr(lib, name).restype = C.c_int

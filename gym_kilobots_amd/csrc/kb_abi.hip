@@ -152,14 +152,19 @@ struct ResetArgs {
     unsigned k0, k1;
     int env_offset, random_theta, random_velocity;
     float mean_x, mean_y, std, lo_x, lo_y, hi_x, hi_y;
+    // kb_reset_envs (all NULL in kb_reset): the envs to reset, word z of their Philox counters, and what to put their objects and lights at
+    const unsigned char *env_mask;
+    const unsigned *episode;
+    const float *obj_pose, *light_pos, *light_vel;
 };
 __global__ void kb_reset_kernel(const Params p, const ResetArgs a) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t T = (size_t)p.E * p.N;
     if (i >= T) return;
     const int e = (int)(i / p.N), b = (int)(i % p.N);
+    if (a.env_mask && !a.env_mask[e]) return;
     U4 c;
-    c.x = (unsigned)(a.env_offset + e); c.y = (unsigned)b; c.z = 0u; c.w = 0u;
+    c.x = (unsigned)(a.env_offset + e); c.y = (unsigned)b; c.z = a.episode ? a.episode[e] : 0u; c.w = 0u;
     const U4 r = kb_philox4x32_10(c, a.k0, a.k1);
     // Box-Muller on u1 in (0, 1], u2 in [0, 1)
     const float u1 = (float)((r.x >> 8) + 1u) * (1.0f / 16777216.0f);
@@ -194,6 +199,27 @@ __global__ void kb_reset_kernel(const Params p, const ResetArgs a) {
     if (p.M > 0) {      // forget the objects' manifold impulses as well
         float *ows = p.buf.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS);
         for (int k = b; k < MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS; k += p.N) ows[k] = -1.0f;
+    }
+    if (a.obj_pose) {   // the env's objects at the caller's poses, at rest and awake (Body.__init__, body.py:32-38)
+        for (int k = b; k < p.M; k += p.N) {
+            const size_t j = (size_t)e * p.M + k;
+            p.buf.ox[j] = a.obj_pose[3 * j + 0]; p.buf.oy[j] = a.obj_pose[3 * j + 1]; p.buf.otheta[j] = a.obj_pose[3 * j + 2];
+            p.buf.ovx[j] = 0.0f; p.buf.ovy[j] = 0.0f; p.buf.ow[j] = 0.0f;
+            if (p.buf.osleep) p.buf.osleep[j] = 0.0f;
+        }
+    }
+    if (a.light_pos || a.light_vel) {
+        for (int k = b; k < p.lcount; k += p.N) {
+            const size_t j = (size_t)e * p.lcount + k;
+            if (a.light_pos) {
+                p.buf.light_x[j] = a.light_pos[2 * j + 0];
+                if (p.buf.light_y) p.buf.light_y[j] = a.light_pos[2 * j + 1];
+            }
+            if (p.buf.light_vx && p.buf.light_vy) {
+                p.buf.light_vx[j] = a.light_vel ? a.light_vel[2 * j + 0] : 0.0f;
+                p.buf.light_vy[j] = a.light_vel ? a.light_vel[2 * j + 1] : 0.0f;
+            }
+        }
     }
 }
 
@@ -637,31 +663,44 @@ int kb_resident_envs_per_cu(kb_sim *sim) {
     return n;
 }
 
-int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, int n_substeps, int flags, void *stream) {
-    if (!sim) return fail(KB_EINVAL, "kb_step: NULL handle");
-    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_step: kb_bind() first");
-    if (n_substeps < 0) return fail(KB_EINVAL, "kb_step: n_substeps < 0");
+// the one launch of kb_step and kb_step_envs (d_env_mask NULL: every env), reported under the caller's name
+static int step_launch(const char *entry, kb_sim *sim, const uint8_t *d_env_mask, const float *d_actions, const float *d_light_action,
+                       int n_substeps, int flags, void *stream) {
+    if (!sim->bound) return fail(KB_ENOTBOUND, "%s: kb_bind() first", entry);
+    if (n_substeps < 0) return fail(KB_EINVAL, "%s: n_substeps < 0", entry);
     if (d_actions && sim->cfg.drive_mode != KB_DRIVE_VELOCITY && sim->cfg.drive_mode != KB_DRIVE_ACCEL && sim->cfg.drive_mode != KB_DRIVE_MIXED)
-        return fail(KB_EINVAL, "kb_step: only the velocity / acceleration drive modes take actions");
+        return fail(KB_EINVAL, "%s: only the velocity / acceleration drive modes take actions", entry);
     if (n_substeps == 0 && !d_actions) return KB_OK;
     Params p = sim->p;
     p.actions = d_actions;
     p.light_action = d_light_action;
+    p.env_mask = d_env_mask;
     p.n_substeps = n_substeps;
     p.flags = flags;
     const kb_step_fn fn = sim->fn;
-    if (!fn) return fail(KB_EINVAL, "kb_step: no kernel for this drive mode / light type");
+    if (!fn) return fail(KB_EINVAL, "%s: no kernel for this drive mode / light type", entry);
     if (p.lds_total > 64 * 1024 && sim->attr_fn != reinterpret_cast<const void *>(fn)) {
         // the attribute belongs to the kernel, not to this sim: raise it to the hardware limit, so that sims of
         // different sizes sharing one instantiation never lower it under each other
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(fn),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
-        if (e2 != hipSuccess) return fail(KB_EHIP, "kb_step: hipFuncSetAttribute: %s", hipGetErrorString(e2));
+        if (e2 != hipSuccess) { snprintf(g_err, sizeof(g_err), "%s: hipFuncSetAttribute: %s", entry, hipGetErrorString(e2)); return KB_EHIP; }
         sim->attr_fn = reinterpret_cast<const void *>(fn);
     }
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3((unsigned)sim->threads), (size_t)p.lds_total,
                        (hipStream_t)stream, p);
-    return launched("kb_step");
+    return launched(entry);
+}
+
+int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, int n_substeps, int flags, void *stream) {
+    if (!sim) return fail(KB_EINVAL, "kb_step: NULL handle");
+    return step_launch("kb_step", sim, nullptr, d_actions, d_light_action, n_substeps, flags, stream);
+}
+
+int kb_step_envs(kb_sim *sim, const uint8_t *d_env_mask, const float *d_actions, const float *d_light_action, int n_substeps, int flags,
+                 void *stream) {
+    if (!sim || !d_env_mask) return fail(KB_EINVAL, "kb_step_envs: NULL argument");
+    return step_launch("kb_step_envs", sim, d_env_mask, d_actions, d_light_action, n_substeps, flags, stream);
 }
 
 int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream) {
@@ -972,10 +1011,9 @@ int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {
     return launched("kb_light_sense");
 }
 
-int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream) {
-    if (!sim || !rp) return fail(KB_EINVAL, "kb_reset: NULL argument");
-    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_reset: kb_bind() first");
-    if (!(rp->std >= 0.0f)) return fail(KB_EINVAL, "kb_reset: std must be >= 0");
+// the spawn launch of kb_reset and kb_reset_envs (d_env_mask NULL: every env, init NULL: nothing but the kilobots' rows)
+static int reset_launch(const char *entry, kb_sim *sim, const kb_reset_params *rp, const uint8_t *d_env_mask, const kb_episode_init *init,
+                        void *stream) {
     const Params &p = sim->p;
     ResetArgs a;
     a.k0 = (unsigned)(rp->seed & 0xFFFFFFFFull); a.k1 = (unsigned)(rp->seed >> 32);
@@ -984,11 +1022,36 @@ int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream) {
     // world_bounds -/+ 0.02 (yaml_kilobots_env.py:350-351), metres
     a.lo_x = -0.5f * sim->cfg.world_width + 0.02f; a.hi_x = 0.5f * sim->cfg.world_width - 0.02f;
     a.lo_y = -0.5f * sim->cfg.world_height + 0.02f; a.hi_y = 0.5f * sim->cfg.world_height - 0.02f;
+    a.env_mask = d_env_mask;
+    a.episode = init ? init->d_episode : nullptr;
+    a.obj_pose = init ? init->d_obj_pose : nullptr;
+    a.light_pos = init ? init->d_light_pos : nullptr;
+    a.light_vel = init ? init->d_light_vel : nullptr;
     const size_t T = (size_t)p.E * p.N;
     hipLaunchKernelGGL(kb_reset_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, a);
-    const int rc = launched("kb_reset");
+    return launched(entry);
+}
+
+int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream) {
+    if (!sim || !rp) return fail(KB_EINVAL, "kb_reset: NULL argument");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_reset: kb_bind() first");
+    if (!(rp->std >= 0.0f)) return fail(KB_EINVAL, "kb_reset: std must be >= 0");
+    const int rc = reset_launch("kb_reset", sim, rp, nullptr, nullptr, stream);
     if (rc != KB_OK) return rc;
     if (rp->resolve) return kb_step(sim, nullptr, nullptr, 1, KB_STEP_NO_DRIVE, stream);
+    return KB_OK;
+}
+
+int kb_reset_envs(kb_sim *sim, const kb_reset_params *rp, const uint8_t *d_env_mask, const kb_episode_init *init, void *stream) {
+    if (!sim || !rp || !d_env_mask) return fail(KB_EINVAL, "kb_reset_envs: NULL argument");
+    if (!(rp->std >= 0.0f)) return fail(KB_EINVAL, "kb_reset_envs: std must be >= 0");
+    if (init && init->d_obj_pose && sim->cfg.num_objects == 0) return fail(KB_EINVAL, "kb_reset_envs: d_obj_pose, but the handle has no objects");
+    if (init && (init->d_light_pos || init->d_light_vel) && sim->cfg.light_type == KB_LIGHT_NONE)
+        return fail(KB_EINVAL, "kb_reset_envs: d_light_pos / d_light_vel, but the handle has no light");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_reset_envs: kb_bind() first");
+    const int rc = reset_launch("kb_reset_envs", sim, rp, d_env_mask, init, stream);
+    if (rc != KB_OK) return rc;
+    if (rp->resolve) return step_launch("kb_reset_envs", sim, d_env_mask, nullptr, nullptr, 1, KB_STEP_NO_DRIVE, stream);
     return KB_OK;
 }
 

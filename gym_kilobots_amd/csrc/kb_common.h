@@ -90,6 +90,7 @@ struct Params {
     float nm_bb, nm_wb;                       // effective mass of a kilobot-kilobot and of a wall-kilobot contact
     float y_bb, y_wb;                         // RN(1 / (im_bot + im_bot)), RN(1 / im_bot): the position sweep divides by multiplying (kb_exact.h) ...
     int exact_div;                            // ... once kb_create has checked kb_div_const against a / K for these two K; 0: the sweep divides
+    const unsigned char *env_mask;            // kb_step_envs: [E] bytes, set per launch like `actions`; an env whose byte is 0 is not stepped.  NULL: every env
 };
 
 

@@ -17,7 +17,8 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None, **cfg):
+                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
+                 max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -50,7 +51,19 @@ class BatchedKilobotsEnv(object):
         the named tuple (src, dst, rel, offsets, count, nnz) of KilobotSim.edges -- every pair of kilobots in range as a
         CSR / COO edge list over the batch, node e * N + i for kilobot i of env e; with a capacity the lists have that fixed
         length and nothing is read back from the device, without one they have nnz entries at the price of one read -- and
-        step() puts the tuple in its info dict under 'edges'.  None adds nothing."""
+        step() puts the tuple in its info dict under 'edges'.  None adds nothing.
+        Episodes of single envs, all off by default (reset(), step() and the info dict are then what they were):
+        max_episode_steps: an env is done once it has taken that many steps since its last reset.
+        done_fn: called as done_fn(prev, actions, obs) like reward_fn, returns a bool tensor [E]: the envs that are done.
+        With either, step() reports done = done_fn(...) | (episode_steps >= max_episode_steps) and puts 'episode_return' and
+        'episode_length' ([E], final for the done envs) in its info dict.
+        auto_reset: step() resets the done envs (reset_envs) before it takes the observations: obs and every observation in
+        the info dict describe the new episode, info['terminal_obs'] holds the poses from before the reset.
+        object_init: [E, M, 3] or [M, 3] (x [m], y [m], theta): where reset() and reset_envs() put the objects, at rest;
+        converted once, as KilobotSim.set_objects_m converts.  None: resets leave the objects alone.
+        light_init: [E, L, 2], [L, 2] or [2] metres (a GradientLight: its angle first): where they put the lights, with
+        velocity 0.  None: resets leave the lights alone.
+        Nothing on this path reads the device back: a step in which no env is done costs two small launches."""
         if sim_factory is None:
             from ..sim import KilobotSim as sim_factory
         if on_status not in ('raise', 'warn', 'ignore'):
@@ -156,7 +169,36 @@ class BatchedKilobotsEnv(object):
         self.action_space = Box(np.tile(lo, (self.num_kilobots, 1)), np.tile(hi, (self.num_kilobots, 1)), dtype=np.float64)
         b = np.array([self.world_width / 2, self.world_height / 2, np.inf])
         self.observation_space = Box(np.tile(-b, (self.num_kilobots, 1)), np.tile(b, (self.num_kilobots, 1)), dtype=np.float32)
-        self.episode_returns = torch.zeros(self.num_envs, dtype=torch.float32, device=self.sim.x.device)
+        dev = self.sim.x.device
+        self.episode_returns = torch.zeros(self.num_envs, dtype=torch.float32, device=dev)
+        # episodes of single envs
+        if max_episode_steps is not None and not int(max_episode_steps) >= 1:
+            raise ValueError('max_episode_steps must be at least 1 or None')
+        self.max_episode_steps = None if max_episode_steps is None else int(max_episode_steps)
+        self.done_fn, self.auto_reset = done_fn, bool(auto_reset)
+        self._episodes = self.max_episode_steps is not None or done_fn is not None or self.auto_reset
+        self.episode_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self.episode_index = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)    # word z of the spawn's Philox counter
+        self._reset_key = None
+        self._object_init = self._light_init = None
+        E, M = self.num_envs, int(cfg.get('num_objects', 0))
+        if object_init is not None:
+            a = np.asarray(object_init.cpu() if torch.is_tensor(object_init) else object_init, np.float64)
+            if M == 0 or a.shape not in ((E, M, 3), (M, 3)):
+                raise ValueError('object_init must have the shape %s or %s in an env with objects' % ((E, M, 3), (M, 3)))
+            a = np.broadcast_to(a, (E, M, 3))
+            w = np.empty((E, M, 3), np.float32)
+            w[..., :2] = (a[..., :2] * nat.WORLD_SCALE).astype(np.float32)      # (as set_objects_m: float64 metres x 25, then rounded)
+            w[..., 2] = a[..., 2].astype(np.float32)
+            self._object_init = torch.from_numpy(w).to(dev)
+        if light_init is not None:
+            if self.sim.light_x is None or light_type == nat.LIGHT_NONE:
+                raise ValueError('light_init given, but the env has no light')
+            shape = tuple(self.sim.light_x.shape) + (2,)
+            a = np.asarray(light_init.cpu() if torch.is_tensor(light_init) else light_init, np.float32)
+            if a.shape not in (shape, shape[1:], (2,)):
+                raise ValueError('light_init must have the shape %s, %s or (2,)' % (shape, shape[1:]))
+            self._light_init = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a, shape))).to(dev)
 
     def seed(self, seed=None):
         if seed is not None:
@@ -190,24 +232,72 @@ class BatchedKilobotsEnv(object):
         """poses: optional (xy [E,N,2] metres, theta [E,N]) uploaded from the host.  Default: the reference's Gaussian
         spawn drawn ON THE DEVICE (kb_reset: Philox4x32-10 keyed by (seed + reset count; global env, bot)), no host
         arrays, no H2D copy; followed by the "step to resolve" of kilobots_env.py:156-157 either way."""
+        templates = self._object_init is not None or self._light_init is not None
+        self._reset_key = (int(self._seed) << 20) + self._resets       # (reset_envs draws the later episodes from the same key)
         if poses is None:
-            self.sim.reset(seed=(int(self._seed) << 20) + self._resets, mean=tuple(float(v) for v in self.spawn_mean),
-                           std=float(self.spawn_std), random_theta=False, random_velocity=False, resolve=True,
-                           env_offset=self.env_offset)
+            kw = dict(seed=self._reset_key, mean=tuple(float(v) for v in self.spawn_mean),
+                      std=float(self.spawn_std), random_theta=False, random_velocity=False, resolve=True,
+                      env_offset=self.env_offset)
+            if templates:       # the spawn of sim.reset() (counter word 0) with the objects and lights put in place before the resolve step
+                self.sim.reset_envs(torch.ones(self.num_envs, dtype=torch.bool, device=self.episode_index.device),
+                                    objects=self._object_init, lights=self._light_init, **kw)
+            else:
+                self.sim.reset(**kw)
             self._resets += 1
         else:
             xy, th = poses
             self.sim.set_poses_m(xy, th)
+            if templates:
+                self._place_templates()
             self.sim.status.zero_()
             self.sim.step(1, flags=nat.STEP_NO_DRIVE)       # "step to resolve", kilobots_env.py:156-157
         self.episode_returns.zero_()
+        self.episode_steps.zero_()
+        self.episode_index.zero_()
         self._steps = 0
         self._check_status('reset()')
         return self.sim.poses()
 
+    def _place_templates(self):
+        """object_init / light_init into every env, at rest: what reset_envs does for the envs it selects."""
+        s = self.sim
+        if self._object_init is not None:
+            s.ox.copy_(self._object_init[..., 0])
+            s.oy.copy_(self._object_init[..., 1])
+            s.otheta.copy_(self._object_init[..., 2])
+            for t in (s.ovx, s.ovy, s.ow, s.osleep):
+                if t is not None:
+                    t.zero_()
+            s.forget_contacts()
+        if self._light_init is not None:
+            s.light_x.copy_(self._light_init[..., 0])
+            if s.light_y is not None:
+                s.light_y.copy_(self._light_init[..., 1])
+            for t in (s.light_vx, s.light_vy):
+                if t is not None:
+                    t.zero_()
+
+    def reset_envs(self, env_mask):
+        """Start a new episode in the envs env_mask selects ([E] bool or uint8 tensor on the sim's device); the others run on
+        untouched (KilobotSim.reset_envs).  The spawn comes from the key of the last reset() and the counter word
+        episode_index[e], which reset() zeroes and this call increments for the selected envs first: the j-th episode of
+        global env e is a pure function of (seed, reset count, e, j), whenever the other envs end, sharded or not.  Puts the
+        objects and lights at object_init / light_init, takes the step to resolve in those envs alone, zeroes their
+        episode_returns and episode_steps, and returns the poses [E, N, 3] of all envs.  Nothing is read back from the device."""
+        if self._reset_key is None:
+            raise ValueError('reset_envs: call reset() first')
+        sel = env_mask if env_mask.dtype == torch.bool else env_mask.ne(0)
+        self.episode_index += sel.to(torch.int32)
+        self.sim.reset_envs(env_mask, seed=self._reset_key, mean=tuple(float(v) for v in self.spawn_mean), std=float(self.spawn_std),
+                            random_theta=False, random_velocity=False, resolve=True, env_offset=self.env_offset,
+                            episode=self.episode_index, objects=self._object_init, lights=self._light_init)
+        self.episode_returns.masked_fill_(sel, 0.0)
+        self.episode_steps.masked_fill_(sel, 0)
+        return self.sim.poses()
+
     def step(self, actions=None, light_action=None):
         """actions [E, N, 2] float32 tensor on the sim's device (None keeps the previous commands)."""
-        prev = self.sim.poses() if self.reward_fn is not None else None
+        prev = self.sim.poses() if self.reward_fn is not None or self.done_fn is not None else None
         self.sim.step(self.steps_per_action, actions=actions, light_action=light_action)
         obs = self.sim.poses()
         if self.reward_fn is not None:
@@ -219,7 +309,19 @@ class BatchedKilobotsEnv(object):
         if self._steps % self._status_interval == 0:
             self._check_status('step()')
         done = torch.zeros(self.num_envs, dtype=torch.bool, device=obs.device)
-        info = {} if self.neighbor_obs is None else {'neighbors': self.neighbors()}
+        info = {}
+        if self._episodes:
+            self.episode_steps += 1
+            if self.done_fn is not None:
+                done = done | self.done_fn(prev, actions, obs)
+            if self.max_episode_steps is not None:
+                done = done | (self.episode_steps >= self.max_episode_steps)
+            info['episode_return'], info['episode_length'] = self.episode_returns.clone(), self.episode_steps.clone()
+            if self.auto_reset:     # before the observations are taken: they describe the new episode
+                info['terminal_obs'] = obs
+                obs = self.reset_envs(done)
+        if self.neighbor_obs is not None:
+            info['neighbors'] = self.neighbors()
         if self.histogram_obs is not None:
             info['neighbor_histogram'] = self.neighbor_histogram()
         if self.object_obs:

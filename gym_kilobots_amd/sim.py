@@ -541,9 +541,58 @@ class KilobotSim:
         with torch.cuda.device(self.device):    # the launch goes to the CURRENT HIP device: make it the sim's
             nat.check(self._lib.kb_set_actions(self._h, p, self._stream()), 'kb_set_actions')
 
-    def step(self, n_substeps=1, actions=None, light_action=None, flags=0):
-        """n_substeps iterations of the reference substep loop in one kernel launch (asynchronous)."""
+    def step(self, n_substeps=1, actions=None, light_action=None, flags=0, env_mask=None):
+        """n_substeps iterations of the reference substep loop in one kernel launch (asynchronous).
+        env_mask: [E] bool or uint8 tensor on the sim's device: only the envs it selects are stepped (kb_step_envs); of the
+        others no byte of any state tensor changes, the fused actions included.  None: every env (kb_step)."""
         pa = self._ptr(actions, (self.num_envs, self.num_bots, 2), 'actions')
         pl = self._ptr(light_action, (self.num_envs, self._lib.kb_light_action_dim(self._h)), 'light_action')
         with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_step(self._h, pa, pl, int(n_substeps), int(flags), self._stream()), 'kb_step')
+            if env_mask is None:
+                nat.check(self._lib.kb_step(self._h, pa, pl, int(n_substeps), int(flags), self._stream()), 'kb_step')
+            else:
+                nat.check(self._lib.kb_step_envs(self._h, self._mask_ptr(env_mask), pa, pl, int(n_substeps), int(flags), self._stream()),
+                          'kb_step_envs')
+
+    def _mask_ptr(self, env_mask):
+        if not (torch.is_tensor(env_mask) and env_mask.is_cuda and env_mask.dtype in (torch.bool, torch.uint8) and env_mask.is_contiguous()
+                and tuple(env_mask.shape) == (self.num_envs,)):
+            raise ValueError('env_mask must be a contiguous bool or uint8 cuda tensor of shape %s' % ((self.num_envs,),))
+        if env_mask.device != self.device:
+            raise ValueError('env_mask lives on %s, the simulator on %s' % (env_mask.device, self.device))
+        return C.c_void_p(env_mask.data_ptr())
+
+    def reset_envs(self, env_mask, seed=0, mean=(0.0, 0.0), std=0.1, random_theta=False, random_velocity=False, resolve=True, env_offset=0,
+                   episode=None, objects=None, lights=None, light_vel=None):
+        """KilobotsEnv.reset of the envs env_mask selects ([E] bool or uint8 on the sim's device), on the device and without a
+        host synchronisation (kb_reset_envs): the spawn of reset() for those envs, then the step to resolve for them alone.  Of
+        the other envs no byte of any state tensor changes.
+        episode: [E] int32 -- word z of the Philox counter (env_offset + env, bot, z, 0) of every env; None: 0, the draw of
+        reset().  Counting the episodes of every env there gives each of its episodes a spawn of its own.
+        objects: [E, M, 3] float32 (ox, oy in world units as stored, otheta): the selected envs' objects are put there at rest.
+        lights, light_vel: [E, L, 2] float32 (or [E, 2] with one light): light_x, light_y and light_vx, light_vy of the selected
+        envs; with lights alone the velocities are zeroed.  All tensors contiguous and on the sim's device."""
+        E, M = self.num_envs, self.num_objects
+        rp = nat.KbResetParams()
+        rp.seed, rp.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
+        rp.mean[0], rp.mean[1], rp.std = float(mean[0]), float(mean[1]), float(std)
+        rp.random_theta, rp.random_velocity, rp.resolve = int(bool(random_theta)), int(bool(random_velocity)), int(bool(resolve))
+        init = nat.KbEpisodeInit()
+        if episode is not None:
+            if not (torch.is_tensor(episode) and episode.is_cuda and episode.dtype in (torch.int32, getattr(torch, 'uint32', torch.int32))
+                    and episode.is_contiguous() and tuple(episode.shape) == (E,)):
+                raise ValueError('episode must be a contiguous int32 cuda tensor of shape %s' % ((E,),))
+            if episode.device != self.device:
+                raise ValueError('episode lives on %s, the simulator on %s' % (episode.device, self.device))
+            init.d_episode = episode.data_ptr()
+        if objects is not None:
+            if M == 0:
+                raise ValueError('objects given, but the sim has no objects')
+            init.d_obj_pose = self._ptr(objects, (E, M, 3), 'objects')
+        if (lights is not None or light_vel is not None) and self.light_x is None:
+            raise ValueError('lights / light_vel given, but the sim has no light')
+        for name, t in (('lights', lights), ('light_vel', light_vel)):
+            if t is not None:
+                setattr(init, 'd_light_pos' if name == 'lights' else 'd_light_vel', self._ptr(t, tuple(self.light_x.shape) + (2,), name))
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_reset_envs(self._h, C.byref(rp), self._mask_ptr(env_mask), C.byref(init), self._stream()), 'kb_reset_envs')

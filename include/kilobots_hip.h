@@ -223,6 +223,20 @@ int kb_set_actions(kb_sim *sim, const float *d_actions, void *stream);
 int kb_step(kb_sim *sim, const float *d_actions, const float *d_light_action, int n_substeps, int flags,
             void *stream);
 
+/* kb_step for the envs a mask selects; the others stay frozen (evaluation with finished envs, the resolve step of
+ * kb_reset_envs).  d_env_mask: [num_envs] bytes in device memory, non-zero = selected (a bool tensor as it stands).
+ *   - A selected env is stepped exactly as kb_step steps it, the fused d_actions included.
+ *   - For an unselected env NO BYTE of any bound buffer changes: poses, commands (the fused set_action does not reach it), the
+ *     warm-start store, sleep_time, nbr_count, status, the light state, the debug outputs.  kb_buffers.scratch is transient by
+ *     contract and excluded.
+ *   - The mask is read once, at the start of the launch, also when n_substeps > 1: the workgroup of an unselected env leaves
+ *     before it has read or written anything else.
+ *   - One launch of the handle's own instantiation on the same grid; kb_step is this call without a mask.
+ * Argument checks in this order: NULL sim or NULL mask -> KB_EINVAL;  an unbound handle -> KB_ENOTBOUND;  then those of
+ * kb_step.  Asynchronous on `stream`. */
+int kb_step_envs(kb_sim *sim, const uint8_t *d_env_mask, const float *d_actions, const float *d_light_action, int n_substeps,
+                 int flags, void *stream);
+
 /* IR-range neighbour sensing on the CURRENT poses, without stepping (e.g. right after a reset): d_count
  * [num_envs][num_bots] uint32 = number of kilobots j != i of the same env with |p_j - p_i|^2 <= (25 radius_m)^2.
  * The same predicate kb_step evaluates at the sensing point of every substep when kb_config.sense_radius > 0.
@@ -596,6 +610,30 @@ typedef struct kb_reset_params {
     int32_t resolve;
 } kb_reset_params;
 int kb_reset(kb_sim *sim, const kb_reset_params *rp, void *stream);
+
+/* KilobotsEnv.reset() for the envs a mask selects, on the device: one env ends its episode and starts the next while the
+ * others run on.  d_env_mask as for kb_step_envs.  For a selected env e:
+ *   - exactly the writes kb_reset makes to the rows of env e, with the Philox counter (env_offset + e, bot, z, 0),
+ *     z = d_episode[e], or 0 when d_episode (or init) is NULL: then the rows equal those of a full kb_reset with the same rp
+ *     bit for bit.  A caller that counts the episodes of every env in d_episode makes the j-th episode of global env e a pure
+ *     function of (seed, e, j), whenever the other envs end and however the batch is sharded;
+ *   - d_obj_pose: ox, oy, otheta are copied bitwise, ovx, ovy, ow set to 0, osleep to 0 when bound (Body.__init__,
+ *     body.py:32-38); the env's ows_acc is forgotten as kb_reset already does;
+ *   - d_light_pos: light_x, light_y are copied; light_vx, light_vy come from d_light_vel, or are 0 when that is NULL and the
+ *     buffers are bound.  (d_light_vel alone sets the velocities only.)
+ *   - rp->resolve != 0 appends kb_step_envs(sim, d_env_mask, NULL, NULL, 1, KB_STEP_NO_DRIVE, stream): at most two launches.
+ * For an unselected env no byte of any bound buffer changes (kb_buffers.scratch excluded, as for kb_step_envs).
+ * Argument checks in this order: NULL sim, rp or mask -> KB_EINVAL;  std not >= 0 -> KB_EINVAL;  d_obj_pose on a handle with
+ * num_objects == 0, d_light_pos or d_light_vel on a handle without a light -> KB_EINVAL;  an unbound handle -> KB_ENOTBOUND.
+ * Random object and light placement is the caller's: it supplies per-env templates, which it can randomise in torch. */
+typedef struct kb_episode_init {            /* every member optional (NULL) */
+    const uint32_t *d_episode;   /* [num_envs]: word z of the Philox counter of env e; NULL = 0 (the draw of kb_reset) */
+    const float *d_obj_pose;     /* [num_envs][num_objects][3]: ox, oy (world units, as stored), otheta */
+    const float *d_light_pos;    /* [num_envs][kb_light_count()][2]: light_x, light_y as stored (GradientLight: angle in [0]) */
+    const float *d_light_vel;    /* [num_envs][kb_light_count()][2]: light_vx, light_vy */
+} kb_episode_init;
+int kb_reset_envs(kb_sim *sim, const kb_reset_params *rp, const uint8_t *d_env_mask,
+                  const kb_episode_init *init /* may be NULL */, void *stream);
 
 /* KilobotsEnv.get_state()['kilobots'] (kilobots_env.py:115-118 -> body.py:63-72):
  * d_out [num_envs][num_bots][3] = (x [m], y [m], theta). */
