@@ -23,6 +23,7 @@ MAX_NEIGHBORS = 16     # KB_MAX_NEIGHBORS: slots per kilobot of kb_sense_neighbo
 HIST_MAX_RINGS, HIST_MAX_SECTORS, HIST_MAX_BINS = 8, 16, 64     # KB_HIST_MAX_*: bin grid of kb_sense_histogram
 REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = range(3)     # kb_reduce_op: how kb_sense_reduce combines the messages heard
 REDUCE_MAX_CHANNELS = 8     # KB_REDUCE_MAX_CHANNELS: floats per message of kb_sense_reduce
+HOPS_UNLIMITED = MAX_BOTS     # KB_HOPS_UNLIMITED: the max_hops of kb_sense_hops that cuts nothing
 GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_sense_grid, a bit each
 MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense_contacts
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
@@ -104,7 +105,7 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset', 'kb_step_envs', 'kb_reset_envs',
+EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_sense_hops', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset', 'kb_step_envs', 'kb_reset_envs',
            'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
            'kb_last_error', 'kb_version']
 
@@ -167,6 +168,8 @@ def load():
     lib.kb_histogram_sectors.restype = C.c_int
     lib.kb_sense_reduce.argtypes = [_P, C.c_float, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]
     lib.kb_sense_reduce.restype = C.c_int
+    lib.kb_sense_hops.argtypes = [_P, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]
+    lib.kb_sense_hops.restype = C.c_int
     lib.kb_get_outline.argtypes = [_P, C.POINTER(KbOutline)]
     lib.kb_get_outline.restype = C.c_int
     lib.kb_sense_objects.argtypes = [_P, _P, _P, _P]

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -798,6 +798,20 @@ int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float s
     hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ReduceLds(p.NP, p.ncell, CP).bytes, (hipStream_t)stream, p, r.reach, r.R2, n_channels, vec,
                        scale, d_values, d_out, d_count);
     return launched("kb_sense_reduce");
+}
+
+int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_hops, int32_t *d_hops, int32_t *d_parent, int32_t *d_root,
+                  int32_t *d_stats, void *stream) {
+    if (!sim || !d_seed || !d_hops) return fail(KB_EINVAL, "kb_sense_hops: NULL argument");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_hops: radius must be positive");
+    if (max_hops < 0) return fail(KB_EINVAL, "kb_sense_hops: max_hops must not be negative");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_hops: kb_bind() first");
+    const Params &p = sim->p;
+    const SenseRange r = sense_range(p, radius_m);
+    const int lim = max_hops < p.N - 1 ? max_hops : p.N - 1;       // no path has more than N - 1 edges: the level loop's bound
+    hipLaunchKernelGGL(kb_hops_kernel, dim3((unsigned)p.E), dim3(256), (size_t)HopsLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, lim,
+                       d_seed, d_hops, d_parent, d_root, d_stats);
+    return launched("kb_sense_hops");
 }
 
 int kb_ray_directions(int n_rays, float *xy) {

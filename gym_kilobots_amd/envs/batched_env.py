@@ -30,7 +30,8 @@ class BatchedKilobotsEnv(object):
         distance and bearing in the kilobot's own frame (KilobotSim.neighbor_histogram): neighbor_histogram() returns it,
         step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing.
         comm_radius: the IR range in metres over which neighbor_reduce(values) aggregates what the kilobots broadcast
-        (KilobotSim.neighbor_reduce).  reset() and step() do not change with it.
+        (KilobotSim.neighbor_reduce) and over which hops(seeds) forms hop-count gradients (KilobotSim.hops).  reset() and
+        step() do not change with it.
         object_obs: True adds what a kilobot sees of the objects and the walls: object_points() returns the nearest point of
         every object and of the arena walls in every kilobot's own frame (KilobotSim.object_points), and step() puts them in
         its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added.
@@ -404,6 +405,13 @@ class BatchedKilobotsEnv(object):
         if self.comm_radius is None:
             raise ValueError('create the env with comm_radius=radius_m to aggregate messages')
         return self.sim.neighbor_reduce(values, self.comm_radius, op=op, scale=scale, count=count)
+
+    def hops(self, seeds, max_hops=None, parent=False, root=False, stats=False):
+        """The hop-count gradient of every kilobot to the nearest of `seeds` ([E, N] bool or uint8 on the device) over the
+        comm_radius the env was created with: KilobotSim.hops."""
+        if self.comm_radius is None:
+            raise ValueError('create the env with comm_radius=radius_m to form hop-count gradients')
+        return self.sim.hops(seeds, self.comm_radius, max_hops=max_hops, parent=parent, root=root, stats=stats)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

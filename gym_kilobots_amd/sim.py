@@ -357,6 +357,38 @@ class KilobotSim:
                                                 C.c_void_p(out[0].data_ptr()), pc, self._stream()), 'kb_sense_reduce')
         return (out[0], out[1]) if count else out[0]
 
+    def hops(self, seeds, radius_m, max_hops=None, parent=False, root=False, stats=False, out=None):
+        """Hop-count gradients on the current poses (kb_sense_hops; no reference counterpart): for every kilobot the number of
+        IR hops (edges of the graph of the kilobots within radius_m, centre to centre) to the nearest seed of its env, by one
+        breadth-first search per env in one launch.  seeds: [E, N] bool or uint8, contiguous, on the sim's device; non-zero =
+        seed.  Returns hops [E, N] int32: 0 at a seed, -1 where no seed is reachable within max_hops (None: no limit).
+        parent=True adds parent [E, N] int32, the LOWEST-indexed neighbour one hop closer (-1 at seeds and where hops is -1);
+        root=True root [E, N] int32, the seed at the end of the parent chain (-1 where hops is -1); stats=True stats [E, 2]
+        int32 = (kilobots reached, seeds included; deepest hop, -1 without a seed).  With any of them the result is the tuple
+        (hops, parent, root, stats) of the ones asked for.  out: the preallocated contiguous tensor(s) to write into, in the
+        shape of the result."""
+        E, N = self.num_envs, self.num_bots
+        if not (torch.is_tensor(seeds) and seeds.is_cuda and seeds.dtype in (torch.bool, torch.uint8) and seeds.is_contiguous()
+                and tuple(seeds.shape) == (E, N)):
+            raise ValueError('seeds must be a contiguous bool or uint8 cuda tensor of shape %s' % ((E, N),))
+        if seeds.device != self.device:
+            raise ValueError('seeds lives on %s, the simulator on %s' % (seeds.device, self.device))
+        if not float(radius_m) > 0.0:
+            raise ValueError('radius_m must be positive')
+        if max_hops is None:
+            max_hops = nat.HOPS_UNLIMITED
+        if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or max_hops < 0:
+            raise ValueError('max_hops must be a non-negative int or None')
+        wanted = [True, bool(parent), bool(root), bool(stats)]
+        shapes = [s for s, w in zip([((E, N), torch.int32, 'hops'), ((E, N), torch.int32, 'parent'), ((E, N), torch.int32, 'root'),
+                                     ((E, 2), torch.int32, 'stats')], wanted) if w]
+        out = list(self._outputs(out, shapes, 'the hops tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
+        ptrs = [C.c_void_p(out[sum(wanted[:i])].data_ptr()) if w else None for i, w in enumerate(wanted)]
+        with torch.cuda.device(self.device):
+            nat.check(self._lib.kb_sense_hops(self._h, float(radius_m), C.c_void_p(seeds.data_ptr()), min(int(max_hops), nat.HOPS_UNLIMITED),
+                                              ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()), 'kb_sense_hops')
+        return tuple(out) if len(out) > 1 else out[0]
+
     def outline(self):
         """The geometry object_points() reads (kb_get_outline) as a KbOutline: the arena bounds and the fixtures grouped by
         body in stable order -- the order that decides ties -- in world units."""

@@ -355,6 +355,36 @@ enum kb_reduce_op { KB_REDUCE_SUM = 0, KB_REDUCE_MIN = 1, KB_REDUCE_MAX = 2 };
 int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float scale, const float *d_values, float *d_out,
                     uint32_t *d_count, void *stream);
 
+/* Hop-count gradients on the CURRENT poses, without stepping: for every kilobot the number of IR hops to the nearest seed of
+ * its env -- the quantity behind self-assembly, leader election, routing and the question whether the swarm is connected --
+ * settled by one breadth-first search per env in ONE launch, instead of one kb_sense_reduce(min) sweep per hop.  Every env is
+ * searched independently.  No reference counterpart.  All results are integers; the only float arithmetic is the predicate:
+ *   Graph: as kb_sense -- Rw = radius_m * 25, R2 = Rw * Rw (on the host);  ex = x_j - x_i, ey = y_j - y_i,
+ *     d2 = ex * ex + ey * ey (each one fp32 operation rounded on its own);  j is a neighbour of i iff j != i && !(d2 > R2).
+ *     The relation is symmetric bit for bit.  Poses are assumed finite, as everywhere else.
+ * d_seed   [num_envs][num_bots] uint8 in device memory: non-zero = seed (the convention of d_env_mask; a bool tensor works
+ *          as it stands).
+ * d_hops   [num_envs][num_bots] int32: 0 for a seed; for any other kilobot the least number of edges on a path to any seed
+ *          of its env if that number is <= max_hops; otherwise -1 (unreachable, or cut by max_hops).
+ * d_parent [num_envs][num_bots] int32 or NULL: -1 for seeds and for kilobots with hops -1; otherwise the LOWEST index j
+ *          within the env that is a neighbour of i and has hops[j] == hops[i] - 1.  Nothing else decides it: not the order
+ *          of the cell lists and not the order in which the search reaches i.
+ * d_root   [num_envs][num_bots] int32 or NULL: a seed gets its own index, a reached kilobot root[parent[i]] -- the seed at
+ *          the end of its parent chain, i.e. the graph-Voronoi assignment to the seeds with ties resolved by the parent
+ *          rule; -1 where hops is -1.
+ * d_stats  [num_envs][2] int32 or NULL: word 0 the number of kilobots with hops >= 0 (seeds included), word 1 the largest
+ *          value in the env's hops, -1 when the env has no seed.  With one seed, stats[0] == num_bots says: connected.
+ * max_hops >= 0: with 0 only the seeds are reached; any value >= num_bots - 1 cuts nothing, and KB_HOPS_UNLIMITED is the
+ *          spelled-out way to ask for that.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_seed / d_hops;  radius_m not > 0;
+ * max_hops < 0.  Then KB_ENOTBOUND.  A radius beyond the arena is fine (the reach clamps to the grid).
+ * Reads x, y and d_seed; writes only the outputs that were given, every element of each on every call, by plain stores.
+ * The result of an env does not depend on the other envs: a shard reproduces its rows.  One launch.  Asynchronous on
+ * `stream`. */
+#define KB_HOPS_UNLIMITED KB_MAX_BOTS
+int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_hops, int32_t *d_hops, int32_t *d_parent,
+                  int32_t *d_root, int32_t *d_stats, void *stream);
+
 /* Object and wall points on the CURRENT poses, without stepping: for every kilobot i and every pushable object m of its env
  * the nearest point of the object's outline in the body frame of i, and the nearest point of the arena walls -- what a
  * decentralised policy sees of the thing it pushes and of what confines it.  Rows are fixed-size, one per object, in object
