@@ -106,7 +106,7 @@ class KbBuffers(C.Structure):
 
 
 EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_sense_hops', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset', 'kb_step_envs', 'kb_reset_envs',
-           'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest',
+           'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest', 'kb_debug_lds',
            'kb_last_error', 'kb_version']
 
 _lib = None
@@ -206,6 +206,10 @@ def load():
     lib.kb_scratch_bytes.restype = C.c_size_t
     lib.kb_exact_selftest.argtypes = [_P, _P, _P]
     lib.kb_exact_selftest.restype = C.c_int
+    # (as above: an older build selected by KB_HIP_LIB has not got the test entry)
+    if hasattr(lib, 'kb_debug_lds') or LIB_PATH == os.path.join(HERE, 'libkilobots_hip.so'):
+        lib.kb_debug_lds.argtypes = [C.c_int, C.c_uint32, _P, _P]
+        lib.kb_debug_lds.restype = C.c_int
     lib.kb_set_block_threads.argtypes = [_P, C.c_int]
     lib.kb_set_block_threads.restype = C.c_int
     lib.kb_last_error.argtypes = []

@@ -257,6 +257,32 @@ __global__ void __launch_bounds__(256) kb_exact_selftest_kernel(float kbb, float
     if (threadIdx.x < 6 && sh[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)sh[threadIdx.x]);
 }
 
+// Test entry kb_debug_lds: fills (mode 0) or inspects (mode 1) the whole LDS of the CUs, so that a test can run the other
+// kernels over LDS that something else has written.  One workgroup takes all 160 KiB of a CU as dynamic LDS (no static LDS
+// here: it would not fit beside them).  Mode 1 stores nothing: count[0] += words equal to `word`, count[1] += words looked at.
+constexpr unsigned DEBUG_LDS_WORDS = (unsigned)LDS_CU / 4u, DEBUG_LDS_THREADS = 256u;
+__global__ void __launch_bounds__(256) kb_debug_lds_kernel(int mode, unsigned word, unsigned long long *count) {
+    extern __shared__ unsigned kb_debug_lds_words[];
+    volatile unsigned *lds = kb_debug_lds_words;
+    if (mode == 0) {
+        for (unsigned i = threadIdx.x; i < DEBUG_LDS_WORDS; i += DEBUG_LDS_THREADS) lds[i] = word;
+        return;
+    }
+    unsigned hit = 0u, seen = 0u;
+    for (unsigned i = threadIdx.x; i < DEBUG_LDS_WORDS; i += DEBUG_LDS_THREADS) {
+        hit += lds[i] == word;
+        ++seen;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        hit += __shfl_down(hit, o);
+        seen += __shfl_down(seen, o);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        atomicAdd(&count[0], (unsigned long long)hit);
+        atomicAdd(&count[1], (unsigned long long)seen);
+    }
+}
+
 thread_local char g_err[512] = "";
 
 float kb_clampf_host(float a, float lo, float hi) { return fmaxf(lo, fminf(a, hi)); }
@@ -1099,6 +1125,19 @@ int kb_exact_selftest(const kb_sim *sim, unsigned long long *d_counts, void *str
     if (hipMemsetAsync(d_counts, 0, 6 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return launched("kb_exact_selftest");
     hipLaunchKernelGGL(kb_exact_selftest_kernel, dim3(1u << 16), dim3(256), 0, (hipStream_t)stream, kbb, kwb, d_counts);
     return launched("kb_exact_selftest");
+}
+
+int kb_debug_lds(int mode, uint32_t word, unsigned long long *d_count, void *stream) {
+    if (mode != 0 && mode != 1) return fail(KB_EINVAL, "kb_debug_lds: mode must be 0 (fill) or 1 (count)");
+    if (mode == 1 && !d_count) return fail(KB_EINVAL, "kb_debug_lds: mode 1 needs d_count");
+    int device = 0, cus = 0;
+    hipError_t err = hipGetDevice(&device);
+    if (err == hipSuccess) err = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void *>(kb_debug_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
+    if (err != hipSuccess || cus <= 0) return fail(KB_EHIP, "kb_debug_lds: %s", hipGetErrorString(err));
+    if (mode == 1 && hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) return launched("kb_debug_lds");
+    hipLaunchKernelGGL(kb_debug_lds_kernel, dim3(2u * (unsigned)cus), dim3(DEBUG_LDS_THREADS), (size_t)LDS_CU, (hipStream_t)stream, mode, (unsigned)word, d_count);
+    return launched("kb_debug_lds");
 }
 
 int kb_contact_capacity(const kb_sim *sim) { return sim ? sim->p.cap : KB_EINVAL; }

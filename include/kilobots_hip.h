@@ -169,7 +169,9 @@ typedef struct kb_buffers {
     float *light_vx, *light_vy;         /* [num_envs][kb_light_count()] MomentumLight velocity (light.py:284-287) */
     float *ox, *oy, *otheta, *ovx, *ovy, *ow; /* objects: [num_envs][num_objects] pose (world units, radians) and body velocity */
     /* warm-start store (Box2D keeps the accumulated normal impulse in each b2Contact): per env a packed
-     * list of kb_contact_capacity() entries, owner bots ascending, ws_cnt[bot] entries per owner */
+     * list of kb_contact_capacity() entries, owner bots ascending, ws_cnt[bot] entries per owner.  The tail of the list, the
+     * positions from min(sum of ws_cnt[env], kb_contact_capacity()) on, means nothing: no entry point ever reads it, and
+     * whatever it holds changes no result */
     uint32_t *ws_key;                   /* required: [num_envs][kb_contact_capacity()] */
     float *ws_acc;                      /* required: [num_envs][kb_contact_capacity()] */
     uint8_t *ws_cnt;                    /* required: [num_envs][num_bots]; zero it to forget all contacts */
@@ -187,7 +189,9 @@ typedef struct kb_buffers {
                                            half of kb_lds_staging_entries() in the kernels with objects or mixed drive laws (the
                                            continuous step is skipped for the rest) */
     void *scratch;                      /* required: kb_scratch_bytes() bytes; contact staging of envs whose
-                                           contacts do not fit the LDS staging area (contents are transient) */
+                                           contacts do not fit the LDS staging area (contents are transient: no launch
+                                           reads a byte of it that the same launch has not written before, so it
+                                           carries nothing from launch to launch and may hold anything) */
     float *ows_acc;                     /* objects: [num_envs][8][KB_OWS_COLS][KB_OWS_WORDS] manifold impulses of the
                                            object-object (column = higher partner) and object-wall (column 8 + wall)
                                            contacts: b2ManifoldPoint id / normalImpulse / tangentImpulse; fill with -1
@@ -699,6 +703,12 @@ int kb_exact_selftest(const kb_sim *sim, unsigned long long *d_counts, void *str
                                                    handle's two K) with the device's own seed instructions against the compiler's IEEE sequences
                                                    over all 2^32 bit patterns.  d_counts (device, 6 words): per form the operands inside its
                                                    guard and the results that differ in a bit */
+int kb_debug_lds(int mode, uint32_t word, unsigned long long *d_count, void *stream);
+                                                /* for tests: one small kernel on twice as many workgroups as the current device has CUs, each
+                                                   with the full 160 KiB of LDS.  mode 0 stores `word` into every LDS word (d_count unused, may be
+                                                   NULL); mode 1 stores nothing and counts into d_count[0] (device, 2 words, zeroed first) the LDS
+                                                   words equal to `word`, into d_count[1] the words looked at: what a kernel finds of its
+                                                   predecessor's LDS.  Another mode, or mode 1 without d_count -> KB_EINVAL.  Asynchronous */
 int kb_resident_envs_per_cu(kb_sim *sim);        /* workgroups (= envs) of this handle's kernel that one CU holds at a time (HIP occupancy query; needs a GPU) */
 int kb_set_block_threads(kb_sim *sim, int threads);  /* multiple of 64 in [64, 512], num_bots <= 2 * threads.  kb_create picks
                                                          the measured best (one kilobot per thread, power-of-two wave count,

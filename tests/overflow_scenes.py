@@ -150,15 +150,20 @@ def plan_inputs(r):
     return [r.N, r.objects, r.objects, int(r.objects > 0 and r.shape is None), r.mode, O.LIGHT_NONE, 0, r.allow_sleep, NCELL, r.capacity, r.threads]
 
 
-def start(r):
-    """(xy [E, N, 2], th [E, N]) in metres / radians"""
+def start(r, order=None, seed_shift=0):
+    """(xy [E, N, 2], th [E, N]) in metres / radians.  order: a permutation of the envs -- env i of the result is env order[i]
+    of the row (tests/test_state_isolation_gpu.py puts the overflowing env first and last); None: the row's own order.
+    seed_shift: added to both spawn seeds -- the twin scene of tests/guarded.py."""
     pitches = {p for kind, p in r.spawn if kind == 'lattice'}
     assert len(pitches) == 1
-    xy, th = scenes.lattice_spawn(E, r.N, seed=LATTICE_SEED, pitch=pitches.pop(), jitter=JITTER)
+    xy, th = scenes.lattice_spawn(E, r.N, seed=LATTICE_SEED + seed_shift, pitch=pitches.pop(), jitter=JITTER)
     for e, (kind, sigma) in enumerate(r.spawn):
         if kind == 'gauss':
-            gxy, gth = scenes.gaussian_spawn(1, r.N, sigma, seed=GAUSS_SEED)
+            gxy, gth = scenes.gaussian_spawn(1, r.N, sigma, seed=GAUSS_SEED + seed_shift)
             xy[e], th[e] = gxy[0], gth[0]
+    if order is not None:
+        assert sorted(order) == list(range(E))
+        xy, th = xy[list(order)], th[list(order)]
     return xy, th
 
 

@@ -97,8 +97,9 @@ def plan_inputs(N, capacity, allow_sleep):
     return [N, 0, 0, 0, O.DRIVE_VELOCITY, O.LIGHT_NONE, 0, allow_sleep, NCELL, capacity, 0]
 
 
-def start(s, E):
-    return scenes.lattice_spawn(E, s.N, SEED, s.pitch, jitter=JITTER)
+def start(s, E, seed=SEED):
+    """seed: another one gives the twin scene of tests/guarded.py -- the same lattice with other jitter and headings"""
+    return scenes.lattice_spawn(E, s.N, seed, s.pitch, jitter=JITTER)
 
 
 def actions(E, N, k):

@@ -95,6 +95,18 @@ def test_create_validates_and_reports(lib):
     assert lib.kb_create(C.byref(cfg), C.byref(h)) == nat.KB_EINVAL
 
 
+def test_debug_lds_checks_its_arguments(lib):
+    """kb_debug_lds answers KB_EINVAL, with a message, before it touches a device: an unknown mode; counting without a
+    place for the counts."""
+    one = C.c_uint64(0)
+    for mode in (-1, 2, 7):
+        assert lib.kb_debug_lds(mode, 1, C.byref(one), None) == nat.KB_EINVAL, mode
+        assert b'kb_debug_lds' in lib.kb_last_error() and b'mode' in lib.kb_last_error()
+    assert lib.kb_debug_lds(1, 1, None, None) == nat.KB_EINVAL
+    assert b'd_count' in lib.kb_last_error()
+    assert one.value == 0
+
+
 def test_largest_config_fits_lds(lib):
     h = C.c_void_p()
     cfg = nat.default_config(4096, 1024)

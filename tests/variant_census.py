@@ -127,6 +127,14 @@ def _light_kw(light, resting):
     return {}
 
 
+def spawn(N, seed_shift=0):
+    """The poses of every row with N kilobots; seed_shift != 0: the twin scene of tests/guarded.py, the same spawn rule with
+    another seed."""
+    if N == 1024:
+        return scenes.lattice_spawn(E, N, seed=7 + seed_shift)
+    return scenes.gaussian_spawn(E, N, sigma=0.05 + 0.0004 * N, seed=N + seed_shift)
+
+
 def scene(row):
     """Everything a run of one census row needs:
       E, N, mode, light, kw     arguments of tests.test_parity_gpu.make_pair / oracle.default_config
@@ -161,10 +169,7 @@ def scene(row):
             s.ovx[:, 1] = 0.0
             s.objects_sleep = bool(allow_sleep)
     s.kw = kw
-    if N == 1024:
-        s.xy, s.th = scenes.lattice_spawn(E, N, seed=7)
-    else:
-        s.xy, s.th = scenes.gaussian_spawn(E, N, sigma=0.05 + 0.0004 * N, seed=N)
+    s.xy, s.th = spawn(N)
 
     # state before the first substep
     if mode in (O.DRIVE_MOTORS, O.DRIVE_MIXED):
