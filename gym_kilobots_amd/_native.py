@@ -105,9 +105,57 @@ class KbBuffers(C.Structure):
     _fields_ = [(n, _P) for n in BUFFER_FIELDS]
 
 
-EXPORTS = ['kb_create', 'kb_destroy', 'kb_bind', 'kb_set_actions', 'kb_step', 'kb_get_poses', 'kb_get_state', 'kb_sense', 'kb_sense_neighbors', 'kb_sense_edges', 'kb_sense_histogram', 'kb_histogram_sectors', 'kb_sense_reduce', 'kb_sense_hops', 'kb_get_outline', 'kb_sense_objects', 'kb_grid_channels', 'kb_sense_grid', 'kb_sense_contacts', 'kb_render_default_style', 'kb_render', 'kb_ray_directions', 'kb_sense_rays', 'kb_light_sense', 'kb_reset', 'kb_step_envs', 'kb_reset_envs',
-           'kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_scratch_bytes', 'kb_light_action_dim', 'kb_light_count', 'kb_block_threads', 'kb_variant_index', 'kb_set_block_threads', 'kb_exact_division', 'kb_exact_selftest', 'kb_debug_lds',
-           'kb_last_error', 'kb_version']
+_I, _F = C.c_int, C.c_float
+# every function include/kilobots_hip.h declares as (restype, argtypes): the one statement of the C ABI on this side, which
+# tests/test_abi_cpu.py holds against the header's prototypes
+SIGNATURES = {
+    'kb_create': (_I, [C.POINTER(KbConfig), _P]),
+    'kb_destroy': (None, [_P]),
+    'kb_bind': (_I, [_P, C.POINTER(KbBuffers)]),
+    'kb_set_actions': (_I, [_P, _P, _P]),
+    'kb_step': (_I, [_P, _P, _P, _I, _I, _P]),
+    'kb_get_poses': (_I, [_P, _P, _P]),
+    'kb_get_state': (_I, [_P, _P, _P]),
+    'kb_sense': (_I, [_P, _F, _P, _P]),
+    'kb_sense_neighbors': (_I, [_P, _F, _I, _P, _P, _P, _P]),
+    'kb_sense_edges': (_I, [_P, _F, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    'kb_sense_histogram': (_I, [_P, _F, _I, _I, _P, _P, _P]),
+    'kb_histogram_sectors': (_I, [_I, _P]),
+    'kb_sense_reduce': (_I, [_P, _F, _I, _I, _F, _P, _P, _P, _P]),
+    'kb_sense_hops': (_I, [_P, _F, _P, _I, _P, _P, _P, _P, _P]),
+    'kb_get_outline': (_I, [_P, C.POINTER(KbOutline)]),
+    'kb_sense_objects': (_I, [_P, _P, _P, _P]),
+    'kb_grid_channels': (_I, [_P, _I]),
+    'kb_sense_grid': (_I, [_P, _I, _I, _I, _P, _P]),
+    'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
+    'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
+    'kb_render': (_I, [_P, _I, _I, _I, C.POINTER(KbRenderStyle), _P, _P, _P, _P]),
+    'kb_ray_directions': (_I, [_I, _P]),
+    'kb_sense_rays': (_I, [_P, _F, _I, _I, _P, _P, _P]),
+    'kb_light_sense': (_I, [_P, _P, _P]),
+    'kb_reset': (_I, [_P, C.POINTER(KbResetParams), _P]),
+    'kb_step_envs': (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    'kb_reset_envs': (_I, [_P, C.POINTER(KbResetParams), _P, C.POINTER(KbEpisodeInit), _P]),
+    'kb_lds_bytes': (_I, [_P]),
+    'kb_resident_envs_per_cu': (_I, [_P]),
+    'kb_contact_capacity': (_I, [_P]),
+    'kb_lds_staging_entries': (_I, [_P]),
+    'kb_scratch_bytes': (C.c_size_t, [_P]),
+    'kb_light_action_dim': (_I, [_P]),
+    'kb_light_count': (_I, [_P]),
+    'kb_block_threads': (_I, [_P]),
+    'kb_variant_index': (_I, [_P]),
+    'kb_set_block_threads': (_I, [_P, _I]),
+    'kb_exact_division': (_I, [_P]),
+    'kb_exact_selftest': (_I, [_P, _P, _P]),
+    'kb_debug_lds': (_I, [_I, C.c_uint32, _P, _P]),
+    'kb_last_error': (C.c_char_p, []),
+    'kb_version': (C.c_char_p, []),
+}
+EXPORTS = list(SIGNATURES)
+# an older build of the library that KB_HIP_LIB selects for an A/B (tools/ab_bench.py) has not got these: it loads, and calling
+# one of them on it raises AttributeError
+OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds'}
 
 _lib = None
 
@@ -132,6 +180,16 @@ def describe_status(bits):
     return '; '.join(msg for b, msg in sorted(STATUS_BITS.items()) if bits & b) or 'ok'
 
 
+def report_status(mode, where, bits, envs=''):
+    """The end of every status check that found `bits` set: KilobotsStatusError for mode 'raise', otherwise a RuntimeWarning
+    charged to whoever called the method that checked.  envs: what the message says of how many envs are flagged."""
+    msg = '%sdevice step status 0x%x%s: %s' % (where and where + ': ', bits, envs, describe_status(bits))
+    if mode == 'raise':
+        raise KilobotsStatusError(msg)
+    import warnings
+    warnings.warn(msg, RuntimeWarning, stacklevel=4)
+
+
 def load():
     """dlopen the HIP library; fails loudly when it has not been built."""
     global _lib
@@ -142,80 +200,11 @@ def load():
             'libkilobots_hip.so is missing (%s). Build it with `python -m gym_kilobots_amd.build` '
             '(needs hipcc; cross-compiles for gfx950 without a GPU). There is no CPU fallback.' % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.kb_create.argtypes = [C.POINTER(KbConfig), C.POINTER(_P)]
-    lib.kb_create.restype = C.c_int
-    lib.kb_destroy.argtypes = [_P]
-    lib.kb_destroy.restype = None
-    lib.kb_bind.argtypes = [_P, C.POINTER(KbBuffers)]
-    lib.kb_bind.restype = C.c_int
-    lib.kb_set_actions.argtypes = [_P, _P, _P]
-    lib.kb_set_actions.restype = C.c_int
-    lib.kb_step.argtypes = [_P, _P, _P, C.c_int, C.c_int, _P]
-    lib.kb_step.restype = C.c_int
-    lib.kb_get_poses.argtypes = [_P, _P, _P]
-    lib.kb_get_poses.restype = C.c_int
-    lib.kb_get_state.argtypes = [_P, _P, _P]
-    lib.kb_get_state.restype = C.c_int
-    lib.kb_sense.argtypes = [_P, C.c_float, _P, _P]
-    lib.kb_sense.restype = C.c_int
-    lib.kb_sense_neighbors.argtypes = [_P, C.c_float, C.c_int, _P, _P, _P, _P]
-    lib.kb_sense_neighbors.restype = C.c_int
-    lib.kb_sense_edges.argtypes = [_P, C.c_float, _P, C.c_int64, _P, _P, _P, _P, _P]
-    lib.kb_sense_edges.restype = C.c_int
-    lib.kb_sense_histogram.argtypes = [_P, C.c_float, C.c_int, C.c_int, _P, _P, _P]
-    lib.kb_sense_histogram.restype = C.c_int
-    lib.kb_histogram_sectors.argtypes = [C.c_int, C.POINTER(C.c_float)]
-    lib.kb_histogram_sectors.restype = C.c_int
-    lib.kb_sense_reduce.argtypes = [_P, C.c_float, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P]
-    lib.kb_sense_reduce.restype = C.c_int
-    lib.kb_sense_hops.argtypes = [_P, C.c_float, _P, C.c_int, _P, _P, _P, _P, _P]
-    lib.kb_sense_hops.restype = C.c_int
-    lib.kb_get_outline.argtypes = [_P, C.POINTER(KbOutline)]
-    lib.kb_get_outline.restype = C.c_int
-    lib.kb_sense_objects.argtypes = [_P, _P, _P, _P]
-    lib.kb_sense_objects.restype = C.c_int
-    lib.kb_grid_channels.argtypes = [_P, C.c_int]
-    lib.kb_grid_channels.restype = C.c_int
-    lib.kb_sense_grid.argtypes = [_P, C.c_int, C.c_int, C.c_int, _P, _P]
-    lib.kb_sense_grid.restype = C.c_int
-    lib.kb_sense_contacts.argtypes = [_P, C.c_int, C.c_float, _P, _P, _P, _P, _P]
-    lib.kb_sense_contacts.restype = C.c_int
-    lib.kb_render_default_style.argtypes = [C.POINTER(KbRenderStyle)]
-    lib.kb_render_default_style.restype = C.c_int
-    lib.kb_render.argtypes = [_P, C.c_int, C.c_int, C.c_int, C.POINTER(KbRenderStyle), _P, _P, _P, _P]
-    lib.kb_render.restype = C.c_int
-    lib.kb_ray_directions.argtypes = [C.c_int, C.POINTER(C.c_float)]
-    lib.kb_ray_directions.restype = C.c_int
-    lib.kb_sense_rays.argtypes = [_P, C.c_float, C.c_int, C.c_int, _P, _P, _P]
-    lib.kb_sense_rays.restype = C.c_int
-    lib.kb_light_sense.argtypes = [_P, _P, _P]
-    lib.kb_light_sense.restype = C.c_int
-    lib.kb_reset.argtypes = [_P, C.POINTER(KbResetParams), _P]
-    lib.kb_reset.restype = C.c_int
-    # (an older build of the library that KB_HIP_LIB selects for an A/B, tools/ab_bench.py, has not got these two: it loads, and
-    #  calling one of them on it raises AttributeError)
-    if hasattr(lib, 'kb_step_envs') or LIB_PATH == os.path.join(HERE, 'libkilobots_hip.so'):
-        lib.kb_step_envs.argtypes = [_P, _P, _P, _P, C.c_int, C.c_int, _P]
-        lib.kb_step_envs.restype = C.c_int
-        lib.kb_reset_envs.argtypes = [_P, C.POINTER(KbResetParams), _P, C.POINTER(KbEpisodeInit), _P]
-        lib.kb_reset_envs.restype = C.c_int
-    for name in ('kb_lds_bytes', 'kb_resident_envs_per_cu', 'kb_contact_capacity', 'kb_lds_staging_entries', 'kb_block_threads', 'kb_variant_index', 'kb_light_action_dim', 'kb_light_count', 'kb_exact_division'):
-        getattr(lib, name).argtypes = [_P]
-        getattr(lib, name).restype = C.c_int
-    lib.kb_scratch_bytes.argtypes = [_P]
-    lib.kb_scratch_bytes.restype = C.c_size_t
-    lib.kb_exact_selftest.argtypes = [_P, _P, _P]
-    lib.kb_exact_selftest.restype = C.c_int
-    # (as above: an older build selected by KB_HIP_LIB has not got the test entry)
-    if hasattr(lib, 'kb_debug_lds') or LIB_PATH == os.path.join(HERE, 'libkilobots_hip.so'):
-        lib.kb_debug_lds.argtypes = [C.c_int, C.c_uint32, _P, _P]
-        lib.kb_debug_lds.restype = C.c_int
-    lib.kb_set_block_threads.argtypes = [_P, C.c_int]
-    lib.kb_set_block_threads.restype = C.c_int
-    lib.kb_last_error.argtypes = []
-    lib.kb_last_error.restype = C.c_char_p
-    lib.kb_version.argtypes = []
-    lib.kb_version.restype = C.c_char_p
+    own = LIB_PATH == os.path.join(HERE, 'libkilobots_hip.so')
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if own or name not in OPTIONAL or hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -224,6 +213,36 @@ def check(rc, what):
     if rc != KB_OK:
         msg = load().kb_last_error().decode('utf-8', 'replace')
         raise KilobotsHipError('%s failed (%d): %s' % (what, rc, msg))
+
+
+def call(lib, name, *args):
+    """lib.name(*args), checked under the entry's own name."""
+    check(getattr(lib, name)(*args), name)
+
+
+def check_radius(radius_m, name='radius_m'):
+    """A radius in metres as a float; ValueError unless it is positive."""
+    radius_m = float(radius_m)
+    if not radius_m > 0.0:
+        raise ValueError('%s must be positive' % name)
+    return radius_m
+
+
+def _mask(value, bits, what, prefix):
+    """An integer mask, a name or an iterable of names (the keys of `bits`) as a validated mask.  what: the argument's name,
+    prefix: that of the constants, for the messages."""
+    if isinstance(value, str):
+        value = (value,)
+    if not isinstance(value, int):
+        mask = 0
+        for name in value:
+            if name not in bits:
+                raise ValueError('%s must be a %s_* mask or made of %s and %r' % (what, prefix, ', '.join(map(repr, list(bits)[:-1])), list(bits)[-1]))
+            mask |= bits[name]
+        value = mask
+    if isinstance(value, bool) or value <= 0 or value & ~sum(bits.values()):
+        raise ValueError('%s must be a non-empty subset of %s' % (what, ' | '.join('%s_%s' % (prefix, name.upper()) for name in bits)))
+    return value
 
 
 def check_histogram_grid(n_rings, n_sectors):
@@ -268,18 +287,7 @@ def check_grid(width, height, planes):
     width, height = int(width), int(height)
     if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
         raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
-    if isinstance(planes, str):
-        planes = (planes,)
-    if not isinstance(planes, int):
-        mask = 0
-        for name in planes:
-            if name not in GRID_PLANES:
-                raise ValueError("planes must be a GRID_* mask or made of 'count', 'flow' and 'objects'")
-            mask |= GRID_PLANES[name]
-        planes = mask
-    if isinstance(planes, bool) or planes <= 0 or planes & ~(GRID_COUNT | GRID_FLOW | GRID_OBJECTS):
-        raise ValueError('planes must be a non-empty subset of GRID_COUNT | GRID_FLOW | GRID_OBJECTS')
-    return width, height, planes
+    return width, height, _mask(planes, GRID_PLANES, 'planes', 'GRID')
 
 
 RENDER_LAYERS = {'objects': RENDER_OBJECTS, 'bots': RENDER_BOTS, 'light': RENDER_LIGHT}
@@ -292,18 +300,7 @@ def check_render(width, height, layers):
     width, height = int(width), int(height)
     if not (1 <= width <= RENDER_MAX_SIDE and 1 <= height <= RENDER_MAX_SIDE):
         raise ValueError('width and height must be in 1..%d' % RENDER_MAX_SIDE)
-    if isinstance(layers, str):
-        layers = (layers,)
-    if not isinstance(layers, int):
-        mask = 0
-        for name in layers:
-            if name not in RENDER_LAYERS:
-                raise ValueError("layers must be a RENDER_* mask or made of 'objects', 'bots' and 'light'")
-            mask |= RENDER_LAYERS[name]
-        layers = mask
-    if isinstance(layers, bool) or layers <= 0 or layers & ~(RENDER_OBJECTS | RENDER_BOTS | RENDER_LIGHT):
-        raise ValueError('layers must be a non-empty subset of RENDER_OBJECTS | RENDER_BOTS | RENDER_LIGHT')
-    return width, height, layers
+    return width, height, _mask(layers, RENDER_LAYERS, 'layers', 'RENDER')
 
 
 def render_style(style=None):
@@ -311,7 +308,7 @@ def render_style(style=None):
     are (R, G, B) in 0..255, 'light_alpha' one such number, 'obj' a list of up to MAX_OBJECTS colours (the rest keep the
     default).  ValueError for an unknown key or a value outside a byte."""
     st = KbRenderStyle()
-    check(load().kb_render_default_style(C.byref(st)), 'kb_render_default_style')
+    call(load(), 'kb_render_default_style', C.byref(st))
 
     def colour(dst, v, key):
         v = [int(c) for c in v]
@@ -344,23 +341,10 @@ def check_rays(radius_m, n_rays, targets):
     """The limits of kb_sense_rays on the radius, the ray count and the targets (a RAY_* mask or an iterable of 'bots' |
     'objects' | 'walls'); ValueError where the library would answer KB_EINVAL -- but for 'objects' on a handle without
     objects, which only the handle knows.  Returns (radius_m, n_rays, targets as an integer mask)."""
-    radius_m, n_rays = float(radius_m), int(n_rays)
-    if not radius_m > 0.0:
-        raise ValueError('radius_m must be positive')
+    radius_m, n_rays = check_radius(radius_m), int(n_rays)
     if not 1 <= n_rays <= MAX_RAYS:
         raise ValueError('n_rays must be in 1..%d' % MAX_RAYS)
-    if isinstance(targets, str):
-        targets = (targets,)
-    if not isinstance(targets, int):
-        mask = 0
-        for name in targets:
-            if name not in RAY_TARGETS:
-                raise ValueError("targets must be a RAY_* mask or made of 'bots', 'objects' and 'walls'")
-            mask |= RAY_TARGETS[name]
-        targets = mask
-    if isinstance(targets, bool) or targets <= 0 or targets & ~(RAY_BOTS | RAY_OBJECTS | RAY_WALLS):
-        raise ValueError('targets must be a non-empty subset of RAY_BOTS | RAY_OBJECTS | RAY_WALLS')
-    return radius_m, n_rays, targets
+    return radius_m, n_rays, _mask(targets, RAY_TARGETS, 'targets', 'RAY')
 
 
 def ray_directions(n_rays):
@@ -368,16 +352,14 @@ def ray_directions(n_rays):
     floats in the kilobot's frame, ray 0 dead ahead, counter-clockwise; no handle and no device needed."""
     n = int(n_rays)
     buf = (C.c_float * (2 * max(min(n, MAX_RAYS), 1)))()
-    check(load().kb_ray_directions(n, buf), 'kb_ray_directions')
+    call(load(), 'kb_ray_directions', n, buf)
     return [(buf[2 * k], buf[2 * k + 1]) for k in range(n)]
 
 
 def check_edges(radius_m, capacity=None):
     """The limits of kb_sense_edges on the radius and the capacity (None: the caller sizes the outputs from the counts);
     ValueError where the library would answer KB_EINVAL.  Returns (radius_m, capacity)."""
-    radius_m = float(radius_m)
-    if not radius_m > 0.0:
-        raise ValueError('radius_m must be positive')
+    radius_m = check_radius(radius_m)
     if capacity is not None:
         if isinstance(capacity, bool) or int(capacity) != capacity:
             raise ValueError('capacity must be an integer or None')
@@ -421,7 +403,7 @@ def histogram_sectors(n_sectors):
     n = int(n_sectors)
     rows = max(n // 2 - 1, 0)
     buf = (C.c_float * (2 * max(rows, 1)))()
-    check(load().kb_histogram_sectors(n, buf), 'kb_histogram_sectors')
+    call(load(), 'kb_histogram_sectors', n, buf)
     return [(buf[2 * m], buf[2 * m + 1]) for m in range(rows)]
 
 
@@ -429,7 +411,7 @@ def outline(handle):
     """The geometry kb_sense_objects reads for a handle (kb_get_outline) as a KbOutline: the arena bounds and the fixtures
     grouped by body in stable order, world units; no device and no bound buffers needed."""
     o = KbOutline()
-    check(load().kb_get_outline(handle, C.byref(o)), 'kb_get_outline')
+    call(load(), 'kb_get_outline', handle, C.byref(o))
     return o
 
 

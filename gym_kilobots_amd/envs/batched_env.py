@@ -2,12 +2,84 @@
 
 Same semantics as DirectControlKilobotsEnv / KilobotsEnv per env, but observations stay on the
 device as torch tensors: poses [E, N, 3] (metres, radians), actions [E, N, 2]."""
+import collections
+
 import numpy as np
 import torch
 
 from .. import _native as nat
 from ..lib.kilobot import Kilobot
 from ..spaces import Box
+
+
+def _neighbor_obs(value, num_objects):
+    radius_m, k = value
+    if not float(radius_m) > 0.0 or not 1 <= int(k) <= nat.MAX_NEIGHBORS:
+        raise ValueError('neighbor_obs must be (radius_m > 0, 1 <= k <= %d)' % nat.MAX_NEIGHBORS)
+    return float(radius_m), int(k)
+
+
+def _histogram_obs(value, num_objects):
+    radius_m, n_rings, n_sectors = value
+    radius_m, grid = float(radius_m), nat.check_histogram_grid(n_rings, n_sectors)
+    return (nat.check_radius(radius_m, 'histogram_obs: radius_m'),) + grid
+
+
+def _object_obs(value, num_objects):
+    if value not in (False, True):
+        raise ValueError('object_obs must be True, False or None')
+    return bool(value)
+
+
+def _grid_obs(value, num_objects):
+    width, height, planes = tuple(value) if len(value) == 3 else tuple(value) + (('count',),)
+    grid = nat.check_grid(width, height, planes)
+    if grid[2] & nat.GRID_OBJECTS and num_objects == 0:
+        raise ValueError("grid_obs: 'objects' asked for, but the env has no objects")
+    return grid
+
+
+def _contact_obs(value, num_objects):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= value <= nat.MAX_CONTACT_SLOTS:
+        raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
+    return int(value)
+
+
+def _ray_obs(value, num_objects):
+    radius_m, n_rays, targets = tuple(value) if len(value) == 3 else tuple(value) + (None,)
+    if targets is None:
+        targets = nat.RAY_BOTS | nat.RAY_WALLS | (nat.RAY_OBJECTS if num_objects > 0 else 0)
+    rays = nat.check_rays(radius_m, n_rays, targets)
+    if rays[2] & nat.RAY_OBJECTS and num_objects == 0:
+        raise ValueError("ray_obs: 'objects' asked for, but the env has no objects")
+    return rays
+
+
+def _edge_obs(value, num_objects):
+    return nat.check_edges(*(tuple(value) if hasattr(value, '__len__') else (value, None)))
+
+
+def _render_size(value, num_objects):
+    width, height = value
+    return nat.check_render(width, height, nat.RENDER_BOTS)[:2]
+
+
+# What an env can be created with besides the poses, a row per constructor keyword.  parse: the user's value (not None) to what
+# the attribute of the keyword's name holds, a TypeError on the way becoming "<keyword> must be <shape>" where a shape is given.
+# keys: where step() puts what the method of the sim returns for the stored value, in this order; none: step() leaves it to the
+# accessor.  form, purpose: "create the env with <keyword>=<form> to <purpose>", for an accessor on an env created without it.
+Option = collections.namedtuple('Option', ('parse', 'shape', 'keys', 'method', 'form', 'purpose'))
+OPTIONS = {
+    'neighbor_obs': Option(_neighbor_obs, None, ('neighbors',), 'neighbors', '(radius_m, k)', 'observe neighbours'),
+    'histogram_obs': Option(_histogram_obs, '(radius_m, n_rings, n_sectors)', ('neighbor_histogram',), 'neighbor_histogram', '(radius_m, n_rings, n_sectors)', 'observe neighbour histograms'),
+    'object_obs': Option(_object_obs, None, ('objects', 'walls'), 'object_points', 'True', 'observe objects and walls'),
+    'grid_obs': Option(_grid_obs, '(width, height) or (width, height, planes)', ('grid',), 'occupancy_grid', '(width, height[, planes])', 'observe occupancy grids'),
+    'contact_obs': Option(_contact_obs, None, ('contacts',), 'contacts', 'k', 'observe contacts'),
+    'ray_obs': Option(_ray_obs, '(radius_m, n_rays) or (radius_m, n_rays, targets)', ('rays',), 'rays', '(radius_m, n_rays[, targets])', 'observe range scans'),
+    'edge_obs': Option(_edge_obs, 'radius_m or (radius_m, capacity)', ('edges',), 'edges', 'radius_m or (radius_m, capacity)', 'observe the IR-range graph'),
+    'render_size': Option(_render_size, '(width, height)', (), 'render', '(width, height)', 'render frames'),
+    'comm_radius': Option(lambda value, num_objects: nat.check_radius(value, 'comm_radius'), 'a radius in metres', (), None, 'radius_m', None),
+}
 
 
 class BatchedKilobotsEnv(object):
@@ -80,74 +152,19 @@ class BatchedKilobotsEnv(object):
         self.env_offset = int(env_offset)
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
-        self.neighbor_obs = None
-        if neighbor_obs is not None:
-            radius_m, k = neighbor_obs
-            if not float(radius_m) > 0.0 or not 1 <= int(k) <= nat.MAX_NEIGHBORS:
-                raise ValueError('neighbor_obs must be (radius_m > 0, 1 <= k <= %d)' % nat.MAX_NEIGHBORS)
-            self.neighbor_obs = (float(radius_m), int(k))
-        self.histogram_obs = None
-        if histogram_obs is not None:
-            try:
-                radius_m, n_rings, n_sectors = histogram_obs
-                radius_m = float(radius_m)
-                n_rings, n_sectors = nat.check_histogram_grid(n_rings, n_sectors)
-            except TypeError as err:
-                raise ValueError('histogram_obs must be (radius_m, n_rings, n_sectors): %s' % err)
-            if not radius_m > 0.0:
-                raise ValueError('histogram_obs: radius_m must be positive')
-            self.histogram_obs = (radius_m, n_rings, n_sectors)
-        self.comm_radius = None
-        if comm_radius is not None:
-            try:
-                comm_radius = float(comm_radius)
-            except TypeError as err:
-                raise ValueError('comm_radius must be a radius in metres: %s' % err)
-            if not comm_radius > 0.0:
-                raise ValueError('comm_radius must be positive')
-            self.comm_radius = comm_radius
-        if object_obs not in (None, False, True):
-            raise ValueError('object_obs must be True, False or None')
-        self.object_obs = bool(object_obs)
-        self.grid_obs = None
-        if grid_obs is not None:
-            try:
-                width, height, planes = tuple(grid_obs) if len(grid_obs) == 3 else tuple(grid_obs) + (('count',),)
-                self.grid_obs = nat.check_grid(width, height, planes)
-            except TypeError as err:
-                raise ValueError('grid_obs must be (width, height) or (width, height, planes): %s' % err)
-            if self.grid_obs[2] & nat.GRID_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
-                raise ValueError("grid_obs: 'objects' asked for, but the env has no objects")
-        self.contact_obs = None
-        if contact_obs is not None:
-            if isinstance(contact_obs, bool) or not isinstance(contact_obs, (int, np.integer)) or not 0 <= contact_obs <= nat.MAX_CONTACT_SLOTS:
-                raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
-            self.contact_obs = int(contact_obs)
-        self.render_size = None
-        if render_size is not None:
-            try:
-                width, height = render_size
-                self.render_size = nat.check_render(width, height, nat.RENDER_BOTS)[:2]
-            except TypeError as err:
-                raise ValueError('render_size must be (width, height): %s' % err)
-        self.ray_obs = None
-        if ray_obs is not None:
-            try:
-                radius_m, n_rays, targets = tuple(ray_obs) if len(ray_obs) == 3 else tuple(ray_obs) + (None,)
-                if targets is None:
-                    targets = nat.RAY_BOTS | nat.RAY_WALLS | (nat.RAY_OBJECTS if int(cfg.get('num_objects', 0)) > 0 else 0)
-                self.ray_obs = nat.check_rays(radius_m, n_rays, targets)
-            except TypeError as err:
-                raise ValueError('ray_obs must be (radius_m, n_rays) or (radius_m, n_rays, targets): %s' % err)
-            if self.ray_obs[2] & nat.RAY_OBJECTS and int(cfg.get('num_objects', 0)) == 0:
-                raise ValueError("ray_obs: 'objects' asked for, but the env has no objects")
-        self.edge_obs = None
-        if edge_obs is not None:
-            try:
-                radius_m, capacity = tuple(edge_obs) if hasattr(edge_obs, '__len__') else (edge_obs, None)
-                self.edge_obs = nat.check_edges(radius_m, capacity)
-            except TypeError as err:
-                raise ValueError('edge_obs must be radius_m or (radius_m, capacity): %s' % err)
+        given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs,
+                     contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs)
+        for name, option in OPTIONS.items():
+            value = given[name]
+            if value is not None:
+                try:
+                    value = option.parse(value, int(cfg.get('num_objects', 0)))
+                except TypeError as err:
+                    if option.shape is None:
+                        raise
+                    raise ValueError('%s must be %s: %s' % (name, option.shape, err))
+            setattr(self, name, value)
+        self.object_obs = bool(self.object_obs)         # (the one keyword that is off as False)
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -214,11 +231,7 @@ class BatchedKilobotsEnv(object):
         bits = self.sim.status_bits()
         if not bits:
             return
-        msg = '%s: device step status 0x%x: %s' % (where, bits, nat.describe_status(bits))
-        if self._on_status == 'raise':
-            raise nat.KilobotsStatusError(msg)
-        import warnings
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+        nat.report_status(self._on_status, where, bits)
         self.sim.status.zero_()
 
     def spawn(self):
@@ -321,97 +334,81 @@ class BatchedKilobotsEnv(object):
             if self.auto_reset:     # before the observations are taken: they describe the new episode
                 info['terminal_obs'] = obs
                 obs = self.reset_envs(done)
-        if self.neighbor_obs is not None:
-            info['neighbors'] = self.neighbors()
-        if self.histogram_obs is not None:
-            info['neighbor_histogram'] = self.neighbor_histogram()
-        if self.object_obs:
-            points = self.object_points()
-            if torch.is_tensor(points):
-                info['walls'] = points
-            else:
-                info['objects'], info['walls'] = points
-        if self.grid_obs is not None:
-            info['grid'] = self.occupancy_grid()
-        if self.contact_obs is not None:
-            info['contacts'] = self.contacts()
-        if self.ray_obs is not None:
-            info['rays'] = self.rays()
-        if self.edge_obs is not None:
-            info['edges'] = self.edges()
+        for name, option in OPTIONS.items():
+            value = getattr(self, name)
+            if option.keys and value is not None and value is not False:      # (by identity: contact_obs=0 is an observation)
+                out = self._observe(name)
+                if len(option.keys) > 1 and not torch.is_tensor(out):
+                    info.update(zip(option.keys, out))
+                else:       # (object_points of an env without objects returns the walls alone)
+                    info[option.keys[-1]] = out
         return obs, reward, done, info
+
+    def _stored(self, name, purpose=None):
+        """What the env holds for the constructor keyword `name`; ValueError if it was created without it."""
+        value = getattr(self, name)
+        if value is None or value is False:
+            raise ValueError('create the env with %s=%s to %s' % (name, OPTIONS[name].form, purpose or OPTIONS[name].purpose))
+        return value
+
+    def _observe(self, name):
+        value = self._stored(name)      # the tuple of the sim method's arguments, its one argument, or True for none
+        args = value if isinstance(value, tuple) else (value,) if value is not True else ()
+        return getattr(self.sim, OPTIONS[name].method)(*args)
 
     def neighbors(self):
         """(index [E, N, k] int32, rel [E, N, k, 4] float32, count [E, N] int32) of the current poses for the
         neighbor_obs=(radius_m, k) the env was created with: KilobotSim.neighbors."""
-        if self.neighbor_obs is None:
-            raise ValueError('create the env with neighbor_obs=(radius_m, k) to observe neighbours')
-        return self.sim.neighbors(*self.neighbor_obs)
+        return self._observe('neighbor_obs')
 
     def neighbor_histogram(self):
         """hist [E, N, n_rings, n_sectors] float32 of the current poses for the histogram_obs=(radius_m, n_rings, n_sectors)
         the env was created with: KilobotSim.neighbor_histogram."""
-        if self.histogram_obs is None:
-            raise ValueError('create the env with histogram_obs=(radius_m, n_rings, n_sectors) to observe neighbour histograms')
-        return self.sim.neighbor_histogram(*self.histogram_obs)
+        return self._observe('histogram_obs')
 
     def object_points(self):
         """(obj [E, N, M, 4], wall [E, N, 4]) float32 of the current poses -- wall alone in an env without objects -- for
         an env created with object_obs=True: KilobotSim.object_points."""
-        if not self.object_obs:
-            raise ValueError('create the env with object_obs=True to observe objects and walls')
-        return self.sim.object_points()
+        return self._observe('object_obs')
 
     def occupancy_grid(self):
         """grid [E, C, height, width] float32 of the current poses for the grid_obs=(width, height[, planes]) the env was
         created with: KilobotSim.occupancy_grid."""
-        if self.grid_obs is None:
-            raise ValueError('create the env with grid_obs=(width, height[, planes]) to observe occupancy grids')
-        return self.sim.occupancy_grid(*self.grid_obs)
+        return self._observe('grid_obs')
 
     def contacts(self):
         """(partner [E, N, k] int32, impulse [E, N, k] float32, touch [E, N, 4] float32, obj [E, M, 2] float32 or None) of the
         contacts of the last world step for the contact_obs=k the env was created with: KilobotSim.contacts."""
-        if self.contact_obs is None:
-            raise ValueError('create the env with contact_obs=k to observe contacts')
-        return self.sim.contacts(self.contact_obs)
+        return self._observe('contact_obs')
 
     def rays(self):
         """(dist [E, N, n_rays] float32, hit [E, N, n_rays] int32) of the current poses for the ray_obs=(radius_m, n_rays[,
         targets]) the env was created with: KilobotSim.rays."""
-        if self.ray_obs is None:
-            raise ValueError('create the env with ray_obs=(radius_m, n_rays[, targets]) to observe range scans')
-        return self.sim.rays(*self.ray_obs)
+        return self._observe('ray_obs')
 
     def edges(self):
         """The named tuple (src, dst, rel, offsets, count, nnz) of the current poses for the edge_obs=radius_m or
         (radius_m, capacity) the env was created with: KilobotSim.edges."""
-        if self.edge_obs is None:
-            raise ValueError('create the env with edge_obs=radius_m or (radius_m, capacity) to observe the IR-range graph')
-        return self.sim.edges(*self.edge_obs)
+        return self._observe('edge_obs')
 
     def render(self, mode='rgb_array'):
         """frames [E, height, width, 3] uint8 of the current state for the render_size=(width, height) the env was created
         with: KilobotSim.render.  Only mode 'rgb_array' exists: there is no window."""
         if mode != 'rgb_array':
             raise NotImplementedError("BatchedKilobotsEnv.render: only mode 'rgb_array' (got %r)" % (mode,))
-        if self.render_size is None:
-            raise ValueError('create the env with render_size=(width, height) to render frames')
-        return self.sim.render(*self.render_size)
+        return self._observe('render_size')
 
     def neighbor_reduce(self, values, op='sum', scale=65536.0, count=False):
         """What every kilobot hears of `values` ([E, N] or [E, N, C] float32 on the device) over the comm_radius the env
         was created with, combined by op ('sum' | 'min' | 'max'): KilobotSim.neighbor_reduce."""
-        if self.comm_radius is None:
-            raise ValueError('create the env with comm_radius=radius_m to aggregate messages')
-        return self.sim.neighbor_reduce(values, self.comm_radius, op=op, scale=scale, count=count)
+        radius_m = self._stored('comm_radius', 'aggregate messages')
+        return self.sim.neighbor_reduce(values, radius_m, op=op, scale=scale, count=count)
 
     def hops(self, seeds, max_hops=None, parent=False, root=False, stats=False):
         """The hop-count gradient of every kilobot to the nearest of `seeds` ([E, N] bool or uint8 on the device) over the
         comm_radius the env was created with: KilobotSim.hops."""
-        if self.comm_radius is None:
-            raise ValueError('create the env with comm_radius=radius_m to form hop-count gradients')
-        return self.sim.hops(seeds, self.comm_radius, max_hops=max_hops, parent=parent, root=root, stats=stats)
+        radius_m = self._stored('comm_radius', 'form hop-count gradients')
+        return self.sim.hops(seeds, radius_m, max_hops=max_hops, parent=parent, root=root, stats=stats)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

@@ -405,11 +405,7 @@ class KilobotsEnv(object):
         if not bits:
             return
         self._status_seen = None
-        msg = '%s: device step status 0x%x: %s' % (where, bits, nat.describe_status(bits))
-        if self._on_status == 'raise':
-            raise nat.KilobotsStatusError(msg)
-        import warnings
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+        nat.report_status(self._on_status, where, bits)
         self._sim.status.zero_()          # warn once per occurrence
 
     def _light_action_tensor(self, action):

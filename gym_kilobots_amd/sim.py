@@ -17,6 +17,23 @@ from ._native import (DRIVE_VELOCITY, DRIVE_ACCEL, DRIVE_MOTORS, DRIVE_SIMPLE_PH
 # what KilobotSim.edges returns
 Edges = collections.namedtuple('Edges', ('src', 'dst', 'rel', 'offsets', 'count', 'nnz'))
 
+# the dtypes a caller's tensor may have: floats, a mask (env_mask, seeds) and 32-bit words (colours, episode counters)
+F32, I32, I64, MASK = (torch.float32,), (torch.int32,), (torch.int64,), (torch.bool, torch.uint8)
+WORD = (torch.int32, getattr(torch, 'uint32', torch.int32))
+
+
+def _ptr(t):
+    """The device pointer of a tensor as the integer ctypes takes for a void *, None (NULL) for an absent one."""
+    return None if t is None else t.data_ptr()
+
+
+def _reset_params(seed, mean, std, random_theta, random_velocity, resolve, env_offset):
+    rp = nat.KbResetParams()
+    rp.seed, rp.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
+    rp.mean[0], rp.mean[1], rp.std = float(mean[0]), float(mean[1]), float(std)
+    rp.random_theta, rp.random_velocity, rp.resolve = int(bool(random_theta)), int(bool(random_velocity)), int(bool(resolve))
+    return rp
+
 
 class KilobotSim:
     """num_envs independent worlds of num_bots kilobots, resident on one GPU.
@@ -39,7 +56,7 @@ class KilobotSim:
         self.num_envs, self.num_bots = num_envs, num_bots
         self.drive_mode, self.light_type = drive_mode, light_type
         self._h = C.c_void_p()
-        nat.check(self._lib.kb_create(C.byref(self.cfg), C.byref(self._h)), 'kb_create')
+        nat.call(self._lib, 'kb_create', C.byref(self.cfg), C.byref(self._h))
         E, N = num_envs, num_bots
         dev = self.device
         f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
@@ -104,10 +121,38 @@ class KilobotSim:
         for name in nat.BUFFER_FIELDS:
             t = getattr(self, name, None)
             setattr(b, name, None if t is None else t.data_ptr())
-        nat.check(self._lib.kb_bind(self._h, C.byref(b)), 'kb_bind')
+        self._call('kb_bind', C.byref(b), stream=False)
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _call(self, name, *args, stream=True):
+        """The library entry `name` on this sim's handle, with the current stream behind args unless stream=False; a failure
+        raises under the entry's own name.  The launch goes to the CURRENT HIP device: make it the sim's."""
+        with torch.cuda.device(self.device):
+            if stream:
+                args += (self._stream(),)
+            nat.check(getattr(self._lib, name)(self._h, *args), name)
+
+    def _mismatch(self, t, dtypes, shape, name):
+        """What keeps t from being the tensor `name` -- contiguous, of one of dtypes, of this shape (an int: of at least
+        that many elements), on the sim's device -- or None if nothing does."""
+        least = isinstance(shape, int)
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype in dtypes and t.is_contiguous()
+                and (t.numel() >= shape if least else tuple(t.shape) == tuple(shape))):
+            dtypes = ' or '.join(dict.fromkeys(str(d).replace('torch.', '') for d in dtypes))
+            return '%s must be a contiguous %s cuda tensor of %s' % (name, dtypes, 'at least %d elements' % shape if least else 'shape %s' % (tuple(shape),))
+        if t.device != self.device:
+            return '%s lives on %s, the simulator on %s' % (name, t.device, self.device)
+
+    def _input(self, t, dtypes, shape, name, optional=False):
+        """The pointer of a caller's tensor (None for None with optional=True); ValueError with what _mismatch says of it."""
+        if t is None and optional:
+            return None
+        why = self._mismatch(t, dtypes, shape, name)
+        if why:
+            raise ValueError(why)
+        return t.data_ptr()
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
@@ -148,7 +193,7 @@ class KilobotSim:
 
     @block_threads.setter
     def block_threads(self, n):
-        nat.check(self._lib.kb_set_block_threads(self._h, int(n)), 'kb_set_block_threads')
+        self._call('kb_set_block_threads', int(n), stream=False)
 
     @property
     def variant_index(self):
@@ -198,8 +243,7 @@ class KilobotSim:
     def poses(self):
         """[num_envs, num_bots, 3] float32 (x [m], y [m], theta): get_state()['kilobots'] of every env."""
         out = torch.empty(self.num_envs, self.num_bots, 3, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_get_poses(self._h, C.c_void_p(out.data_ptr()), self._stream()), 'kb_get_poses')
+        self._call('kb_get_poses', out.data_ptr())
         return out
 
     def host_state(self):
@@ -207,8 +251,7 @@ class KilobotSim:
         arrays, metres / radians: one launch and ONE copy to the host (kb_get_state), for get_state() after every step."""
         N, M = self.num_bots, self.num_objects
         out = torch.empty(self.num_envs, 3 * (N + M) + 1, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_get_state(self._h, C.c_void_p(out.data_ptr()), self._stream()), 'kb_get_state')
+        self._call('kb_get_state', out.data_ptr())
         h = out.cpu().numpy()
         E = self.num_envs
         return (h[:, :3 * N].reshape(E, N, 3), h[:, 3 * N:3 * (N + M)].reshape(E, M, 3),
@@ -231,19 +274,14 @@ class KilobotSim:
         bits = self.status_bits()
         if bits:
             bad = int((self.status != 0).sum().item())
-            msg = '%sdevice step status 0x%x in %d of %d envs: %s' % (where and where + ': ', bits, bad, self.num_envs, describe_status(bits))
-            if mode == 'raise':
-                raise KilobotsStatusError(msg)
-            import warnings
-            warnings.warn(msg, RuntimeWarning, stacklevel=3)
+            nat.report_status(mode, where, bits, ' in %d of %d envs' % (bad, self.num_envs))
         return bits
 
     def sense(self, radius_m, out=None):
         """IR-range neighbour sensing on the current poses: [num_envs, num_bots] int32 counts of the kilobots within
         radius_m (centre to centre) of each kilobot (kb_sense; no reference counterpart)."""
         out, = self._outputs(out, [((self.num_envs, self.num_bots), torch.int32, 'count')], 'the count tensor')
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense(self._h, float(radius_m), C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense')
+        self._call('kb_sense', float(radius_m), out.data_ptr())
         return out
 
     def neighbors(self, radius_m, k, out=None, count=True):
@@ -258,11 +296,9 @@ class KilobotSim:
             raise ValueError('k must be in 1..%d' % nat.MAX_NEIGHBORS)
         shapes = [((E, N, k), torch.int32, 'index'), ((E, N, k, 4), torch.float32, 'rel')] + ([((E, N), torch.int32, 'count')] if count else [])
         out = self._outputs(out, shapes, 'a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes)))
-        pc = C.c_void_p(out[2].data_ptr()) if count else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_neighbors(self._h, float(radius_m), k, C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()),
-                                                   pc, self._stream()), 'kb_sense_neighbors')
-        return (out[0], out[1], out[2] if count else None)
+        out = tuple(out) + (() if count else (None,))
+        self._call('kb_sense_neighbors', float(radius_m), k, *map(_ptr, out))
+        return out
 
     def edges(self, radius_m, capacity=None, rel=True, src=True, out=None):
         """The whole IR-range graph on the current poses (kb_sense_edges; no reference counterpart): every pair of kilobots of
@@ -303,14 +339,9 @@ class KilobotSim:
         capacity), src / dst / rel / count contiguous tensors or None.  The sizes are checked here, because the library cannot:
         src, dst and rel hold at least `capacity` entries, offsets and count one per row."""
         rows, capacity = self.num_envs * self.num_bots, int(capacity)
-        for t, dtype, least, name in ((offsets, torch.int64, rows + 1, 'offsets'), (src, torch.int32, capacity, 'src'), (dst, torch.int32, capacity, 'dst'),
-                                      (rel, torch.float32, 4 * capacity, 'rel'), (count, torch.int32, rows, 'count')):
-            if t is not None and not (t.is_cuda and t.device == self.device and t.dtype == dtype and t.is_contiguous() and t.numel() >= least):
-                raise ValueError('%s must be a contiguous %s tensor of at least %d elements on %s' % (name, str(dtype).replace('torch.', ''), least, self.device))
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_edges(self._h, float(radius_m), ptr(offsets), int(capacity), ptr(src), ptr(dst), ptr(rel), ptr(count),
-                                               self._stream()), 'kb_sense_edges')
+        po, ps, pd, pr, pc = (self._input(t, dtypes, least, name, optional=True) for t, dtypes, least, name in (
+            (offsets, I64, rows + 1, 'offsets'), (src, I32, capacity, 'src'), (dst, I32, capacity, 'dst'), (rel, F32, 4 * capacity, 'rel'), (count, I32, rows, 'count')))
+        self._call('kb_sense_edges', float(radius_m), po, capacity, ps, pd, pr, pc)
 
     def neighbor_histogram(self, radius_m, n_rings, n_sectors, out=None, count=False):
         """Local neighbour histograms on the current poses (kb_sense_histogram; no reference counterpart): for every kilobot
@@ -320,14 +351,10 @@ class KilobotSim:
         with count=True.  out: a preallocated contiguous hist tensor to write into (with count=True: the tuple (hist, count))."""
         E, N = self.num_envs, self.num_bots
         n_rings, n_sectors = nat.check_histogram_grid(n_rings, n_sectors)
-        if not float(radius_m) > 0.0:
-            raise ValueError('radius_m must be positive')
+        radius_m = nat.check_radius(radius_m)
         shapes = [((E, N, n_rings, n_sectors), torch.float32, 'hist')] + ([((E, N), torch.int32, 'count')] if count else [])
         out = self._outputs(out, shapes, 'the tuple (hist, count)' if count else 'the hist tensor')
-        pc = C.c_void_p(out[1].data_ptr()) if count else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_histogram(self._h, float(radius_m), n_rings, n_sectors, C.c_void_p(out[0].data_ptr()),
-                                                   pc, self._stream()), 'kb_sense_histogram')
+        self._call('kb_sense_histogram', radius_m, n_rings, n_sectors, out[0].data_ptr(), out[1].data_ptr() if count else None)
         return (out[0], out[1]) if count else out[0]
 
     def neighbor_reduce(self, values, radius_m, op='sum', scale=65536.0, out=None, count=False):
@@ -341,20 +368,12 @@ class KilobotSim:
         heard) with count=True; the mean is result / count.  out: a preallocated tensor to write into, which may be values
         itself (with count=True: the tuple (result, count))."""
         E, N = self.num_envs, self.num_bots
-        if not (torch.is_tensor(values) and values.is_cuda and values.dtype == torch.float32 and values.is_contiguous()
-                and values.dim() in (2, 3) and tuple(values.shape[:2]) == (E, N)):
-            raise ValueError('values must be a contiguous float32 cuda tensor of shape %s or %s' % ((E, N), (E, N, 'C')))
-        if values.device != self.device:
-            raise ValueError('values lives on %s, the simulator on %s' % (values.device, self.device))
+        pv = self._input(values, F32, (E, N) + tuple(getattr(values, 'shape', ())[2:3]), 'values')
         op, n_channels, scale = nat.check_reduce(op, values.shape[2] if values.dim() == 3 else 1, scale)
-        if not float(radius_m) > 0.0:
-            raise ValueError('radius_m must be positive')
+        radius_m = nat.check_radius(radius_m)
         shapes = [(tuple(values.shape), torch.float32, 'result')] + ([((E, N), torch.int32, 'count')] if count else [])
         out = self._outputs(out, shapes, 'the tuple (result, count)' if count else 'the result tensor')
-        pc = C.c_void_p(out[1].data_ptr()) if count else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_reduce(self._h, float(radius_m), op, n_channels, scale, C.c_void_p(values.data_ptr()),
-                                                C.c_void_p(out[0].data_ptr()), pc, self._stream()), 'kb_sense_reduce')
+        self._call('kb_sense_reduce', radius_m, op, n_channels, scale, pv, out[0].data_ptr(), out[1].data_ptr() if count else None)
         return (out[0], out[1]) if count else out[0]
 
     def hops(self, seeds, radius_m, max_hops=None, parent=False, root=False, stats=False, out=None):
@@ -368,13 +387,8 @@ class KilobotSim:
         (hops, parent, root, stats) of the ones asked for.  out: the preallocated contiguous tensor(s) to write into, in the
         shape of the result."""
         E, N = self.num_envs, self.num_bots
-        if not (torch.is_tensor(seeds) and seeds.is_cuda and seeds.dtype in (torch.bool, torch.uint8) and seeds.is_contiguous()
-                and tuple(seeds.shape) == (E, N)):
-            raise ValueError('seeds must be a contiguous bool or uint8 cuda tensor of shape %s' % ((E, N),))
-        if seeds.device != self.device:
-            raise ValueError('seeds lives on %s, the simulator on %s' % (seeds.device, self.device))
-        if not float(radius_m) > 0.0:
-            raise ValueError('radius_m must be positive')
+        ps = self._input(seeds, MASK, (E, N), 'seeds')
+        radius_m = nat.check_radius(radius_m)
         if max_hops is None:
             max_hops = nat.HOPS_UNLIMITED
         if isinstance(max_hops, bool) or not isinstance(max_hops, (int, np.integer)) or max_hops < 0:
@@ -383,10 +397,8 @@ class KilobotSim:
         shapes = [s for s, w in zip([((E, N), torch.int32, 'hops'), ((E, N), torch.int32, 'parent'), ((E, N), torch.int32, 'root'),
                                      ((E, 2), torch.int32, 'stats')], wanted) if w]
         out = list(self._outputs(out, shapes, 'the hops tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
-        ptrs = [C.c_void_p(out[sum(wanted[:i])].data_ptr()) if w else None for i, w in enumerate(wanted)]
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_hops(self._h, float(radius_m), C.c_void_p(seeds.data_ptr()), min(int(max_hops), nat.HOPS_UNLIMITED),
-                                              ptrs[0], ptrs[1], ptrs[2], ptrs[3], self._stream()), 'kb_sense_hops')
+        given = iter(out)
+        self._call('kb_sense_hops', radius_m, ps, min(int(max_hops), nat.HOPS_UNLIMITED), *(next(given).data_ptr() if w else None for w in wanted))
         return tuple(out) if len(out) > 1 else out[0]
 
     def outline(self):
@@ -410,10 +422,7 @@ class KilobotSim:
         out = self._outputs(out, shapes, 'the tuple (obj, wall)' if len(shapes) == 2 else 'the %s tensor' % shapes[0][2])
         if any(t.data_ptr() % 16 for t in out):
             raise ValueError('out: the tensors must be 16-byte aligned')
-        po = C.c_void_p(out[0].data_ptr()) if M > 0 else None
-        pw = C.c_void_p(out[-1].data_ptr()) if walls else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_objects(self._h, po, pw, self._stream()), 'kb_sense_objects')
+        self._call('kb_sense_objects', out[0].data_ptr() if M > 0 else None, out[-1].data_ptr() if walls else None)
         return out if len(out) == 2 else out[0]
 
     def grid_channels(self, planes=('count',)):
@@ -438,8 +447,7 @@ class KilobotSim:
         width, height, planes = nat.check_grid(width, height, planes)
         channels = self.grid_channels(planes)
         out, = self._outputs(out, [((self.num_envs, channels, height, width), torch.float32, 'grid')], 'the grid tensor')
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_grid(self._h, width, height, planes, C.c_void_p(out.data_ptr()), self._stream()), 'kb_sense_grid')
+        self._call('kb_sense_grid', width, height, planes, out.data_ptr())
         return out
 
     def contacts(self, k=8, scale=65536.0, out=None):
@@ -465,10 +473,7 @@ class KilobotSim:
         out = list(self._outputs(out, shapes, 'a tuple of %d tensors (%s)' % (len(shapes), ', '.join(n for _, _, n in shapes))))
         partner, impulse = (out.pop(0), out.pop(0)) if k else (None, None)
         touch, obj = out[0], out[1] if M > 0 else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_contacts(self._h, k, scale, ptr(partner), ptr(impulse), ptr(touch), ptr(obj), self._stream()),
-                      'kb_sense_contacts')
+        self._call('kb_sense_contacts', k, scale, _ptr(partner), _ptr(impulse), _ptr(touch), _ptr(obj))
         return partner, impulse, touch, obj
 
     def render(self, width, height, layers=('objects', 'bots', 'light'), style=None, body_rgb=None, mark_rgb=None, out=None):
@@ -483,20 +488,8 @@ class KilobotSim:
         width, height, layers = nat.check_render(width, height, layers)
         st = style if isinstance(style, nat.KbRenderStyle) else nat.render_style(style)
         out, = self._outputs(out, [((self.num_envs, height, width, 3), torch.uint8, 'rgb')], 'the rgb tensor')
-        ptrs = []
-        for name, t in (('body_rgb', body_rgb), ('mark_rgb', mark_rgb)):
-            if t is None:
-                ptrs.append(None)
-                continue
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype in (torch.int32, getattr(torch, 'uint32', torch.int32)) and t.is_contiguous()
-                    and tuple(t.shape) == (self.num_envs, self.num_bots)):
-                raise ValueError('%s must be a contiguous int32 or uint32 cuda tensor of shape %s' % (name, (self.num_envs, self.num_bots)))
-            if t.device != self.device:
-                raise ValueError('%s lives on %s, the simulator on %s' % (name, t.device, self.device))
-            ptrs.append(C.c_void_p(t.data_ptr()))
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_render(self._h, width, height, layers, C.byref(st), ptrs[0], ptrs[1], C.c_void_p(out.data_ptr()), self._stream()),
-                      'kb_render')
+        pb, pm = (self._input(t, WORD, (self.num_envs, self.num_bots), name, optional=True) for name, t in (('body_rgb', body_rgb), ('mark_rgb', mark_rgb)))
+        self._call('kb_render', width, height, layers, C.byref(st), pb, pm, out.data_ptr())
         return out
 
     def rays(self, radius_m, n_rays, targets=None, out=None, hit=True):
@@ -517,9 +510,7 @@ class KilobotSim:
             raise ValueError("targets: 'objects' asked for, but the sim has no objects")
         shapes = [((E, N, n_rays), torch.float32, 'dist')] + ([((E, N, n_rays), torch.int32, 'hit')] if hit else [])
         out = self._outputs(out, shapes, 'the tuple (dist, hit)' if hit else 'the dist tensor')
-        ph = C.c_void_p(out[1].data_ptr()) if hit else None
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_sense_rays(self._h, radius_m, n_rays, targets, C.c_void_p(out[0].data_ptr()), ph, self._stream()), 'kb_sense_rays')
+        self._call('kb_sense_rays', radius_m, n_rays, targets, out[0].data_ptr(), out[1].data_ptr() if hit else None)
         return out[0], out[1] if hit else None
 
     def _outputs(self, out, shapes, what):
@@ -531,10 +522,9 @@ class KilobotSim:
         if len(out) != len(shapes):
             raise ValueError('out must be %s' % what)
         for t, (s, d, n) in zip(out, shapes):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.is_contiguous() and tuple(t.shape) == s):
-                raise ValueError('out: %s must be a contiguous %s cuda tensor of shape %s' % (n, str(d).replace('torch.', ''), s))
-            if t.device != self.device:
-                raise ValueError('out: %s lives on %s, the simulator on %s' % (n, t.device, self.device))
+            why = self._mismatch(t, (d,), s, 'out: ' + n)
+            if why:
+                raise ValueError(why)
         return out
 
     def light_sense(self, light_action=None):
@@ -543,56 +533,33 @@ class KilobotSim:
         _loop runs on the host between the sensing and the motor law (kilobots_env.py:171-184)."""
         if self.light_value is None:
             raise ValueError('light_sense needs the sensing outputs: create the sim with debug_outputs=True')
-        pl = self._ptr(light_action, (self.num_envs, self._lib.kb_light_action_dim(self._h)), 'light_action')
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_light_sense(self._h, pl, self._stream()), 'kb_light_sense')
+        self._call('kb_light_sense', self._light_action_ptr(light_action))
 
     def reset(self, seed=0, mean=(0.0, 0.0), std=0.1, random_theta=False, random_velocity=False, resolve=True, env_offset=0):
         """KilobotsEnv.reset of every env on the device (kb_reset): Gaussian spawn clipped to the bounds -/+ 0.02 m
         (yaml_kilobots_env.py:346-352), Philox4x32-10 keyed by (seed; env_offset + env, bot), then the step to resolve."""
-        rp = nat.KbResetParams()
-        rp.seed, rp.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
-        rp.mean[0], rp.mean[1], rp.std = float(mean[0]), float(mean[1]), float(std)
-        rp.random_theta, rp.random_velocity, rp.resolve = int(bool(random_theta)), int(bool(random_velocity)), int(bool(resolve))
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_reset(self._h, C.byref(rp), self._stream()), 'kb_reset')
+        self._call('kb_reset', C.byref(_reset_params(seed, mean, std, random_theta, random_velocity, resolve, env_offset)))
 
     # ------------------------------------------------------------------ stepping
-    def _ptr(self, t, shape, name):
-        if t is None:
-            return None
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
-            raise ValueError('%s must be a contiguous float32 cuda tensor of shape %s' % (name, tuple(shape)))
-        if t.device != self.device:
-            raise ValueError('%s lives on %s, the simulator on %s' % (name, t.device, self.device))
-        return C.c_void_p(t.data_ptr())
+    def _actions_ptr(self, actions):
+        return self._input(actions, F32, (self.num_envs, self.num_bots, 2), 'actions', optional=True)
+
+    def _light_action_ptr(self, light_action):
+        return self._input(light_action, F32, (self.num_envs, self._lib.kb_light_action_dim(self._h)), 'light_action', optional=True)
 
     def set_actions(self, actions):
         """set_action of every kilobot (clamped); actions [E, N, 2] cuda float32 or None (= zeros)."""
-        p = self._ptr(actions, (self.num_envs, self.num_bots, 2), 'actions')
-        with torch.cuda.device(self.device):    # the launch goes to the CURRENT HIP device: make it the sim's
-            nat.check(self._lib.kb_set_actions(self._h, p, self._stream()), 'kb_set_actions')
+        self._call('kb_set_actions', self._actions_ptr(actions))
 
     def step(self, n_substeps=1, actions=None, light_action=None, flags=0, env_mask=None):
         """n_substeps iterations of the reference substep loop in one kernel launch (asynchronous).
         env_mask: [E] bool or uint8 tensor on the sim's device: only the envs it selects are stepped (kb_step_envs); of the
         others no byte of any state tensor changes, the fused actions included.  None: every env (kb_step)."""
-        pa = self._ptr(actions, (self.num_envs, self.num_bots, 2), 'actions')
-        pl = self._ptr(light_action, (self.num_envs, self._lib.kb_light_action_dim(self._h)), 'light_action')
-        with torch.cuda.device(self.device):
-            if env_mask is None:
-                nat.check(self._lib.kb_step(self._h, pa, pl, int(n_substeps), int(flags), self._stream()), 'kb_step')
-            else:
-                nat.check(self._lib.kb_step_envs(self._h, self._mask_ptr(env_mask), pa, pl, int(n_substeps), int(flags), self._stream()),
-                          'kb_step_envs')
-
-    def _mask_ptr(self, env_mask):
-        if not (torch.is_tensor(env_mask) and env_mask.is_cuda and env_mask.dtype in (torch.bool, torch.uint8) and env_mask.is_contiguous()
-                and tuple(env_mask.shape) == (self.num_envs,)):
-            raise ValueError('env_mask must be a contiguous bool or uint8 cuda tensor of shape %s' % ((self.num_envs,),))
-        if env_mask.device != self.device:
-            raise ValueError('env_mask lives on %s, the simulator on %s' % (env_mask.device, self.device))
-        return C.c_void_p(env_mask.data_ptr())
+        args = self._actions_ptr(actions), self._light_action_ptr(light_action), int(n_substeps), int(flags)
+        if env_mask is None:
+            self._call('kb_step', *args)
+        else:
+            self._call('kb_step_envs', self._input(env_mask, MASK, (self.num_envs,), 'env_mask'), *args)
 
     def reset_envs(self, env_mask, seed=0, mean=(0.0, 0.0), std=0.1, random_theta=False, random_velocity=False, resolve=True, env_offset=0,
                    episode=None, objects=None, lights=None, light_vel=None):
@@ -605,26 +572,12 @@ class KilobotSim:
         lights, light_vel: [E, L, 2] float32 (or [E, 2] with one light): light_x, light_y and light_vx, light_vy of the selected
         envs; with lights alone the velocities are zeroed.  All tensors contiguous and on the sim's device."""
         E, M = self.num_envs, self.num_objects
-        rp = nat.KbResetParams()
-        rp.seed, rp.env_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)
-        rp.mean[0], rp.mean[1], rp.std = float(mean[0]), float(mean[1]), float(std)
-        rp.random_theta, rp.random_velocity, rp.resolve = int(bool(random_theta)), int(bool(random_velocity)), int(bool(resolve))
-        init = nat.KbEpisodeInit()
-        if episode is not None:
-            if not (torch.is_tensor(episode) and episode.is_cuda and episode.dtype in (torch.int32, getattr(torch, 'uint32', torch.int32))
-                    and episode.is_contiguous() and tuple(episode.shape) == (E,)):
-                raise ValueError('episode must be a contiguous int32 cuda tensor of shape %s' % ((E,),))
-            if episode.device != self.device:
-                raise ValueError('episode lives on %s, the simulator on %s' % (episode.device, self.device))
-            init.d_episode = episode.data_ptr()
-        if objects is not None:
-            if M == 0:
-                raise ValueError('objects given, but the sim has no objects')
-            init.d_obj_pose = self._ptr(objects, (E, M, 3), 'objects')
+        rp = _reset_params(seed, mean, std, random_theta, random_velocity, resolve, env_offset)
+        if objects is not None and M == 0:
+            raise ValueError('objects given, but the sim has no objects')
         if (lights is not None or light_vel is not None) and self.light_x is None:
             raise ValueError('lights / light_vel given, but the sim has no light')
-        for name, t in (('lights', lights), ('light_vel', light_vel)):
-            if t is not None:
-                setattr(init, 'd_light_pos' if name == 'lights' else 'd_light_vel', self._ptr(t, tuple(self.light_x.shape) + (2,), name))
-        with torch.cuda.device(self.device):
-            nat.check(self._lib.kb_reset_envs(self._h, C.byref(rp), self._mask_ptr(env_mask), C.byref(init), self._stream()), 'kb_reset_envs')
+        light_shape = None if self.light_x is None else tuple(self.light_x.shape) + (2,)
+        init = nat.KbEpisodeInit(self._input(episode, WORD, (E,), 'episode', optional=True), self._input(objects, F32, (E, M, 3), 'objects', optional=True),
+                                 self._input(lights, F32, light_shape, 'lights', optional=True), self._input(light_vel, F32, light_shape, 'light_vel', optional=True))
+        self._call('kb_reset_envs', C.byref(rp), self._input(env_mask, MASK, (E,), 'env_mask'), C.byref(init))

@@ -1,6 +1,7 @@
 """C-ABI checks that need no GPU: the library builds, loads and exports every symbol that
 include/kilobots_hip.h declares; host-side argument validation and error reporting."""
 import ctypes as C
+import functools
 import os
 import re
 
@@ -25,6 +26,68 @@ def test_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.kb_version().startswith(b'kilobots_hip')
+
+
+SCALARS = {'int': C.c_int, 'float': C.c_float, 'int64_t': C.c_int64, 'uint32_t': C.c_uint32, 'size_t': C.c_size_t}
+MIRRORS = {'kb_config': nat.KbConfig, 'kb_buffers': nat.KbBuffers, 'kb_outline': nat.KbOutline, 'kb_render_style': nat.KbRenderStyle,
+           'kb_reset_params': nat.KbResetParams, 'kb_episode_init': nat.KbEpisodeInit}
+
+
+def ctypes_of(c_type, returned=False):
+    """The ctypes types that may stand for a C type of the header (qualifiers and the parameter's name taken off)."""
+    base, stars = c_type.replace('*', ' ').split(), c_type.count('*')
+    base = ' '.join(w for w in base if w != 'const')
+    if stars == 0:
+        return (None,) if base == 'void' and returned else (SCALARS[base],)
+    if returned and (base, stars) == ('char', 1):
+        return (C.c_char_p,)
+    if stars == 1 and base in MIRRORS:
+        return (C.c_void_p, C.POINTER(MIRRORS[base]))
+    return (C.c_void_p,)
+
+
+@functools.lru_cache(None)
+def prototypes():
+    """{name: (return type, [parameter types])} as C text, of every function include/kilobots_hip.h declares."""
+    hdr = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'kilobots_hip.h')).read(), flags=re.S)
+    found = {}
+    for ret, name, params in re.findall(r'^([\w \*]+?)\s*\b(kb_[a-z_]+)\s*\(([^()]*)\)\s*;', hdr, flags=re.M):
+        params = [] if params.strip() == 'void' else [re.sub(r'\w+\s*$', '', p.strip()) for p in params.split(',')]
+        assert name not in found and all(p.strip() for p in params), name
+        found[name] = (ret, params)
+    return found
+
+
+def abi_mismatches(signatures, bound):
+    """Where `signatures` (a table like nat.SIGNATURES) or what `bound(name)` returns as (restype, argtypes) departs from
+    the header's prototypes: one line per return type or parameter."""
+    protos, bad = prototypes(), []
+    if set(protos) != set(signatures):
+        bad.append('names: %s' % sorted(set(protos) ^ set(signatures)))
+    for name, (ret, params) in protos.items():
+        for what, (restype, argtypes) in (('table', signatures.get(name, (0, []))), ('library', bound(name))):
+            if restype not in ctypes_of(ret, returned=True):
+                bad.append('%s: %s returns %r for %r' % (what, name, restype, ret))
+            if len(argtypes or []) != len(params):
+                bad.append('%s: %s takes %d arguments for %d' % (what, name, len(argtypes or []), len(params)))
+            bad += ['%s: %s argument %d is %r for %r' % (what, name, k, a, p) for k, (a, p) in enumerate(zip(argtypes or [], params))
+                    if a not in ctypes_of(p)]
+    return bad
+
+
+def test_every_binding_has_the_types_of_its_prototype(lib):
+    """Return type and every parameter of every function the header declares, in the table of the binding and on the loaded
+    library; and the check itself sees any single entry of the table that is given another type."""
+    assert nat.OPTIONAL <= set(nat.SIGNATURES) and nat.EXPORTS == list(nat.SIGNATURES)
+    on_lib = lambda name: (getattr(lib, name).restype, getattr(lib, name).argtypes)
+    assert abi_mismatches(nat.SIGNATURES, on_lib) == []
+    wrong = lambda t: C.c_double if t is C.c_float else C.c_float
+    for name, (restype, argtypes) in nat.SIGNATURES.items():
+        others = [(wrong(restype), argtypes)] + [(restype, argtypes[:k] + [wrong(argtypes[k])] + argtypes[k + 1:]) for k in range(len(argtypes))]
+        others += [(restype, argtypes + [C.c_void_p])] + ([(restype, argtypes[:-1])] if argtypes else [])
+        for other in others:
+            assert abi_mismatches(dict(nat.SIGNATURES, **{name: other}), on_lib), (name, other)
+            assert abi_mismatches(nat.SIGNATURES, lambda n: other if n == name else on_lib(n)), (name, other)
 
 
 def test_struct_layouts_match_header(tmp_path):
@@ -143,6 +206,22 @@ def test_sim_fails_loudly_without_gpu():
     from gym_kilobots_amd.sim import KilobotSim
     with pytest.raises(nat.KilobotsHipError):
         KilobotSim(1, 16)
+
+
+def test_the_input_check_names_argument_dtypes_and_shape():
+    """The one check of a caller's tensor (KilobotSim._mismatch), as far as it goes without a device: a tensor that is not
+    on a GPU, or no tensor at all, is told the argument, every accepted dtype and the shape or the least size."""
+    import torch
+    from gym_kilobots_amd import sim as S
+    me = S.KilobotSim.__new__(S.KilobotSim)        # no handle, no device: the check needs neither
+    me.device = torch.device('cuda:0')
+    for t in (torch.zeros(3, 2), None, [[0.0] * 2] * 3):
+        assert me._mismatch(t, S.F32, (3, 2), 'actions') == 'actions must be a contiguous float32 cuda tensor of shape (3, 2)'
+    assert me._mismatch(torch.zeros(4, dtype=torch.bool), S.MASK, (4,), 'env_mask') == 'env_mask must be a contiguous bool or uint8 cuda tensor of shape (4,)'
+    assert me._mismatch(torch.zeros(9), S.I64, 10, 'offsets') == 'offsets must be a contiguous int64 cuda tensor of at least 10 elements'
+    assert me._input(None, S.F32, (3, 2), 'actions', optional=True) is None
+    with pytest.raises(ValueError, match='actions must be'):
+        me._input(None, S.F32, (3, 2), 'actions')
 
 
 def test_object_configuration_is_validated(lib):

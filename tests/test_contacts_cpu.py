@@ -106,6 +106,14 @@ def test_batched_env_contact_obs_without_a_gpu():
     with pytest.raises(ValueError):
         env.contacts()
 
+    class Recording(OracleBackend):
+        def contacts(self, k):
+            return ('contacts', k)
+    for k in (0, 8):        # k = 0 is an observation like any other: step() asks the sim for it
+        env = BatchedKilobotsEnv(3, 16, sim_factory=Recording, seed=3, contact_obs=k)
+        env.reset()
+        assert env.step(a)[3] == {'contacts': ('contacts', k)} and env.contacts() == ('contacts', k)
+
 
 # ---- the restatement on the oracle's store ------------------------------------------------------------------------------------
 @pytest.fixture(scope='module')
