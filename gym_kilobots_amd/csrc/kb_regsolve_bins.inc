@@ -273,7 +273,17 @@
 #ifdef KB_PROFILE
         if (lane == 0) atomicMax(&misc[M_PROF], (unsigned)maxD);
         if (tid == 0) atomicAdd(&KB_PROF(M_PROF_DEPTH), (unsigned)maxD);
-        KB_STAMP(7);     // register load + depth sweep of wave 0 (no barrier: wave-local time)
+        {
+            // waves of the env that hold two slots (word 36), and the rounds one sweep of this wave runs -- a level split over
+            // the two slots is swept twice -- as a maximum over the env's waves (word 38, added up in word 37 behind the
+            // barrier at the end of the position sweeps) and for wave 0 (word 39); words from 13 on go out in units of 16
+            unsigned rounds_ = 0;
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) rounds_ += dhi[j] >= dlo[j] ? (unsigned)(dhi[j] - dlo[j] + 1) : 0u;
+            if (lane == 0) { if (mycnt > 64u) atomicAdd(&KB_PROF(36), 16u); atomicMax(&KB_PROF(38), rounds_); }
+            if (tid == 0) atomicAdd(&KB_PROF(39), 16u * rounds_);
+        }
+        KB_STAMP(7);    // register load + depth sweep of wave 0 (no barrier: wave-local time)
 #endif
     }
     KB_ABLATE_EXIT(9);     // register set-up: light load, depth pass, dealing, full load

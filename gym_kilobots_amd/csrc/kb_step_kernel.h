@@ -1281,8 +1281,25 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             // Placement of the islands on the waves in order of size: the largest (= deepest) islands share the first
             // waves, the many tiny ones fill the rest.  A wave sweeps as many rounds as its deepest island has levels
             // and the LDS pipeline is shared, so what counts is the SUM of those depths over the waves -- about a third
-            // less than with a hash placement.  Counting sort over 32 size classes; results never depend on it.
-            unsigned *szSum = bkStart, *szPre = bkStart + 32, *szFill = bkFill;     // (zeroed in the flatten phase)
+            // less than with a hash placement.  Counting sort over 32 size classes (class q: islands of 32 - q contacts,
+            // class 0: 32 and more); results never depend on it.
+            //   kernels with objects: consecutive stretches of `chunk` contacts in that order, an island goes to the wave
+            //     its first contact falls on.
+            //   kernels without objects: next-fit packing in that order (tools/placement_model.py states the rule and
+            //     the form computed here).  A wave is closed at 64 contacts -- one register slot: no dealing, no level
+            //     swept in two rounds (kb_regsolve_bins.inc) -- as long as what is still unplaced fits the waves behind it
+            //     at 128 each, less the most a closed wave can waste (the size of the largest island left, minus one);
+            //     from the first wave where that fails on, the waves close at 128.  The two-slot waves so come last, among
+            //     the smallest (shallowest) islands.  Wave 0 does the walk over the class totals, one step per wave: the
+            //     wave takes every class that still fits as a whole and of the first one that does not as many islands
+            //     as fit.  It leaves the first contact of every wave, counted in walk order, and the contacts per wave;
+            //     a root finds its wave by comparing the place of its first contact -- its class's start plus what the
+            //     class's atomic counter gives it -- against those.  An env with an island of 32 contacts or more (class
+            //     0 is of mixed sizes), or whose packing runs out of waves (the even split then overloads a wave as well),
+            //     keeps the even split -- wave starts every ceil(ncon / nsolve) contacts -- so no env leaves the
+            //     register path that the even split keeps on it.
+            unsigned *szSum = bkStart, *szPre = bkStart + 32, *szFill = bkFill, *szTab = bkFill + 32;     // (the first three zeroed in the flatten phase)
+            static_assert(MAX_WAVES <= 32 && lds::nbk(2) >= 32 + MAX_WAVES, "szTab: a word per wave behind the 32 class counters");
             for (int b = tid; b < N + M; b += nt) {
                 if (parent[b] != (unsigned)b) continue;
                 const unsigned cnt_ = islCnt[b];
@@ -1293,23 +1310,76 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 const unsigned v_ = lane < 32 ? szSum[lane] : 0u;
                 const unsigned incl = wave_incl_scan(v_);
                 if (lane < 32) szPre[lane] = incl - v_;
-                if (lane < nw) misc[M_WCNT + lane] = 0;
+                if constexpr (BINS) {
+                    // lane q: the islands of s = 32 - q contacts lie at [excl, incl) of the walk
+                    const unsigned excl = incl - v_;
+                    const unsigned s_ = 32u - min(lane, 31u);
+                    // x / s = (x * mg) >> 16 for x <= 128: mg = floor(65536 / s) + 1 overshoots 65536 / s by at most 1, the
+                    // product x / s by less than 2^-9, and x / s lies at least 1 / 31 below the next integer
+                    const unsigned mg_ = (unsigned)(65536.5f * __builtin_amdgcn_rcpf((float)s_)) + 1u;
+                    const unsigned total = (unsigned)__builtin_amdgcn_readlane((int)incl, 31);
+                    bool even = __builtin_amdgcn_readfirstlane((int)v_) != 0;      // an island of 32 contacts or more
+                    bool two = false;
+                    unsigned pos = 0, first = lane == 0u ? 0u : total;      // lane w: first contact of wave w
+                    if (!even) {
+#pragma unroll
+                        for (unsigned w = 0; w < (unsigned)nsolve; ++w) {
+                            if (pos >= total) break;
+                            const unsigned s = 32u - (unsigned)__builtin_ctzll(__ballot(incl > pos));     // the largest island left
+                            two = two || total - pos + s > ((unsigned)nsolve - 1u - w) * (129u - s) + 65u;
+                            const unsigned end = pos + (two ? 128u : 64u);
+                            const unsigned long long m_ = __ballot(incl > end);       // the classes that do not fit as a whole
+                            unsigned nxt = total;
+                            if (m_ != 0ull) {
+                                const int q = __builtin_ctzll(m_);
+                                const unsigned start = max(pos, (unsigned)__builtin_amdgcn_readlane((int)excl, q));
+                                nxt = start + (((end - start) * (unsigned)__builtin_amdgcn_readlane((int)mg_, q)) >> 16) * (32u - (unsigned)q);
+                            }
+                            first = lane == w + 1u ? nxt : first;
+                            pos = nxt;
+                        }
+                        even = pos < total;
+                    }
+                    // contacts per wave: up to the first contact of the next one (the even split: the roots count them)
+                    const unsigned mine = even ? 0u : (unsigned)__shfl_down((int)first, 1) - first;
+                    if (even) first = lane * max(((unsigned)ncon + (unsigned)nsolve - 1u) / (unsigned)nsolve, 1u);
+                    if (lane >= (unsigned)nsolve) first = 0xFFFFFFFFu;
+                    if (lane < MAX_WAVES) szTab[lane] = lane == 0u ? (even ? 1u : 0u) : first;
+                    if (lane < nw) misc[M_WCNT + lane] = mine;
+                } else if (lane < nw) misc[M_WCNT + lane] = 0;
             }
             __syncthreads();
-            // the first nw - 1 waves get about 60 contacts each (one register slot: no dealing, one-slot rounds), the
-            // last one the remaining small islands (two slots, but only one or two depth levels)
-            unsigned chunk = 60u;
-            if ((unsigned)ncon > 60u * (unsigned)(nw - 1) + 124u) chunk = ((unsigned)ncon - 124u + (unsigned)nw - 2u) / (unsigned)(nw - 1);
-            if (BINS) chunk = ((unsigned)ncon + (unsigned)nsolve - 1u) / (unsigned)nsolve;      // (the sweeping waves share the contacts evenly, the largest islands first)
-            for (int b = tid; b < N + M; b += nt) {
-                if (parent[b] != (unsigned)b) continue;
-                const unsigned cnt_ = islCnt[b];
-                if (cnt_ == 0) continue;
-                const unsigned q_ = 32u - min(cnt_, 32u);
-                const unsigned at = szPre[q_] + atomicAdd(&szFill[q_], cnt_);
-                const unsigned w_ = min(at / max(chunk, 1u), (unsigned)nsolve - 1u);
-                islWave[b] = (unsigned char)w_;
-                atomicAdd(&misc[M_WCNT + w_], cnt_);
+            if constexpr (BINS) {
+                unsigned st_[MAX_WAVES];        // (block-uniform; the words of the waves that do not sweep: never reached)
+#pragma unroll
+                for (int k = 0; k < MAX_WAVES; ++k) st_[k] = szTab[k];
+                const bool even = st_[0] != 0u;
+                for (int b = tid; b < N + M; b += nt) {
+                    if (parent[b] != (unsigned)b) continue;
+                    const unsigned cnt_ = islCnt[b];
+                    if (cnt_ == 0) continue;
+                    const unsigned q_ = 32u - min(cnt_, 32u);
+                    const unsigned at = szPre[q_] + atomicAdd(&szFill[q_], cnt_);
+                    unsigned w_ = 0;
+#pragma unroll
+                    for (int k = 1; k < MAX_WAVES; ++k) w_ += at >= st_[k] ? 1u : 0u;
+                    islWave[b] = (unsigned char)w_;
+                    if (even) atomicAdd(&misc[M_WCNT + w_], cnt_);
+                }
+            } else {
+                // the first nw - 1 waves get about 60 contacts each, the last one the remaining small islands
+                unsigned chunk = 60u;
+                if ((unsigned)ncon > 60u * (unsigned)(nw - 1) + 124u) chunk = ((unsigned)ncon - 124u + (unsigned)nw - 2u) / (unsigned)(nw - 1);
+                for (int b = tid; b < N + M; b += nt) {
+                    if (parent[b] != (unsigned)b) continue;
+                    const unsigned cnt_ = islCnt[b];
+                    if (cnt_ == 0) continue;
+                    const unsigned q_ = 32u - min(cnt_, 32u);
+                    const unsigned at = szPre[q_] + atomicAdd(&szFill[q_], cnt_);
+                    const unsigned w_ = min(at / max(chunk, 1u), (unsigned)nsolve - 1u);
+                    islWave[b] = (unsigned char)w_;
+                    atomicAdd(&misc[M_WCNT + w_], cnt_);
+                }
             }
             __syncthreads();
             maxw = 0;
@@ -2383,6 +2453,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         KB_STAMP_PRE(25);        // ... + waiting for the wave with the most position sweeps
 #ifdef KB_PROFILE
         if (BINS && reg && tid == 0) atomicAdd(&KB_PROF(9), misc[M_PROF]);   // deepest wave of the env (kb_regsolve_bins.inc: no barrier in front of this one)
+        // rounds of one sweep of the env's slowest wave (words from 13 on go out in units of 16); the running maximum starts over
+        if (BINS && reg && tid == 0) { atomicAdd(&KB_PROF(37), 16u * KB_PROF(38)); KB_PROF(38) = 0u; }
 #endif
         KB_RETID();
         KB_ABLATE_EXIT(13);    // position sweeps

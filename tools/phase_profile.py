@@ -97,6 +97,10 @@ def main():
     b_ = raw[:, 31:36].mean(0) * 16
     print('  sorted bins, wave 0, cumulative since the drive barrier: boundary scan %.0f, + scatter and barrier %.0f, + slots settled %.0f; since the offset scan: contacts staged %.0f, + barrier %.0f' % tuple(b_))
     print('  wave 0 per substep: keys %.1f, depth rounds/sweep %.1f (deepest wave of the env %.1f), position sweeps %.2f, reg-path fraction %.2f' % (ex[0], ex[4], ex[1], ex[2], ex[3]))
+    # sorted-bin register solver (kb_regsolve_bins.inc): a level that lies in both register slots of a wave is swept in two rounds
+    place = raw[:, [36, 37, 39]].mean(0)
+    print('  island placement per env-substep: waves with two register slots %.2f, rounds of one sweep (split levels included): '
+          'slowest wave %.2f, wave 0 %.2f' % tuple(place))
 
 
 if __name__ == '__main__':
