@@ -53,6 +53,9 @@ constexpr int KREG = KB_KREG;               // contacts a lane can keep in regis
 #ifndef KB_KREG_BINS
 #define KB_KREG_BINS (2 * KB_NSOLVE_DIV)                  // ... in the kernels without objects, where only half the waves of a workgroup sweep (kb_regsolve_bins.inc)
 #endif
+#ifndef KB_SETUP_FUSED
+#define KB_SETUP_FUSED 2                // register set-up of a wave of at most 64 contacts (A/B knob, see kb_regsolve_bins.inc): 0 = as a two-slot wave; 1 = one slot, loaded once; 2 = ... and its warm start rides in the depth rounds
+#endif
 
 enum { M_NCON = 0, M_TOTAL = 1, M_ANY = 2, M_STATUS = 3, M_MAXISL = 4, M_PROF = 5, M_XTRA = 6, M_XFILL = 7, M_WCNT = 8, M_WAKE = 32 /* .. 63: one bit per kilobot (sleeping; the -DKB_PROFILE build keeps its stamps there and does not implement the wake rule) */, M_WFILL = 8 + MAX_WAVES, M_COUNT = 8 + 2 * MAX_WAVES };
 static_assert(M_COUNT <= 64, "misc area");

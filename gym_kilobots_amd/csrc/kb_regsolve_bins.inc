@@ -35,6 +35,7 @@
     for (int j = 0; j < KRB; ++j) { slotLevels[j] = 0ull; dlo[j] = 1; dhi[j] = 0; }
     int maxD = 0;
     unsigned mycnt = 0;
+    bool twoSlot = false;           // (wave-uniform) the wave holds more than 64 contacts
     const float nm_bb = p.nm_bb, nm_wb = p.nm_wb;
 #ifdef KB_SOLVER_PRIO
     __builtin_amdgcn_s_setprio(KB_SOLVER_PRIO);     // the serial chain of the substep: ahead of the other envs' throughput phases
@@ -44,232 +45,344 @@
         // pointer at the end of its stretch of lOrder, so the stretch is two words read side by side. ----
         mycnt = misc[M_WCNT + wave];
         const unsigned mybase = misc[M_WFILL + wave] - mycnt;
-        unsigned lk[KRB];           // key (6) | rank (8) << 8 | staging index << 16 | valid << 31;  key 63: contact of a sleeping island
-        unsigned lp[KRB];           // a | b << 16 (body indices; a wall is WALL_CODE + w)
-        int rdepth[KRB];
-        unsigned klo[KRB], khi[KRB];    // the slot's key as a bit (none: no contact, or one of a sleeping island)
+        // A wave of at most 64 contacts -- since the packed placement most waves of an env, the deep ones among them -- holds
+        // nothing behind slot 0: it takes the one-slot set-up below.  The test is scalar and picks a whole version of every
+        // trip, so in a two-slot wave both slots still issue their loads together.
+        twoSlot = KB_SETUP_FUSED == 0 || (unsigned)__builtin_amdgcn_readfirstlane((int)mycnt) > 64u;
+        if (twoSlot) {
+            unsigned lk[KRB];          // key (6) | rank (8) << 8 | staging index << 16 | valid << 31;  key 63: contact of a sleeping island
+            unsigned lp[KRB];           // a | b << 16 (body indices; a wall is WALL_CODE + w)
+            int rdepth[KRB];
+            unsigned klo[KRB], khi[KRB];    // the slot's key as a bit (none: no contact, or one of a sleeping island)
 #define RB_A(j) ((int)(lp[j] & 0xFFFFu))
 #define RB_B(j) ((int)(lp[j] >> 16))
-        // Both slots go through every trip together: the lanes without a contact read entry 0 and drop what they get, so no
-        // slot waits under a branch of its own for the slot in front of it (as in label_pass_bins).
-        {
-            unsigned c_[KRB], inf_[KRB];
-            bool v_[KRB], awake_[KRB];
+            // Both slots go through every trip together: the lanes without a contact read entry 0 and drop what they get, so no
+            // slot waits under a branch of its own for the slot in front of it (as in label_pass_bins).
+            {
+                unsigned c_[KRB], inf_[KRB];
+                bool v_[KRB], awake_[KRB];
 #pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const unsigned idx = lane + 64u * j;
-                v_[j] = idx < mycnt;
-                c_[j] = lOrder[v_[j] ? mybase + idx : 0u];
+                for (int j = 0; j < KRB; ++j) {
+                    const unsigned idx = lane + 64u * j;
+                    v_[j] = idx < mycnt;
+                    c_[j] = lOrder[v_[j] ? mybase + idx : 0u];
+                }
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    c_[j] = v_[j] ? c_[j] : 0u;
+                    lp[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]];
+                }
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) { lp[j] = v_[j] ? lp[j] : 0u; awake_[j] = true; }
+                if (SLEEP) {
+                    unsigned root_[KRB];
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) root_[j] = parent[lp[j] >> 16];
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) awake_[j] = active[root_[j]] != 0;
+                }
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    const unsigned cls = inf_[j] & 0x7Fu, r = (inf_[j] >> 8) & 0xFFu;
+                    unsigned key = cls * RK + (r < RK - 1 ? r : RK - 1);
+                    const bool on = v_[j] && awake_[j];
+                    if (!on) key = 63u;     // in no round (depth 0), its impulse is carried over
+                    const unsigned bit = on ? 1u << (key & 31u) : 0u;
+                    klo[j] = key < 32u ? bit : 0u; khi[j] = key < 32u ? 0u : bit;
+                    if (on && r >= RK - 1) atomicMax(&bkMaxRank[wave * NUM_CLS + cls], r);
+                    lk[j] = v_[j] ? (key | (r << 8) | (c_[j] << 16) | 0x80000000u) : 0u;
+                    rdepth[j] = 0;
+                }
             }
+            // keys present in the wave, and those of them that the slots behind slot 0 hold as well (wave-uniform)
+            unsigned long long keymask = 0ull, restmask = 0ull;
+            {
+                unsigned mlo = 0, mhi = 0, rlo = 0, rhi = 0;
 #pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                c_[j] = v_[j] ? c_[j] : 0u;
-                lp[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]];
+                for (int j = 0; j < KRB; ++j) { mlo |= klo[j]; mhi |= khi[j]; if (j > 0) { rlo |= klo[j]; rhi |= khi[j]; } }
+                mlo = wave_or(mlo); mhi = wave_or(mhi);
+                keymask = ((unsigned long long)mhi << 32) | mlo;
+                if (mycnt > 64u) { rlo = wave_or(rlo); rhi = wave_or(rhi); restmask = ((unsigned long long)rhi << 32) | rlo; }
             }
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) { lp[j] = v_[j] ? lp[j] : 0u; awake_[j] = true; }
-            if (SLEEP) {
-                unsigned root_[KRB];
-#pragma unroll
-                for (int j = 0; j < KRB; ++j) root_[j] = parent[lp[j] >> 16];
-#pragma unroll
-                for (int j = 0; j < KRB; ++j) awake_[j] = active[root_[j]] != 0;
-            }
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const unsigned cls = inf_[j] & 0x7Fu, r = (inf_[j] >> 8) & 0xFFu;
-                unsigned key = cls * RK + (r < RK - 1 ? r : RK - 1);
-                const bool on = v_[j] && awake_[j];
-                if (!on) key = 63u;     // in no round (depth 0), its impulse is carried over
-                const unsigned bit = on ? 1u << (key & 31u) : 0u;
-                klo[j] = key < 32u ? bit : 0u; khi[j] = key < 32u ? 0u : bit;
-                if (on && r >= RK - 1) atomicMax(&bkMaxRank[wave * NUM_CLS + cls], r);
-                lk[j] = v_[j] ? (key | (r << 8) | (c_[j] << 16) | 0x80000000u) : 0u;
-                rdepth[j] = 0;
-            }
-        }
-        // keys present in the wave, and those of them that the slots behind slot 0 hold as well (wave-uniform)
-        unsigned long long keymask = 0ull, restmask = 0ull;
-        {
-            unsigned mlo = 0, mhi = 0, rlo = 0, rhi = 0;
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) { mlo |= klo[j]; mhi |= khi[j]; if (j > 0) { rlo |= klo[j]; rhi |= khi[j]; } }
-            mlo = wave_or(mlo); mhi = wave_or(mhi);
-            keymask = ((unsigned long long)mhi << 32) | mlo;
-            if (mycnt > 64u) { rlo = wave_or(rlo); rhi = wave_or(rhi); restmask = ((unsigned long long)rhi << 32) | rlo; }
-        }
-        wave_sync();   // bkMaxRank of this wave
+            wave_sync();   // bkMaxRank of this wave
 #ifdef KB_PROFILE
-        if (tid == 0) { atomicAdd(&KB_PROF(8), (unsigned)__popcll(keymask)); atomicAdd(&KB_PROF(11), 1u); }
+            if (tid == 0) { atomicAdd(&KB_PROF(8), (unsigned)__popcll(keymask)); atomicAdd(&KB_PROF(11), 1u); }
 #endif
-        KB_STAMP_PRE(19);    // (profile build) wave 0: contacts grouped + light load
-        // ---- dependency depth of every contact: 1 + the depth of the latest earlier contact (canonical key order) on either
-        // of its bodies.  Contacts of equal depth never share a body, and sweeping by increasing depth keeps the relative
-        // order of any two contacts that do -- so depth rounds give exactly the result of the key-by-key sweep. ----
-        unsigned *bodyDepth = islCnt;   // zeroed before the contacts were grouped
-        {
-            // A round is one LDS trip under the EXEC mask of the lanes whose contact is of the round: the round a contact
-            // belongs to (its key; in the open-ended rank bucket its key and rank) and the addresses of its two bodies are
-            // made once, a wall contact names its kilobot twice (max(d, d) + 1: the wall has no depth), a slot without a
-            // contact of the key is left out by a scalar test, and the highest ranks of the wave's open-ended buckets are
-            // fetched once, one class per lane.
-            char *const bdB = reinterpret_cast<char *>(bodyDepth);
+            KB_STAMP_PRE(19);    // (profile build) wave 0: contacts grouped + light load
+            // ---- dependency depth of every contact: 1 + the depth of the latest earlier contact (canonical key order) on either
+            // of its bodies.  Contacts of equal depth never share a body, and sweeping by increasing depth keeps the relative
+            // order of any two contacts that do -- so depth rounds give exactly the result of the key-by-key sweep. ----
+            unsigned *bodyDepth = islCnt;   // zeroed before the contacts were grouped
+            {
+                // A round is one LDS trip under the EXEC mask of the lanes whose contact is of the round: the round a contact
+                // belongs to (its key; in the open-ended rank bucket its key and rank) and the addresses of its two bodies are
+                // made once, a wall contact names its kilobot twice (max(d, d) + 1: the wall has no depth), a slot without a
+                // contact of the key is left out by a scalar test, and the highest ranks of the wave's open-ended buckets are
+                // fetched once, one class per lane.
+                char *const bdB = reinterpret_cast<char *>(bodyDepth);
 #define RB_BD(off) (*reinterpret_cast<unsigned *>(bdB + (off)))
-            unsigned rc[KRB], ia4[KRB], ib4[KRB];
+                unsigned rc[KRB], ia4[KRB], ib4[KRB];
 #pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const unsigned key = lk[j] & 63u, r = (lk[j] >> 8) & 0xFFu;
-                const bool on = (lk[j] >> 31) != 0u && key != 63u;
-                rc[j] = on ? ((key % RK) == RK - 1 ? (key | (r << 6)) : key) : 0xFFFFFFFFu;
-                ib4[j] = 4u * (unsigned)RB_B(j);
-                ia4[j] = RB_A(j) < WALL_CODE ? 4u * (unsigned)RB_A(j) : ib4[j];
-            }
-            const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
-            for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
-                const unsigned key_ = (unsigned)__builtin_ctzll(m_);
-                const bool rest_ = ((restmask >> key_) & 1ull) != 0ull;
-                auto depth_round = [&](unsigned code_) __attribute__((always_inline)) {
-                    // (the contacts of a round share no body: the slots may go one after the other)
+                for (int j = 0; j < KRB; ++j) {
+                    const unsigned key = lk[j] & 63u, r = (lk[j] >> 8) & 0xFFu;
+                    const bool on = (lk[j] >> 31) != 0u && key != 63u;
+                    rc[j] = on ? ((key % RK) == RK - 1 ? (key | (r << 6)) : key) : 0xFFFFFFFFu;
+                    ib4[j] = 4u * (unsigned)RB_B(j);
+                    ia4[j] = RB_A(j) < WALL_CODE ? 4u * (unsigned)RB_A(j) : ib4[j];
+                }
+                const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
+                for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
+                    const unsigned key_ = (unsigned)__builtin_ctzll(m_);
+                    const bool rest_ = ((restmask >> key_) & 1ull) != 0ull;
+                    auto depth_round = [&](unsigned code_) __attribute__((always_inline)) {
+                        // (the contacts of a round share no body: the slots may go one after the other)
 #pragma unroll
-                    for (int j = 0; j < KRB; ++j) {
-                        if (j == 0 || rest_) {
-                            if (rc[j] == code_) {
-                                const unsigned d = max(RB_BD(ia4[j]), RB_BD(ib4[j])) + 1u;
-                                rdepth[j] = (int)d;
-                                RB_BD(ib4[j]) = d;
-                                RB_BD(ia4[j]) = d;
+                        for (int j = 0; j < KRB; ++j) {
+                            if (j == 0 || rest_) {
+                                if (rc[j] == code_) {
+                                    const unsigned d = max(RB_BD(ia4[j]), RB_BD(ib4[j])) + 1u;
+                                    rdepth[j] = (int)d;
+                                    RB_BD(ib4[j]) = d;
+                                    RB_BD(ia4[j]) = d;
+                                }
                             }
                         }
+                        wave_sync();
+                    };
+                    if ((key_ % RK) < RK - 1) depth_round(key_);
+                    else {
+                        const unsigned maxr_ = (unsigned)__builtin_amdgcn_readlane((int)mrow, (int)(key_ / RK));
+                        for (unsigned r_ = RK - 1; r_ <= maxr_; ++r_) depth_round(key_ | (r_ << 6));
                     }
-                    wave_sync();
-                };
-                if ((key_ % RK) < RK - 1) depth_round(key_);
-                else {
-                    const unsigned maxr_ = (unsigned)__builtin_amdgcn_readlane((int)mrow, (int)(key_ / RK));
-                    for (unsigned r_ = RK - 1; r_ <= maxr_; ++r_) depth_round(key_ | (r_ << 6));
                 }
-            }
 #undef RB_BD
-        }
+            }
 #pragma unroll
-        for (int j = 0; j < KRB; ++j) maxD = max(maxD, rdepth[j]);
-        maxD = (int)wave_umax((unsigned)maxD);
-        KB_STAMP_PRE(20);    // ... + depth pass
-        // ---- deal the contacts to (lane, slot) in order of depth: the 64 shallowest go to slot 0, the next 64 to slot 1, ...
-        // A depth level then lives in one slot (two at a boundary), and a round only pays for the slots that hold contacts
-        // of its level. ----
-        if (mycnt > 64u) {
-            // the place of every contact first (ballots and lane counts, nothing waits for memory), then one write per slot,
-            // and both slots read back side by side
-            unsigned at[KRB];
+            for (int j = 0; j < KRB; ++j) maxD = max(maxD, rdepth[j]);
+            maxD = (int)wave_umax((unsigned)maxD);
+            KB_STAMP_PRE(20);    // ... + depth pass
+            // ---- deal the contacts to (lane, slot) in order of depth: the 64 shallowest go to slot 0, the next 64 to slot 1, ...
+            // A depth level then lives in one slot (two at a boundary), and a round only pays for the slots that hold contacts
+            // of its level. ----
+            if (mycnt > 64u) {
+                // the place of every contact first (ballots and lane counts, nothing waits for memory), then one write per slot,
+                // and both slots read back side by side
+                unsigned at[KRB];
 #pragma unroll
-            for (int j = 0; j < KRB; ++j) at[j] = 0u;
-            unsigned base_ = 0;
-            for (int d_ = SLEEP ? 0 : 1; d_ <= maxD; ++d_) {      // (depth 0: contacts of sleeping islands)
+                for (int j = 0; j < KRB; ++j) at[j] = 0u;
+                unsigned base_ = 0;
+                for (int d_ = SLEEP ? 0 : 1; d_ <= maxD; ++d_) {      // (depth 0: contacts of sleeping islands)
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) {
+                        const bool is = (lk[j] >> 31) && rdepth[j] == d_;
+                        const unsigned long long m_ = __ballot(is);
+                        const unsigned mine = __builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_, base_));
+                        at[j] = is ? mine : at[j];
+                        base_ += (unsigned)__popcll(m_);
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < KRB; ++j)
+                    if (lk[j] >> 31) {
+                        lOrder[mybase + at[j]] = (unsigned short)((lk[j] >> 16) & 0xFFFu);
+                        lCbk[mybase + at[j]] = (unsigned short)rdepth[j];
+                    }
+                wave_sync();
+                unsigned short o_[KRB], l_[KRB];
 #pragma unroll
                 for (int j = 0; j < KRB; ++j) {
-                    const bool is = (lk[j] >> 31) && rdepth[j] == d_;
-                    const unsigned long long m_ = __ballot(is);
-                    const unsigned mine = __builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_, base_));
-                    at[j] = is ? mine : at[j];
-                    base_ += (unsigned)__popcll(m_);
+                    const unsigned i_ = mybase + ((lk[j] >> 31) ? lane + 64u * j : 0u);
+                    o_[j] = lOrder[i_]; l_[j] = lCbk[i_];
                 }
-            }
-#pragma unroll
-            for (int j = 0; j < KRB; ++j)
-                if (lk[j] >> 31) {
-                    lOrder[mybase + at[j]] = (unsigned short)((lk[j] >> 16) & 0xFFFu);
-                    lCbk[mybase + at[j]] = (unsigned short)rdepth[j];
-                }
-            wave_sync();
-            unsigned short o_[KRB], l_[KRB];
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const unsigned i_ = mybase + ((lk[j] >> 31) ? lane + 64u * j : 0u);
-                o_[j] = lOrder[i_]; l_[j] = lCbk[i_];
-            }
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const bool v_ = (lk[j] >> 31) != 0u;
-                lk[j] = v_ ? ((lk[j] & 0x8000FFFFu) | ((unsigned)o_[j] << 16)) : lk[j];
-                rdepth[j] = v_ ? (int)l_[j] : rdepth[j];
-            }
-        }
-        KB_STAMP_PRE(21);    // ... + dealing
-        // depth levels present in every slot (bit min(depth, 63)), wave-uniform
-#pragma unroll
-        for (int j = 0; j < KRB; ++j) {
-            const unsigned long long mine = (lk[j] >> 31) ? 1ull << min(rdepth[j], 63) : 0ull;
-            const unsigned lo = wave_or((unsigned)mine), hi = wave_or((unsigned)(mine >> 32));
-            slotLevels[j] = ((unsigned long long)hi << 32) | (unsigned long long)lo;
-            // the levels of a slot are a contiguous range (the dealing above; without it everything sits in slot 0), and the
-            // ranges of successive slots follow each other: a sweep is slot 0's levels in order, then slot 1's, ... --
-            // contacts of one level never share a body, so a level split over two slots may run in two rounds.
-            const unsigned long long lv = slotLevels[j] >> 1;      // (level 0: contacts of sleeping islands, in no round)
-            dlo[j] = lv ? (int)__builtin_ctzll(lv) + 1 : 1;
-            dhi[j] = lv ? ((lv >> 62) ? maxD : 64 - (int)__builtin_clzll(lv)) : 0;
-        }
-        // ---- full load of the contacts ----
-        // Two trips for both slots together: the contact's words, then its bodies.  The lanes without a contact load
-        // contact 0 and body 0 and keep the idle record (no bodies, no impulse, normal (1, 0)).
-        {
-            unsigned c_[KRB], pr_[KRB], inf_[KRB], root_[KRB];
-            float acc_[KRB];
-            float2 pa_[KRB], pb_[KRB];
-            bool v_[KRB];
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                v_[j] = (lk[j] >> 31) != 0u;
-                c_[j] = v_[j] ? (lk[j] >> 16) & 0xFFFu : 0u;
-                pr_[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]]; acc_[j] = lAcc[c_[j]];
-            }
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                pr_[j] = v_[j] ? pr_[j] : 0u;
-                const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
-                pa_[j] = pos[a >= WALL_CODE ? b : a]; pb_[j] = pos[b]; root_[j] = parent[b];
-            }
-            bool pairOn[KRB];
-            float dx[KRB], dy[KRB], dd[KRB], wnx[KRB], wny[KRB];
-            bool ieee = false;
-#pragma unroll
-            for (int j = 0; j < KRB; ++j) {
-                const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
-                const bool wallA = a >= WALL_CODE, flip = (inf_[j] & 0x80u) != 0u;
-                ra[j] = wallA ? WOFF + 8u * (unsigned)(a - WALL_CODE) : 8u * (unsigned)a;
-                rb[j] = 8u * (unsigned)b;
-                racc[j] = v_[j] ? acc_[j] : 0.0f;
-                rm[j] = v_[j] ? (c_[j] | ((unsigned)rdepth[j] << 12) | (flip ? 1u << 21 : 0u) | (root_[j] << 22)) : 0u;
-                // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
-                float dist;
-                wall_geom(p, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
-                if (flip) { wnx[j] = -wnx[j]; wny[j] = -wny[j]; }
-                dx[j] = pb_[j].x - pa_[j].x; dy[j] = pb_[j].y - pa_[j].y;
-                dd[j] = dx[j] * dx[j] + dy[j] * dy[j];
-                pairOn[j] = v_[j] && !wallA && dd[j] > B2_EPSILON * B2_EPSILON;
-                ieee = ieee || (pairOn[j] && !kb_exact_guard(dd[j]));
-                if (wallA) { rnx[j] = wnx[j]; rny[j] = wny[j]; } else { rnx[j] = 1.0f; rny[j] = 0.0f; }
-            }
-            // the IEEE sequences of sqrtf and the division are two dozen dependent instructions; with every pair of the wave
-            // inside the proven range one correction step on the hardware seeds gives the same bits (kb_exact.h)
-            if (__builtin_expect(__builtin_amdgcn_ballot_w64(ieee) == 0ull, 1)) {
 #pragma unroll
                 for (int j = 0; j < KRB; ++j) {
-                    const float len = kb_sqrt_refine(dd[j], __builtin_amdgcn_sqrtf(dd[j]), __builtin_amdgcn_rsqf(dd[j]));
-                    const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
-                    if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < KRB; ++j) {
-                    const float len = sqrtf(dd[j]);
-                    const float inv = 1.0f / len;
-                    if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                    const bool v_ = (lk[j] >> 31) != 0u;
+                    lk[j] = v_ ? ((lk[j] & 0x8000FFFFu) | ((unsigned)o_[j] << 16)) : lk[j];
+                    rdepth[j] = v_ ? (int)l_[j] : rdepth[j];
                 }
             }
-        }
+            KB_STAMP_PRE(21);    // ... + dealing
+            // depth levels present in every slot (bit min(depth, 63)), wave-uniform
+#pragma unroll
+            for (int j = 0; j < KRB; ++j) {
+                const unsigned long long mine = (lk[j] >> 31) ? 1ull << min(rdepth[j], 63) : 0ull;
+                const unsigned lo = wave_or((unsigned)mine), hi = wave_or((unsigned)(mine >> 32));
+                slotLevels[j] = ((unsigned long long)hi << 32) | (unsigned long long)lo;
+                // the levels of a slot are a contiguous range (the dealing above; without it everything sits in slot 0), and the
+                // ranges of successive slots follow each other: a sweep is slot 0's levels in order, then slot 1's, ... --
+                // contacts of one level never share a body, so a level split over two slots may run in two rounds.
+                const unsigned long long lv = slotLevels[j] >> 1;      // (level 0: contacts of sleeping islands, in no round)
+                dlo[j] = lv ? (int)__builtin_ctzll(lv) + 1 : 1;
+                dhi[j] = lv ? ((lv >> 62) ? maxD : 64 - (int)__builtin_clzll(lv)) : 0;
+            }
+            // ---- full load of the contacts ----
+            // Two trips for both slots together: the contact's words, then its bodies.  The lanes without a contact load
+            // contact 0 and body 0 and keep the idle record (no bodies, no impulse, normal (1, 0)).
+            {
+                unsigned c_[KRB], pr_[KRB], inf_[KRB], root_[KRB];
+                float acc_[KRB];
+                float2 pa_[KRB], pb_[KRB];
+                bool v_[KRB];
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    v_[j] = (lk[j] >> 31) != 0u;
+                    c_[j] = v_[j] ? (lk[j] >> 16) & 0xFFFu : 0u;
+                    pr_[j] = lPair[c_[j]]; inf_[j] = lInfo[c_[j]]; acc_[j] = lAcc[c_[j]];
+                }
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    pr_[j] = v_[j] ? pr_[j] : 0u;
+                    const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
+                    pa_[j] = pos[a >= WALL_CODE ? b : a]; pb_[j] = pos[b]; root_[j] = parent[b];
+                }
+                bool pairOn[KRB];
+                float dx[KRB], dy[KRB], dd[KRB], wnx[KRB], wny[KRB];
+                bool ieee = false;
+#pragma unroll
+                for (int j = 0; j < KRB; ++j) {
+                    const int a = (int)(pr_[j] & 0xFFFFu), b = (int)(pr_[j] >> 16);
+                    const bool wallA = a >= WALL_CODE, flip = (inf_[j] & 0x80u) != 0u;
+                    ra[j] = wallA ? WOFF + 8u * (unsigned)(a - WALL_CODE) : 8u * (unsigned)a;
+                    rb[j] = 8u * (unsigned)b;
+                    racc[j] = v_[j] ? acc_[j] : 0.0f;
+                    rm[j] = v_[j] ? (c_[j] | ((unsigned)rdepth[j] << 12) | (flip ? 1u << 21 : 0u) | (root_[j] << 22)) : 0u;
+                    // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
+                    float dist;
+                    wall_geom(p, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
+                    if (flip) { wnx[j] = -wnx[j]; wny[j] = -wny[j]; }
+                    dx[j] = pb_[j].x - pa_[j].x; dy[j] = pb_[j].y - pa_[j].y;
+                    dd[j] = dx[j] * dx[j] + dy[j] * dy[j];
+                    pairOn[j] = v_[j] && !wallA && dd[j] > B2_EPSILON * B2_EPSILON;
+                    ieee = ieee || (pairOn[j] && !kb_exact_guard(dd[j]));
+                    if (wallA) { rnx[j] = wnx[j]; rny[j] = wny[j]; } else { rnx[j] = 1.0f; rny[j] = 0.0f; }
+                }
+                // the IEEE sequences of sqrtf and the division are two dozen dependent instructions; with every pair of the wave
+                // inside the proven range one correction step on the hardware seeds gives the same bits (kb_exact.h)
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(ieee) == 0ull, 1)) {
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) {
+                        const float len = kb_sqrt_refine(dd[j], __builtin_amdgcn_sqrtf(dd[j]), __builtin_amdgcn_rsqf(dd[j]));
+                        const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
+                        if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < KRB; ++j) {
+                        const float len = sqrtf(dd[j]);
+                        const float inv = 1.0f / len;
+                        if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                    }
+                }
+            }
 #undef RB_A
 #undef RB_B
+        } else {
+            // ---- one-slot wave: slot 1 keeps the idle record it starts with -- none of its loads, keys, masks, levels,
+            // geometry or refinements is issued -- and slot 0 is loaded once, in arrival order (nothing is dealt), in three
+            // trips in front of the depth pass: lOrder;  the contact's words;  its bodies.  The depth field of rm is filled by
+            // the round that assigns it, so nothing is read again behind the depth pass. ----
+            const bool v_ = lane < mycnt;
+            unsigned c_ = lOrder[v_ ? mybase + lane : 0u];
+            c_ = v_ ? c_ : 0u;
+            unsigned pr_ = lPair[c_];
+            const unsigned inf_ = lInfo[c_];
+            const float acc_ = lAcc[c_];
+            pr_ = v_ ? pr_ : 0u;
+            const int a = (int)(pr_ & 0xFFFFu), b = (int)(pr_ >> 16);
+            const bool wallA = a >= WALL_CODE, flip = (inf_ & 0x80u) != 0u;
+            const float2 pa_ = pos[wallA ? b : a], pb_ = pos[b];
+            const unsigned root_ = parent[b];
+            bool awake_ = true;
+            if (SLEEP) awake_ = active[root_] != 0;
+            // the round of the contact: its key, in the open-ended rank bucket its key and rank (none: no contact, or one of a
+            // sleeping island -- key 63, in no round, depth 0, its impulse is carried over)
+            const unsigned cls = inf_ & 0x7Fu, r = (inf_ >> 8) & 0xFFu;
+            const unsigned key = cls * RK + (r < RK - 1 ? r : RK - 1);
+            const bool on = v_ && awake_;
+            if (on && r >= RK - 1) atomicMax(&bkMaxRank[wave * NUM_CLS + cls], r);
+            const unsigned rc = on ? (r >= RK - 1 ? (key | (r << 6)) : key) : 0xFFFFFFFFu;
+            const unsigned bit = on ? 1u << (key & 31u) : 0u;
+            const unsigned long long keymask = ((unsigned long long)wave_or(key < 32u ? 0u : bit) << 32) | wave_or(key < 32u ? bit : 0u);
+            // the record, as the full load of a two-slot wave makes it
+            ra[0] = wallA ? WOFF + 8u * (unsigned)(a - WALL_CODE) : 8u * (unsigned)a;
+            rb[0] = 8u * (unsigned)b;
+            racc[0] = v_ ? acc_ : 0.0f;
+            rm[0] = v_ ? (c_ | (flip ? 1u << 21 : 0u) | (root_ << 22)) : 0u;
+            {
+                // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
+                float dist, wnx, wny;
+                wall_geom(p, wallA ? a - WALL_CODE : 0, pb_.x, pb_.y, dist, wnx, wny);
+                if (flip) { wnx = -wnx; wny = -wny; }
+                const float dx = pb_.x - pa_.x, dy = pb_.y - pa_.y;
+                const float dd = dx * dx + dy * dy;
+                const bool pairOn = v_ && !wallA && dd > B2_EPSILON * B2_EPSILON;
+                if (wallA) { rnx[0] = wnx; rny[0] = wny; } else { rnx[0] = 1.0f; rny[0] = 0.0f; }
+                // (one correction step on the hardware seeds where every pair of the wave is inside the proven range: kb_exact.h)
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(pairOn && !kb_exact_guard(dd)) == 0ull, 1)) {
+                    const float len = kb_sqrt_refine(dd, __builtin_amdgcn_sqrtf(dd), __builtin_amdgcn_rsqf(dd));
+                    const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
+                    if (pairOn) { rnx[0] = dx * inv; rny[0] = dy * inv; }
+                } else {
+                    const float len = sqrtf(dd);
+                    const float inv = 1.0f / len;
+                    if (pairOn) { rnx[0] = dx * inv; rny[0] = dy * inv; }
+                }
+            }
+            wave_sync();   // bkMaxRank of this wave
+#ifdef KB_PROFILE
+            if (tid == 0) { atomicAdd(&KB_PROF(8), (unsigned)__popcll(keymask)); atomicAdd(&KB_PROF(11), 1u); }
+#endif
+            KB_STAMP_PRE(19);    // (profile build) wave 0: contacts grouped + load
+            // ---- depth pass, as in a two-slot wave: one round per key present in the wave, in canonical order.  That is the
+            // order of b2ContactSolver::WarmStart, the contacts of a round share no body, and a contact's impulse acc * n depends
+            // on nothing another contact writes: every body sees the same sequence of v -+ im * P whether the warm start goes
+            // key by key or rides in these rounds.  So a lane whose contact is of the round also warm-starts its two bodies:
+            // two more reads beside the bodyDepth words, two more writes, the same trip -- and no warm-start pass of its own.
+            // (The expressions are those of the pass below: a wall is a body at rest with inverse mass 0.) ----
+            {
+                char *const bdB = reinterpret_cast<char *>(islCnt);     // bodyDepth: zeroed before the contacts were grouped
+#define RB_BD(off) (*reinterpret_cast<unsigned *>(bdB + (off)))
+                const unsigned ib4 = rb[0] >> 1, ia4 = wallA ? ib4 : ra[0] >> 1;       // (a wall has no depth: max(d, d) + 1)
+                const float Px = racc[0] * rnx[0], Py = racc[0] * rny[0];
+                const float ima = wallA ? 0.0f : p.im_bot;
+                const float dax = ima * Px, day = ima * Py, dbx = p.im_bot * Px, dby = p.im_bot * Py;
+                const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
+                unsigned depth_ = 0;
+                for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
+                    const unsigned key_ = (unsigned)__builtin_ctzll(m_);
+                    auto depth_round = [&](unsigned code_) __attribute__((always_inline)) {
+                        if (rc == code_) {
+                            const unsigned d = max(RB_BD(ia4), RB_BD(ib4)) + 1u;
+                            if (KB_SETUP_FUSED >= 2) {
+                                const float2 va = RB_VEL(ra[0]), vb = RB_VEL(rb[0]);
+                                RB_VEL(ra[0]) = make_float2(va.x - dax, va.y - day);
+                                RB_VEL(rb[0]) = make_float2(vb.x + dbx, vb.y + dby);
+                            }
+                            depth_ = d;
+                            RB_BD(ib4) = d;
+                            RB_BD(ia4) = d;
+                        }
+                        wave_sync();
+                    };
+                    if ((key_ % RK) < RK - 1) depth_round(key_);
+                    else {
+                        const unsigned maxr_ = (unsigned)__builtin_amdgcn_readlane((int)mrow, (int)(key_ / RK));
+                        for (unsigned r_ = RK - 1; r_ <= maxr_; ++r_) depth_round(key_ | (r_ << 6));
+                    }
+                }
+#undef RB_BD
+                rm[0] |= depth_ << 12;
+                maxD = (int)wave_umax(depth_);
+                KB_STAMP_PRE(20);    // ... + depth pass with the warm start in its rounds
+                KB_STAMP_PRE(21);    // (nothing is dealt)
+                // depth levels present in slot 0 (bit min(depth, 63)); slot 1 holds none
+                const unsigned long long mine = v_ ? 1ull << min(depth_, 63u) : 0ull;
+                slotLevels[0] = ((unsigned long long)wave_or((unsigned)(mine >> 32)) << 32) | (unsigned long long)wave_or((unsigned)mine);
+                const unsigned long long lv = slotLevels[0] >> 1;      // (level 0: contacts of sleeping islands, in no round)
+                dlo[0] = lv ? (int)__builtin_ctzll(lv) + 1 : 1;
+                dhi[0] = lv ? ((lv >> 62) ? maxD : 64 - (int)__builtin_clzll(lv)) : 0;
+            }
+        }
 #ifdef KB_PROFILE
         if (lane == 0) atomicMax(&misc[M_PROF], (unsigned)maxD);
         if (tid == 0) atomicAdd(&KB_PROF(M_PROF_DEPTH), (unsigned)maxD);
@@ -286,27 +399,29 @@
         KB_STAMP(7);    // register load + depth sweep of wave 0 (no barrier: wave-local time)
 #endif
     }
-    KB_ABLATE_EXIT(9);     // register set-up: light load, depth pass, dealing, full load
+    KB_ABLATE_EXIT(9);     // register set-up: light load, depth pass, dealing, full load -- and the warm start of the one-slot waves
     // one round of a sweep on slot j: the contacts of depth level d_ (a contact with depth 0 -- none, or of a sleeping island -- is in no round)
 #define RB_ON(j) (RB_DEPTH(j) == d_)
     if (solving) {
-        // b2ContactSolver::WarmStart
+        // b2ContactSolver::WarmStart of the two-slot waves, level by level (a one-slot wave has done it in its depth rounds)
+        if (twoSlot || KB_SETUP_FUSED < 2) {
 #pragma unroll
-        for (int j = 0; j < KRB; ++j) {
-            for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
-                if (RB_ON(j)) {
-                    const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
-                    const float Px = racc[j] * rnx[j], Py = racc[j] * rny[j];
-                    const float ima = RB_WALL(j) ? 0.0f : p.im_bot;
-                    RB_VEL(ra[j]) = make_float2(va.x - ima * Px, va.y - ima * Py);
-                    RB_VEL(rb[j]) = make_float2(vb.x + p.im_bot * Px, vb.y + p.im_bot * Py);
+            for (int j = 0; j < KRB; ++j) {
+                for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
+                    if (RB_ON(j)) {
+                        const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
+                        const float Px = racc[j] * rnx[j], Py = racc[j] * rny[j];
+                        const float ima = RB_WALL(j) ? 0.0f : p.im_bot;
+                        RB_VEL(ra[j]) = make_float2(va.x - ima * Px, va.y - ima * Py);
+                        RB_VEL(rb[j]) = make_float2(vb.x + p.im_bot * Px, vb.y + p.im_bot * Py);
+                    }
+                    wave_sync();
                 }
-                wave_sync();
             }
         }
-        KB_STAMP_PRE(29);    // (profile build) warm start of wave 0, since the register set-up
+        KB_STAMP_PRE(29);    // (profile build) warm-start pass of wave 0, since the register set-up (a one-slot wave: nothing left to do)
     }
-    KB_ABLATE_EXIT(10);    // warm start
+    KB_ABLATE_EXIT(10);    // warm-start pass of the two-slot waves
     if (solving) {
         // SolveVelocityConstraints: friction 0, restitution 0, one manifold point.  Only the lanes whose contact is of the round's
         // level execute (EXEC mask); a wall is a body at rest with inverse mass 0 (its "velocity" is rewritten as 0 - 0 * P).

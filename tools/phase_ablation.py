@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PHASES = ['(launch + state load)', 'drive law + bin counters', 'bins sorted (scan, scatter, settle)', 'find owned contacts', 'packed-list offsets (scan)',
           'stage contacts (owner)', 'label: impulses + island hooking', 'flatten roots', 'census + placement + group by wave',
-          'register set-up (load, depth, dealing)', 'warm start', '10 velocity sweeps', 'store + integrate', 'position sweeps',
+          'register set-up (load, depth, dealing; one-slot waves: with their warm start)', 'warm-start pass (two-slot waves)', '10 velocity sweeps', 'store + integrate', 'position sweeps',
           'continuous step', 'end of substep + write-back']
 STATE = '/tmp/kb_abl_state.pt'
 

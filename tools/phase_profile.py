@@ -86,9 +86,14 @@ def main():
     pre = raw[:, 16:19].mean(0) * 16
     print('  wave 0 before the barrier (own work): drive+grid %.0f, count pass %.0f, emit pass %.0f' % tuple(pre))
     sub_ = raw[:, 19:22].mean(0) * 16
-    print('  wave 0 inside the register set-up, cumulative since the sort barrier: light load %.0f, + depth pass %.0f, + dealing %.0f' % tuple(sub_))
+    # (kb_regsolve_bins.inc) where wave 0 holds at most 64 contacts it loads its one slot once, in front of the depth pass -- 'load' is
+    # then the whole load, normals included --, warm-starts inside the depth rounds and deals nothing; a two-slot wave 0 has the light
+    # load there, the dealing behind the depth pass and the full load behind that (the rest of 'reg load+depth')
+    print('  wave 0 inside the register set-up, cumulative since the sort barrier: load (one slot: all of it; two slots: light load) %.0f, '
+          '+ depth pass (one slot: with the warm start in its rounds) %.0f, + dealing (two slots only) %.0f' % tuple(sub_))
     fine = raw[:, 24:31].mean(0) * 16
-    print('  since the register set-up: warm start %.0f, + 10 velocity sweeps of wave 0 %.0f (then its impulses and its integration, no barrier)' % (fine[5], fine[6]))
+    print('  since the register set-up: warm-start pass (two-slot wave 0 only; a one-slot wave has none) %.0f, + 10 velocity sweeps of wave 0 %.0f '
+          '(then its impulses and its integration, no barrier)' % (fine[5], fine[6]))
     print('  velocity + integrate + position of the env-substep (wave 0\'s warm start to the barrier behind the position sweeps) %.0f'
           % (mean[4] + mean[5] + fine[1]))
     print('  since wave 0\'s own integration: own position sweeps %.0f, + the barrier behind them (the env\'s slowest wave through velocity, '
