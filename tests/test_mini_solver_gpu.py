@@ -1,47 +1,23 @@
 """The HIP path itself (through the C ABI) against the INDEPENDENT restatement of Box2D's step (tools/box2d_mini.py,
 tests/golden/mini_solver.json): the same fixtures that pin the oracle on the CPU, replayed on the device with the same
-float32 tolerances -- discrete solver, friction, block solver, polygon / circle / wall manifolds, continuous step."""
+float32 tolerances -- discrete solver, friction, block solver, polygon / circle / wall manifolds, polygons made by
+b2PolygonShape::Set, compound bodies, and the continuous step of circles AND polygons (the mini-solver runs Box2D's general
+b2TimeOfImpact on b2Distance there; the device its closed-form support-vertex distance).  The scenes come through
+tests/mini_scenes.py, which builds the configuration from the object CLASSES the way the env does.
+
+The polygon / compound / polygon-TOI scenes (those with a derived tolerance) are additionally held to the oracle bit for bit
+at every step, with the comparison of the parity tests: a tolerance hit in the first test then says "the restatement of
+Box2D is wrong" (oracle and kernel share it), not "the port is wrong"."""
 import numpy as np
 import pytest
 import torch
 
-from oracle import oracle as O
+from tests import mini_scenes as MS
 from tests.test_oracle_vs_mini_solver import FIX
 
 pytestmark = pytest.mark.gpu
 
-
-def _sim_for(sc):
-    from gym_kilobots_amd.sim import KilobotSim
-    objs = sc['objects']
-    kw = dict(toi_walls=1 if sc.get('toi') else 0, damping_model=1 if sc['damping'] == 'linear' else 0,
-              allow_sleep=1 if sc.get('sleep') else 0)
-    if objs:
-        pad = O.MAX_OBJECTS - len(objs)
-        kw.update(num_objects=len(objs),
-                  obj_shape=[O.SHAPE_CIRCLE if o['shape'] == 'circle' else O.SHAPE_BOX for o in objs] + [0] * pad,
-                  obj_nverts=[0 if o['shape'] == 'circle' else 4 for o in objs] + [0] * pad,
-                  obj_radius=[(o['r'] / 25.0) if o['shape'] == 'circle' else 0.0 for o in objs] + [0.075] * pad,
-                  obj_verts=[[[0.0, 0.0]] if o['shape'] == 'circle' else [[o['hx'], o['hy']]] for o in objs] + [[[0.0, 0.0]]] * pad)
-    kb = np.array(sc['kilobots'], np.float64)
-    mixed = kb.shape[1] > 5
-    if mixed:
-        kw.update(mode_density=[2.0, 2.0, 1.0, 1.0, 1.0])
-    g = KilobotSim(1, len(kb), O.DRIVE_MIXED if mixed else O.DRIVE_VELOCITY, **kw)
-    dev = g.x.device
-    if mixed:
-        g.bot_mode.copy_(torch.tensor(np.where(kb[None, :, 5] == 2.0, O.DRIVE_VELOCITY, O.DRIVE_MOTORS), dtype=torch.uint8, device=dev))
-        g.motor_l.zero_()
-        g.motor_r.zero_()
-    g.x.copy_(torch.tensor(kb[None, :, 0], dtype=torch.float32, device=dev))
-    g.y.copy_(torch.tensor(kb[None, :, 1], dtype=torch.float32, device=dev))
-    g.theta.copy_(torch.tensor(kb[None, :, 2], dtype=torch.float32, device=dev))
-    g.forget_contacts()
-    g.set_actions(torch.tensor(kb[None, :, 3:5], dtype=torch.float32, device=dev).contiguous())
-    for name, key in (('ox', 'x'), ('oy', 'y'), ('otheta', 'theta'), ('ovx', 'vx'), ('ovy', 'vy'), ('ow', 'w')):
-        if objs:
-            getattr(g, name).copy_(torch.tensor([[o[key] for o in objs]], dtype=torch.float32, device=dev))
-    return g
+_sim_for = MS.sim_for
 
 
 @pytest.mark.parametrize('name', sorted(FIX))
@@ -71,4 +47,20 @@ def test_hip_path_follows_the_independent_solver(name):
             assert np.abs(o[:, :2] - w[:, :2]).max() <= tol, (name, k, 'object position')
             assert np.abs(o[:, 2] - w[:, 2]).max() <= 10 * tol, (name, k, 'object angle')
             assert np.abs(o[:, 3:] - w[:, 3:]).max() <= 200 * tol, (name, k, 'object velocity')
+    assert int(g.status.max().item()) == 0
+
+
+@pytest.mark.parametrize('name', sorted(n for n in FIX if 'f32_f64_gap' in FIX[n]))
+def test_hip_path_equals_the_oracle_bit_for_bit(name):
+    """Poses, object poses and velocities, the manifold impulses with their feature ids (`ows_acc`), the kilobots' warm-start
+    store and `status`, after every single-substep launch."""
+    from tests.test_parity_gpu import OBJ_FIELDS, assert_same, assert_ws_same
+    sc = FIX[name]
+    assert len(sc['kilobots']) <= 3 and len(sc['trajectory']) <= 80
+    o, g = MS.oracle_for(sc), MS.sim_for(sc, debug_outputs=True)
+    for k in range(len(sc['trajectory'])):
+        o.step(1)
+        g.step(1)
+        assert_same(o, g, '%s step %d' % (name, k), OBJ_FIELDS + ('status',))
+        assert_ws_same(o, g, '%s step %d' % (name, k))
     assert int(g.status.max().item()) == 0

@@ -12,41 +12,71 @@ It is NOT Box2D: box2d-py cannot be installed here, so this is still a restateme
 What it buys is independence: two derivations agreeing on contact manifolds, effective masses, the friction / block
 solver, warm starting by feature id, position correction and the integrator.
 
-Scope: b2World::Step(dt, velIters, posIters) with allowSleep = False, no gravity, no joints; continuousPhysics optional
-(World(continuous=True)): b2World::SolveTOI for CIRCLES against the static edges (non-bullet bodies only meet static bodies
-there): b2TimeOfImpact with the closed-form circle-centre / edge separation, b2Body::Advance, the TOI mini-island with
+Scope: b2World::Step(dt, velIters, posIters), allowSleep optional, no gravity, no joints; continuousPhysics optional
+(World(continuous=True)): b2World::SolveTOI for every fixture of a dynamic body against the static edges (non-bullet bodies
+only meet static bodies there), each contact under Box2D's cap of b2_maxSubSteps = 8: circles take the closed-form
+circle-centre / edge separation (time_of_impact_edge_circle); polygons, compound bodies included, take the general route in
+Box2D's own structure -- b2TimeOfImpact (sweeps with local centre and b2Sweep::Normalize, target = max(slop, total radius -
+3 slop), tolerance slop / 4, outer loop of 20, push-back loop of b2_maxPolygonVertices, 50-step bisection / secant root
+finder, all five output states) on b2Distance (proxies of a circle, a polygon and an edge as a chain child; the simplex with
+its 1-, 2- and 3-point solvers and its cache; 20 iterations; the duplicate-support exit; useRadii = false) and
+b2SeparationFunction with its three types e_points / e_faceA / e_faceB.  Then b2Body::Advance, the TOI mini-island with
 b2ContactSolver::SolveTOIPositionConstraints (Baumgarte 0.75, 20 iterations), a velocity solve without warm starting and the
-integration of the rest of the step; polygons take no part in the continuous step here.  Discrete step:
+integration of the rest of the step.  tests/test_mini_toi_closed_form.py holds the general route to the closed form on
+edge-circle sweeps.  b2PolygonShape::Set is complete (Polygon.set: welding, gift-wrapped hull from the right-most point,
+normals, centroid), so a polygon may be given clockwise and from any vertex.  set_precision(64) reruns everything in
+float64: the gap to the float32 run is the restatement's own rounding sensitivity, from which the generator derives the
+tolerances of the polygon scenes.  Discrete step:
   b2CollideCircles, b2CollidePolygonAndCircle, b2CollidePolygons, b2CollideEdgeAndCircle, b2CollideEdgeAndPolygon for a
   lone edge (no ghost vertices), b2Contact::Update (impulses carried over by feature id), b2Island::Solve (damping model
   selectable: Pade of 2.3.1 or the clamped linear form of 2.3.0), b2ContactSolver (friction, restitution threshold,
   2-point block solver with its four cases), position solver with Baumgarte 0.2, translation / rotation clamps.
-All arithmetic is numpy.float32, one rounding per operation, in the operation order of the C++ source as far as the
+All arithmetic is numpy.float32 by default, one rounding per operation, in the operation order of the C++ source as far as the
 author recalls it; comparisons with the oracle therefore use a tolerance, not bit equality.
 """
 import math
+import os
 
 import numpy as np
 
-f32 = np.float32
-PI = f32(3.14159265359)
-LINEAR_SLOP = f32(0.005)
-ANGULAR_SLOP = f32(2.0 / 180.0) * PI
-POLYGON_RADIUS = f32(2.0) * LINEAR_SLOP
+MAX_POLYGON_VERTICES = 8
 MAX_MANIFOLD_POINTS = 2
-VELOCITY_THRESHOLD = f32(1.0)
-BAUMGARTE = f32(0.2)
-MAX_LINEAR_CORRECTION = f32(0.2)
-MAX_TRANSLATION = f32(2.0)
-MAX_ROTATION = f32(0.5) * PI
-TIME_TO_SLEEP = f32(0.5)                                     # b2_timeToSleep
-LINEAR_SLEEP_TOLERANCE = f32(0.01)                           # b2_linearSleepTolerance
-ANGULAR_SLEEP_TOLERANCE = f32(2.0) / f32(180.0) * PI         # b2_angularSleepTolerance
-EPSILON = f32(1.192092896e-07)
-TOI_BAUMGARTE = f32(0.75)
 MAX_SUB_STEPS = 8
 MAX_TOI_CONTACTS = 32
-MAXFLOAT = f32(3.402823466e+38)
+
+
+def set_precision(bits):
+    """The precision switch: 32 (the default) makes every f32(...) and every constant numpy.float32, 64 makes them
+    numpy.float64 (same algorithm, same constants, no float32 rounding).  The difference between the two runs of a scene is
+    the restatement's own rounding sensitivity there.  BOX2D_MINI_PRECISION=64 selects float64 at import."""
+    global f32, PI, LINEAR_SLOP, ANGULAR_SLOP, POLYGON_RADIUS, VELOCITY_THRESHOLD, BAUMGARTE, MAX_LINEAR_CORRECTION
+    global MAX_TRANSLATION, MAX_ROTATION, TIME_TO_SLEEP, LINEAR_SLEEP_TOLERANCE, ANGULAR_SLEEP_TOLERANCE, EPSILON
+    global TOI_BAUMGARTE, MAXFLOAT
+    if int(bits) not in (32, 64):
+        raise ValueError('precision is 32 or 64 bits')
+    f32 = np.float32 if int(bits) == 32 else np.float64
+    PI = f32(3.14159265359)
+    LINEAR_SLOP = f32(0.005)
+    ANGULAR_SLOP = f32(2.0 / 180.0) * PI
+    POLYGON_RADIUS = f32(2.0) * LINEAR_SLOP
+    VELOCITY_THRESHOLD = f32(1.0)
+    BAUMGARTE = f32(0.2)
+    MAX_LINEAR_CORRECTION = f32(0.2)
+    MAX_TRANSLATION = f32(2.0)
+    MAX_ROTATION = f32(0.5) * PI
+    TIME_TO_SLEEP = f32(0.5)                                     # b2_timeToSleep
+    LINEAR_SLEEP_TOLERANCE = f32(0.01)                           # b2_linearSleepTolerance
+    ANGULAR_SLEEP_TOLERANCE = f32(2.0) / f32(180.0) * PI         # b2_angularSleepTolerance
+    EPSILON = f32(1.192092896e-07)
+    TOI_BAUMGARTE = f32(0.75)
+    MAXFLOAT = f32(3.402823466e+38)
+
+
+def precision():
+    return 32 if f32 is np.float32 else 64
+
+
+set_precision(os.environ.get('BOX2D_MINI_PRECISION', '32'))
 
 
 # ---------------------------------------------------------------------------------------------- b2Math
@@ -164,6 +194,54 @@ class Polygon:
         p.centroid = _centroid(p.vertices)
         return p
 
+    @staticmethod
+    def set(points):
+        """b2PolygonShape::Set for points in any order and rotation direction: weld points closer than half a linear slop
+        (Box2D 2.3.1 itself compares the SQUARED distance with 0.5 * b2_linearSlop, which welds up to 0.05 apart; no shape
+        here has vertices that close, so the two readings agree), gift-wrap the convex hull counter-clockwise from the
+        right-most point (the lowest one on a tie), then normals and centroid."""
+        ps = []
+        for x, y in points[:MAX_POLYGON_VERTICES]:
+            v = V(x, y)
+            half = f32(0.5) * LINEAR_SLOP
+            if all(dist_sq(v, q) >= half * half for q in ps):
+                ps.append(v)
+        n = len(ps)
+        assert n >= 3, 'degenerate polygon (Box2D falls back to a unit box)'
+        i0, x0 = 0, ps[0].x
+        for i in range(1, n):
+            x = ps[i].x
+            if x > x0 or (x == x0 and ps[i].y < ps[i0].y):
+                i0, x0 = i, x
+        hull, ih = [], i0
+        while True:
+            hull.append(ih)
+            ie = 0
+            for j in range(1, n):
+                if ie == ih:
+                    ie = j
+                    continue
+                r = ps[ie] - ps[ih]
+                v = ps[j] - ps[ih]
+                c = cross(r, v)
+                if c < 0.0:
+                    ie = j
+                if c == 0.0 and v.length_sq() > r.length_sq():       # collinear: keep the farther point
+                    ie = j
+            ih = ie
+            if ie == i0:
+                break
+        assert len(hull) >= 3, 'degenerate polygon (Box2D falls back to a unit box)'
+        p = Polygon()
+        p.vertices = [ps[i].copy() for i in hull]
+        m = len(p.vertices)
+        for i in range(m):
+            edge = p.vertices[(i + 1) % m] - p.vertices[i]
+            assert edge.length_sq() > EPSILON * EPSILON
+            p.normals.append(cross_vs(edge, 1.0).normalized())
+        p.centroid = _centroid(p.vertices)
+        return p
+
     def compute_mass(self, density):
         """b2PolygonShape::ComputeMass: triangle fan about the average vertex."""
         n = len(self.vertices)
@@ -266,12 +344,16 @@ class Body:
             self.set_awake(True)
         self.w = w
 
-    def advance(self, alpha):
-        """b2Body::Advance -> b2Sweep::Advance + SynchronizeTransform"""
+    def advance_sweep(self, alpha):
+        """b2Sweep::Advance: the start of the sweep moves to time alpha, its end stays"""
         beta = (f32(alpha) - self.alpha0) / (f32(1.0) - self.alpha0)
         self.c0 = self.c0 + beta * (self.c - self.c0)
         self.a0 = self.a0 + beta * (self.a - self.a0)
         self.alpha0 = f32(alpha)
+
+    def advance(self, alpha):
+        """b2Body::Advance -> b2Sweep::Advance + SynchronizeTransform"""
+        self.advance_sweep(alpha)
         self.c, self.a = self.c0.copy(), self.a0
         self.synchronize_transform()
 
@@ -638,6 +720,7 @@ class Contact:
         self.fA, self.fB, self.fn = _evaluate(fA, fB)
         self.manifold = Manifold()
         self.touching = False
+        self.enabled = True                        # b2Contact::e_enabledFlag
         self.toi, self.toi_valid, self.toi_count = f32(1.0), False, 0
         self.friction = f32(np.sqrt(self.fA.friction * self.fB.friction))          # b2MixFriction
         self.restitution = max(self.fA.restitution, self.fB.restitution)           # b2MixRestitution
@@ -645,6 +728,7 @@ class Contact:
     def update(self):
         """b2Contact::Update: new manifold, impulses of points with a matching id carried over."""
         old = self.manifold
+        self.enabled = True                        # "re-enable this contact"
         bA, bB = self.fA.body, self.fB.body
         new = self.fn(self.fA.shape, bA.xf, self.fB.shape, bB.xf)
         if new.type is None:
@@ -701,7 +785,7 @@ class World:
             self._solve_toi(dt, vel_iters)
         self.inv_dt0 = f32(1.0) / dt
 
-    # ------------------------------------------------------------------ b2World::SolveTOI (circles against static edges)
+    # ------------------------------------------------------------------ b2World::SolveTOI (dynamic bodies against static edges)
     def _solve_toi(self, dt, vel_iters):
         for b in self.bodies:
             b.alpha0 = f32(0.0)
@@ -710,7 +794,7 @@ class World:
         while True:
             min_c, min_alpha = None, f32(1.0)
             for c in self.contacts:
-                if c.toi_count > MAX_SUB_STEPS:
+                if not c.enabled or c.toi_count > MAX_SUB_STEPS:
                     continue
                 if c.toi_valid:
                     alpha = c.toi
@@ -721,14 +805,16 @@ class World:
                         continue
                     if not ((bA.dynamic and bA.awake) or (bB.dynamic and bB.awake)):
                         continue                                   # b2World::SolveTOI: "is there a reason to collide?"
-                    if not (c.fA.shape.kind == 'edge' and c.fB.shape.kind == 'circle'):
-                        continue                                   # (polygons: not covered by this restatement)
-                    alpha0 = max(bA.alpha0, bB.alpha0)
+                    alpha0 = max(bA.alpha0, bB.alpha0)            # put the sweeps onto the same time interval
                     if bA.alpha0 < alpha0:
-                        bA.advance(alpha0)
+                        bA.advance_sweep(alpha0)
                     elif bB.alpha0 < alpha0:
-                        bB.advance(alpha0)
-                    state, beta = time_of_impact_edge_circle(c.fA.shape, bA, c.fB.shape, bB)
+                        bB.advance_sweep(alpha0)
+                    if c.fA.shape.kind == 'edge' and c.fB.shape.kind == 'circle':
+                        state, beta = time_of_impact_edge_circle(c.fA.shape, bA, c.fB.shape, bB)      # closed form
+                    else:                                          # every fixture of a body against every edge
+                        state, beta = time_of_impact(DistanceProxy(c.fA.shape), Sweep.of(bA),
+                                                     DistanceProxy(c.fB.shape), Sweep.of(bB))
                     alpha = min(alpha0 + (f32(1.0) - alpha0) * beta, f32(1.0)) if state == 'touching' else f32(1.0)
                     c.toi, c.toi_valid = alpha, True
                 if alpha < min_alpha:
@@ -742,7 +828,8 @@ class World:
             min_c.update()
             min_c.toi_valid = False
             min_c.toi_count += 1
-            if not min_c.touching:
+            if not min_c.touching:                                 # not an event after all: undo, and leave the contact out
+                min_c.enabled = False
                 for b, c0, a0, c, a, al in backup:
                     b.c0, b.a0, b.c, b.a, b.alpha0 = c0, a0, c, a, al
                     b.synchronize_transform()
@@ -1196,6 +1283,338 @@ def time_of_impact_edge_circle(E, bA, C, bB):
         if done:
             break
     return 'failed', t1
+
+
+# ---------------------------------------------------------------------------------------------- b2Distance
+class DistanceProxy:
+    """b2DistanceProxy::Set: a circle is its centre, a polygon its vertices, an edge taken as a chain child its two end
+    points (b2ChainShape::GetChildEdge + b2DistanceProxy: two vertices, the ghost vertices play no part in GJK)."""
+
+    def __init__(self, shape):
+        if shape.kind == 'circle':
+            self.vertices = [shape.p]
+        elif shape.kind == 'polygon':
+            self.vertices = shape.vertices
+        else:
+            self.vertices = [shape.v1, shape.v2]
+        self.radius = shape.radius
+
+    def support(self, d):
+        """b2DistanceProxy::GetSupport"""
+        best, best_value = 0, dot(self.vertices[0], d)
+        for i in range(1, len(self.vertices)):
+            value = dot(self.vertices[i], d)
+            if value > best_value:
+                best, best_value = i, value
+        return best
+
+
+class SimplexCache:
+    """b2SimplexCache"""
+
+    def __init__(self):
+        self.metric, self.count, self.indexA, self.indexB = f32(0.0), 0, [0, 0, 0], [0, 0, 0]
+
+
+class _SV:
+    """b2SimplexVertex"""
+    __slots__ = ('wA', 'wB', 'w', 'a', 'indexA', 'indexB')
+
+    def __init__(self, proxyA, xfA, ia, proxyB, xfB, ib, a=0.0):
+        self.indexA, self.indexB = ia, ib
+        self.wA, self.wB = xf_mul(xfA, proxyA.vertices[ia]), xf_mul(xfB, proxyB.vertices[ib])
+        self.w = self.wB - self.wA
+        self.a = f32(a)
+
+
+class Simplex:
+    """b2Simplex"""
+
+    def __init__(self, cache, proxyA, xfA, proxyB, xfB):
+        """b2Simplex::ReadCache"""
+        self.v = [_SV(proxyA, xfA, cache.indexA[i], proxyB, xfB, cache.indexB[i]) for i in range(cache.count)]
+        if len(self.v) > 1:                      # a simplex that changed its size a lot is thrown away
+            metric1, metric2 = cache.metric, self.metric()
+            if metric2 < f32(0.5) * metric1 or f32(2.0) * metric1 < metric2 or metric2 < EPSILON:
+                self.v = []
+        if not self.v:
+            self.v = [_SV(proxyA, xfA, 0, proxyB, xfB, 0, 1.0)]
+
+    def write_cache(self, cache):
+        cache.metric, cache.count = self.metric(), len(self.v)
+        for i, sv in enumerate(self.v):
+            cache.indexA[i], cache.indexB[i] = sv.indexA, sv.indexB
+
+    def search_direction(self):
+        if len(self.v) == 1:
+            return -self.v[0].w
+        e12 = self.v[1].w - self.v[0].w
+        sgn = cross(e12, -self.v[0].w)
+        return cross_sv(1.0, e12) if sgn > 0.0 else cross_vs(e12, 1.0)
+
+    def closest_point(self):
+        if len(self.v) == 1:
+            return self.v[0].w.copy()
+        if len(self.v) == 2:
+            return self.v[0].a * self.v[0].w + self.v[1].a * self.v[1].w
+        return V()
+
+    def witness_points(self):
+        v = self.v
+        if len(v) == 1:
+            return v[0].wA.copy(), v[0].wB.copy()
+        if len(v) == 2:
+            return v[0].a * v[0].wA + v[1].a * v[1].wA, v[0].a * v[0].wB + v[1].a * v[1].wB
+        pA = v[0].a * v[0].wA + v[1].a * v[1].wA + v[2].a * v[2].wA
+        return pA, pA.copy()
+
+    def metric(self):
+        v = self.v
+        if len(v) == 1:
+            return f32(0.0)
+        if len(v) == 2:
+            return (v[0].w - v[1].w).length()
+        return cross(v[1].w - v[0].w, v[2].w - v[0].w)
+
+    def solve2(self):
+        """b2Simplex::Solve2: closest point of the segment w1 w2 to the origin in barycentric coordinates"""
+        v1, v2 = self.v
+        w1, w2 = v1.w, v2.w
+        e12 = w2 - w1
+        d12_2 = -dot(w1, e12)
+        if d12_2 <= 0.0:                         # vertex region of w1
+            v1.a = f32(1.0)
+            self.v = [v1]
+            return
+        d12_1 = dot(w2, e12)
+        if d12_1 <= 0.0:                         # vertex region of w2
+            v2.a = f32(1.0)
+            self.v = [v2]
+            return
+        inv = f32(1.0) / (d12_1 + d12_2)
+        v1.a, v2.a = d12_1 * inv, d12_2 * inv
+
+    def solve3(self):
+        """b2Simplex::Solve3: vertex regions, edge regions, interior"""
+        v1, v2, v3 = self.v
+        w1, w2, w3 = v1.w, v2.w, v3.w
+        e12 = w2 - w1
+        d12_1, d12_2 = dot(w2, e12), -dot(w1, e12)
+        e13 = w3 - w1
+        d13_1, d13_2 = dot(w3, e13), -dot(w1, e13)
+        e23 = w3 - w2
+        d23_1, d23_2 = dot(w3, e23), -dot(w2, e23)
+        n123 = cross(e12, e13)
+        d123_1, d123_2, d123_3 = n123 * cross(w2, w3), n123 * cross(w3, w1), n123 * cross(w1, w2)
+        one = f32(1.0)
+        if d12_2 <= 0.0 and d13_2 <= 0.0:
+            v1.a = one
+            self.v = [v1]
+        elif d12_1 > 0.0 and d12_2 > 0.0 and d123_3 <= 0.0:
+            inv = one / (d12_1 + d12_2)
+            v1.a, v2.a = d12_1 * inv, d12_2 * inv
+            self.v = [v1, v2]
+        elif d13_1 > 0.0 and d13_2 > 0.0 and d123_2 <= 0.0:
+            inv = one / (d13_1 + d13_2)
+            v1.a, v3.a = d13_1 * inv, d13_2 * inv
+            self.v = [v1, v3]
+        elif d12_1 <= 0.0 and d23_2 <= 0.0:
+            v2.a = one
+            self.v = [v2]
+        elif d13_1 <= 0.0 and d23_1 <= 0.0:
+            v3.a = one
+            self.v = [v3]
+        elif d23_1 > 0.0 and d23_2 > 0.0 and d123_1 <= 0.0:
+            inv = one / (d23_1 + d23_2)
+            v2.a, v3.a = d23_1 * inv, d23_2 * inv
+            self.v = [v3, v2]                    # Box2D: m_v1 = m_v3, m_v2 stays
+        else:
+            inv = one / (d123_1 + d123_2 + d123_3)
+            v1.a, v2.a, v3.a = d123_1 * inv, d123_2 * inv, d123_3 * inv
+
+
+def distance(cache, proxyA, xfA, proxyB, xfB):
+    """b2Distance with useRadii = false: GJK between the core shapes, warm-started from `cache`, which it rewrites.
+    Returns (pointA, pointB, distance, iterations)."""
+    simplex = Simplex(cache, proxyA, xfA, proxyB, xfB)
+    it = 0
+    while it < 20:                               # k_maxIters
+        saved = [(sv.indexA, sv.indexB) for sv in simplex.v]
+        if len(simplex.v) == 2:
+            simplex.solve2()
+        elif len(simplex.v) == 3:
+            simplex.solve3()
+        if len(simplex.v) == 3:                  # the origin is inside the triangle: overlap
+            break
+        d = simplex.search_direction()
+        if d.length_sq() < EPSILON * EPSILON:    # the origin is probably on a segment; the caller sees distance ~ 0
+            break
+        ia = proxyA.support(rot_mulT(xfA.q, -d))
+        ib = proxyB.support(rot_mulT(xfB.q, d))
+        it += 1
+        if (ia, ib) in saved:                    # the new support point is an old one: no progress possible
+            break
+        simplex.v.append(_SV(proxyA, xfA, ia, proxyB, xfB, ib))
+    pA, pB = simplex.witness_points()
+    simplex.write_cache(cache)
+    return pA, pB, (pA - pB).length(), it
+
+
+# ---------------------------------------------------------------------------------------------- b2TimeOfImpact
+class Sweep:
+    """b2Sweep: the motion of a body's centre of mass and angle over t in [0, 1]"""
+
+    def __init__(self, local_center, c0, a0, c, a, alpha0=0.0):
+        self.local_center, self.c0, self.a0, self.c, self.a = local_center, c0, f32(a0), c, f32(a)
+        self.alpha0 = f32(alpha0)
+
+    @staticmethod
+    def of(body):
+        return Sweep(body.local_center.copy(), body.c0.copy(), body.a0, body.c.copy(), body.a, body.alpha0)
+
+    def transform(self, beta):
+        """b2Sweep::GetTransform: interpolate the centre, then shift to the body origin"""
+        beta = f32(beta)
+        one = f32(1.0)
+        p = (one - beta) * self.c0 + beta * self.c
+        q = Rot((one - beta) * self.a0 + beta * self.a)
+        return XF(p - rot_mul(q, self.local_center), q)
+
+    def normalize(self):
+        """b2Sweep::Normalize: both angles shifted by the same multiple of 2 pi so that a0 lies in [0, 2 pi)"""
+        two_pi = f32(2.0) * PI
+        d = two_pi * f32(np.floor(self.a0 / two_pi))
+        self.a0, self.a = self.a0 - d, self.a - d
+
+
+class SeparationFunction:
+    """b2SeparationFunction: the separation of the two swept shapes along an axis fixed in one of them (or in the world),
+    chosen from the simplex that b2Distance left in the cache."""
+
+    def __init__(self, cache, proxyA, sweepA, proxyB, sweepB, t1):
+        """b2SeparationFunction::Initialize"""
+        self.proxyA, self.proxyB, self.sweepA, self.sweepB = proxyA, proxyB, sweepA, sweepB
+        xfA, xfB = sweepA.transform(t1), sweepB.transform(t1)
+        assert 0 < cache.count < 3
+        if cache.count == 1:
+            self.type = 'points'
+            pA = xf_mul(xfA, proxyA.vertices[cache.indexA[0]])
+            pB = xf_mul(xfB, proxyB.vertices[cache.indexB[0]])
+            self.axis = (pB - pA).normalized()
+            self.local_point = V()
+        elif cache.indexA[0] == cache.indexA[1]:
+            self.type = 'faceB'                  # two points on B, one on A
+            b1, b2 = proxyB.vertices[cache.indexB[0]], proxyB.vertices[cache.indexB[1]]
+            self.axis = cross_vs(b2 - b1, 1.0).normalized()
+            normal = rot_mul(xfB.q, self.axis)
+            self.local_point = f32(0.5) * (b1 + b2)
+            pB = xf_mul(xfB, self.local_point)
+            pA = xf_mul(xfA, proxyA.vertices[cache.indexA[0]])
+            if dot(pA - pB, normal) < 0.0:
+                self.axis = -self.axis
+        else:
+            self.type = 'faceA'                  # two points on A, one or two on B
+            a1, a2 = proxyA.vertices[cache.indexA[0]], proxyA.vertices[cache.indexA[1]]
+            self.axis = cross_vs(a2 - a1, 1.0).normalized()
+            normal = rot_mul(xfA.q, self.axis)
+            self.local_point = f32(0.5) * (a1 + a2)
+            pA = xf_mul(xfA, self.local_point)
+            pB = xf_mul(xfB, proxyB.vertices[cache.indexB[0]])
+            if dot(pB - pA, normal) < 0.0:
+                self.axis = -self.axis
+
+    def find_min_separation(self, t):
+        """b2SeparationFunction::FindMinSeparation: (separation, indexA, indexB) of the deepest vertices at time t"""
+        xfA, xfB = self.sweepA.transform(t), self.sweepB.transform(t)
+        if self.type == 'points':
+            ia = self.proxyA.support(rot_mulT(xfA.q, self.axis))
+            ib = self.proxyB.support(rot_mulT(xfB.q, -self.axis))
+        elif self.type == 'faceA':
+            ia, ib = -1, self.proxyB.support(rot_mulT(xfB.q, -rot_mul(xfA.q, self.axis)))
+        else:
+            ia, ib = self.proxyA.support(rot_mulT(xfA.q, -rot_mul(xfB.q, self.axis))), -1
+        return self._separation(ia, ib, xfA, xfB), ia, ib
+
+    def evaluate(self, ia, ib, t):
+        """b2SeparationFunction::Evaluate: the separation of the same two features at another time"""
+        return self._separation(ia, ib, self.sweepA.transform(t), self.sweepB.transform(t))
+
+    def _separation(self, ia, ib, xfA, xfB):
+        if self.type == 'points':
+            pA, pB = xf_mul(xfA, self.proxyA.vertices[ia]), xf_mul(xfB, self.proxyB.vertices[ib])
+            return dot(pB - pA, self.axis)
+        if self.type == 'faceA':
+            normal = rot_mul(xfA.q, self.axis)
+            pA, pB = xf_mul(xfA, self.local_point), xf_mul(xfB, self.proxyB.vertices[ib])
+            return dot(pB - pA, normal)
+        normal = rot_mul(xfB.q, self.axis)
+        pB, pA = xf_mul(xfB, self.local_point), xf_mul(xfA, self.proxyA.vertices[ia])
+        return dot(pA - pB, normal)
+
+
+def time_of_impact(proxyA, sweepA, proxyB, sweepB, t_max=1.0):
+    """b2TimeOfImpact (conservative advancement on the separation function).  Returns (state, t) with state one of
+    'failed' | 'overlapped' | 'touching' | 'separated' ('unknown' is the initial value and never comes back)."""
+    state, t_out = 'unknown', f32(t_max)
+    sweepA = Sweep(sweepA.local_center, sweepA.c0, sweepA.a0, sweepA.c, sweepA.a, sweepA.alpha0)
+    sweepB = Sweep(sweepB.local_center, sweepB.c0, sweepB.a0, sweepB.c, sweepB.a, sweepB.alpha0)
+    sweepA.normalize()                           # large angles hurt the root finder
+    sweepB.normalize()
+    t_max = f32(t_max)
+    total_radius = proxyA.radius + proxyB.radius
+    target = max(LINEAR_SLOP, total_radius - f32(3.0) * LINEAR_SLOP)
+    tolerance = f32(0.25) * LINEAR_SLOP
+    t1 = f32(0.0)
+    cache = SimplexCache()
+    outer = 0
+    while True:
+        xfA, xfB = sweepA.transform(t1), sweepB.transform(t1)
+        _, _, dist, _ = distance(cache, proxyA, xfA, proxyB, xfB)
+        if dist <= 0.0:                          # failure of the caller: the shapes already overlap
+            state, t_out = 'overlapped', f32(0.0)
+            break
+        if dist < target + tolerance:
+            state, t_out = 'touching', t1
+            break
+        fcn = SeparationFunction(cache, proxyA, sweepA, proxyB, sweepB, t1)
+        # the deepest point at t2 is pushed back to the target separation, one vertex after the other
+        done, t2 = False, t_max
+        for _push_back in range(MAX_POLYGON_VERTICES):
+            s2, ia, ib = fcn.find_min_separation(t2)
+            if s2 > target + tolerance:          # the final configuration is separated
+                state, t_out, done = 'separated', t_max, True
+                break
+            if s2 > target - tolerance:          # the deepest point has reached the target: advance the outer loop
+                t1 = t2
+                break
+            s1 = fcn.evaluate(ia, ib, t1)
+            if s1 < target - tolerance:          # the separation function is not conservative here
+                state, t_out, done = 'failed', t1, True
+                break
+            if s1 <= target + tolerance:         # t1 holds: a vertex that is at the target now goes deeper
+                state, t_out, done = 'touching', t1, True
+                break
+            a1, a2 = t1, t2
+            for root_iter in range(50):          # 1-D root finder on [t1, t2]: bisection on even, secant on odd counts
+                if root_iter & 1:
+                    t = a1 + (target - s1) * (a2 - a1) / (s2 - s1)
+                else:
+                    t = f32(0.5) * (a1 + a2)
+                s = fcn.evaluate(ia, ib, t)
+                if abs(s - target) < tolerance:
+                    t2 = t
+                    break
+                if s > target:
+                    a1, s1 = t, s
+                else:
+                    a2, s2 = t, s
+        outer += 1
+        if done:
+            break
+        if outer == 20:                          # k_maxIterations: the root finder got stuck
+            state, t_out = 'failed', t1
+            break
+    return state, t_out
 
 
 def world_manifold(m, xfA, rA, xfB, rB):
