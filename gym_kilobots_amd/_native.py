@@ -167,8 +167,8 @@ class KilobotsHipError(RuntimeError):
 STATUS_BITS = {
     1: 'contact capacity overflow: contacts were dropped (raise kb_config.contact_capacity or spread the spawn)',
     2: 'warm-start slot overflow: a kilobot touches more partners than kb_config.ws_slots, their impulses are not carried over',
-    4: 'a device staging limit was hit (more than 64 kilobots on one fixture, 255 kilobot-object contacts in one env, 63 partners in one cell pair or a contact dependency chain deeper than the level table of the cooperative sweep)',
-    8: 'continuous step skipped for some kilobots: more kilobots near the walls in one substep than the staging area holds',
+    4: 'a device staging limit was exceeded (more than 64 kilobots on one fixture, a rank above 255 in one (cell, direction) group of contacts, more than 63 partners of one kilobot in one direction, or a contact dependency chain deeper than the level table of the cooperative sweep: 44 x waves - 2 levels)',
+    8: 'continuous step skipped for some kilobots: more kilobots that may meet a wall in one substep than the kernel keeps candidates for (min(kb_lds_staging_entries, num_bots); half the staging entries with objects or mixed drive laws)',
 }
 
 

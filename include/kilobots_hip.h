@@ -178,16 +178,24 @@ typedef struct kb_buffers {
     float *light_value, *light_gx, *light_gy; /* optional outputs: last sensed light (kilobots_env.py:176-180) */
     float *cmd_vx, *cmd_vy, *cmd_w;     /* optional outputs: body velocity written by the drive law */
     int32_t *status;                    /* required: [num_envs]; bit0 contact capacity overflow,
-                                           bit1 warm-start slot overflow, bit2 a device staging limit was hit (more than 64 kilobots
-                                           on one fixture, 255 kilobot-object contacts in one env, 63 partners in one cell pair, or --
-                                           kernels without objects, an env swept by the whole workgroup -- a chain of contacts that
-                                           depend on each other deeper than the level table: 44 x waves of the workgroup - 2 levels,
-                                           at least 62),
+                                           bit1 warm-start slot overflow, bit2 a device staging limit was exceeded in one substep of
+                                           the env (the env is then flagged, not bit-exact; each number is the largest that is
+                                           still exact): 255 as the largest rank in one group of contacts -- 256 kilobot-kilobot
+                                           contacts whose owners lie in one cell and whose partners lie in one of the five
+                                           directions same cell, E, N, NE, NW of it; 63 partners of one kilobot in one such
+                                           direction (never the first to be exceeded: 63 kilobots in one cell within reach of one
+                                           kilobot touch each other in more than 256 pairs); 64 kilobots on one fixture (kernels
+                                           with objects or mixed drive laws); and -- kernels without objects, an env swept level by
+                                           level by a workgroup of two waves or more -- 44 x waves of the workgroup - 2 levels of
+                                           contacts that depend on each other (86 at two waves; a one-wave workgroup sweeps its
+                                           lists and has no such limit),
                                            bit3 more kilobots that may meet a wall in the continuous step of one substep than the
-                                           kernel keeps candidates for: min(kb_lds_staging_entries(), num_bots) in the kernels without
-                                           objects (688 at 1024 kilobots; a staging area of num_bots entries or more cannot run out),
-                                           half of kb_lds_staging_entries() in the kernels with objects or mixed drive laws (the
-                                           continuous step is skipped for the rest) */
+                                           kernel keeps candidates for (the continuous step is skipped for the rest); the largest
+                                           number it keeps: min(kb_lds_staging_entries(), num_bots) in the kernels without objects
+                                           (688 at 1024 kilobots; a staging area of num_bots entries or more cannot run out; a small
+                                           contact_capacity shrinks the staging area with it), kb_lds_staging_entries() / 2 in the
+                                           kernels with objects or mixed drive laws.  tests/limits_model.py restates every one of
+                                           these counts on the CPU */
     void *scratch;                      /* required: kb_scratch_bytes() bytes; contact staging of envs whose
                                            contacts do not fit the LDS staging area (contents are transient: no launch
                                            reads a byte of it that the same launch has not written before, so it
