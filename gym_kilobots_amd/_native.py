@@ -127,6 +127,7 @@ SIGNATURES = {
     'kb_sense_objects': (_I, [_P, _P, _P, _P]),
     'kb_grid_channels': (_I, [_P, _I]),
     'kb_sense_grid': (_I, [_P, _I, _I, _I, _P, _P]),
+    'kb_sense_coverage': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
     'kb_render': (_I, [_P, _I, _I, _I, C.POINTER(KbRenderStyle), _P, _P, _P, _P]),
@@ -288,6 +289,17 @@ def check_grid(width, height, planes):
     if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
         raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
     return width, height, _mask(planes, GRID_PLANES, 'planes', 'GRID')
+
+
+def check_coverage(width, height):
+    """The limits of kb_sense_coverage on the grid; ValueError where the library would answer KB_EINVAL.  Returns (width,
+    height)."""
+    if isinstance(width, bool) or isinstance(height, bool):
+        raise ValueError('width and height must be integers')
+    width, height = int(width), int(height)
+    if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
+        raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
+    return width, height
 
 
 RENDER_LAYERS = {'objects': RENDER_OBJECTS, 'bots': RENDER_BOTS, 'light': RENDER_LIGHT}

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -286,9 +286,7 @@ __global__ void __launch_bounds__(256) kb_debug_lds_kernel(int mode, unsigned wo
 thread_local char g_err[512] = "";
 
 float kb_clampf_host(float a, float lo, float hi) { return fmaxf(lo, fminf(a, hi)); }
-// reach of the sensing stencil in cells: cell indices are monotone in the coordinate, and two kilobots within Rw differ
-// by at most floor(Rw / cell) + 1 cells (the small margin covers the rounding of the cell computation)
-int sense_reach(float Rw, float inv_cell) { return (int)floorf(Rw * inv_cell + 1e-3f) + 1; }
+// (sense_reach, the reach of a sensing stencil in cells, is in kb_sense.h: kb_coverage_kernel stops its search by it)
 
 // kb_div_const (kb_exact.h) against a / K for one divisor of the position sweep, a = -C: every mantissa of the binade of the
 // largest |C| (0.2), a stride through the mantissas of every smaller binade that |C| can reach (the form is invariant under
@@ -970,6 +968,20 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
         return launched("kb_sense_grid");
     }
     return KB_OK;
+}
+
+int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int32_t *d_owner, float *d_dist, float *d_cell, float *d_stats,
+                      void *stream) {
+    if (!sim) return fail(KB_EINVAL, "kb_sense_coverage: NULL handle");
+    if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_sense_coverage: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
+    if (!d_owner && !d_dist && !d_cell && !d_stats) return fail(KB_EINVAL, "kb_sense_coverage: d_owner, d_dist, d_cell and d_stats are all NULL");
+    if (reinterpret_cast<uintptr_t>(d_cell) & 15u) return fail(KB_EINVAL, "kb_sense_coverage: d_cell must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_coverage: kb_bind() first");
+    const Params &p = sim->p;
+    const CoverageArgs a = {gw, gh, (p.xmax - p.xmin) / (float)gw, (p.ymax - p.ymin) / (float)gh};       // (kb_outline.arena is these four)
+    hipLaunchKernelGGL(kb_coverage_kernel, dim3((unsigned)p.E), dim3(256), (size_t)CoverageLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, a, d_select,
+                       d_owner, d_dist, reinterpret_cast<float4 *>(d_cell), d_stats);
+    return launched("kb_sense_coverage");
 }
 
 int kb_render_default_style(kb_render_style *out) {

@@ -1,5 +1,5 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
+// kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
@@ -14,11 +14,18 @@ namespace kb {
 // The cell lists of the broadphase grid off the poses of one env in global memory: pos[b] and cellOf[b] of every kilobot
 // (cell indices clamp to the grid), head[cell] -> nextb chains (plain heads: no hash).  o: index of the env's first kilobot.
 // The order inside a chain is the order of the exchanges; nothing that reads the lists may depend on it.  Ends on a barrier.
-__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, float2 *pos, unsigned short *head,
-                                                    unsigned short *nextb, unsigned short *cellOf, int tid, int nt) {
+// keep(b): only these kilobots enter the lists; of the others pos[b] = (NaN, NaN), cellOf[b] = EMPTY16, and no chain holds them.
+template <typename Keep>
+__device__ __forceinline__ void kb_build_cell_lists_of(const Params &p, size_t o, float2 *pos, unsigned short *head,
+                                                       unsigned short *nextb, unsigned short *cellOf, int tid, int nt, Keep keep) {
     for (int c = tid; c < p.ncell; c += nt) head[c] = EMPTY16;
     __syncthreads();
     for (int b = tid; b < p.N; b += nt) {
+        if (!keep(b)) {
+            pos[b].x = pos[b].y = __uint_as_float(0x7FC00000u);
+            cellOf[b] = EMPTY16;
+            continue;
+        }
         const float bx = p.buf.x[o + b], by = p.buf.y[o + b];
         pos[b].x = bx; pos[b].y = by;
         int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
@@ -31,6 +38,15 @@ __device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, f
     }
     __syncthreads();
 }
+// ... of every kilobot of the env
+__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, float2 *pos, unsigned short *head,
+                                                    unsigned short *nextb, unsigned short *cellOf, int tid, int nt) {
+    kb_build_cell_lists_of(p, o, pos, head, nextb, cellOf, tid, nt, [](int) { return true; });
+}
+
+// reach of the sensing stencil in cells: cell indices are monotone in the coordinate, and two kilobots within Rw differ
+// by at most floor(Rw / cell) + 1 cells (the small margin covers the rounding of the cell computation)
+__host__ __device__ inline int sense_reach(float Rw, float inv_cell) { return (int)floorf(Rw * inv_cell + 1e-3f) + 1; }
 
 // The stencil walk of kilobot a (in `cell`, at pa): every cell within reach s of its own, eight list heads per LDS round trip
 // (most cells are empty), down each chain.  Calls hit(b, ex, ey, dd) for every kilobot b != a with !(dd > R2),
@@ -1386,6 +1402,197 @@ __global__ void __launch_bounds__(256) kb_contacts_kernel(const ContactsArgs A, 
                     reinterpret_cast<unsigned *>(d_impulse)[row + i] = used ? (unsigned)best[i] : 0u;
                 }
             }
+        }
+    }
+}
+
+// ---- kb_sense_coverage: nearest-kilobot fields and Voronoi cells of every env ----------------------------------------------
+#ifndef KB_COVERAGE_RING_COST
+#define KB_COVERAGE_RING_COST 2         // what a broadphase cell of a ring costs, in kilobots looked at: a cell centre searches ring k while the (2 k + 1)^2 cells up to it cost no more than looking through all num_bots kilobots, which it does after them; 0: rings only, a large number (1 << 20): never a ring (A/B knob)
+#endif
+constexpr int COVERAGE_RING_COST = KB_COVERAGE_RING_COST;
+static_assert(COVERAGE_RING_COST >= 0 && COVERAGE_RING_COST <= (1 << 20), "kb_coverage_kernel: ring cost");
+struct CoverageArgs { int gw, gh; float cw, ch; };      // the grid and the host constants of the definition (include/kilobots_hip.h)
+struct CoverageLds {    // byte offsets: pos (float2) at 0, acc (u64: n << 42 | SX << 21 | SY), red[4] (u64) + wmax[4] (u32), dmax (u32), nextb, cellOf, head (u16 each)
+    int acc, red, dmax, nextb, cellOf, head, bytes;
+    __host__ __device__ constexpr CoverageLds(int NP, int ncell)
+        : acc(8 * NP), red(16 * NP), dmax(16 * NP + 64), nextb(20 * NP + 64), cellOf(22 * NP + 64), head(24 * NP + 64), bytes(24 * NP + 64 + 2 * ncell + 16) {}
+};
+// (the image does not grow with the grid; the grid bounds what one accumulator word holds: n <= 128 * 128 < 2^15 and
+// SX, SY <= 128 * 128 * 127 < 2^21 share 64 bits)
+static_assert(CoverageLds(KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024 && KB_GRID_MAX_SIDE * KB_GRID_MAX_SIDE < (1 << 15) &&
+              KB_GRID_MAX_SIDE * KB_GRID_MAX_SIDE * (KB_GRID_MAX_SIDE - 1) < (1 << 21), "kb_coverage_kernel: LDS image");
+
+// Nearest-kilobot fields (kb_sense_coverage): one workgroup per env; the poses of the selected kilobots and their cell lists in
+// LDS (kb_build_cell_lists_of), a kilobot that is not selected as a NaN pose that no chain holds.  One cell centre of the
+// caller's grid per lane and pass; a wave takes a TILE of 8 x 8 centres, so that its lanes search about equally far (with a
+// wave on 64 consecutive centres of a row every wave waited for the lane that is farthest from the swarm: 2.3 against 1.7 ms at
+// 64 x 48).  A centre keeps the least (bits of d2, b) of the kilobots it meets -- d2 >= 0, so the order of the bit
+// patterns is the order of the values, and the patterns of a NaN lie above the initial one and never win -- and meets them in
+// two ways:
+//  RINGS.  Ring k = the broadphase cells at Chebyshev distance k of the centre's own (clamped) cell.  After ring k the search
+//   is over once no kilobot outside rings 0..k can have d2_b <= best, "<=" so that a tie with a lower index is seen too.  Such
+//   a kilobot has fl(ex^2) <= fl(fl(ex^2) + fl(ey^2)) = d2_b <= best (rounding is monotone, the other square is >= 0), hence
+//   |ex| <= sqrt(best) (1 + u) + 2^-75 with u = 2^-24 (the product rounds by 1 + u, or underflows by at most 2^-150), and
+//   |x_b - cx| <= |ex| / (1 - u) (a difference rounds by 1 + u and is exact where it is subnormal); likewise in y.  The
+//   correctly rounded s = sqrtf(best) is >= sqrt(best) (1 - u), so |x_b - cx| <= s (1 + 3.2 u) + 2^-74, and
+//   R = fl(fl(s * (1 + 16 u)) + 1e-6f) >= s (1 + 13 u) + 0.99e-6 is an upper bound of both offsets, whatever best is.  Two
+//   coordinates within R of each other have cell indices at most sense_reach(R, inv_cell) apart -- the bound sense_reach
+//   argues, which holds for clamped indices and for a cell centre's own index by the argument above kb_render_kernel -- so
+//   every such kilobot lies in rings 0..sense_reach(R): the search stops when that number is <= k, and also when ring k
+//   reached the far corner of the grid.  A best that is no number never stops it.  Fewer than gw + gh rings are walked, and
+//   only while the (2 k + 1)^2 cells up to ring k are cheaper than the second way (COVERAGE_RING_COST).
+//  ALL.  A centre the rings have not settled starts again and looks through pos[0 .. N) in ascending order, where "<" alone
+//   gives a tie to the lower index: all lanes read the same four kilobots at a time, which the LDS broadcasts.  Far from every
+//   kilobot the rings cost more head reads than there are kilobots; next to them two rings settle it.  Both ways win
+//   somewhere.
+// Both terminate on any poses: a chain holds each kilobot at most once, and the owner is used as an index only if < N.
+// The per-kilobot accumulators of d_cell are LDS words the owners' lanes add to (ds_add_u64, ds_max_u32: nothing comes back);
+// the 64-bit cost and the worst d2 are per-lane partials reduced through the wave and LDS: integers, any order gives the same
+// bits.  Every output word is written exactly once, by a plain store.
+__global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const CoverageArgs A, const unsigned char *d_select, int *d_owner,
+                                                          float *d_dist, float4 *d_cell, float *d_stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N, W = A.gw, H = A.gh;
+    const CoverageLds L(p.NP, p.ncell);
+    float2 *pos = reinterpret_cast<float2 *>(smem);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(smem + L.acc);
+    unsigned long long *red = reinterpret_cast<unsigned long long *>(smem + L.red);
+    unsigned *wmax = reinterpret_cast<unsigned *>(smem + L.red + 32);
+    unsigned *dmax = reinterpret_cast<unsigned *>(smem + L.dmax);
+    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
+    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
+    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const size_t o = (size_t)e * N, po = (size_t)e * H * W;
+    const int npix = W * H;
+    const float INF = __uint_as_float(0x7F800000u);
+    constexpr unsigned NONE = 0x7F800001u;      // above the bits of every d2 that is a number (d2 >= 0: the order of the bits is the order of the values) and below those of a NaN
+    for (int b = tid; b < N; b += nt) { acc[b] = 0ull; dmax[b] = 0u; }
+    int mine = 0;
+    kb_build_cell_lists_of(p, o, pos, head, nextb, cellOf, tid, nt, [&](int b) {
+        const bool keep = !d_select || d_select[o + b] != 0;
+        mine |= (int)keep;
+        return keep;
+    });
+    if (!__syncthreads_or(mine)) {      // no candidate in the env (uniform)
+        for (int f = tid; f < npix; f += nt) {
+            if (d_owner) d_owner[po + f] = -1;
+            if (d_dist) d_dist[po + f] = INF;
+        }
+        if (d_cell) for (int b = tid; b < N; b += nt) d_cell[o + b] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (d_stats && tid < 2) d_stats[2 * (size_t)e + tid] = INF;
+        return;
+    }
+    // What only the epilogue needs waits in vector registers, of which the search leaves most free: kept in scalar registers
+    // across the search loops these pointers were spilled (the empty asm hands them back as per-lane values).
+    int late = (d_cell ? 1 : 0) | (d_stats ? 2 : 0);       // which of the two the caller gave
+    const float *theta = p.buf.theta;
+    asm volatile("" : "+v"(theta), "+v"(d_cell), "+v"(d_stats), "+v"(late));
+    long long cost = 0;
+    unsigned worst = 0u;
+    int *own = d_owner ? d_owner + po : nullptr;
+    float *dst = d_dist ? d_dist + po : nullptr;
+    int rings = 0;      // (uniform: the rings worth walking in an env of N kilobots)
+    while (rings < p.gw + p.gh && (2 * rings + 1) * (2 * rings + 1) * COVERAGE_RING_COST <= N) ++rings;
+    // a wave takes a tile of 8 x 8 centres (flatter where the grid has fewer than 8 rows): its lanes search equally far
+    const int TH = H >= 8 ? 8 : H >= 4 ? 4 : H >= 2 ? 2 : 1, TW = 64 / TH;
+    const int tilesX = (W + TW - 1) / TW, tiles = tilesX * ((H + TH - 1) / TH);
+    const int lx = (tid & 63) & (TW - 1), ly = (tid & 63) / TW;
+    for (int T = tid >> 6; T < tiles; T += nt >> 6) {
+        const int ix = (T % tilesX) * TW + lx, iy = (T / tilesX) * TH + ly;
+        if (ix >= W || iy >= H) continue;
+        const int f = iy * W + ix;
+        const float cx = p.xmin + ((float)ix + 0.5f) * A.cw, cy = p.ymin + ((float)iy + 0.5f) * A.ch;
+        int bx = (int)floorf((cx - p.xmin) * p.inv_cell);
+        int by = (int)floorf((cy - p.ymin) * p.inv_cell);
+        bx = bx < 0 ? 0 : (bx >= p.gw ? p.gw - 1 : bx);
+        by = by < 0 ? 0 : (by >= p.gh ? p.gh - 1 : by);
+        unsigned bdb = NONE, bi = 0xFFFFFFFFu;      // the least (bits of d2, b) so far
+        auto take = [&](const unsigned b, const float2 pb) {
+            const float ex = pb.x - cx, ey = pb.y - cy;
+            const unsigned db = __float_as_uint(ex * ex + ey * ey);
+            const bool less = (db < bdb) | ((db == bdb) & (b < bi));       // (no branch: two compares and two selects)
+            bdb = less ? db : bdb;
+            bi = less ? b : bi;
+        };
+        const int kfull = max(max(bx, p.gw - 1 - bx), max(by, p.gh - 1 - by));      // the ring that holds the far corner
+        const int klast = min(rings - 1, kfull);
+        bool settled = false;
+        for (int k = 0; k <= klast; ++k) {
+            // the 8 k cells of the ring in one loop (one level of divergence less than row by row): the row below, the row
+            // above, then the two ends of the rows between them; what the grid does not hold is passed over
+            const int side = 2 * k + 1, cnt = k == 0 ? 1 : 8 * k;
+            for (int j = 0; j < cnt; ++j) {
+                const int m = j - 2 * side;
+                const int ox = m < 0 ? bx - k + (j < side ? j : j - side) : ((m & 1) ? bx + k : bx - k);
+                const int oy = m < 0 ? (j < side ? by - k : by + k) : by - k + 1 + (m >> 1);
+                if ((unsigned)ox >= (unsigned)p.gw || (unsigned)oy >= (unsigned)p.gh) continue;
+                for (unsigned b = head[oy * p.gw + ox]; b != (unsigned)EMPTY16;) {
+                    const float2 pb = pos[b];
+                    const unsigned nb = nextb[b];
+                    take(b, pb);
+                    b = nb;
+                }
+            }
+            if (k == kfull) { settled = true; break; }
+            const float R = sqrtf(__uint_as_float(bdb)) * 1.000001f + 1e-6f;
+            if (R * p.inv_cell < 65536.0f && sense_reach(R, p.inv_cell) <= k) { settled = true; break; }       // (the bound: the reach stays a small integer)
+        }
+        if (!settled) {     // in ascending order, from nothing: "<" alone gives a tie to the lower index; four poses per LDS round trip
+            bdb = NONE;
+            bi = 0xFFFFFFFFu;
+            auto scan = [&](const unsigned b, const float x, const float y) {
+                const float ex = x - cx, ey = y - cy;
+                const unsigned db = __float_as_uint(ex * ex + ey * ey);
+                const bool less = db < bdb;
+                bdb = less ? db : bdb;
+                bi = less ? b : bi;
+            };
+            int b = 0;
+            for (; b + 4 <= N; b += 4) {
+                const float4 q0 = reinterpret_cast<const float4 *>(pos + b)[0], q1 = reinterpret_cast<const float4 *>(pos + b)[1];
+                scan(b, q0.x, q0.y); scan(b + 1, q0.z, q0.w); scan(b + 2, q1.x, q1.y); scan(b + 3, q1.z, q1.w);
+            }
+            for (; b < N; ++b) scan(b, pos[b].x, pos[b].y);
+        }
+        const float bd = __uint_as_float(bdb);
+        if (own) own[f] = (int)bi;
+        if (dst) dst[f] = sqrtf(bd) / WORLD_SCALE;
+        if ((late & 1) && bi < (unsigned)N) {
+            atomicAdd(&acc[bi], 1ull << 42 | (unsigned long long)ix << 21 | (unsigned long long)iy);
+            atomicMax(&dmax[bi], __float_as_uint(bd));
+        }
+        cost += (long long)rintf(fminf(bd * 65536.0f, 0x1p40f));
+        worst = max(worst, __float_as_uint(bd));
+    }
+    if (late & 2) {
+        for (int off = 32; off > 0; off >>= 1) {
+            cost += __shfl_down(cost, off);
+            worst = max(worst, __shfl_down(worst, off));
+        }
+        if ((tid & 63) == 0) { red[tid >> 6] = (unsigned long long)cost; wmax[tid >> 6] = worst; }
+    }
+    __syncthreads();
+    if ((late & 2) && tid == 0) {
+        long long total = 0;
+        unsigned w = 0u;
+        for (int i = 0; i < nt / 64; ++i) { total += (long long)red[i]; w = max(w, wmax[i]); }
+        d_stats[2 * (size_t)e] = ((float)total / 65536.0f) / 625.0f;
+        d_stats[2 * (size_t)e + 1] = sqrtf(__uint_as_float(w)) / WORLD_SCALE;
+    }
+    if (late & 1) {
+        for (int b = tid; b < N; b += nt) {
+            const unsigned long long a = acc[b];
+            const int n = (int)(a >> 42), SX = (int)(a >> 21) & 0x1FFFFF, SY = (int)a & 0x1FFFFF;
+            float4 row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (n > 0) {        // (an owner: a selected kilobot, pos[b] its pose)
+                const float mx = p.xmin + (((float)SX / (float)n) + 0.5f) * A.cw, my = p.ymin + (((float)SY / (float)n) + 0.5f) * A.ch;
+                const float dx = mx - pos[b].x, dy = my - pos[b].y;
+                float sn, cs;
+                kb_sincosf(theta[o + b], sn, cs);
+                row = make_float4((cs * dx + sn * dy) / WORLD_SCALE, (cs * dy - sn * dx) / WORLD_SCALE, (float)n, sqrtf(__uint_as_float(dmax[b])) / WORLD_SCALE);
+            }
+            d_cell[o + b] = row;
         }
     }
 }

@@ -39,6 +39,11 @@ def _grid_obs(value, num_objects):
     return grid
 
 
+def _coverage_obs(value, num_objects):
+    width, height = value
+    return nat.check_coverage(width, height)
+
+
 def _contact_obs(value, num_objects):
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= value <= nat.MAX_CONTACT_SLOTS:
         raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
@@ -74,6 +79,7 @@ OPTIONS = {
     'histogram_obs': Option(_histogram_obs, '(radius_m, n_rings, n_sectors)', ('neighbor_histogram',), 'neighbor_histogram', '(radius_m, n_rings, n_sectors)', 'observe neighbour histograms'),
     'object_obs': Option(_object_obs, None, ('objects', 'walls'), 'object_points', 'True', 'observe objects and walls'),
     'grid_obs': Option(_grid_obs, '(width, height) or (width, height, planes)', ('grid',), 'occupancy_grid', '(width, height[, planes])', 'observe occupancy grids'),
+    'coverage_obs': Option(_coverage_obs, '(width, height)', ('coverage',), 'coverage', '(width, height)', 'observe nearest-kilobot fields'),
     'contact_obs': Option(_contact_obs, None, ('contacts',), 'contacts', 'k', 'observe contacts'),
     'ray_obs': Option(_ray_obs, '(radius_m, n_rays) or (radius_m, n_rays, targets)', ('rays',), 'rays', '(radius_m, n_rays[, targets])', 'observe range scans'),
     'edge_obs': Option(_edge_obs, 'radius_m or (radius_m, capacity)', ('edges',), 'edges', 'radius_m or (radius_m, capacity)', 'observe the IR-range graph'),
@@ -89,7 +95,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
+                 object_obs=None, grid_obs=None, coverage_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
                  max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
@@ -110,6 +116,11 @@ class BatchedKilobotsEnv(object):
         grid_obs: (width, height) or (width, height, planes) adds what a CENTRAL policy is fed, a fixed-size image of the
         whole table: occupancy_grid() returns [E, C, height, width] (KilobotSim.occupancy_grid; planes made of 'count',
         'flow' and 'objects', default ('count',)), and step() puts it in its info dict under 'grid'.  None adds nothing.
+        coverage_obs: (width, height) adds the nearest-kilobot fields of a coverage or dispersion task: coverage() returns the
+        named tuple (owner [E, height, width], dist [E, height, width], cells [E, N, 4], stats [E, 2]) of KilobotSim.coverage --
+        which kilobot is nearest to every cell centre of the table and how far, the Voronoi cell of every kilobot with its
+        centroid in the kilobot's own frame, the locational cost and the worst-covered distance -- and step() puts the tuple in
+        its info dict under 'coverage'.  None adds nothing.
         contact_obs: k, an int in 0..16, adds touch and push sensing from the contacts the solver acted on in the last world
         step: contacts() returns (partner [E, N, k], impulse [E, N, k], touch [E, N, 4], obj [E, M, 2] or None)
         (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
@@ -152,7 +163,7 @@ class BatchedKilobotsEnv(object):
         self.env_offset = int(env_offset)
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
-        given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs,
+        given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs, coverage_obs=coverage_obs,
                      contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs)
         for name, option in OPTIONS.items():
             value = given[name]
@@ -375,6 +386,12 @@ class BatchedKilobotsEnv(object):
         """grid [E, C, height, width] float32 of the current poses for the grid_obs=(width, height[, planes]) the env was
         created with: KilobotSim.occupancy_grid."""
         return self._observe('grid_obs')
+
+    def coverage(self):
+        """The named tuple (owner [E, height, width] int32, dist [E, height, width] float32, cells [E, N, 4] float32, stats
+        [E, 2] float32) of the current poses for the coverage_obs=(width, height) the env was created with:
+        KilobotSim.coverage."""
+        return self._observe('coverage_obs')
 
     def contacts(self):
         """(partner [E, N, k] int32, impulse [E, N, k] float32, touch [E, N, 4] float32, obj [E, M, 2] float32 or None) of the

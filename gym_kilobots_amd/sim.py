@@ -16,6 +16,8 @@ from ._native import (DRIVE_VELOCITY, DRIVE_ACCEL, DRIVE_MOTORS, DRIVE_SIMPLE_PH
 
 # what KilobotSim.edges returns
 Edges = collections.namedtuple('Edges', ('src', 'dst', 'rel', 'offsets', 'count', 'nnz'))
+# ... and KilobotSim.coverage
+Coverage = collections.namedtuple('Coverage', ('owner', 'dist', 'cells', 'stats'))
 
 # the dtypes a caller's tensor may have: floats, a mask (env_mask, seeds) and 32-bit words (colours, episode counters)
 F32, I32, I64, MASK = (torch.float32,), (torch.int32,), (torch.int64,), (torch.bool, torch.uint8)
@@ -449,6 +451,35 @@ class KilobotSim:
         out, = self._outputs(out, [((self.num_envs, channels, height, width), torch.float32, 'grid')], 'the grid tensor')
         self._call('kb_sense_grid', width, height, planes, out.data_ptr())
         return out
+
+    def coverage(self, width, height, select=None, owner=True, dist=True, cells=True, stats=True, out=None):
+        """Nearest-kilobot fields on the current poses (kb_sense_coverage; no reference counterpart): the arena of every env
+        cut into width x height cells as in occupancy_grid(), and for every cell centre the nearest kilobot of the env -- the
+        Voronoi partition of the table on this grid.  Returns the named tuple Coverage(owner, dist, cells, stats): owner
+        [E, height, width] int32, the index of the nearest kilobot (ties to the lower index); dist [E, height, width] float32,
+        its distance in metres; cells [E, N, 4] float32, the Voronoi cell of every kilobot as (centroid metres ahead, centroid
+        metres to the left, area in grid cells, largest distance of one of its cell centres in metres) -- the first two are
+        the step of Lloyd's coverage control in the kilobot's own frame --, zeros for a kilobot that owns nothing; stats
+        [E, 2] float32 = (the sum over the cells of the squared distance in square metres, a fixed-point sum at 2^-16 world
+        units squared that does not depend on the order; the distance of the worst-covered cell centre in metres).  A part
+        switched off (owner=False, ...) is None and is not computed; at least one must be on.  select: [E, N] bool or uint8
+        on the sim's device, the kilobots that take part (None: all); an env that selects none has owner -1, dist and stats
+        +inf.  out: the preallocated contiguous tensors to write into, a tuple of the parts that are on; every element is
+        written."""
+        E, N = self.num_envs, self.num_bots
+        width, height = nat.check_coverage(width, height)
+        wanted = [bool(owner), bool(dist), bool(cells), bool(stats)]
+        if not any(wanted):
+            raise ValueError('coverage: at least one of owner, dist, cells and stats must be on')
+        ps = self._input(select, MASK, (E, N), 'select', optional=True)
+        shapes = [s for s, w in zip([((E, height, width), torch.int32, 'owner'), ((E, height, width), torch.float32, 'dist'),
+                                     ((E, N, 4), torch.float32, 'cells'), ((E, 2), torch.float32, 'stats')], wanted) if w]
+        given = iter(self._outputs(out, shapes, 'the tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
+        parts = [next(given) if w else None for w in wanted]
+        if parts[2] is not None and parts[2].data_ptr() % 16:
+            raise ValueError('out: cells must be 16-byte aligned')
+        self._call('kb_sense_coverage', width, height, ps, *map(_ptr, parts))
+        return Coverage(*parts)
 
     def contacts(self, k=8, scale=65536.0, out=None):
         """Touch and push sensing from the contact store of the last step (kb_sense_contacts; Body.collides_with of every

@@ -484,6 +484,43 @@ int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream);
 int kb_grid_channels(const kb_sim *sim, int planes);
 int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *stream);
 
+/* Nearest-kilobot fields on the CURRENT poses, without stepping: for every cell centre of a gw x gh grid over the arena, which
+ * kilobot of the env is nearest and how far away it is -- the Voronoi partition of the table among the kilobots, the cell of
+ * every kilobot with its area and its centroid (the target of Lloyd's coverage control), the locational cost and the
+ * worst-covered point.  No reference counterpart.  One launch; asynchronous on `stream`.  Every operation below is one fp32
+ * operation rounded on its own, with correctly rounded divisions and square roots:
+ *   Host constants: those of the occupancy grids above: (xmin, xmax, ymin, ymax) = kb_outline.arena;  cw = (xmax - xmin) / (float)gw,
+ *     ch = (ymax - ymin) / (float)gh.  The centre of cell (iy, ix):  cx = xmin + ((float)ix + 0.5f) * cw,
+ *     cy = ymin + ((float)iy + 0.5f) * ch  (the formula of KB_GRID_OBJECTS); row iy = 0 is the ymin edge.
+ *   Candidates: the kilobots b of the env with d_select[e][b] != 0 (bytes, the convention of d_seed and d_env_mask); NULL: all
+ *     of them.  A kilobot outside the arena takes part with its true position.
+ *   Per cell: ex = x_b - cx, ey = y_b - cy, d2 = ex * ex + ey * ey.  The owner is the candidate with the smallest
+ *     (bits of d2 compared as unsigned integers, b): ties go to the lower index, and nothing else decides it.
+ *   d_owner [num_envs][gh][gw] int32: the owner's index within its env.
+ *   d_dist  [num_envs][gh][gw] float32: sqrt(d2 of the owner) / 25, metres.
+ *   d_cell  [num_envs][num_bots][4] float32, 16-byte aligned: the Voronoi cell of kilobot b on this grid.  n = the number of
+ *     cells it owns, SX = the sum of ix and SY = the sum of iy over them (int32; at most 16384 * 127 < 2^24, so (float)SX is
+ *     exact), D = the largest d2 among them (the maximum of the bit patterns).  With n > 0:
+ *     mx = xmin + (((float)SX / (float)n) + 0.5f) * cw, my likewise from SY, ymin and ch;  dx = mx - x_b, dy = my - y_b;
+ *     (s, c) = the library's sine and cosine of theta_b;  the row is ((c * dx + s * dy) / 25, (c * dy - s * dx) / 25, (float)n,
+ *     sqrt(D) / 25): the centroid of the cell ahead and to the left in metres, its area in cells, its radius in metres.  With
+ *     n == 0, or for a kilobot that is not a candidate: four +0.0f.
+ *   d_stats [num_envs][2] float32.  Word 0, the locational cost: q = (int64) rint(min(d2 of the owner * 65536.0f, 0x1p40f)),
+ *     round half to even;  acc = the int64 sum of q over the cells;  the word is ((float)acc / 65536.0f) / 625.0f, square
+ *     metres summed over the cells (int -> float to nearest even): exact on the quantised values and independent of any order.
+ *     The caller scales it by the area of a cell or divides it by gw * gh.  Word 1: sqrt(the largest d2 of an owner) / 25, the
+ *     distance of the worst-covered cell centre in metres.
+ *   An env without a candidate: d_owner = -1 and d_dist = +inf everywhere, its d_cell rows are zero, its d_stats (+inf, +inf).
+ * Each output may be NULL and is then not computed; every element of every output given is written on every call, by a plain
+ * store (nothing needs clearing beforehand).  1 <= gw, gh <= KB_GRID_MAX_SIDE.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim;  gw, gh;  all four outputs NULL;  a d_cell
+ * that is not 16-byte aligned.  Only then comes KB_ENOTBOUND.
+ * Reads x, y and d_select, theta only with d_cell; writes the outputs only.  The result of an env does not depend on the other
+ * envs.  Poses are assumed finite: with one that is not, the result of its env is unspecified (the call still ends and writes
+ * nothing but the outputs). */
+int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int32_t *d_owner, float *d_dist, float *d_cell,
+                      float *d_stats, void *stream);
+
 /* Touch and push sensing from the contact store, without stepping: who touches whom, and how hard -- what the solver alone
  * knows (Body.collides_with, body.py:87-90, walks b2Body.contacts; the impulses have no reference counterpart).  A pure
  * function of ws_key / ws_acc / ws_cnt as the last kb_step left them: the Box2D contact list of the last world step.
