@@ -57,6 +57,10 @@ constexpr int KREG = KB_KREG;               // contacts a lane can keep in regis
 #define KB_SETUP_FUSED 2                // register set-up of a wave of at most 64 contacts (A/B knob, see kb_regsolve_bins.inc): 0 = as a two-slot wave; 1 = one slot, loaded once; 2 = ... and its warm start rides in the depth rounds
 #endif
 
+#ifndef KB_ARGS_SCOPED
+#define KB_ARGS_SCOPED 1                // fixed-size kernels without objects: arguments re-read per phase (A/B knob, see kb_step_kernel.h: KB_REARG); 0 = carried from the kernel top
+#endif
+
 enum { M_NCON = 0, M_TOTAL = 1, M_ANY = 2, M_STATUS = 3, M_MAXISL = 4, M_PROF = 5, M_XTRA = 6, M_XFILL = 7, M_WCNT = 8, M_WAKE = 32 /* .. 63: one bit per kilobot (sleeping; the -DKB_PROFILE build keeps its stamps there and does not implement the wake rule) */, M_WFILL = 8 + MAX_WAVES, M_COUNT = 8 + 2 * MAX_WAVES };
 static_assert(M_COUNT <= 64, "misc area");
 
@@ -136,8 +140,10 @@ __device__ __forceinline__ void kb_light_circular(float sx, float sy, float lx, 
 }
 
 // ---- light models shared by the step kernel and kb_light_sense (same operations in the same order: same bits) ----
+// (AR: Params, or Params in the constant address space -- the kernel-argument segment itself, kb_step_kernel.h: KB_REARG)
 // SinglePositionLight.step of the single circular light, light.py:59-75; la = this env's action (2 floats)
-__device__ __forceinline__ void kb_light_single_step(const Params &p, const float *la, float h, float &lx, float &ly) {
+template <class AR>
+__device__ __forceinline__ void kb_light_single_step(const AR &p, const float *la, float h, float &lx, float &ly) {
     float ax = fminf(fmaxf(la[0], p.act_lo[0]), p.act_hi[0]);
     float ay = fminf(fmaxf(la[1], p.act_lo[1]), p.act_hi[1]);
     float nlx = lx + ax * h, nly = ly + ay * h;
@@ -146,7 +152,8 @@ __device__ __forceinline__ void kb_light_single_step(const Params &p, const floa
 }
 // Light.step of every component of the general model: light.py:59-75 (positional), 300-316 (momentum), 237-253 (gradient);
 // la = this env's action (ladim floats)
-__device__ __forceinline__ void kb_light_general_step(const Params &p, const float *la, float h, float (&glx)[KB_MAX_LIGHTS],
+template <class AR>
+__device__ __forceinline__ void kb_light_general_step(const AR &p, const float *la, float h, float (&glx)[KB_MAX_LIGHTS],
                                                       float (&gly)[KB_MAX_LIGHTS], float (&glvx)[KB_MAX_LIGHTS], float (&glvy)[KB_MAX_LIGHTS]) {
     if (p.light_type == KB_LIGHT_GRADIENT) {
         const float pi = 3.14159265358979323846f;
@@ -177,7 +184,8 @@ __device__ __forceinline__ void kb_light_general_step(const Params &p, const flo
 }
 // value_and_gradients of the general model at one sensor position (metres): light.py:176-189, 137-141;
 // GradientLight: projection on the gradient direction (intent of light.py:255-260)
-__device__ __forceinline__ void kb_light_general_sense(const Params &p, const float (&glx)[KB_MAX_LIGHTS], const float (&gly)[KB_MAX_LIGHTS],
+template <class AR>
+__device__ __forceinline__ void kb_light_general_sense(const AR &p, const float (&glx)[KB_MAX_LIGHTS], const float (&gly)[KB_MAX_LIGHTS],
                                                        float sx, float sy, float &val, float &gx, float &gy) {
     if (p.light_type == KB_LIGHT_GRADIENT) {
         float s_, c_;
@@ -294,6 +302,19 @@ __device__ __forceinline__ unsigned wave_incl_scan(unsigned v) {   // inclusive 
     return v;
 }
 
+// What the solvers and the continuous step read of the kernel arguments, as a copy a phase makes at its head (kb_step_kernel.h:
+// phase-scoped arguments) -- so that no sweep and no event loop carries a scalar load: the arena for wall_geom, and the
+// constants of the contact arithmetic.
+struct SolveArgs {
+    float xmin, ymin, xmax, ymax, h;
+    int vel_iters, pos_iters, exact_div;
+    float im_bot, r_bot, nm_bb, nm_wb, y_bb, y_wb;
+};
+template <class AR>
+__device__ __forceinline__ SolveArgs solve_args(const AR &p) {
+    return {p.xmin, p.ymin, p.xmax, p.ymax, p.h, p.vel_iters, p.pos_iters, p.exact_div, p.im_bot, p.r_bot, p.nm_bb, p.nm_wb, p.y_bb, p.y_wb};
+}
+
 template <class AR>
 __device__ __forceinline__ void wall_geom(const AR &p, int wl, float x, float y, float &dist, float &nx, float &ny) {
     switch (wl) {
@@ -375,7 +396,8 @@ __device__ __forceinline__ bool kb_toi_no_event(const AR &p, int wl, float tt, f
 // b2World::SolveTOI + b2Island::SolveTOI for one circular body against the arena walls (the only TOI events Box2D
 // computes for non-bullet bodies).  (x0,y0,a0): pose at the start of the step; (x,y,a): pose after b2Island::Solve;
 // (vx,vy,w): velocity after the solve; updated in place.
-__device__ __forceinline__ void kb_toi_walls_body(const Params &p, float R, float im, float x0, float y0, float a0,
+template <class AR>
+__device__ __forceinline__ void kb_toi_walls_body(const AR &p, float R, float im, float x0, float y0, float a0,
                                                   float &x, float &y, float &a, float &vx, float &vy, float &w) {
     const float h = p.h;
     const float total = R + B2_POLYGON_RADIUS;

@@ -17,8 +17,8 @@
     float *sAcc_ = big ? gAcc : lAcc;
     unsigned short *cbk_ = big ? gCbk : lCbk, *order_ = big ? gOrder : lOrder;
     // sorted records: 16 B per contact behind the staging records of all envs
-    unsigned *sp2 = reinterpret_cast<unsigned *>(g.scratch) + (size_t)p.E * p.cap * 4 + wo * 4;
-    float *snx = reinterpret_cast<float *>(sp2 + p.cap), *sny = snx + p.cap, *sacc2 = sny + p.cap;
+    unsigned *sp2 = reinterpret_cast<unsigned *>(ka->buf.scratch) + (size_t)ka->E * ka->cap * 4 + wo * 4;
+    float *snx = reinterpret_cast<float *>(sp2 + ka->cap), *sny = snx + ka->cap, *sacc2 = sny + ka->cap;
     // ... and their impulses in LDS: the pair array of the staging area is dead once the records are sorted (contacts staged in
     // the global slice: the whole LDS staging area, three arrays of capL words, is idle); envs beyond that keep them in the record
 #ifndef KB_COOP_PD
@@ -89,7 +89,7 @@
         float nx = 1.0f, ny = 0.0f;
         if (a >= WALL_CODE) {
             float dist;
-            wall_geom(p, a - WALL_CODE, pos[b].x, pos[b].y, dist, nx, ny);
+            wall_geom(ca, a - WALL_CODE, pos[b].x, pos[b].y, dist, nx, ny);
             if (flip) { nx = -nx; ny = -ny; }
         } else {
             const float dx = pos[b].x - pos[a].x, dy = pos[b].y - pos[a].y;
@@ -111,7 +111,7 @@
     }
     KB_STAMP_PRE(20);    // ... + counting sort by depth into consecutive records
     const int nsorted = (int)bkStart[maxD + 1];
-    const float nm_bb = p.nm_bb, nm_wb = p.nm_wb;
+    const float nm_bb = ca.nm_bb, nm_wb = ca.nm_wb;
     KB_ABLATE_EXIT(9);
     // ---- 3. warm start and velocity passes, level by level.  What a thread needs of a record never changes during the passes
     //         (pair, normal: 12 B), so it is requested PD levels ahead -- a round is shorter than a trip to L2 / HBM ----
@@ -122,7 +122,7 @@
     auto vel_passes = [&](auto acc_in_lds_) __attribute__((always_inline)) {
         constexpr bool AL = decltype(acc_in_lds_)::value;
         constexpr int PD = KB_COOP_PD;
-        const int nsteps = (p.vel_iters + 1) * maxD;      // (pass, level) in sequence; pass 0 = b2ContactSolver::WarmStart
+        const int nsteps = (ca.vel_iters + 1) * maxD;      // (pass, level) in sequence; pass 0 = b2ContactSolver::WarmStart
         unsigned rpr[PD];
         float rnx_[PD], rny_[PD];
         bool rhave[PD];
@@ -161,13 +161,13 @@
                     if constexpr (AL) acc = accL[ii]; else acc = sacc2[ii];
                     if (warm) {
                         const float Px = acc * nx, Py = acc * ny;
-                        if (!wallA) { vel[a].x -= p.im_bot * Px; vel[a].y -= p.im_bot * Py; }
-                        vel[b].x += p.im_bot * Px; vel[b].y += p.im_bot * Py;
+                        if (!wallA) { vel[a].x -= ca.im_bot * Px; vel[a].y -= ca.im_bot * Py; }
+                        vel[b].x += ca.im_bot * Px; vel[b].y += ca.im_bot * Py;
                     } else {
                         float vax = 0.0f, vay = 0.0f;
                         if (!wallA) { vax = vel[a].x; vay = vel[a].y; }
                         const float vbx = vel[b].x, vby = vel[b].y;
-                        const float ima = wallA ? 0.0f : p.im_bot, imb = p.im_bot;
+                        const float ima = wallA ? 0.0f : ca.im_bot, imb = ca.im_bot;
                         const float dvx = vbx - vax, dvy = vby - vay;
                         const float vn = dvx * nx + dvy * ny;
                         float lambda = -((wallA ? nm_wb : nm_bb) * vn);
@@ -229,7 +229,7 @@
         pos[b].x += h * vxx; pos[b].y += h * vyy;
         th[q] += h * ww;
         vel[b].x = vxx; vel[b].y = vyy; bw[q] = ww;
-        if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+        if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (ca.pos_iters <= 0 ? 1 : 0));
     }
     __syncthreads();
     KB_STAMP(5);
@@ -239,6 +239,7 @@
     // PD levels ahead here as well (wrapping into the next iteration; a request too many is only a load).
     {
         constexpr int PD = 4;
+        const int posIters = ca.pos_iters;      // (phase-scoped arguments: loaded in front of the sweeps)
         unsigned rpr[PD];
         bool rhave[PD];
         int dreq = 0;
@@ -252,7 +253,7 @@
         for (int u = 0; u < PD; ++u) request(rpr[u], rhave[u]);
         int d_ = 0, u_ = 0;      // u_: which of the PD request registers holds the current level
         int nS = maxD > 0 ? (int)bkStart[1] : 0, nE = maxD > 0 ? (int)bkStart[2] : 0;
-        for (int it = 0; it < p.pos_iters; ++it) {
+        for (int it = 0; it < posIters; ++it) {
             unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;
             bool viol = false;
             for (int lv = 0; lv < maxD; ++lv) {
@@ -269,25 +270,25 @@
                     const int isl = (int)parent[b];
                     if (act[isl]) {
                         float nx, ny, sep;
-                        const float ima = a < WALL_CODE ? p.im_bot : 0.0f, imb = p.im_bot;
+                        const float ima = a < WALL_CODE ? ca.im_bot : 0.0f, imb = ca.im_bot;
                         const float bx = pos[b].x, by = pos[b].y;
                         float axx = 0.0f, ayy = 0.0f;
                         if (a >= WALL_CODE) {
                             const bool flipped = a >= WALL_CODE + 4;      // manifold normal fixed at detection
                             float dist, wx, wy;
-                            wall_geom(p, (a - WALL_CODE) & 3, bx, by, dist, wx, wy);
+                            wall_geom(ca, (a - WALL_CODE) & 3, bx, by, dist, wx, wy);
                             nx = flipped ? -wx : wx; ny = flipped ? -wy : wy;
                             const float along = flipped ? -dist : dist;
-                            sep = along - B2_POLYGON_RADIUS - p.r_bot;
+                            sep = along - B2_POLYGON_RADIUS - ca.r_bot;
                         } else {
                             axx = pos[a].x; ayy = pos[a].y;
                             const float dx = bx - axx, dy = by - ayy;
                             const float len = sqrtf(dx * dx + dy * dy);
                             nx = dx; ny = dy;
                             if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
-                            sep = (dx * nx + dy * ny) - p.r_bot - p.r_bot;
+                            sep = (dx * nx + dy * ny) - ca.r_bot - ca.r_bot;
                         }
-                        if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                        if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == posIters - 1) islWave[isl] = 3; }
                         const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                         const float K = ima + imb;
                         const float imp = K > 0.0f ? -C / K : 0.0f;

@@ -36,7 +36,10 @@
     int maxD = 0;
     unsigned mycnt = 0;
     bool twoSlot = false;           // (wave-uniform) the wave holds more than 64 contacts
-    const float nm_bb = p.nm_bb, nm_wb = p.nm_wb;
+    // (phase-scoped arguments: `ca` was loaded in front of the barrier that opens the solver; nothing from here to the end of the
+    //  position sweeps reads the argument segment, so no wave's chain waits for scalar memory)
+    const float nm_bb = ca.nm_bb, nm_wb = ca.nm_wb;
+    const int velIters = ca.vel_iters, posIters = ca.pos_iters;
 #ifdef KB_SOLVER_PRIO
     __builtin_amdgcn_s_setprio(KB_SOLVER_PRIO);     // the serial chain of the substep: ahead of the other envs' throughput phases
 #endif
@@ -248,7 +251,7 @@
                     rm[j] = v_[j] ? (c_[j] | ((unsigned)rdepth[j] << 12) | (flip ? 1u << 21 : 0u) | (root_[j] << 22)) : 0u;
                     // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
                     float dist;
-                    wall_geom(p, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
+                    wall_geom(ca, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
                     if (flip) { wnx[j] = -wnx[j]; wny[j] = -wny[j]; }
                     dx[j] = pb_[j].x - pa_[j].x; dy[j] = pb_[j].y - pa_[j].y;
                     dd[j] = dx[j] * dx[j] + dy[j] * dy[j];
@@ -311,7 +314,7 @@
             {
                 // velocity-phase normal from the start-of-step positions (b2WorldManifold::Initialize)
                 float dist, wnx, wny;
-                wall_geom(p, wallA ? a - WALL_CODE : 0, pb_.x, pb_.y, dist, wnx, wny);
+                wall_geom(ca, wallA ? a - WALL_CODE : 0, pb_.x, pb_.y, dist, wnx, wny);
                 if (flip) { wnx = -wnx; wny = -wny; }
                 const float dx = pb_.x - pa_.x, dy = pb_.y - pa_.y;
                 const float dd = dx * dx + dy * dy;
@@ -344,8 +347,8 @@
 #define RB_BD(off) (*reinterpret_cast<unsigned *>(bdB + (off)))
                 const unsigned ib4 = rb[0] >> 1, ia4 = wallA ? ib4 : ra[0] >> 1;       // (a wall has no depth: max(d, d) + 1)
                 const float Px = racc[0] * rnx[0], Py = racc[0] * rny[0];
-                const float ima = wallA ? 0.0f : p.im_bot;
-                const float dax = ima * Px, day = ima * Py, dbx = p.im_bot * Px, dby = p.im_bot * Py;
+                const float ima = wallA ? 0.0f : ca.im_bot;
+                const float dax = ima * Px, day = ima * Py, dbx = ca.im_bot * Px, dby = ca.im_bot * Py;
                 const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
                 unsigned depth_ = 0;
                 for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
@@ -411,9 +414,9 @@
                     if (RB_ON(j)) {
                         const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
                         const float Px = racc[j] * rnx[j], Py = racc[j] * rny[j];
-                        const float ima = RB_WALL(j) ? 0.0f : p.im_bot;
+                        const float ima = RB_WALL(j) ? 0.0f : ca.im_bot;
                         RB_VEL(ra[j]) = make_float2(va.x - ima * Px, va.y - ima * Py);
-                        RB_VEL(rb[j]) = make_float2(vb.x + p.im_bot * Px, vb.y + p.im_bot * Py);
+                        RB_VEL(rb[j]) = make_float2(vb.x + ca.im_bot * Px, vb.y + ca.im_bot * Py);
                     }
                     wave_sync();
                 }
@@ -425,7 +428,7 @@
     if (solving) {
         // SolveVelocityConstraints: friction 0, restitution 0, one manifold point.  Only the lanes whose contact is of the round's
         // level execute (EXEC mask); a wall is a body at rest with inverse mass 0 (its "velocity" is rewritten as 0 - 0 * P).
-        for (int it = 0; it < p.vel_iters; ++it) {
+        for (int it = 0; it < velIters; ++it) {
 #pragma unroll
             for (int j = 0; j < KRB; ++j) {
                 for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
@@ -433,7 +436,7 @@
                         const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
                         const bool wallA = RB_WALL(j);
                         const float nx = rnx[j], ny = rny[j];
-                        const float ima = wallA ? 0.0f : p.im_bot, imb = p.im_bot;
+                        const float ima = wallA ? 0.0f : ca.im_bot, imb = ca.im_bot;
                         const float dvx = vb.x - va.x, dvy = vb.y - va.y;
                         const float vn = dvx * nx + dvy * ny;
                         float lambda = -((wallA ? nm_wb : nm_bb) * vn);
@@ -472,7 +475,7 @@
     {
         // (islWave is idle from here on) island state for the sleep bookkeeping: bit 1 = has an awake body,
         // bit 0 = position constraints not solved (set by the last position sweep; always without sweeps)
-        const unsigned char unsolved = (unsigned char)(p.pos_iters <= 0 ? 1 : 0);
+        const unsigned char unsolved = (unsigned char)(posIters <= 0 ? 1 : 0);
         char *const sxB = reinterpret_cast<char *>(startX), *const syB = reinterpret_cast<char *>(startY);
         // one body: the pose at the start of the substep (continuous step), the clamped velocity and the new position;
         // off8 = byte offset of the body inside the float2 arrays
@@ -554,7 +557,7 @@
     // SolvePositionConstraints; an island stops once its minSeparation >= -3 slop.  The island flags are read once per
     // iteration; depth levels without an active contact in this wave are skipped altogether.
     if (solving) {
-        for (int it = 0; it < p.pos_iters; ++it) {
+        for (int it = 0; it < posIters; ++it) {
             unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;
             bool viol = false;
             bool ron[KRB];
@@ -567,16 +570,16 @@
                     const bool wallA = RB_WALL(j);
                     const int isl = RB_ISL(j);
                     float nx, ny, sep;
-                    const float ima = wallA ? 0.0f : p.im_bot, imb = p.im_bot;
+                    const float ima = wallA ? 0.0f : ca.im_bot, imb = ca.im_bot;
                     const float2 pb = RB_POS(rb[j]);
                     const float bx = pb.x, by = pb.y;
                     float axx = 0.0f, ayy = 0.0f;
                     if (wallA) {
                         float dist, wx, wy;
-                        wall_geom(p, RB_WALLIDX(j), bx, by, dist, wx, wy);
+                        wall_geom(ca, RB_WALLIDX(j), bx, by, dist, wx, wy);
                         nx = RB_FLIP(j) ? -wx : wx; ny = RB_FLIP(j) ? -wy : wy;   // manifold normal fixed at detection
                         const float along = RB_FLIP(j) ? -dist : dist;
-                        sep = along - B2_POLYGON_RADIUS - p.r_bot;
+                        sep = along - B2_POLYGON_RADIUS - ca.r_bot;
                     } else {
                         const float2 pa = RB_POS(ra[j]);
                         axx = pa.x; ayy = pa.y;
@@ -594,12 +597,12 @@
                             nx = dx; ny = dy;
                             if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
                         }
-                        sep = (dx * nx + dy * ny) - p.r_bot - p.r_bot;
+                        sep = (dx * nx + dy * ny) - ca.r_bot - ca.r_bot;
                     }
-                    if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                    if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == posIters - 1) islWave[isl] = 3; }
                     const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                     const float K = ima + imb;
-                    const float imp = __builtin_expect(p.exact_div, 1) ? kb_div_const(-C, K, wallA ? p.y_wb : p.y_bb) : (K > 0.0f ? -C / K : 0.0f);
+                    const float imp = __builtin_expect(ca.exact_div, 1) ? kb_div_const(-C, K, wallA ? ca.y_wb : ca.y_bb) : (K > 0.0f ? -C / K : 0.0f);
                     const float Px = imp * nx, Py = imp * ny;
                     if (!wallA) RB_POS(ra[j]) = make_float2(axx - ima * Px, ayy - ima * Py);
                     RB_POS(rb[j]) = make_float2(bx + imb * Px, by + imb * Py);

@@ -1,5 +1,6 @@
 // kb_step_kernel.h -- the world-step kernel template (see kb_common.h for the overview).
 #pragma once
+#include <type_traits>
 #include <utility>
 
 #include "kb_common.h"
@@ -40,6 +41,17 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     constexpr bool PAR_DS = FN != 0 && BINS;
     static_assert(!SLEEP || FN == 0 || !OBJ, "the fixed-size instantiations with objects do not carry the sleep state");
     extern __shared__ __align__(16) unsigned char smem[];
+    // Phase-scoped arguments (the fixed-size kernels without objects): every argument is read through `ka`, a pointer to the
+    // kernel-argument segment in the constant address space, and KB_RETID takes that pointer through an opaque scalar copy at
+    // the head of every phase.  What a phase uses it loads there with scalar loads, instead of carrying every argument of the
+    // kernel -- 110 words of them in VGPR lanes, read back one v_readlane at a time -- from the kernel top through all the
+    // phases.  In the other kernels `ka` points at the by-value argument and is never made opaque: they read it as before.
+    constexpr bool SCOPED = KB_ARGS_SCOPED && FN != 0 && !OBJ;
+    using ArgPtr = std::conditional_t<SCOPED, const __attribute__((address_space(4))) Params *, const Params *>;
+    ArgPtr ka;
+    if constexpr (SCOPED) ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    else ka = &p;
+#define KB_REARG() do { if constexpr (SCOPED) { ka = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(ka)); } } while (0)
     {
         // kb_step_envs: the workgroup of an env that the mask leaves out is gone before it has touched anything.  The kernel
         // arguments lie in host memory and a first read of one of their 64-byte lines is a round trip of its own; the exit
@@ -47,7 +59,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // asked for in the same trip -- otherwise theirs comes second, + 0.9 % on the headline
         static_assert(sizeof(Params) >= 6 * 64, "the six lines asked for are kernel arguments");
         const __attribute__((address_space(4))) unsigned *ka_ = (const __attribute__((address_space(4))) unsigned *)__builtin_amdgcn_kernarg_segment_ptr();
-        const __attribute__((address_space(1))) unsigned char *m_ = (const __attribute__((address_space(1))) unsigned char *)p.env_mask;
+        const __attribute__((address_space(1))) unsigned char *m_ = (const __attribute__((address_space(1))) unsigned char *)ka->env_mask;
         asm volatile("" : "+s"(m_) : "s"(ka_[0]), "s"(ka_[16]), "s"(ka_[32]), "s"(ka_[48]), "s"(ka_[64]), "s"(ka_[80]));
         if (m_ && !m_[blockIdx.x]) return;
     }
@@ -61,17 +73,17 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const int nw = nt >> 6;
     const int nsolve = BINS ? (nw >= KB_NSOLVE_DIV ? nw / KB_NSOLVE_DIV : 1) : nw;      // waves that sweep the contacts (kb_regsolve_bins.inc: the solver is issue-bound, fewer waves fill their lanes better)
-    const int N = FN ? FN : p.N, NP = FN ? ((FN + 3) & ~3) : p.NP, S = p.S;
+    const int N = FN ? FN : ka->N, NP = FN ? ((FN + 3) & ~3) : ka->NP, S = p.S;
     size_t o = (size_t)e * N;
-    size_t wo = (size_t)e * p.cap;       // this env's slice of the packed warm-start / scratch arrays
+    size_t wo = (size_t)e * ka->cap;       // this env's slice of the packed warm-start / scratch arrays
     const float h = p.h;
 
-    const int NB = FN ? ((FN + 3) & ~3) + KB_MAX_OBJECTS + 4 : p.NB;
-    const int capL_ = (BINS && FN != 0) ? ldsb::CAPL : p.capL;
+    const int NB = FN ? ((FN + 3) & ~3) + KB_MAX_OBJECTS + 4 : ka->NB;
+    const int capL_ = (BINS && FN != 0) ? ldsb::CAPL : ka->capL;
     // sparse swarms: the bins are a hash of the cells (bin = cell & hmask, kb_create: a power of two >= 2 N) instead of one
     // bin per cell of the arena; a bin may then hold kilobots of several cells and every candidate's cell is checked.
     // The set of contacts and their canonical order (which use the cell coordinates) do not change.
-    const bool hashed = FN == 0 && p.hmask != 0;
+    const bool hashed = FN == 0 && ka->hmask != 0;
     // LDS arrays (offsets: namespace lds / ldsb in kb_launch.h)
     // (the fixed-size instantiations with objects keep room for the object tables: all their offsets are compile-time constants)
     const int fx = lds::fixed(OBJ || FN != 0, nw), ot_ = lds::objtab(nw);
@@ -117,21 +129,21 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     float *objW = (float *)(smem + ot_ + lds::OBJW), *objA = (float *)(smem + ot_ + lds::OBJA), *objA0 = (float *)(smem + ot_ + lds::OBJA0);
     unsigned long long *mcMask = (unsigned long long *)(smem + ot_ + lds::MCMASK);   // manifold constraints owned by wave w
     float *objSlp = (float *)(smem + ot_ + lds::OBJSLP);                              // sleep time of object m (< 0: asleep)
-    const int M = OBJ ? p.M : 0;   // OBJ = false: every object loop below folds away
+    const int M = OBJ ? ka->M : 0;   // OBJ = false: every object loop below folds away
     // MIX: KB_DRIVE_MIXED, any mix of the five drive laws in one env (the reference steps whatever is in _kilobots,
     // kilobots_env.py:183-184): the law of every kilobot comes from kb_buffers.bot_mode, its inverse mass (the classes have
-    // different densities, kilobot.py:25 / :214) from p.im_mode[law].  Instantiated on the code path with objects (per-body
+    // different densities, kilobot.py:25 / :214) from ka->im_mode[law].  Instantiated on the code path with objects (per-body
     // masses in the contacts' registers), one-wave workgroups.
     constexpr bool MIX = DRIVE_MODE == KB_DRIVE_MIXED;
     static_assert(!MIX || (OBJ && FN == 0), "mixed drive laws run on the generic code path with per-body masses");
-    unsigned char *botLaw = smem + (MIX ? p.botlaw_off : 0);     // MIX: [NP] law of every kilobot of the env (masses of contact partners)
-#define KB_IM_BOT(a_) (MIX ? p.im_mode[botLaw[a_]] : p.im_bot)     // inverse mass of kilobot a_
+    unsigned char *botLaw = smem + (MIX ? ka->botlaw_off : 0);     // MIX: [NP] law of every kilobot of the env (masses of contact partners)
+#define KB_IM_BOT(a_) (MIX ? ka->im_mode[botLaw[a_]] : ka->im_bot)     // inverse mass of kilobot a_
     // inverse mass / radius of a body id: kilobot < N, object N + m, wall >= WALL_CODE (static, edge skin radius)
     auto bim = [&](int id) __attribute__((always_inline)) -> float {
         return id >= WALL_CODE ? 0.0f : ((!OBJ || id < N) ? KB_IM_BOT(id) : objBody[(id - N) * BT_WORDS + BT_IM]);
     };
     auto brad = [&](int id) __attribute__((always_inline)) -> float {
-        return id >= WALL_CODE ? B2_POLYGON_RADIUS : ((!OBJ || id < N) ? p.r_bot : objBody[(id - N) * BT_WORDS + BT_RADIUS]);
+        return id >= WALL_CODE ? B2_POLYGON_RADIUS : ((!OBJ || id < N) ? ka->r_bot : objBody[(id - N) * BT_WORDS + BT_RADIUS]);
     };
     // is body id a polygon object (kilobot - polygon contacts carry a lever arm on the object)
     auto bpoly = [&](int id) __attribute__((always_inline)) -> bool {
@@ -139,14 +151,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     };
     ObjCtx ox;
     ox.pos = pos; ox.vel = vel; ox.objW = objW; ox.objA = objA; ox.objTab = objTab; ox.objBody = objBody;
-    ox.mc = (float *)(smem + lds::mcarea(fx, NB, capL_, NP, p.nhead));
-    ox.N = N; ox.MCN = p.nmc; ox.mu_oo = p.mu_oo; ox.mu_ow = p.mu_ow;
-    const int NMC = OBJ ? p.nmc : 0;      // manifold-constraint candidates (fixture pairs, fixture-wall)
-    const int F = OBJ ? p.F : 0;          // fixtures of the objects (>= M)
+    ox.mc = (float *)(smem + lds::mcarea(fx, NB, capL_, NP, ka->nhead));
+    ox.N = N; ox.MCN = ka->nmc; ox.mu_oo = ka->mu_oo; ox.mu_ow = ka->mu_ow;
+    const int NMC = OBJ ? ka->nmc : 0;      // manifold-constraint candidates (fixture pairs, fixture-wall)
+    const int F = OBJ ? ka->F : 0;          // fixtures of the objects (>= M)
 
-    const kb_buffers &g = p.buf;
     // (kernels with objects: the cell heads are a hash table of the cells for sparse swarms, like the bins)
-    auto hix = [&](int cell_) __attribute__((always_inline)) -> int { return hashed ? (cell_ & p.hmask) : cell_; };
+    auto hix = [&](int cell_) __attribute__((always_inline)) -> int { return hashed ? (cell_ & ka->hmask) : cell_; };
     // contact staging in global scratch, used when an env has more contacts than fit the LDS staging area
     unsigned *gPair, *gInfo;
     float *gAcc;
@@ -158,11 +169,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     do {                                                                                            \
         int e_ = blockIdx.x;                                                                        \
         asm volatile("" : "+s"(e_));                                                                \
-        e = e_; o = (size_t)e * N; wo = (size_t)e * p.cap;                                          \
-        gPair = reinterpret_cast<unsigned *>(g.scratch) + wo * 4;                                   \
-        gInfo = gPair + p.cap;                                                                      \
-        gAcc = reinterpret_cast<float *>(gInfo + p.cap);                                            \
-        gCbk = reinterpret_cast<unsigned short *>(gAcc + p.cap); gOrder = gCbk + p.cap;             \
+        KB_REARG();                                                                                 \
+        e = e_; o = (size_t)e * N; wo = (size_t)e * ka->cap;                                          \
+        gPair = reinterpret_cast<unsigned *>(ka->buf.scratch) + wo * 4;                                   \
+        gInfo = gPair + ka->cap;                                                                      \
+        gAcc = reinterpret_cast<float *>(gInfo + ka->cap);                                            \
+        gCbk = reinterpret_cast<unsigned short *>(gAcc + ka->cap); gOrder = gCbk + ka->cap;             \
     } while (0)
     KB_ENV_ADDRESSES();
 
@@ -183,10 +195,10 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #define KB_LAW(q) (MIX ? law[q] : DRIVE_MODE)
     // Velocity control, sorted-bin image: the command (v, omega) of a kilobot waits for the drive phase in the LDS velocity array
     // (idle between the substeps, indexed by id) instead of in two registers that the allocator would keep in scratch memory
-    // from the kernel start on; between fused substeps it is read again from g.v / g.w, where the kernel start left it.
+    // from the kernel start on; between fused substeps it is read again from ka->buf.v / ka->buf.w, where the kernel start left it.
     constexpr bool PARK = BINS && !MIX && DRIVE_MODE == KB_DRIVE_VELOCITY;
 #define KB_SLOT(q, b_) (BINS ? ms[q] : (b_))     // index of kilobot b_ (= tid + q * nt) in the per-body LDS arrays
-    // Every load of the kernel start is issued before the first store: the set_action stores (g.v / g.w) may alias anything as far
+    // Every load of the kernel start is issued before the first store: the set_action stores (ka->buf.v / ka->buf.w) may alias anything as far
     // as the compiler can tell, and loads that follow them in program order would wait for the previous kilobot's round trip to
     // HBM -- four dependent trips per thread (state, action, state, action) instead of one.
     float ldx[BPT], ldy[BPT];
@@ -201,29 +213,29 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         ldx[q] = 0.0f; ldy[q] = 0.0f; ldc[q] = 0u; lda[q] = make_float2(z_, z_);
         ms[q] = b < N ? b : NB - 1;
         if (b < N) {
-            ldx[q] = g.x[o + b]; ldy[q] = g.y[o + b]; th[q] = g.theta[o + b];
-            if (MIX) law[q] = min((int)g.bot_mode[o + b], 4);
-            if (SLEEP) slp[q] = g.sleep_time[o + b];
-            ldc[q] = g.ws_cnt[o + b];
+            ldx[q] = ka->buf.x[o + b]; ldy[q] = ka->buf.y[o + b]; th[q] = ka->buf.theta[o + b];
+            if (MIX) law[q] = min((int)ka->buf.bot_mode[o + b], 4);
+            if (SLEEP) slp[q] = ka->buf.sleep_time[o + b];
+            ldc[q] = ka->buf.ws_cnt[o + b];
             // (a velocity action replaces the stored command: nothing to load then)
             const bool velmode = KB_LAW(q) == KB_DRIVE_VELOCITY || KB_LAW(q) == KB_DRIVE_ACCEL;
-            if (velmode && !(KB_LAW(q) == KB_DRIVE_VELOCITY && p.actions)) { cv[q] = g.v[o + b]; cw[q] = g.w[o + b]; }
-            if (KB_LAW(q) == KB_DRIVE_ACCEL) { av[q] = g.acc_v[o + b]; aw[q] = g.acc_w[o + b]; }
-            if (p.actions && velmode) lda[q] = reinterpret_cast<const float2 *>(p.actions)[o + b];
+            if (velmode && !(KB_LAW(q) == KB_DRIVE_VELOCITY && ka->actions)) { cv[q] = ka->buf.v[o + b]; cw[q] = ka->buf.w[o + b]; }
+            if (KB_LAW(q) == KB_DRIVE_ACCEL) { av[q] = ka->buf.acc_v[o + b]; aw[q] = ka->buf.acc_w[o + b]; }
+            if (ka->actions && velmode) lda[q] = reinterpret_cast<const float2 *>(ka->actions)[o + b];
         }
     }
     // Sorted-bin image: the packed warm-start list of the previous launch is requested together with the state (the same trip
     // to HBM); how many of its entries exist is only known behind the offset scan below.
     unsigned pfKey[2] = {0u, 0u};
     float pfAcc[2] = {0.0f, 0.0f};
-    if (BINS && p.n_substeps > 0) {
+    if (BINS && ka->n_substeps > 0) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int i = tid + q * nt;
-            if (i < capL_ && i < p.cap) { pfKey[q] = g.ws_key[wo + i]; pfAcc[q] = g.ws_acc[wo + i]; }
+            if (i < capL_ && i < ka->cap) { pfKey[q] = ka->buf.ws_key[wo + i]; pfAcc[q] = ka->buf.ws_acc[wo + i]; }
         }
     }
-    int hasAct = __builtin_amdgcn_readfirstlane((int)(p.actions != nullptr));
+    int hasAct = __builtin_amdgcn_readfirstlane((int)(ka->actions != nullptr));
     asm volatile("" : "+s"(hasAct));      // (opaque: the two "is there an action" branches must not be merged again)
 #pragma unroll
     for (int q = 0; q < BPT; ++q) {
@@ -238,12 +250,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 if (KB_LAW(q) == KB_DRIVE_VELOCITY) {
                     cv[q] = fmaxf(fminf(a.x, 0.01f), 0.0f);
                     cw[q] = fmaxf(fminf(a.y, mw), -mw);
-                    g.v[o + b] = cv[q]; g.w[o + b] = cw[q];
+                    ka->buf.v[o + b] = cv[q]; ka->buf.w[o + b] = cw[q];
                 } else if (KB_LAW(q) == KB_DRIVE_ACCEL) {
                     const float aw_ = 0.2f * 3.14159265358979323846f;
                     av[q] = fmaxf(fminf(a.x, 0.005f), -0.005f);
                     aw[q] = fmaxf(fminf(a.y, aw_), -aw_);
-                    g.acc_v[o + b] = av[q]; g.acc_w[o + b] = aw[q];
+                    ka->buf.acc_v[o + b] = av[q]; ka->buf.acc_w[o + b] = aw[q];
                 }
             }
             if (PARK) vel[b] = make_float2(cv[q], cw[q]);
@@ -253,43 +265,43 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     // pushable objects: pose and velocity live in LDS (pos / vel / objA / objW), thread m integrates object m
     if (tid < M) {
         const size_t oi = (size_t)e * M + tid;
-        pos[N + tid].x = g.ox[oi]; pos[N + tid].y = g.oy[oi]; vel[N + tid].x = g.ovx[oi]; vel[N + tid].y = g.ovy[oi];
-        objA[tid] = g.otheta[oi]; objW[tid] = g.ow[oi];
-        if (SLEEP) objSlp[tid] = g.osleep[oi];
-        const float lx = p.obody[tid][BT_LCX], ly = p.obody[tid][BT_LCY];
+        pos[N + tid].x = ka->buf.ox[oi]; pos[N + tid].y = ka->buf.oy[oi]; vel[N + tid].x = ka->buf.ovx[oi]; vel[N + tid].y = ka->buf.ovy[oi];
+        objA[tid] = ka->buf.otheta[oi]; objW[tid] = ka->buf.ow[oi];
+        if (SLEEP) objSlp[tid] = ka->buf.osleep[oi];
+        const float lx = ka->obody[tid][BT_LCX], ly = ka->obody[tid][BT_LCY];
         if (lx != 0.0f || ly != 0.0f) {    // the state holds the body origin, the solver works on the centre of mass
-            const XF t = xf_make(g.ox[oi], g.oy[oi], g.otheta[oi]);
+            const XF t = xf_make(ka->buf.ox[oi], ka->buf.oy[oi], ka->buf.otheta[oi]);
             const V2 cm = xf_mul(t, mk2(lx, ly));
             pos[N + tid].x = cm.x; pos[N + tid].y = cm.y;
         }
     }
-    for (int k = tid; k < F * OT_WORDS; k += nt) objTab[k] = p.otab[k / OT_WORDS][k % OT_WORDS];
-    for (int k = tid; k < M * BT_WORDS; k += nt) objBody[k] = p.obody[k / BT_WORDS][k % BT_WORDS];
+    for (int k = tid; k < F * OT_WORDS; k += nt) objTab[k] = ka->otab[k / OT_WORDS][k % OT_WORDS];
+    for (int k = tid; k < M * BT_WORDS; k += nt) objBody[k] = ka->obody[k / BT_WORDS][k % BT_WORDS];
     // manifold-constraint candidate t (object pair / object-wall) is looked after by lane t of wave 0
     bool mcTouch = false;
     float *owsMine = nullptr;
-    if (BINS) { for (int c = tid; c < ldsb::bin_entries(p.nhead) / 2; c += nt) reinterpret_cast<unsigned *>(E1)[c] = 0u; }
-    else for (int c = tid; c < p.nhead; c += nt) head[c] = EMPTY16;
+    if (BINS) { for (int c = tid; c < ldsb::bin_entries(ka->nhead) / 2; c += nt) reinterpret_cast<unsigned *>(E1)[c] = 0u; }
+    else for (int c = tid; c < ka->nhead; c += nt) head[c] = EMPTY16;
     if (tid == 0) misc[M_STATUS] = 0;
     float lx = 0.0f, ly = 0.0f;
-    if (LIGHT_TYPE == KB_LIGHT_CIRCULAR) { lx = g.light_x[e]; ly = g.light_y[e]; }
+    if (LIGHT_TYPE == KB_LIGHT_CIRCULAR) { lx = ka->buf.light_x[e]; ly = ka->buf.light_y[e]; }
     // general light model: state of every component in registers (wave-uniform values)
     constexpr bool LGEN = LIGHT_TYPE == KB_LIGHT_GENERAL;
     float glx[KB_MAX_LIGHTS], gly[KB_MAX_LIGHTS], glvx[KB_MAX_LIGHTS], glvy[KB_MAX_LIGHTS];
 #pragma unroll
     for (int i = 0; i < KB_MAX_LIGHTS; ++i) {
         glx[i] = 0.0f; gly[i] = 0.0f; glvx[i] = 0.0f; glvy[i] = 0.0f;
-        if (LGEN && i < p.lcount) {
-            glx[i] = g.light_x[(size_t)e * p.lcount + i];
-            if (p.light_type != KB_LIGHT_GRADIENT) gly[i] = g.light_y[(size_t)e * p.lcount + i];
-            if (p.lkind[i] == KB_LIGHT_MOMENTUM) { glvx[i] = g.light_vx[(size_t)e * p.lcount + i]; glvy[i] = g.light_vy[(size_t)e * p.lcount + i]; }
+        if (LGEN && i < ka->lcount) {
+            glx[i] = ka->buf.light_x[(size_t)e * ka->lcount + i];
+            if (ka->light_type != KB_LIGHT_GRADIENT) gly[i] = ka->buf.light_y[(size_t)e * ka->lcount + i];
+            if (ka->lkind[i] == KB_LIGHT_MOMENTUM) { glvx[i] = ka->buf.light_vx[(size_t)e * ka->lcount + i]; glvy[i] = ka->buf.light_vy[(size_t)e * ka->lcount + i]; }
         }
     }
     // value_and_gradients of the general model at one sensor position (metres): kb_common.h
     auto sense_general = [&](float sx, float sy, float &val, float &gx, float &gy) __attribute__((always_inline)) {
-        kb_light_general_sense(p, glx, gly, sx, sy, val, gx, gy);
+        kb_light_general_sense(*ka, glx, gly, sx, sy, val, gx, gy);
     };
-    const bool drive = !(p.flags & KB_STEP_NO_DRIVE);
+    const bool drive = !(ka->flags & KB_STEP_NO_DRIVE);
     const float rr2 = p.rr2, rw2 = p.rw2;     // (r + r)^2, (polygonRadius + r)^2: host-evaluated, scalar registers
     __syncthreads();
     // warm-start list of the previous substep: offsets, and an LDS image of the packed entries if it fits
@@ -307,15 +319,15 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     }
     if (oldInLds) {
         for (unsigned i = tid + (BINS ? 2 * nt : 0); i < oldTotal; i += nt) {
-            const unsigned k = g.ws_key[wo + i];
+            const unsigned k = ka->buf.ws_key[wo + i];
             oldKey[i] = (unsigned short)(k >= KEY_OBJ ? OBJ_CODE + (k - KEY_OBJ) : (k >= KEY_WALL ? WALL_CODE + (k - KEY_WALL) : k));
-            oldAcc[i] = g.ws_acc[wo + i];
+            oldAcc[i] = ka->buf.ws_acc[wo + i];
         }
     }
     __syncthreads();
 
     KB_STAMP(13);    // kernel start: state loads, warm-start scan and list load
-    for (int sub = 0; sub < p.n_substeps; ++sub) {
+    for (int sub = 0; sub < ka->n_substeps; ++sub) {
         KB_ENV_ADDRESSES();
         // The thread index is re-read (through an opaque copy) at the top of every substep and of every phase: addresses
         // and predicates derived from it are then computed where they are used instead of being kept alive -- in spilled
@@ -327,13 +339,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #endif
 #define KB_RETID() do { int w_ = __builtin_amdgcn_readfirstlane(wave_s); asm volatile("" : "+s"(w_));                                                                  \
                         int l_ = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(l_));    \
-                        wave = w_; lane = l_; tid = (w_ << 6) | l_; } while (0)
+                        wave = w_; lane = l_; tid = (w_ << 6) | l_; KB_REARG(); } while (0)
         KB_RETID();
         // ---- light.step: SinglePositionLight.step, light.py:59-75 (uniform per env) ----
-        if (p.light_action && LGEN && drive)
-            kb_light_general_step(p, p.light_action + (size_t)e * p.ladim, h, glx, gly, glvx, glvy);
-        if (p.light_action && LIGHT_TYPE == KB_LIGHT_CIRCULAR && drive)
-            kb_light_single_step(p, p.light_action + 2 * e, h, lx, ly);
+        if (ka->light_action && LGEN && drive)
+            kb_light_general_step(*ka, ka->light_action + (size_t)e * ka->ladim, h, glx, gly, glvx, glvy);
+        if (ka->light_action && LIGHT_TYPE == KB_LIGHT_CIRCULAR && drive)
+            kb_light_single_step(*ka, ka->light_action + 2 * e, h, lx, ly);
         // ---- sensing + drive law + damping; grid insertion; reset per-substep scratch ----
         // sorted bins: position, damped velocity, cell and arrival index in its bin of this thread's kilobots, kept in
         // registers until the kilobot's slot of this substep is known
@@ -358,13 +370,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     if (KB_LAW(q) != KB_DRIVE_SIMPLE_PHOTOTAXIS) {  // kilobot.py:54-55: world point of (0, -r)
                         float s, c;
                         kb_sincosf(t, s, c);
-                        const float lx0 = 0.0f, ly0 = -p.r_bot;
+                        const float lx0 = 0.0f, ly0 = -ka->r_bot;
                         sx = (c * lx0 - s * ly0) + bx;
                         sy = (s * lx0 + c * ly0) + by;
                     }
                     if (LGEN) sense_general(sx / WORLD_SCALE, sy / WORLD_SCALE, lval, lgx, lgy);
-                    else kb_light_circular(sx / WORLD_SCALE, sy / WORLD_SCALE, lx, ly, p.light_radius, lval, lgx, lgy);
-                    if (g.light_value) { g.light_value[o + b] = lval; g.light_gx[o + b] = lgx; g.light_gy[o + b] = lgy; }
+                    else kb_light_circular(sx / WORLD_SCALE, sy / WORLD_SCALE, lx, ly, ka->light_radius, lval, lgx, lgy);
+                    if (ka->buf.light_value) { ka->buf.light_value[o + b] = lval; ka->buf.light_gx[o + b] = lgx; ka->buf.light_gy[o + b] = lgy; }
                 }
                 switch (KB_LAW(q)) {
                 case KB_DRIVE_ACCEL: {  // kilobot.py:294-300
@@ -387,21 +399,21 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     bvx = c * sp; bvy = s * sp; bww = cwq;
                 } break;
                 case KB_DRIVE_PHOTOTAXIS: {  // kilobot.py:318-333
-                    int upd = g.pt_update[o + b];
+                    int upd = ka->buf.pt_update[o + b];
                     if (upd % 6 == 0) {
                         float meas = lval;
-                        if (meas > g.pt_threshold[o + b] || g.pt_nochange[o + b] >= 15) {
-                            g.pt_threshold[o + b] = meas + 0.01f;
-                            if (g.pt_dir[o + b] == 0) { g.pt_dir[o + b] = 1; g.motor_l[o + b] = 0; g.motor_r[o + b] = 255; }
-                            else { g.pt_dir[o + b] = 0; g.motor_l[o + b] = 255; g.motor_r[o + b] = 0; }
-                            g.pt_nochange[o + b] = 0;
-                        } else g.pt_nochange[o + b] += 1;
+                        if (meas > ka->buf.pt_threshold[o + b] || ka->buf.pt_nochange[o + b] >= 15) {
+                            ka->buf.pt_threshold[o + b] = meas + 0.01f;
+                            if (ka->buf.pt_dir[o + b] == 0) { ka->buf.pt_dir[o + b] = 1; ka->buf.motor_l[o + b] = 0; ka->buf.motor_r[o + b] = 255; }
+                            else { ka->buf.pt_dir[o + b] = 0; ka->buf.motor_l[o + b] = 255; ka->buf.motor_r[o + b] = 0; }
+                            ka->buf.pt_nochange[o + b] = 0;
+                        } else ka->buf.pt_nochange[o + b] += 1;
                     }
-                    g.pt_update[o + b] = upd + 1;
-                    kb_motor_law(g.motor_l[o + b], g.motor_r[o + b], t, h, bvx, bvy, bww);
+                    ka->buf.pt_update[o + b] = upd + 1;
+                    kb_motor_law(ka->buf.motor_l[o + b], ka->buf.motor_r[o + b], t, h, bvx, bvy, bww);
                 } break;
                 case KB_DRIVE_MOTORS:
-                    kb_motor_law(g.motor_l[o + b], g.motor_r[o + b], t, h, bvx, bvy, bww);
+                    kb_motor_law(ka->buf.motor_l[o + b], ka->buf.motor_r[o + b], t, h, bvx, bvy, bww);
                     break;
                 case KB_DRIVE_SIMPLE_PHOTOTAXIS: {  // kilobot.py:191-203
                     float n = sqrtf(lgx * lgx + lgy * lgy);
@@ -412,7 +424,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 default: break;
                 }
             }
-            if (g.cmd_vx) { g.cmd_vx[o + b] = bvx; g.cmd_vy[o + b] = bvy; g.cmd_w[o + b] = bww; }
+            if (ka->buf.cmd_vx) { ka->buf.cmd_vx[o + b] = bvx; ka->buf.cmd_vy[o + b] = bvy; ka->buf.cmd_w[o + b] = bww; }
             if (SLEEP) {
                 // kilobot.py:123-127 assigns angularVelocity / linearVelocity: b2Body::SetAngularVelocity / SetLinearVelocity
                 // wake a sleeping body iff the value is non-zero (w * w > 0, b2Dot(v, v) > 0); one that stays asleep has
@@ -422,32 +434,32 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 active[b] = 0;       // "the island rooted here has an awake body": set in the flatten phase
             }
             // b2Island::Solve: v *= 1/(1 + h c)  (SimplePhototaxisKilobot sets linearDamping = 0, kilobot.py:203)
-            const float kl = (KB_LAW(q) == KB_DRIVE_SIMPLE_PHOTOTAXIS) ? 1.0f / (1.0f + h * 0.0f) : p.kl_bot;
-            bw[q] = bww * p.ka_bot;
-            int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
-            int cy = (int)floorf((by - p.ymin) * p.inv_cell);
-            cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
-            cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-            const int cell = cy * p.gw + cx;
+            const float kl = (KB_LAW(q) == KB_DRIVE_SIMPLE_PHOTOTAXIS) ? 1.0f / (1.0f + h * 0.0f) : ka->kl_bot;
+            bw[q] = bww * ka->ka_bot;
+            int cx = (int)floorf((bx - ka->xmin) * ka->inv_cell);
+            int cy = (int)floorf((by - ka->ymin) * ka->inv_cell);
+            cx = cx < 0 ? 0 : (cx >= ka->gw ? ka->gw - 1 : cx);
+            cy = cy < 0 ? 0 : (cy >= ka->gh ? ka->gh - 1 : cy);
+            const int cell = cy * ka->gw + cx;
             if (BINS) {
                 // broadphase: count the kilobot into its bin (entry bin + 1 of the boundary array; 16-bit counters, two per word)
                 sbx[q] = bx; sby[q] = by; svx[q] = bvx * kl; svy[q] = bvy * kl; scell[q] = cx | (cy << 12);
-                const int bi = (hashed ? (cell & p.hmask) : cell) + 1;
+                const int bi = (hashed ? (cell & ka->hmask) : cell) + 1;
                 const unsigned old = atomicAdd(reinterpret_cast<unsigned *>(E1) + (bi >> 1), 1u << (16 * (bi & 1)));
                 sarr[q] = (int)((old >> (16 * (bi & 1))) & 0xFFFFu);
-                if (SENSE && p.sense_s > 0) reinterpret_cast<unsigned short *>(lAcc)[b] = 0;   // (dead until the emit pass: the neighbour counters of the sensing pass, by slot)
+                if (SENSE && ka->sense_s > 0) reinterpret_cast<unsigned short *>(lAcc)[b] = 0;   // (dead until the emit pass: the neighbour counters of the sensing pass, by slot)
             } else {
                 vel[b].x = bvx * kl; vel[b].y = bvy * kl;
                 parent[b] = b;
                 // broadphase: push the bot on its cell's list
                 cellOf[b] = (unsigned short)cell;
                 nextb[b] = (unsigned short)kb_exch16(head, hix(cell), (unsigned)b);
-                if (SENSE && p.sense_s > 0) newOff[b] = 0;       // (dead until the scan behind the label pass: the neighbour counters of the sensing pass)
+                if (SENSE && ka->sense_s > 0) newOff[b] = 0;       // (dead until the scan behind the label pass: the neighbour counters of the sensing pass)
             }
         }
         if (tid < M) { start[N + tid].x = pos[N + tid].x; start[N + tid].y = pos[N + tid].y; objA0[tid] = objA[tid]; }
         if (tid < M) {   // b2Island::Solve damping of the objects; they keep their velocity between substeps
-            vel[N + tid].x *= p.kl_obj; vel[N + tid].y *= p.kl_obj; objW[tid] *= p.ka_obj;
+            vel[N + tid].x *= ka->kl_obj; vel[N + tid].y *= ka->kl_obj; objW[tid] *= ka->ka_obj;
             parent[N + tid] = N + tid;
             objCnt[tid] = 0;
             if (SLEEP) active[N + tid] = 0;
@@ -481,13 +493,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int idx = off + s0 + u;
-                        k4[u] = (s0 + u < cnt && idx < p.cap) ? g.ws_key[wo + idx] : 0xFFFFFFFFu;
+                        k4[u] = (s0 + u < cnt && idx < ka->cap) ? ka->buf.ws_key[wo + idx] : 0xFFFFFFFFu;
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         if (k4[u] == key32) {
-                            const float a_ = g.ws_acc[wo + off + s0 + u];
-                            if (SLEEP) g.ws_acc[wo + off + s0 + u] = -1.0f - a_;
+                            const float a_ = ka->buf.ws_acc[wo + off + s0 + u];
+                            if (SLEEP) ka->buf.ws_acc[wo + off + s0 + u] = -1.0f - a_;
                             return a_;
                         }
                 }
@@ -499,9 +511,14 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         unsigned newTotal = 0;        // entries of the packed warm-start list of this substep
         if constexpr (BINS) {
             // =============== sorted-bin broadphase + contact emission (kernels without objects) ===============
+            // (phase-scoped arguments: what the loops of the phases below read of the grid is loaded once per phase into these, in
+            //  front of the barrier that opens the phase, so that no loop carries a scalar load and its wait)
+            int gw_ = ka->gw, gh_ = ka->gh;
+            float invCell_ = ka->inv_cell;
+#define KB_GRID_ARGS() do { KB_REARG(); gw_ = ka->gw; gh_ = ka->gh; invCell_ = ka->inv_cell; } while (0)
             // 1. boundaries of the bins: inclusive scan of the counters (E1[b] .. E1[b + 1] = slots of bin b)
             {
-                const int nchunks = ldsb::bin_entries(p.nhead) >> 3;
+                const int nchunks = ldsb::bin_entries(ka->nhead) >> 3;
                 if (nchunks <= nt) block_scan_bins<true>(E1, nchunks, 1, wsum, tid);
                 else block_scan_bins<false>(E1, nchunks, (nchunks + nt - 1) / nt, wsum, tid);
             }
@@ -511,8 +528,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             for (int q = 0; q < BPT; ++q) {
                 const int b = tid + q * nt;
                 if (b >= N) continue;
-                const int cell = SC_CY(scell[q]) * p.gw + SC_CX(scell[q]);
-                const int bin = hashed ? (cell & p.hmask) : cell;
+                const int cell = SC_CY(scell[q]) * gw_ + SC_CX(scell[q]);
+                const int bin = hashed ? (cell & ka->hmask) : cell;
                 tmpSort[(int)E1[bin] + sarr[q]] = (unsigned short)b;
             }
             __syncthreads();
@@ -524,8 +541,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             for (int q = 0; q < BPT; ++q) {
                 const int b = tid + q * nt;
                 if (b >= N) continue;
-                const int cell = SC_CY(scell[q]) * p.gw + SC_CX(scell[q]);
-                const int bin = hashed ? (cell & p.hmask) : cell;
+                const int cell = SC_CY(scell[q]) * gw_ + SC_CX(scell[q]);
+                const int bin = hashed ? (cell & ka->hmask) : cell;
                 const int s0 = (int)E1[bin], s1 = (int)E1[bin + 1];
                 int rank = 0;
                 if (s1 - s0 > 1)
@@ -544,21 +561,22 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 vel[NB - 5 + tid] = make_float2(z_, z_);
             }
             KB_STAMP_PRE(33);    // ... + wave 0's kilobots settled in their slots
+            KB_GRID_ARGS();
             __syncthreads();
             KB_STAMP(0);
             KB_RETID();
             KB_ABLATE_EXIT(2);     // bins sorted
             // ---- IR-range neighbour sensing (kb_config.sense_radius): at the sensing point of the substep, like the light
             //      (kilobots_env.py:174-180), off the bins that the contact search uses ----
-            if (SENSE && p.sense_s > 0 && drive) {
+            if (SENSE && ka->sense_s > 0 && drive) {
 #pragma unroll 1
                 for (int q = 0; q < BPT; ++q) {
                     const int b = tid + q * nt;
                     if (b >= N) continue;
                     const int sl = q == 0 ? ms[0] : ms[BPT - 1];
                     const int sc = q == 0 ? scell[0] : scell[BPT - 1];
-                    if (hashed) kb_sense_bins_hashed(pos, E1, cellOfSlot, reinterpret_cast<unsigned *>(lAcc), sl, SC_CX(sc), SC_CY(sc), p.gw, p.gh, p.sense_s, p.sense_r2, p.hmask);
-                    else kb_sense_bins(pos, E1, reinterpret_cast<unsigned *>(lAcc), sl, SC_CX(sc), SC_CY(sc), p.gw, p.gh, p.sense_s, p.sense_r2);
+                    if (hashed) kb_sense_bins_hashed(pos, E1, cellOfSlot, reinterpret_cast<unsigned *>(lAcc), sl, SC_CX(sc), SC_CY(sc), gw_, gh_, ka->sense_s, ka->sense_r2, ka->hmask);
+                    else kb_sense_bins(pos, E1, reinterpret_cast<unsigned *>(lAcc), sl, SC_CX(sc), SC_CY(sc), gw_, gh_, ka->sense_s, ka->sense_r2);
                 }
             }
             // ---- narrowphase, pass 1 (thread per kilobot): the contacts the kilobot owns -- touching partners of the half
@@ -569,7 +587,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             // ([same | E], [N | NE], [NW]); hashed bins: one run per cell.  sp = first slot of the run's second cell.
             constexpr int NR = FN ? 3 : 5;
             auto candidate_runs = [&](int sa, int cx, int cy, int (&lo)[NR], int (&hi)[NR], int (&sp)[NR], int (&tc)[5]) __attribute__((always_inline)) {
-                const int gw = p.gw, gh = p.gh;
+                const int gw = gw_, gh = gh_;
                 const int cell = cy * gw + cx;
                 const bool e_ok = cx + 1 < gw, n_ok = cy + 1 < gh, w_ok = cx > 0;
                 tc[0] = cell; tc[1] = cell + 1; tc[2] = cell + gw; tc[3] = cell + gw + 1; tc[4] = cell + gw - 1;
@@ -585,7 +603,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     const bool ok[5] = {true, e_ok, n_ok, n_ok && e_ok, n_ok && w_ok};
 #pragma unroll
                     for (int k = 0; k < 5; ++k) {
-                        const int bin = hashed ? (tc[k] & p.hmask) : tc[k];
+                        const int bin = hashed ? (tc[k] & ka->hmask) : tc[k];
                         const int l_ = ok[k] ? (int)E1[bin] : 0, h_ = ok[k] ? (int)E1[bin + 1] : 0;
                         lo[k] = k == 0 ? sa + 1 : l_; hi[k] = h_; sp[k] = h_;
                     }
@@ -663,7 +681,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                 for (int wl = 0; wl < 4; ++wl) {
                     float dist, nx, ny;
-                    wall_geom(p, wl, ax, ay, dist, nx, ny);
+                    wall_geom(*ka, wl, ax, ay, dist, nx, ny);
                     if (dist * dist > rw2) continue;
                     wm |= (1u << wl) | (dist < 0.0f ? 16u << wl : 0u);     // (bit 4 + wl: centre outside the wall line, the manifold normal points outwards)
                 }
@@ -682,6 +700,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 static_assert(BPT == 2 && MAX_WAVES <= 8, "two rows of per-wave sums in the 16-word scratch");
                 const unsigned inc0 = wave_incl_scan(snm[0]), inc1 = wave_incl_scan(snm[1]);
                 if (lane == 63) { wsum[wave] = inc0; wsum[8 + wave] = inc1; }
+                KB_GRID_ARGS();
                 __syncthreads();
                 KB_ABLATE_EXIT(3);     // owned contacts found
                 unsigned b0 = 0, b1 = 0, t0 = 0, t1 = 0;
@@ -696,18 +715,18 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             KB_STAMP(1);
             KB_RETID();
             KB_ABLATE_EXIT(4);     // offsets of the packed list
-            if (SENSE && p.sense_s > 0 && drive) {      // the neighbour counters lie where the emit pass stages the impulses
+            if (SENSE && ka->sense_s > 0 && drive) {      // the neighbour counters lie where the emit pass stages the impulses
 #pragma unroll
                 for (int q = 0; q < BPT; ++q) {
                     const int b = tid + q * nt;
-                    if (b < N) g.nbr_count[o + b] = (unsigned)reinterpret_cast<unsigned short *>(lAcc)[ms[q]];
+                    if (b < N) ka->buf.nbr_count[o + b] = (unsigned)reinterpret_cast<unsigned short *>(lAcc)[ms[q]];
                 }
                 __syncthreads();
             }
             const unsigned extras = misc[M_XTRA];      // contacts beyond the warm-start slots of their owner: solved, never stored
-            const int capS = FN ? capL_ : min(capL_, p.cap);      // (a contact_capacity below the LDS staging area still bounds the list)
-            big = p.solver_mode >= 3 || newTotal + extras > (unsigned)capS;
-            stageCap = big ? p.cap : capS;
+            const int capS = FN ? capL_ : min(capL_, ka->cap);      // (a contact_capacity below the LDS staging area still bounds the list)
+            big = ka->solver_mode >= 3 || newTotal + extras > (unsigned)capS;
+            stageCap = big ? ka->cap : capS;
             if (newTotal + extras > (unsigned)stageCap && tid == 0) atomicOr(&misc[M_STATUS], 1u);
             ncon = (int)min(newTotal + extras, (unsigned)stageCap);
             // ---- narrowphase, pass 2 (the owner's thread, as light as possible: its trip count is the busiest lane's): stage the
@@ -729,8 +748,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 newOff[b] = (unsigned short)myOff[q];
                 if (ntot == 0u) continue;
                 const unsigned base = myOff[q], nst = snm[q];
-                const int cell = cy * p.gw + cx;
-                const unsigned common = ((unsigned)(cx & 1) << 12) | ((unsigned)(cy & 1) << 13) | (sa > (int)E1[hashed ? (cell & p.hmask) : cell] ? 1u << 14 : 0u);
+                const int cell = cy * gw_ + cx;
+                const unsigned common = ((unsigned)(cx & 1) << 12) | ((unsigned)(cy & 1) << 13) | (sa > (int)E1[hashed ? (cell & ka->hmask) : cell] ? 1u << 14 : 0u);
                 int curk = -1;
                 unsigned jk = 0;
                 unsigned wleft = wm & 15u;
@@ -764,6 +783,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             };
             if (big) stage_pass(gPair, gInfo); else stage_pass(lPair, lInfo);
             KB_STAMP_PRE(34);    // (cumulative since the offset scan) wave 0's owned contacts staged
+            KB_GRID_ARGS();
             __syncthreads();
             KB_STAMP_PRE(35);    // ... + barrier
             KB_RETID();
@@ -822,12 +842,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         if ((raw >> 14) & 1u) {
                             // rank base of the (cell, direction) group: its contacts owned by the kilobots of the cell in front of the owner
                             const float2 pa = pos[a];
-                            int cx = (int)floorf((pa.x - p.xmin) * p.inv_cell);
-                            int cy = (int)floorf((pa.y - p.ymin) * p.inv_cell);
-                            cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
-                            cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-                            const int cell = cy * p.gw + cx;
-                            for (int s_ = (int)E1[hashed ? (cell & p.hmask) : cell]; s_ < (int)a; ++s_) {
+                            int cx = (int)floorf((pa.x - ka->xmin) * invCell_);
+                            int cy = (int)floorf((pa.y - ka->ymin) * invCell_);
+                            cx = cx < 0 ? 0 : (cx >= gw_ ? gw_ - 1 : cx);
+                            cy = cy < 0 ? 0 : (cy >= gh_ ? gh_ - 1 : cy);
+                            const int cell = cy * gw_ + cx;
+                            for (int s_ = (int)E1[hashed ? (cell & ka->hmask) : cell]; s_ < (int)a; ++s_) {
                                 if (hashed && (int)cellOfSlot[s_] != cell) continue;
                                 r += (dirCnt[s_] >> (6 * k)) & 63u;
                             }
@@ -861,12 +881,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     if ((raw >> 14) & 1u) {
                         // rank base of the (cell, direction) group: its contacts owned by the kilobots of the cell in front of the owner
                         const float2 pa = pos[a];
-                        int cx = (int)floorf((pa.x - p.xmin) * p.inv_cell);
-                        int cy = (int)floorf((pa.y - p.ymin) * p.inv_cell);
-                        cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
-                        cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-                        const int cell = cy * p.gw + cx;
-                        for (int s_ = (int)E1[hashed ? (cell & p.hmask) : cell]; s_ < (int)a; ++s_) {
+                        int cx = (int)floorf((pa.x - ka->xmin) * invCell_);
+                        int cy = (int)floorf((pa.y - ka->ymin) * invCell_);
+                        cx = cx < 0 ? 0 : (cx >= gw_ ? gw_ - 1 : cx);
+                        cy = cy < 0 ? 0 : (cy >= gh_ ? gh_ - 1 : cy);
+                        const int cell = cy * gw_ + cx;
+                        for (int s_ = (int)E1[hashed ? (cell & ka->hmask) : cell]; s_ < (int)a; ++s_) {
                             if (hashed && (int)cellOfSlot[s_] != cell) continue;
                             r += (dirCnt[s_] >> (6 * k)) & 63u;
                         }
@@ -899,16 +919,16 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         } else {
             // ---- IR-range neighbour sensing (kb_config.sense_radius): at the sensing point of the substep, like the light
             //      (kilobots_env.py:174-180), off the cell lists that the contact search uses ----
-            if (SENSE && p.sense_s > 0 && drive)
-                kb_sense_pass(pos, head, nextb, cellOf, reinterpret_cast<unsigned *>(newOff), N, nt, tid, p.gw, p.gh, p.sense_s, p.sense_r2, hashed ? p.hmask : 0);
+            if (SENSE && ka->sense_s > 0 && drive)
+                kb_sense_pass(pos, head, nextb, cellOf, reinterpret_cast<unsigned *>(newOff), N, nt, tid, ka->gw, ka->gh, ka->sense_s, ka->sense_r2, hashed ? ka->hmask : 0);
             // object-object / object-wall manifolds (b2Contact::Update) + their velocity-constraint set-up: candidate t
-            // is lane t of wave 0; the record lives in LDS, the previous substep's impulses come from g.ows_acc
+            // is lane t of wave 0; the record lives in LDS, the previous substep's impulses come from ka->buf.ows_acc
             if (OBJ && wave == 0) {
                 mcTouch = false;
                 if (lane < NMC) {
-                    owsMine = g.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS);
+                    owsMine = ka->buf.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS);
                     Arena ar;
-                    ar.xmin = p.xmin; ar.ymin = p.ymin; ar.xmax = p.xmax; ar.ymax = p.ymax;
+                    ar.xmin = ka->xmin; ar.ymin = ka->ymin; ar.xmax = ka->xmax; ar.ymax = ka->ymax;
                     mcTouch = mc_detect(ox, ar, F, lane, owsMine);
                     if (SLEEP && !mcTouch) {
                         // b2Contact::Update: an object pair that was touching in the previous step (a stored manifold) and is not any
@@ -932,7 +952,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll 1
                 for (int a = tid; a < N; a += nt) {
                     const int cell = cellOf[a];
-                    const int cx = cell % p.gw, cy = cell / p.gw;
+                    const int cx = cell % ka->gw, cy = cell / ka->gw;
                     const float ax = pos[a].x, ay = pos[a].y;
                     unsigned cnt = 0, mine = 0;
                     unsigned hd[5];      // heads of the five cell lists, fetched together (one LDS round trip)
@@ -940,8 +960,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                     for (int k = 0; k < 5; ++k) {
                         const int ox = cx + dir_dx(k), oy = cy + dir_dy(k);
-                        const bool in = ox >= 0 && ox < p.gw && oy < p.gh;
-                        tcell[k] = in ? oy * p.gw + ox : cell;
+                        const bool in = ox >= 0 && ox < ka->gw && oy < ka->gh;
+                        tcell[k] = in ? oy * ka->gw + ox : cell;
                         hd[k] = in ? (unsigned)head[hix(tcell[k])] : (unsigned)EMPTY16;
                     }
                     // the five lists are walked in lockstep: one LDS round trip serves the next candidate of every list that
@@ -986,7 +1006,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                     for (int wl = 0; wl < 4; ++wl) {
                         float dist, nx, ny;
-                        wall_geom(p, wl, ax, ay, dist, nx, ny);
+                        wall_geom(*ka, wl, ax, ay, dist, nx, ny);
                         if (dist * dist > rw2) continue;
                         mine++;
                         const unsigned c = atomicAdd(&misc[M_NCON], 1u);
@@ -1003,11 +1023,11 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         const float *T = objTab + f * OT_WORDS;
                         const int m = ot_body(T);
                         const float dx = pos[N + m].x - ax, dy = pos[N + m].y - ay;
-                        const float ro = p.r_bot + T[OT_BOUND];       // circle: contact radius; polygon: bounding radius
+                        const float ro = ka->r_bot + T[OT_BOUND];       // circle: contact radius; polygon: bounding radius
                         if (dx * dx + dy * dy > ro * ro) continue;
                         if (T[OT_KIND] != 0.0f) {
                             V2 ln, lp;
-                            if (!collide_poly_circle(T, body_xf(ox, N + m), mk2(ax, ay), p.r_bot, ln, lp)) continue;
+                            if (!collide_poly_circle(T, body_xf(ox, N + m), mk2(ax, ay), ka->r_bot, ln, lp)) continue;
                         }
                         mine++;
                         const unsigned pos = atomicAdd(&objCnt[f], 1u);
@@ -1022,7 +1042,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     wsCntNew[a] = (unsigned char)mine;
                 }
             };
-            big = p.solver_mode >= 3;
+            big = ka->solver_mode >= 3;
             if (!big) {
                 find_pass(lPair, lInfo, capL_);
                 KB_STAMP_PRE(17);
@@ -1036,12 +1056,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 }
             }
             if (big) {
-                find_pass(gPair, gInfo, p.cap);
+                find_pass(gPair, gInfo, ka->cap);
                 __syncthreads();
             }
             KB_STAMP(1);
             KB_RETID();
-            stageCap = big ? p.cap : capL_;
+            stageCap = big ? ka->cap : capL_;
             if ((int)misc[M_NCON] > stageCap && tid == 0) atomicOr(&misc[M_STATUS], 1u);
             ncon = min((int)misc[M_NCON], stageCap);
 
@@ -1077,7 +1097,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                         for (int w2 = 0; w2 < 4; ++w2) {
                             float dist, nx, ny;
-                            wall_geom(p, w2, ax, ay, dist, nx, ny);
+                            wall_geom(*ka, w2, ax, ay, dist, nx, ny);
                             if (!(dist * dist > rw2)) slot++;
                         }
                         slot += (int)((inf0 >> 8) & 15u);      // lower objects this kilobot touches (counted by the find pass)
@@ -1103,7 +1123,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
 #pragma unroll
                         for (int w2 = 0; w2 < 3; ++w2) {
                             float dist, nx, ny;
-                            wall_geom(p, w2, ax, ay, dist, nx, ny);
+                            wall_geom(*ka, w2, ax, ay, dist, nx, ny);
                             if (w2 < wl && !(dist * dist > rw2)) r++;
                         }
                         cls = CLS_WALL | (int)(inf0 & 0x80u);
@@ -1113,7 +1133,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         const int a = pr & 0xFFFF;
                         const unsigned b = pr >> 16;
                         const int cell = cellOf[a];
-                        const int cx = cell % p.gw, cy = cell / p.gw;
+                        const int cx = cell % ka->gw, cy = cell / ka->gw;
                         const float ax = pos[a].x, ay = pos[a].y;
                         if (k == 0) cls = CLS_SAME;
                         else if (k == 1) cls = CLS_E + (cx & 1);
@@ -1130,7 +1150,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         // position of b among a's touching partners of this direction, in ascending id order
                         int j = 0;
                         if (((dc >> (6 * k)) & 63u) > 1u) {
-                            const int oc = (cy + dir_dy(k)) * p.gw + (cx + dir_dx(k));
+                            const int oc = (cy + dir_dy(k)) * ka->gw + (cx + dir_dx(k));
                             for (unsigned b2 = head[hix(oc)]; b2 != (unsigned)EMPTY16; b2 = nextb[b2]) {
                                 if (b2 >= b || (k == 0 && (int)b2 <= a) || (hashed && (int)cellOf[b2] != oc)) continue;
                                 const float2 pb2 = pos[b2];
@@ -1179,10 +1199,10 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 const int b = tid + q * nt;
                 if (b >= N) continue;
                 const int cnt = wsCnt[b], off = wsOff[b];
-                for (int s_ = 0; s_ < cnt && off + s_ < p.cap; ++s_) {
-                    const float a_ = oldInLds ? oldAcc[off + s_] : g.ws_acc[wo + off + s_];
+                for (int s_ = 0; s_ < cnt && off + s_ < ka->cap; ++s_) {
+                    const float a_ = oldInLds ? oldAcc[off + s_] : ka->buf.ws_acc[wo + off + s_];
                     if (a_ < 0.0f) continue;      // matched: still touching
-                    unsigned key = oldInLds ? (unsigned)oldKey[off + s_] : g.ws_key[wo + off + s_];
+                    unsigned key = oldInLds ? (unsigned)oldKey[off + s_] : ka->buf.ws_key[wo + off + s_];
                     if (!oldInLds) key = key >= KEY_OBJ ? OBJ_CODE + (key - KEY_OBJ) : (key >= KEY_WALL ? WALL_CODE + (key - KEY_WALL) : key);
                     if (key >= (unsigned)WALL_CODE) continue;
                     if (slp[q] < 0.0f) slp[q] = 0.0f;
@@ -1208,7 +1228,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             if (!BINS) head[hix(cellOf[b])] = EMPTY16;
             if (!SLEEP) active[b] = 1;
             active[NB + b] = 0;
-            if (!BINS && SENSE && p.sense_s > 0 && drive) g.nbr_count[o + b] = (unsigned)newOff[b];
+            if (!BINS && SENSE && ka->sense_s > 0 && drive) ka->buf.nbr_count[o + b] = (unsigned)newOff[b];
         }
         if (tid < 64) bkStart[tid] = 0;     // size-class counters of the island placement
         if (tid < 32) bkFill[tid] = 0;
@@ -1257,7 +1277,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // (Sorted bins, several waves, solver_mode 0: nobody reads the contacts per wave of the default placement -- the
         //  placement by size below zeroes and recounts them, and with a giant island or the global staging slice `reg` is false
         //  whatever they say -- so the eight hot counters are left alone.)
-        const bool wcntDead = BINS && nw > 1 && p.solver_mode == 0;
+        const bool wcntDead = BINS && nw > 1 && ka->solver_mode == 0;
         auto census = [&](const unsigned *sPair) __attribute__((always_inline)) {
             for (int c = tid; c < ncon; c += nt) {
                 const unsigned root = parent[sPair[c] >> 16];
@@ -1275,9 +1295,9 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         //   reg : every wave can hold its contacts in registers (<= KREG per lane) -> no contact arrays in the sweeps
         //   list: per-wave sweeps over the staged contact arrays
         // (a one-wave workgroup is its own cooperative group; it may still take the register path)
-        bool coopForced = misc[M_MAXISL] > (unsigned)GIANT_ISLAND || p.solver_mode == 2 || p.solver_mode == 4;
+        bool coopForced = misc[M_MAXISL] > (unsigned)GIANT_ISLAND || ka->solver_mode == 2 || ka->solver_mode == 4;
         bool coop = coopForced || nw == 1;
-        if (!coop && !big && p.solver_mode == 0) {
+        if (!coop && !big && ka->solver_mode == 0) {
             // Placement of the islands on the waves in order of size: the largest (= deepest) islands share the first
             // waves, the many tiny ones fill the rest.  A wave sweeps as many rounds as its deepest island has levels
             // and the LDS pipeline is shared, so what counts is the SUM of those depths over the waves -- about a third
@@ -1385,8 +1405,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             maxw = 0;
             for (int w = 0; w < nw; ++w) maxw = max(maxw, misc[M_WCNT + w]);
         }
-        bool reg = !coopForced && !big && maxw <= 64u * KRX && p.solver_mode == 0;
-        if (!coop && !big && maxw > 64u * KRX && p.solver_mode == 0) {
+        bool reg = !coopForced && !big && maxw <= 64u * KRX && ka->solver_mode == 0;
+        if (!coop && !big && maxw > 64u * KRX && ka->solver_mode == 0) {
             // The default placement (root id mod #waves) overloads a wave.  Place the islands of BIG_ISLAND contacts or
             // more one by one, largest first, each on the wave with the least load (ties: lowest root / lowest wave);
             // the small ones stay where they are.  Results do not depend on the placement, only the time does.
@@ -1436,7 +1456,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // Kernels without objects: whatever does not fit the registers (an overloaded wave, contacts staged in the global slice) is
         // swept by the whole workgroup level by level as well -- the per-wave list sweeps go key by key (~ 20 rounds per pass where
         // the levels are ~ 12) and are left to the one-wave workgroups and the test knob.
-        if (BINS && nw > 1 && !reg && p.solver_mode == 0) { coopForced = true; coop = true; }
+        if (BINS && nw > 1 && !reg && ka->solver_mode == 0) { coopForced = true; coop = true; }
         if (OBJ && wave == 0) {   // which wave sweeps which manifold constraint (slot nw: all of them)
             const bool on = lane < NMC && mcTouch && (!SLEEP || active[mci(ox, MC_ISL, lane)] != 0);
             const unsigned w_ = on ? (unsigned)islWave[mci(ox, MC_ISL, lane)] : 0u;
@@ -1469,7 +1489,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         auto mc_clear_flags = [&](unsigned long long mask, bool leader, unsigned char *act) __attribute__((always_inline)) {
             if (leader) for (unsigned long long m_ = mask; m_; m_ &= m_ - 1) act[mci(ox, MC_ISL, __builtin_ctzll(m_))] = 0;
         };
-        // StoreImpulses of the manifold constraints: candidate t owns entry (owner, column) of g.ows_acc
+        // StoreImpulses of the manifold constraints: candidate t owns entry (owner, column) of ka->buf.ows_acc
         auto mc_store = [&]() __attribute__((always_inline)) {
             if (OBJ && wave == 0 && lane < NMC) {
                 int owner, col;
@@ -1533,6 +1553,8 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             }
             __syncthreads();
         };
+        // (phase-scoped arguments: what the sorted-bin solvers read of the arguments, loaded in front of the barrier that opens them)
+        SolveArgs ca;
         if (reg) {
             // register solver: it only needs each wave's contacts grouped together (any order inside a wave)
             for (int b = tid; b < N + M; b += nt) islCnt[b] = 0;   // reused as per-body dependency depth
@@ -1567,11 +1589,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     lOrder[base + atomicAdd(&misc[M_WFILL + w], 1u)] = (unsigned short)c;
                 }
             }
+            if (BINS) { KB_REARG(); ca = solve_args(*ka); }
             __syncthreads();
         } else if (big) bucket_sort(gPair, gInfo, gCbk, gOrder);
         else bucket_sort(lPair, lInfo, lCbk, lOrder);
         KB_STAMP(3);
         KB_RETID();
+        if (!(BINS && reg)) ca = solve_args(*ka);
         KB_ABLATE_EXIT(8);     // census, placement, contacts grouped by wave
 
         // a giant island (or the test knob): the whole workgroup sweeps, level by level (kernels without objects; one-wave
@@ -1601,11 +1625,11 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             float rrAx[KREG], rrAy[KREG], rlnx[KREG], rlny[KREG], rlpx[KREG], rlpy[KREG];
             unsigned mlo = 0, mhi = 0;
             // without objects the masses / radii of a contact follow from "is A a wall": no registers needed
-            const float nm_bb = p.nm_bb, nm_wb = p.nm_wb;
-#define R_IMA(j) (OBJ ? rima[j] : (ra[j] < WALL_CODE ? p.im_bot : 0.0f))
-#define R_IMB(j) (OBJ ? rimb[j] : p.im_bot)
-#define R_RA(j) (OBJ ? rra[j] : (ra[j] < WALL_CODE ? p.r_bot : B2_POLYGON_RADIUS))
-#define R_RB(j) (OBJ ? rrb[j] : p.r_bot)
+            const float nm_bb = ca.nm_bb, nm_wb = ca.nm_wb;
+#define R_IMA(j) (OBJ ? rima[j] : (ra[j] < WALL_CODE ? ca.im_bot : 0.0f))
+#define R_IMB(j) (OBJ ? rimb[j] : ca.im_bot)
+#define R_RA(j) (OBJ ? rra[j] : (ra[j] < WALL_CODE ? ca.r_bot : B2_POLYGON_RADIUS))
+#define R_RB(j) (OBJ ? rrb[j] : ca.r_bot)
 #define R_NM(j) (OBJ ? rnm[j] : (ra[j] < WALL_CODE ? nm_bb : nm_wb))
             // ---- light load: bodies and key of the contacts of this wave, in arrival order ----
 #pragma unroll
@@ -1776,11 +1800,11 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         const XF xo = body_xf(ox, b);
                         const V2 bc = mk2(pos[a].x, pos[a].y);
                         V2 ln = mk2(0.0f, 0.0f), lp = mk2(0.0f, 0.0f);
-                        collide_poly_circle(T, xo, bc, p.r_bot, ln, lp);
+                        collide_poly_circle(T, xo, bc, ca.r_bot, ln, lp);
                         const V2 normal = rot_mul(xo, ln);
                         const V2 planePoint = xf_mul(xo, lp);
                         const V2 cA = v_add(bc, v_scale(T[OT_RADIUS] - v_dot(v_sub(bc, planePoint), normal), normal));
-                        const V2 cB = v_sub(bc, v_scale(p.r_bot, normal));
+                        const V2 cB = v_sub(bc, v_scale(ca.r_bot, normal));
                         const V2 point = v_scale(0.5f, v_add(cA, cB));
                         const V2 rA = v_sub(point, mk2(pos[b].x, pos[b].y));
                         const float rnA = v_cross(rA, normal);
@@ -1790,7 +1814,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         rnm[j] = kNormal > 0.0f ? 1.0f / kNormal : 0.0f;
                     } else if (a >= WALL_CODE) {
                         float dist, nx, ny;
-                        wall_geom(p, a - WALL_CODE, pos[b].x, pos[b].y, dist, nx, ny);
+                        wall_geom(ca, a - WALL_CODE, pos[b].x, pos[b].y, dist, nx, ny);
                         if (rflip[j]) { nx = -nx; ny = -ny; }
                         rnx[j] = nx; rny[j] = ny;
                     } else {
@@ -1854,7 +1878,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             // SolveVelocityConstraints: friction 0, restitution 0, one manifold point.  Slot by slot, level by level; only the
             // lanes whose contact is of the round's level execute (EXEC mask).
             const int DUMMY = NB - 1;
-            for (int it = 0; it < p.vel_iters; ++it) {
+            for (int it = 0; it < ca.vel_iters; ++it) {
 #pragma unroll
                 for (int j = 0; j < KREG; ++j) {
                     for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
@@ -1907,7 +1931,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             if (tid == 0) atomicAdd(&KB_PROF(9), misc[M_PROF]);   // deepest wave of the env (replaces the contacts-per-wave slot)
 #endif
             // StoreImpulses -> packed warm-start list of the next substep (LDS image and/or global)
-            const bool last = sub == p.n_substeps - 1;
+            const bool last = sub == ka->n_substeps - 1;
 #pragma unroll
             for (int j = 0; j < KREG; ++j) {
                 if (BINS) {      // the contact is staged at its position in the packed list: the list goes out as a whole at the end of the substep
@@ -1919,12 +1943,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 const int owner = a < WALL_CODE ? a : b;
                 const unsigned key16 = a >= WALL_CODE ? (unsigned)a : (b >= N ? (unsigned)OBJ_CODE + ((lInfo[rc[j]] >> 24) & 15u) : (unsigned)b);
                 const unsigned pos = (unsigned)newOff[owner] + (unsigned)rslot[j];
-                if (pos >= (unsigned)p.cap) continue;
+                if (pos >= (unsigned)ka->cap) continue;
                 if (newInLds) { oldKey[pos] = (unsigned short)key16; oldAcc[pos] = racc[j]; }
                 if (last || !newInLds) {
-                    g.ws_key[wo + pos] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE)
+                    ka->buf.ws_key[wo + pos] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE)
                                        : (key16 >= (unsigned)OBJ_CODE ? KEY_OBJ + (key16 - OBJ_CODE) : key16);
-                    g.ws_acc[wo + pos] = racc[j];
+                    ka->buf.ws_acc[wo + pos] = racc[j];
                 }
             }
             // integrate positions (b2Island::Solve)
@@ -1950,7 +1974,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 vel[b].x = vxx; vel[b].y = vyy; bw[q] = ww;
                 // (islWave is idle from here on) island state for the sleep bookkeeping: bit 1 = has an awake body,
                 // bit 0 = position constraints not solved (set by the last position sweep; always without sweeps)
-                if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+                if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (ca.pos_iters <= 0 ? 1 : 0));
             }
             if (tid < M) {   // objects: same integrator (b2Island writes the clamped velocity back to the body)
                 const int b = N + tid;
@@ -1965,7 +1989,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 vel[b].x = vxx; vel[b].y = vyy; objW[tid] = ww;
                 pos[b].x += h * vxx; pos[b].y += h * vyy;
                 objA[tid] += h * ww;
-                if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+                if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (ca.pos_iters <= 0 ? 1 : 0));
             }
             __syncthreads();
             KB_STAMP(5);
@@ -1973,7 +1997,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             KB_ABLATE_EXIT(12);    // impulses stored, positions integrated
             // SolvePositionConstraints; an island stops once its minSeparation >= -3 slop.  The island flags are read
             // once per iteration; depth levels without an active contact in this wave are skipped altogether.
-            for (int it = 0; it < p.pos_iters; ++it) {
+            for (int it = 0; it < ca.pos_iters; ++it) {
                 unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;
                 bool viol = false;
                 bool ron[KREG];
@@ -1992,9 +2016,9 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             const V2 normal = rot_mul(xo, mk2(rlnx[j], rlny[j]));
                             const V2 planePoint = xf_mul(xo, mk2(rlpx[j], rlpy[j]));
                             const V2 clipPoint = mk2(pos[a].x, pos[a].y);
-                            const float sep = v_dot(v_sub(clipPoint, planePoint), normal) - T[BT_RADIUS] - p.r_bot;
+                            const float sep = v_dot(v_sub(clipPoint, planePoint), normal) - T[BT_RADIUS] - ca.r_bot;
                             const V2 rA = v_sub(clipPoint, mk2(pos[b].x, pos[b].y));
-                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == ca.pos_iters - 1) islWave[isl] = 3; }
                             const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                             const float rnA = v_cross(rA, normal);
                             const float K = T[BT_IM] + KB_IM_BOT(a) + T[BT_II] * rnA * rnA;
@@ -2010,7 +2034,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         float axx = 0.0f, ayy = 0.0f;
                         if (a >= WALL_CODE) {
                             float dist, wx, wy;
-                            wall_geom(p, a - WALL_CODE, bx, by, dist, wx, wy);
+                            wall_geom(ca, a - WALL_CODE, bx, by, dist, wx, wy);
                             nx = rflip[j] ? -wx : wx; ny = rflip[j] ? -wy : wy;   // manifold normal fixed at detection
                             const float along = rflip[j] ? -dist : dist;
                             sep = along - R_RA(j) - R_RB(j);
@@ -2022,7 +2046,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
                             sep = (dx * nx + dy * ny) - R_RA(j) - R_RB(j);
                         }
-                        if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                        if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == ca.pos_iters - 1) islWave[isl] = 3; }
                         const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                         const float K = ima + imb;
                         const float imp = K > 0.0f ? -C / K : 0.0f;
@@ -2034,7 +2058,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         wave_sync();
                     }
                 }
-                if (OBJ && myMc) { viol |= mc_position_pass(myMc, lane == 0, act, nxt, it == p.pos_iters - 1); wave_sync(); }
+                if (OBJ && myMc) { viol |= mc_position_pass(myMc, lane == 0, act, nxt, it == ca.pos_iters - 1); wave_sync(); }
 #ifdef KB_PROFILE
                 if (tid == 0) atomicAdd(&KB_PROF(10), 1u);
 #endif
@@ -2064,7 +2088,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             auto solve_list = [&](unsigned *sPair, unsigned *sInfo, float *sAcc, unsigned short *cbk,
                                   unsigned short *order, float *sN, const bool haveN) __attribute__((always_inline)) {
                 const bool HN = PF && haveN;
-                float *sNx = sN, *sNy = sN + p.cap, *sNm = sN + 2 * p.cap;
+                float *sNx = sN, *sNy = sN + ka->cap, *sNm = sN + 2 * ka->cap;
                 // a "round" = all contacts of one key owned by this (virtual) wave.  coop: the workgroup is one
                 // virtual wave and rounds are separated by s_barrier; otherwise every wave runs alone.
                 const int myw = coop ? 0 : wave;
@@ -2201,7 +2225,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 float nx, ny;                                                                       \
                 if (a >= WALL_CODE) {                                                               \
                     float dist_;                                                                    \
-                    wall_geom(p, a - WALL_CODE, pos[b].x, pos[b].y, dist_, nx, ny);                       \
+                    wall_geom(ca, a - WALL_CODE, pos[b].x, pos[b].y, dist_, nx, ny);                       \
                     if (flip) { nx = -nx; ny = -ny; }                                               \
                 } else {                                                                            \
                     const float dx_ = pos[b].x - pos[a].x, dy_ = pos[b].y - pos[a].y;                           \
@@ -2222,7 +2246,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                         const int m = b - N;
                         const float *T = objTab + ((KB_INF >> 24) & 15u) * OT_WORDS;      // the fixture that is touched
                         PolyCon pc;
-                        poly_contact_setup(T, body_xf(ox, b), pos[b].x, pos[b].y, mk2(pos[a].x, pos[a].y), p.r_bot, KB_IM_BOT(a), pc);
+                        poly_contact_setup(T, body_xf(ox, b), pos[b].x, pos[b].y, mk2(pos[a].x, pos[a].y), ca.r_bot, KB_IM_BOT(a), pc);
                         const float acc = KB_ACC;
                         const float Px = acc * pc.normal.x, Py = acc * pc.normal.y;
                         objW[m] -= T[OT_II] * (pc.rA.x * Py - pc.rA.y * Px);
@@ -2243,7 +2267,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 })
                 if (OBJ && myMc) { mc_warm_pass(myMc, leader); KB_ROUND_SYNC(); }
                 // SolveVelocityConstraints
-                for (int it = 0; it < p.vel_iters; ++it) {
+                for (int it = 0; it < ca.vel_iters; ++it) {
                     KB_FOR_ROUNDS(true, true, {
                         const unsigned pr = KB_PR;
                         const int a = pr & 0xFFFF, b = pr >> 16;
@@ -2252,7 +2276,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             const int m = b - N;
                             const float *T = objTab + ((KB_INF >> 24) & 15u) * OT_WORDS;
                             PolyCon pc;
-                            poly_contact_setup(T, body_xf(ox, b), pos[b].x, pos[b].y, mk2(pos[a].x, pos[a].y), p.r_bot, KB_IM_BOT(a), pc);
+                            poly_contact_setup(T, body_xf(ox, b), pos[b].x, pos[b].y, mk2(pos[a].x, pos[a].y), ca.r_bot, KB_IM_BOT(a), pc);
                             const float wA = objW[m];
                             const float dvx = (vel[a].x - vel[b].x) - (-wA * pc.rA.y), dvy = (vel[a].y - vel[b].y) - (wA * pc.rA.x);
                             const float vn = dvx * pc.normal.x + dvy * pc.normal.y;
@@ -2295,7 +2319,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 KB_RETID();
                 mc_store();
                 // StoreImpulses -> packed warm-start list of the next substep
-                const bool last = sub == p.n_substeps - 1;
+                const bool last = sub == ka->n_substeps - 1;
                 for (int c = tid; c < (BINS ? 0 : ncon); c += nt) {      // (sorted bins: the staged contacts are the packed list; it goes out at the end of the substep)
                     const unsigned inf = sInfo[c];
                     const int sl = (inf >> 16) & 0xFF;
@@ -2306,12 +2330,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     const float acc = sAcc[c];
                     const unsigned key16 = a >= WALL_CODE ? (unsigned)a : (b >= N ? (unsigned)OBJ_CODE + ((inf >> 24) & 15u) : (unsigned)b);
                     const unsigned pos = (unsigned)newOff[owner] + (unsigned)sl;
-                    if (pos >= (unsigned)p.cap) continue;
+                    if (pos >= (unsigned)ka->cap) continue;
                     if (newInLds) { oldKey[pos] = (unsigned short)key16; oldAcc[pos] = acc; }
                     if (last || !newInLds) {
-                        g.ws_key[wo + pos] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE)
+                        ka->buf.ws_key[wo + pos] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE)
                                            : (key16 >= (unsigned)OBJ_CODE ? KEY_OBJ + (key16 - OBJ_CODE) : key16);
-                        g.ws_acc[wo + pos] = acc;
+                        ka->buf.ws_acc[wo + pos] = acc;
                     }
                 }
                 // integrate positions (b2Island::Solve)
@@ -2335,7 +2359,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     pos[b].x += h * vxx; pos[b].y += h * vyy;
                     th[q] += h * ww;
                     vel[b].x = vxx; vel[b].y = vyy; bw[q] = ww;
-                    if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+                    if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (ca.pos_iters <= 0 ? 1 : 0));
                 }
                 if (tid < M) {   // objects
                     const int b = N + tid;
@@ -2350,13 +2374,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     vel[b].x = vxx; vel[b].y = vyy; objW[tid] = ww;
                     pos[b].x += h * vxx; pos[b].y += h * vyy;
                     objA[tid] += h * ww;
-                    if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (p.pos_iters <= 0 ? 1 : 0));
+                    if (SLEEP) islWave[b] = (unsigned char)((active[b] ? 2 : 0) | (ca.pos_iters <= 0 ? 1 : 0));
                 }
                 __syncthreads();
                 KB_STAMP(5);
                 KB_RETID();
                 // SolvePositionConstraints; an island stops once its minSeparation >= -3 slop
-                for (int it = 0; it < p.pos_iters; ++it) {
+                for (int it = 0; it < ca.pos_iters; ++it) {
                     unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;
                     bool viol = false;
                     KB_FOR_ROUNDS(false, false, {
@@ -2369,14 +2393,14 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             const int m = b - N;
                             const float *T = objTab + ((KB_INF >> 24) & 15u) * OT_WORDS;
                             V2 ln, lp;
-                            collide_poly_circle(T, xf_of_body(objBody + m * BT_WORDS, start[b].x, start[b].y, objA0[m]), mk2(start[a].x, start[a].y), p.r_bot, ln, lp);
+                            collide_poly_circle(T, xf_of_body(objBody + m * BT_WORDS, start[b].x, start[b].y, objA0[m]), mk2(start[a].x, start[a].y), ca.r_bot, ln, lp);
                             const XF xo = body_xf(ox, b);
                             const V2 normal = rot_mul(xo, ln);
                             const V2 planePoint = xf_mul(xo, lp);
                             const V2 clipPoint = mk2(pos[a].x, pos[a].y);
-                            const float sep = v_dot(v_sub(clipPoint, planePoint), normal) - T[OT_RADIUS] - p.r_bot;
+                            const float sep = v_dot(v_sub(clipPoint, planePoint), normal) - T[OT_RADIUS] - ca.r_bot;
                             const V2 rA = v_sub(clipPoint, mk2(pos[b].x, pos[b].y));
-                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == ca.pos_iters - 1) islWave[isl] = 3; }
                             const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                             const float rnA = v_cross(rA, normal);
                             const float K = T[OT_IM] + KB_IM_BOT(a) + T[OT_II] * rnA * rnA;
@@ -2392,7 +2416,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             float axx = 0.0f, ayy = 0.0f;
                             if (a >= WALL_CODE) {
                                 float dist, wx, wy;
-                                wall_geom(p, a - WALL_CODE, bx, by, dist, wx, wy);
+                                wall_geom(ca, a - WALL_CODE, bx, by, dist, wx, wy);
                                 const bool flipped = (KB_INF & 0x80) != 0;   // manifold normal fixed at detection
                                 nx = flipped ? -wx : wx; ny = flipped ? -wy : wy;
                                 const float along = flipped ? -dist : dist;
@@ -2405,7 +2429,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                                 if (!(len < B2_EPSILON)) { const float inv = 1.0f / len; nx = dx * inv; ny = dy * inv; }
                                 sep = (dx * nx + dy * ny) - rda - rdb;
                             }
-                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == p.pos_iters - 1) islWave[isl] = 3; }
+                            if (sep < -3.0f * B2_LINEAR_SLOP) { nxt[isl] = 1; viol = true; if (SLEEP && it == ca.pos_iters - 1) islWave[isl] = 3; }
                             const float C = kb_clampf(B2_BAUMGARTE * (sep + B2_LINEAR_SLOP), -B2_MAX_LINEAR_CORRECTION, 0.0f);
                             const float K = ima + imb;
                             const float imp = K > 0.0f ? -C / K : 0.0f;
@@ -2414,7 +2438,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                             pos[b].x = bx + imb * Px; pos[b].y = by + imb * Py;
                         }
                     })
-                    if (OBJ && myMc) { viol |= mc_position_pass(myMc, leader, act, nxt, it == p.pos_iters - 1); KB_ROUND_SYNC(); }
+                    if (OBJ && myMc) { viol |= mc_position_pass(myMc, leader, act, nxt, it == ca.pos_iters - 1); KB_ROUND_SYNC(); }
 #ifdef KB_PROFILE
                     if (tid == 0) atomicAdd(&KB_PROF(10), 1u);
 #endif
@@ -2445,7 +2469,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             };
             if (big) {
                 // normals + effective masses of the records: 12 B per contact behind the 16-byte records of all envs
-                float *gN = reinterpret_cast<float *>(g.scratch) + (size_t)p.E * p.cap * 4 + wo * 3;
+                float *gN = reinterpret_cast<float *>(ka->buf.scratch) + (size_t)ka->E * ka->cap * 4 + wo * 3;
                 solve_list(gPair, gInfo, gAcc, gCbk, gOrder, gN, true);
             } else solve_list(lPair, lInfo, lAcc, lCbk, lOrder, nullptr, false);
         }
@@ -2466,7 +2490,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             // Per island: minimum of the sleep times (non-negative floats order like their bit patterns) in the contact
             // staging area, which is idle between the position sweeps and the continuous step (2 capL >= NB words).
             // (sorted-bin image: wherever NB words are idle by now -- the bin boundaries or the staged pairs, kb_create decides)
-            unsigned *islMin = BINS ? reinterpret_cast<unsigned *>(smem + (FN ? ldsb::binE(NB, NP, false, capL_) : p.islmin_off)) : lPair;
+            unsigned *islMin = BINS ? reinterpret_cast<unsigned *>(smem + (FN ? ldsb::binE(NB, NP, false, capL_) : ka->islmin_off)) : lPair;
             const float linTolSqr = B2_LINEAR_SLEEP_TOL * B2_LINEAR_SLEEP_TOL, angTolSqr = B2_ANGULAR_SLEEP_TOL * B2_ANGULAR_SLEEP_TOL;
             for (int b = tid; b < N + M; b += nt) islMin[b] = 0x7F7FFFFFu;      // b2_maxFloat
             __syncthreads();
@@ -2525,7 +2549,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // kilobot in a hundred env-substeps: without a candidate the kernels without objects go on behind the barrier of the
         // collection -- no processing loop, no barrier behind it, no read-back, no barrier in front of the list image.
         bool toiRecords = false;     // block-uniform: candidate records were written (or the objects ran their continuous step)
-        if (p.toi_walls) {
+        if (ka->toi_walls) {
             // candidate records (body, angle at the start of the substep, angle, angular velocity) in arrays that are idle by now;
             // sorted-bin image: the staged impulses and keys must survive to the end of the substep (they are the packed list)
             float *cTh0 = reinterpret_cast<float *>(BINS ? parent : lInfo), *cTh = BINS ? reinterpret_cast<float *>(lPair) : lAcc;
@@ -2551,7 +2575,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                 //  measured: it gives the whole gain back, DESIGN.md "Continuous step")
                 bool none = true;
 #pragma unroll
-                for (int wl = 0; wl < 4; ++wl) none &= kb_toi_no_event(p, wl, p.toi_tt, xa, ya, xb, yb);
+                for (int wl = 0; wl < 4; ++wl) none &= kb_toi_no_event(*ka, wl, ka->toi_tt, xa, ya, xb, yb);
                 if (none) continue;          // no wall can have an event: the body would leave kb_toi_walls_body as it came
                 const int i = (int)atomicAdd(&misc[M_NCON], 1u);
                 if (i >= candMax) { atomicOr(&misc[M_STATUS], 8u); continue; }
@@ -2566,17 +2590,17 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             if (toiRecords) {
                 for (int i = tid; i < ncand; i += nt) {
                     const int b = BINS ? (int)cSlot[i] : (int)lPair[i];
-                    float R = p.r_bot, im = KB_IM_BOT(b);
+                    float R = ka->r_bot, im = KB_IM_BOT(b);
                     asm volatile("" : "+v"(R), "+v"(im));   // per-lane copies: keeps the two constants out of the scalar file over the event loop
                     float x_ = pos[b].x, y_ = pos[b].y, a_ = cTh[i], vx_ = vel[b].x, vy_ = vel[b].y, w_ = cW[i];
-                    kb_toi_walls_body(p, R, im, BINS ? startX[b] : start[b].x, BINS ? startY[b] : start[b].y, cTh0[i], x_, y_, a_, vx_, vy_, w_);
+                    kb_toi_walls_body(*ka, R, im, BINS ? startX[b] : start[b].x, BINS ? startY[b] : start[b].y, cTh0[i], x_, y_, a_, vx_, vy_, w_);
                     pos[b].x = x_; pos[b].y = y_; vel[b].x = vx_; vel[b].y = vy_; cTh[i] = a_; cW[i] = w_;
                 }
                 if (OBJ && tid < M && !(SLEEP && objSlp[tid] < 0.0f)) {   // objects: the TOI sub-solve runs on the manifold-constraint records of their wall contacts
                     Arena ar;
-                    ar.xmin = p.xmin; ar.ymin = p.ymin; ar.xmax = p.xmax; ar.ymax = p.ymax;
-                    toi_walls_object(ox, ar, F, tid, start[N + tid].x, start[N + tid].y, objA0[tid], p.h, p.vel_iters,
-                                     g.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS));
+                    ar.xmin = ka->xmin; ar.ymin = ka->ymin; ar.xmax = ka->xmax; ar.ymax = ka->ymax;
+                    toi_walls_object(ox, ar, F, tid, start[N + tid].x, start[N + tid].y, objA0[tid], p.h, ka->vel_iters,
+                                     ka->buf.ows_acc + (size_t)e * (MAXOBJ * KB_OWS_COLS * KB_OWS_WORDS));
                 }
                 KB_STAMP_PRE(27);    // ... + wave 0's own candidates processed
                 __syncthreads();
@@ -2590,7 +2614,7 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
         // The state of an object between substeps is its body origin (what one-substep launches store and load, and
         // what the specification's substep does): bodies whose centre of mass is off the origin go through the same
         // origin -> centre of mass conversion inside a fused launch, so that fusing never changes a bit.
-        if (OBJ && tid < M && sub + 1 < p.n_substeps &&
+        if (OBJ && tid < M && sub + 1 < ka->n_substeps &&
             (objBody[tid * BT_WORDS + BT_LCX] != 0.0f || objBody[tid * BT_WORDS + BT_LCY] != 0.0f)) {
             const XF t0 = body_xf(ox, N + tid);                                   // b2Body::SynchronizeTransform
             const XF t1 = xf_make(t0.p.x, t0.p.y, objA[tid]);
@@ -2598,12 +2622,12 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
             pos[N + tid].x = cm.x; pos[N + tid].y = cm.y;
         }
         // the new warm-start list becomes the old one (nothing of this is read again behind the last substep of a launch)
-        const bool lastSub = sub == p.n_substeps - 1;
+        const bool lastSub = sub == ka->n_substeps - 1;
         if (PARK && !lastSub) {      // the commands of the next substep's drive phase (the velocity array is idle behind the last barrier)
 #pragma unroll
             for (int q = 0; q < BPT; ++q) {
                 const int b = tid + q * nt;
-                if (b < N) vel[b] = make_float2(g.v[o + b], g.w[o + b]);
+                if (b < N) vel[b] = make_float2(ka->buf.v[o + b], ka->buf.w[o + b]);
             }
         }
         if (!lastSub) for (int b = tid; b < NP; b += nt) { wsCnt[b] = wsCntNew[b]; wsOff[b] = newOff[b]; }
@@ -2619,13 +2643,13 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
                     const float acc = sAcc[i];
                     if (newInLds && !lastSub) { oldKey[i] = (unsigned short)key16; oldAcc[i] = acc; }
                     if (lastSub || !newInLds) {
-                        g.ws_key[wo + i] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE) : key16;
-                        g.ws_acc[wo + i] = acc;
+                        ka->buf.ws_key[wo + i] = key16 >= (unsigned)WALL_CODE ? KEY_WALL + (key16 - WALL_CODE) : key16;
+                        ka->buf.ws_acc[wo + i] = acc;
                     }
                 }
             };
             if (big) list_out(gInfo, gAcc); else list_out(lInfo, lAcc);
-            if (!lastSub) for (int c = tid; c < ldsb::bin_entries(p.nhead) / 2; c += nt) reinterpret_cast<unsigned *>(E1)[c] = 0u;     // (the bucket tables lay over the bin boundaries)
+            if (!lastSub) for (int c = tid; c < ldsb::bin_entries(ka->nhead) / 2; c += nt) reinterpret_cast<unsigned *>(E1)[c] = 0u;     // (the bucket tables lay over the bin boundaries)
         }
         oldInLds = newInLds;
         oldTotal = newTotal;
@@ -2639,39 +2663,39 @@ __global__ void __launch_bounds__(TIER == 1 ? 64 : 64 * KB_MAX_WAVES, (TIER == 1
     for (int q = 0; q < BPT; ++q) {
         const int b = tid + q * nt;
         if (b < N) {
-            g.x[o + b] = pos[KB_SLOT(q, b)].x; g.y[o + b] = pos[KB_SLOT(q, b)].y; g.theta[o + b] = th[q];
-            if (SLEEP && p.n_substeps > 0) g.sleep_time[o + b] = slp[q];
-            if (p.n_substeps > 0) g.ws_cnt[o + b] = wsCntNew[b];      // (the counts of the last substep)
-            if (KB_LAW(q) == KB_DRIVE_ACCEL && p.n_substeps > 0 && drive) { g.v[o + b] = cv[q]; g.w[o + b] = cw[q]; }
+            ka->buf.x[o + b] = pos[KB_SLOT(q, b)].x; ka->buf.y[o + b] = pos[KB_SLOT(q, b)].y; ka->buf.theta[o + b] = th[q];
+            if (SLEEP && ka->n_substeps > 0) ka->buf.sleep_time[o + b] = slp[q];
+            if (ka->n_substeps > 0) ka->buf.ws_cnt[o + b] = wsCntNew[b];      // (the counts of the last substep)
+            if (KB_LAW(q) == KB_DRIVE_ACCEL && ka->n_substeps > 0 && drive) { ka->buf.v[o + b] = cv[q]; ka->buf.w[o + b] = cw[q]; }
         }
     }
-    if (tid < M && p.n_substeps > 0) {
+    if (tid < M && ka->n_substeps > 0) {
         const size_t oi = (size_t)e * M + tid;
-        g.ox[oi] = pos[N + tid].x; g.oy[oi] = pos[N + tid].y; g.otheta[oi] = objA[tid];
+        ka->buf.ox[oi] = pos[N + tid].x; ka->buf.oy[oi] = pos[N + tid].y; ka->buf.otheta[oi] = objA[tid];
         if (objBody[tid * BT_WORDS + BT_LCX] != 0.0f || objBody[tid * BT_WORDS + BT_LCY] != 0.0f) {   // b2Body::SynchronizeTransform
             const XF t = body_xf(ox, N + tid);
-            g.ox[oi] = t.p.x; g.oy[oi] = t.p.y;
+            ka->buf.ox[oi] = t.p.x; ka->buf.oy[oi] = t.p.y;
         }
-        g.ovx[oi] = vel[N + tid].x; g.ovy[oi] = vel[N + tid].y; g.ow[oi] = objW[tid];
-        if (SLEEP) g.osleep[oi] = objSlp[tid];
+        ka->buf.ovx[oi] = vel[N + tid].x; ka->buf.ovy[oi] = vel[N + tid].y; ka->buf.ow[oi] = objW[tid];
+        if (SLEEP) ka->buf.osleep[oi] = objSlp[tid];
     }
     if (tid == 0) {
-        if (LIGHT_TYPE == KB_LIGHT_CIRCULAR && p.light_action && drive) { g.light_x[e] = lx; g.light_y[e] = ly; }
-        if (LGEN && p.light_action && drive) {
+        if (LIGHT_TYPE == KB_LIGHT_CIRCULAR && ka->light_action && drive) { ka->buf.light_x[e] = lx; ka->buf.light_y[e] = ly; }
+        if (LGEN && ka->light_action && drive) {
 #pragma unroll
             for (int i = 0; i < KB_MAX_LIGHTS; ++i) {
-                if (i >= p.lcount) break;
-                g.light_x[(size_t)e * p.lcount + i] = glx[i];
-                if (p.light_type != KB_LIGHT_GRADIENT) g.light_y[(size_t)e * p.lcount + i] = gly[i];
-                if (p.lkind[i] == KB_LIGHT_MOMENTUM) { g.light_vx[(size_t)e * p.lcount + i] = glvx[i]; g.light_vy[(size_t)e * p.lcount + i] = glvy[i]; }
+                if (i >= ka->lcount) break;
+                ka->buf.light_x[(size_t)e * ka->lcount + i] = glx[i];
+                if (ka->light_type != KB_LIGHT_GRADIENT) ka->buf.light_y[(size_t)e * ka->lcount + i] = gly[i];
+                if (ka->lkind[i] == KB_LIGHT_MOMENTUM) { ka->buf.light_vx[(size_t)e * ka->lcount + i] = glvx[i]; ka->buf.light_vy[(size_t)e * ka->lcount + i] = glvy[i]; }
             }
         }
-        if (misc[M_STATUS]) atomicOr(&g.status[e], (int)misc[M_STATUS]);
+        if (misc[M_STATUS]) atomicOr(&ka->buf.status[e], (int)misc[M_STATUS]);
 #ifdef KB_PROFILE
         atomicAdd(&KB_PROF(22), (unsigned)clock64() - prof_t);     // write-back (thread 0's own stores)
-        for (int k = 0; k < 8; ++k) g.status[p.E + 40 * e + k] += (int)(KB_PROF(k) >> 4);   // units of 16 cycles
-        for (int k = 8; k < 13; ++k) g.status[p.E + 40 * e + k] += (int)KB_PROF(k);
-        for (int k = 13; k < 40; ++k) g.status[p.E + 40 * e + k] += (int)(KB_PROF(k) >> 4);
+        for (int k = 0; k < 8; ++k) ka->buf.status[ka->E + 40 * e + k] += (int)(KB_PROF(k) >> 4);   // units of 16 cycles
+        for (int k = 8; k < 13; ++k) ka->buf.status[ka->E + 40 * e + k] += (int)KB_PROF(k);
+        for (int k = 13; k < 40; ++k) ka->buf.status[ka->E + 40 * e + k] += (int)(KB_PROF(k) >> 4);
 #endif
     }
 }
