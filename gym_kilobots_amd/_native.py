@@ -27,6 +27,7 @@ HOPS_UNLIMITED = MAX_BOTS     # KB_HOPS_UNLIMITED: the max_hops of kb_sense_hops
 GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_sense_grid, a bit each
 MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense_contacts
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
+MAX_TARGETS = 1024     # KB_MAX_TARGETS: slots of the target shape of kb_sense_targets
 RENDER_OBJECTS, RENDER_BOTS, RENDER_LIGHT = 1, 2, 4     # KB_RENDER_*: the layers of kb_render, a bit each
 RENDER_MAX_SIDE = 2048     # KB_RENDER_MAX_SIDE: pixels along either side of a frame of kb_render
 RAY_BOTS, RAY_OBJECTS, RAY_WALLS = 1, 2, 4     # KB_RAY_*: what the rays of kb_sense_rays can hit, a bit each
@@ -128,6 +129,7 @@ SIGNATURES = {
     'kb_grid_channels': (_I, [_P, _I]),
     'kb_sense_grid': (_I, [_P, _I, _I, _I, _P, _P]),
     'kb_sense_coverage': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'kb_sense_targets': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
     'kb_render': (_I, [_P, _I, _I, _I, C.POINTER(KbRenderStyle), _P, _P, _P, _P]),
@@ -300,6 +302,19 @@ def check_coverage(width, height):
     if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
         raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
     return width, height
+
+
+def check_targets(n_targets, tol_m):
+    """The limits of kb_sense_targets on the number of slots and the tolerance in metres; ValueError where the library would
+    answer KB_EINVAL.  Returns (n_targets, tol_m)."""
+    if isinstance(n_targets, bool) or isinstance(tol_m, bool):
+        raise ValueError('n_targets must be an integer and tol_m a number')
+    n_targets, tol_m = int(n_targets), float(tol_m)
+    if not 1 <= n_targets <= MAX_TARGETS:
+        raise ValueError('n_targets must be in 1..%d' % MAX_TARGETS)
+    if not 0.0 <= tol_m < float('inf'):
+        raise ValueError('tol_m must be finite and not negative')
+    return n_targets, tol_m
 
 
 RENDER_LAYERS = {'objects': RENDER_OBJECTS, 'bots': RENDER_BOTS, 'light': RENDER_LIGHT}

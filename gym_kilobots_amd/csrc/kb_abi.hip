@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage, kb_sense_targets) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -982,6 +982,22 @@ int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int3
     hipLaunchKernelGGL(kb_coverage_kernel, dim3((unsigned)p.E), dim3(256), (size_t)CoverageLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, a, d_select,
                        d_owner, d_dist, reinterpret_cast<float4 *>(d_cell), d_stats);
     return launched("kb_sense_coverage");
+}
+
+int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, const uint8_t *d_bot_select,
+                     const uint8_t *d_slot_select, int32_t *d_index, float *d_rel, int32_t *d_owner, float *d_dist, float *d_stats, void *stream) {
+    if (!sim || !d_points) return fail(KB_EINVAL, "kb_sense_targets: NULL argument");
+    if (n_targets < 1 || n_targets > KB_MAX_TARGETS) return fail(KB_EINVAL, "kb_sense_targets: 1 <= n_targets <= KB_MAX_TARGETS (1024) required");
+    if (!(tol_m >= 0.0f) || !std::isfinite(tol_m)) return fail(KB_EINVAL, "kb_sense_targets: tol_m must be finite and not negative");
+    if (!d_index && !d_rel && !d_owner && !d_dist && !d_stats) return fail(KB_EINVAL, "kb_sense_targets: d_index, d_rel, d_owner, d_dist and d_stats are all NULL");
+    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_targets: d_rel must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_targets: kb_bind() first");
+    const Params &p = sim->p;
+    const float Tw = tol_m * WORLD_SCALE;
+    const TargetsArgs a = {p.N, n_targets, per_env != 0, Tw * Tw};
+    hipLaunchKernelGGL(kb_targets_kernel, dim3((unsigned)p.E), dim3(TARGETS_THREADS), (size_t)TargetsLds(p.N, n_targets).bytes, (hipStream_t)stream, a, p.buf.x,
+                       p.buf.y, p.buf.theta, d_points, d_bot_select, d_slot_select, d_index, reinterpret_cast<float4 *>(d_rel), d_owner, d_dist, d_stats);
+    return launched("kb_sense_targets");
 }
 
 int kb_render_default_style(kb_render_style *out) {

@@ -1,6 +1,7 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
 // kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
-// kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_grid, which bins
+// kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_targets, which meets
+// the slots of a target shape, every kilobot against every slot, and needs none either; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
@@ -1594,6 +1595,249 @@ __global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const 
             }
             d_cell[o + b] = row;
         }
+    }
+}
+
+// ---- kb_sense_targets: kilobot-to-slot matching of every env ---------------------------------------------------------------
+constexpr int TARGETS_THREADS = 256;        // the workgroup kb_sense_targets launches: a lane owns at most KB_MAX_BOTS / 256 entries of a side
+constexpr unsigned TARGETS_NONE = 0x7F800001u;      // above the bits of every d2 that is a number, +inf included
+struct TargetsArgs { int N, K, per_env; float T2; };        // the sizes, whether the points are per env, and the host constant of the definition (include/kilobots_hip.h)
+struct TargetsLds {     // byte offsets: bpos (float2) at 0, spos (float2), bres, sres (u64: bits of d2 << 32 | compacted index of the winner), red (u64 sum[2]; u32 worst[2], within[2], wsum[4]), bidx, sidx (u16)
+    int spos, bres, sres, red, bidx, sidx, bytes;
+    __host__ __device__ constexpr TargetsLds(int N, int K)      // (every array padded to four entries: the passes read four positions per round trip)
+        : spos(8 * ((N + 3) & ~3)), bres(spos + 8 * ((K + 3) & ~3)), sres(bres + spos), red(2 * bres), bidx(red + 48), sidx(bidx + spos / 4),
+          bytes((sidx + 2 * ((K + 3) & ~3) + 15) & ~15) {}
+};
+static_assert(TargetsLds(KB_MAX_BOTS, KB_MAX_TARGETS).bytes <= 64 * 1024 && KB_MAX_BOTS <= 4 * TARGETS_THREADS && KB_MAX_TARGETS <= 4 * TARGETS_THREADS &&
+              KB_MAX_BOTS <= 0xFFFF && KB_MAX_TARGETS <= 0xFFFF, "kb_targets_kernel: LDS image");
+
+// One direction of kb_targets_kernel: a lane owns the entries i0 + 256 j, j < NJ, of mine[0 .. nmine), keeps their running
+// best in registers and walks other[k0 .. k1) in ascending order -- every lane of a wave reads the same four positions at a
+// time, which the LDS broadcasts.  "<" alone gives a tie to the entry met first, the lower index.  ox - mx is tx - x_b when the
+// kilobots own and its negation when the slots do: the squares, and with them d2, are the same bits.  The key of the walk is
+// bits of the least d2 << 32 | index of its entry in other; res[i] = that key, or with SHARED, where several waves walk parts
+// of other for the same owners, the least of res[i] and the key by an LDS atomic.  k0 is a multiple of 4; nmine >= 1.
+template <int NJ, bool SHARED>
+__device__ __forceinline__ void kb_targets_nearest(const float2 *mine, const int nmine, const float2 *other, const int k0, const int k1,
+                                                   unsigned long long *res, const int i0) {
+    float mx[NJ], my[NJ];
+    unsigned bd[NJ], bi[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int i = i0 + TARGETS_THREADS * j;
+        const float2 m = mine[i < nmine ? i : 0];       // (a lane past the end works on entry 0 and stores nothing)
+        mx[j] = m.x; my[j] = m.y;
+        bd[j] = TARGETS_NONE; bi[j] = 0xFFFFFFFFu;
+    }
+    auto take = [&](const unsigned k, const float ox, const float oy) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const float ex = ox - mx[j], ey = oy - my[j];
+            const unsigned db = __float_as_uint(ex * ex + ey * ey);
+            const bool less = db < bd[j];
+            bd[j] = less ? db : bd[j];
+            bi[j] = less ? k : bi[j];
+        }
+    };
+    int k = k0;
+    for (; k + 4 <= k1; k += 4) {
+        const float4 q0 = reinterpret_cast<const float4 *>(other + k)[0], q1 = reinterpret_cast<const float4 *>(other + k)[1];
+        take(k, q0.x, q0.y); take(k + 1, q0.z, q0.w); take(k + 2, q1.x, q1.y); take(k + 3, q1.z, q1.w);
+    }
+    for (; k < k1; ++k) take(k, other[k].x, other[k].y);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int i = i0 + TARGETS_THREADS * j;
+        const unsigned long long key = (unsigned long long)bd[j] << 32 | bi[j];
+        if (i < nmine) {
+            if (SHARED) atomicMin(&res[i], key);
+            else res[i] = key;
+        }
+    }
+}
+// ... with as many entries per lane as nmine (uniform) asks for.  With at most 128 owners (64) the lanes of two (three) waves
+// would idle while the others walk: there every wave takes the same owners and a half (a quarter) of other, whole waves on one
+// part, and the parts meet in res, which the caller has filled with ones -- the least key is the same in whatever order they arrive.
+__device__ __forceinline__ void kb_targets_side(const float2 *mine, const int nmine, const float2 *other, const int nother, unsigned long long *res, const int tid) {
+    if (nmine <= TARGETS_THREADS / 2) {
+        const int owners = nmine <= 64 ? 64 : 128, parts = TARGETS_THREADS / owners;
+        const int per = ((nother + parts - 1) / parts + 3) & ~3;
+        const int k0 = min((tid / owners) * per, nother);
+        kb_targets_nearest<1, true>(mine, nmine, other, k0, min(k0 + per, nother), res, tid & (owners - 1));
+        return;
+    }
+    switch ((nmine + TARGETS_THREADS - 1) / TARGETS_THREADS) {
+    case 1: kb_targets_nearest<1, false>(mine, nmine, other, 0, nother, res, tid); break;
+    case 2: kb_targets_nearest<2, false>(mine, nmine, other, 0, nother, res, tid); break;
+    case 3: kb_targets_nearest<3, false>(mine, nmine, other, 0, nother, res, tid); break;
+    default: kb_targets_nearest<4, false>(mine, nmine, other, 0, nother, res, tid); break;
+    }
+}
+// The per-lane partials of one direction (fixed-point cost, bits of the largest d2, entries within tolerance) through the wave,
+// then one LDS atomic each per wave: integers, any order gives the same bits.
+__device__ __forceinline__ void kb_targets_reduce(long long cost, unsigned far, unsigned fill, unsigned long long *sum, unsigned *worst, unsigned *within, const int tid) {
+    for (int off = 32; off > 0; off >>= 1) {
+        cost += __shfl_down(cost, off);
+        far = max(far, __shfl_down(far, off));
+        fill += __shfl_down(fill, off);
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(sum, (unsigned long long)cost);
+        atomicMax(worst, far);
+        atomicAdd(within, fill);
+    }
+}
+
+// Kilobot-to-slot matching (kb_sense_targets): one workgroup of 256 lanes per env.  STAGING: lane tid looks at the ceil(N / 256)
+// consecutive kilobots from tid * ceil(N / 256) on and at as many consecutive slots; a prefix sum of the two counts over the
+// workgroup (one packed word: kilobots low, slots high) gives every lane where its selected entries go, so that each side is
+// COMPACTED to its selected entries in ascending index: bpos / spos hold the positions (the slots converted to world units,
+// one multiplication each), bidx / sidx the index an entry came from.  What is not selected gets its constants here.  An env
+// with an empty side writes its constants and leaves.  PASSES: the kilobot-to-slot direction (kb_targets_side: the lanes own
+// kilobots and walk all slots), then the slot-to-kilobot direction (the lanes own slots and walk all kilobots): about
+// 2 nb ns distance evaluations, exact by construction -- there is nothing to bound and no list to build, and on compacted
+// sides every lane of a wave does the same work; a side of few owners is shared out among the waves, each walking a part of
+// the other side (kb_targets_side; the result words start as ones for that).  A direction no output needs is not walked: the slots' only for d_index
+// alone, the kilobots' only for d_owner and d_dist.  Each pass leaves the key bits of d2 << 32 | compacted winner per entry in LDS.
+// EPILOGUES, after one barrier: a lane takes its entries again, maps the winner back through sidx / bidx, forms the row of d_rel
+// from the positions in LDS (mutual: the slot's winner is this kilobot, by compacted index) and adds to the partials of
+// d_stats (kb_targets_reduce).  The winner's index is clamped before it is used as one, so that poses that are no numbers
+// cannot make the kernel read or write anything but its own.  Every output word is written exactly once, by a plain store.
+__global__ void __launch_bounds__(TARGETS_THREADS) kb_targets_kernel(const TargetsArgs A, const float *x, const float *y, const float *theta, const float *d_points,
+                                                                     const unsigned char *d_bot_select, const unsigned char *d_slot_select, int *d_index,
+                                                                     float4 *d_rel, int *d_owner, float *d_dist, float *d_stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, N = A.N, K = A.K;
+    const TargetsLds L(N, K);
+    float2 *bpos = reinterpret_cast<float2 *>(smem);
+    float2 *spos = reinterpret_cast<float2 *>(smem + L.spos);
+    unsigned long long *bres = reinterpret_cast<unsigned long long *>(smem + L.bres);
+    unsigned long long *sres = reinterpret_cast<unsigned long long *>(smem + L.sres);
+    unsigned long long *sum = reinterpret_cast<unsigned long long *>(smem + L.red);
+    unsigned *worst = reinterpret_cast<unsigned *>(smem + L.red + 16);
+    unsigned *within = worst + 2, *wsum = worst + 4;
+    unsigned short *bidx = reinterpret_cast<unsigned short *>(smem + L.bidx);
+    unsigned short *sidx = reinterpret_cast<unsigned short *>(smem + L.sidx);
+    const size_t o = (size_t)e * N, ko = (size_t)e * K;
+    const float *pts = d_points + (A.per_env ? 2 * ko : 0);
+    const float INF = __uint_as_float(0x7F800000u);
+    const bool toSlot = d_index || d_rel || d_stats, toBot = d_owner || d_dist || d_stats || d_rel;     // the directions some output needs
+    if (tid < 2) { sum[tid] = 0ull; worst[tid] = 0u; within[tid] = 0u; }
+    // staging: which of this lane's consecutive entries are selected, and where they go
+    const int cb = (N + TARGETS_THREADS - 1) / TARGETS_THREADS, cs = (K + TARGETS_THREADS - 1) / TARGETS_THREADS;
+    unsigned mb = 0u, ms = 0u;
+    for (int j = 0; j < cb; ++j) {
+        const int b = tid * cb + j;
+        if (b < N && (!d_bot_select || d_bot_select[o + b] != 0)) mb |= 1u << j;
+    }
+    for (int j = 0; j < cs; ++j) {
+        const int t = tid * cs + j;
+        if (t < K && (!d_slot_select || d_slot_select[ko + t] != 0)) ms |= 1u << j;
+    }
+    const unsigned cnt = (unsigned)__popc(mb) | (unsigned)__popc(ms) << 16;        // (a wave sums to at most 256 in either half: no carry)
+    const unsigned incl = wave_incl_scan(cnt);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    unsigned base = 0u, total = 0u;
+    for (int w = 0; w < TARGETS_THREADS / 64; ++w) {
+        const unsigned s = wsum[w];
+        if (w < (tid >> 6)) base += s;
+        total += s;
+    }
+    const int nb = __builtin_amdgcn_readfirstlane((int)(total & 0xFFFFu)), ns = __builtin_amdgcn_readfirstlane((int)(total >> 16));
+    int ib = (int)((base + incl - cnt) & 0xFFFFu), is = (int)((base + incl - cnt) >> 16);
+    for (int j = 0; j < cb; ++j) {
+        const int b = tid * cb + j;
+        if (b >= N) break;
+        if ((mb >> j) & 1u) {
+            bpos[ib] = make_float2(x[o + b], y[o + b]);
+            bidx[ib] = (unsigned short)b;
+            ++ib;
+        } else {
+            if (d_index) d_index[o + b] = -1;
+            if (d_rel) d_rel[o + b] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    for (int j = 0; j < cs; ++j) {
+        const int t = tid * cs + j;
+        if (t >= K) break;
+        if ((ms >> j) & 1u) {
+            spos[is] = make_float2(pts[2 * t] * WORLD_SCALE, pts[2 * t + 1] * WORLD_SCALE);
+            sidx[is] = (unsigned short)t;
+            ++is;
+        } else {
+            if (d_owner) d_owner[ko + t] = -1;
+            if (d_dist) d_dist[ko + t] = 0.0f;
+        }
+    }
+    for (int i = tid; i < nb; i += TARGETS_THREADS) bres[i] = ~0ull;       // (above every key: what waves that share owners take the least against)
+    for (int u = tid; u < ns; u += TARGETS_THREADS) sres[u] = ~0ull;
+    __syncthreads();
+    if (nb == 0 || ns == 0) {       // an empty side (uniform): nothing to match
+        for (int i = tid; i < nb; i += TARGETS_THREADS) {
+            const int b = bidx[i];
+            if (d_index) d_index[o + b] = -1;
+            if (d_rel) d_rel[o + b] = make_float4(0.0f, 0.0f, INF, 0.0f);
+        }
+        for (int u = tid; u < ns; u += TARGETS_THREADS) {
+            const int t = sidx[u];
+            if (d_owner) d_owner[ko + t] = -1;
+            if (d_dist) d_dist[ko + t] = INF;
+        }
+        if (d_stats && tid < 6) d_stats[6 * (size_t)e + tid] = tid < 4 ? INF : 0.0f;
+        return;
+    }
+    if (toSlot) kb_targets_side(bpos, nb, spos, ns, bres, tid);
+    if (toBot) kb_targets_side(spos, ns, bpos, nb, sres, tid);
+    __syncthreads();
+    if (toSlot) {
+        long long cost = 0;
+        unsigned far = 0u, fill = 0u;
+        for (int i = tid; i < nb; i += TARGETS_THREADS) {
+            const unsigned long long r = bres[i];
+            const int b = bidx[i], u = (int)min((unsigned)r, (unsigned)(ns - 1));
+            const unsigned db = (unsigned)(r >> 32);
+            const float d2 = __uint_as_float(db);
+            if (d_index) d_index[o + b] = sidx[u];
+            if (d_rel) {
+                const float ex = spos[u].x - bpos[i].x, ey = spos[u].y - bpos[i].y;
+                float sn, cs_;
+                kb_sincosf(theta[o + b], sn, cs_);
+                d_rel[o + b] = make_float4((cs_ * ex + sn * ey) / WORLD_SCALE, (cs_ * ey - sn * ex) / WORLD_SCALE, sqrtf(d2) / WORLD_SCALE,
+                                           (unsigned)sres[u] == (unsigned)i ? 1.0f : 0.0f);
+            }
+            cost += (long long)rintf(fminf(d2 * 65536.0f, 0x1p40f));
+            far = max(far, db);
+            fill += !(d2 > A.T2) ? 1u : 0u;
+        }
+        if (d_stats) kb_targets_reduce(cost, far, fill, sum, worst, within, tid);
+    }
+    if (toBot) {
+        long long cost = 0;
+        unsigned far = 0u, fill = 0u;
+        for (int u = tid; u < ns; u += TARGETS_THREADS) {
+            const unsigned long long r = sres[u];
+            const int t = sidx[u], i = (int)min((unsigned)r, (unsigned)(nb - 1));
+            const unsigned db = (unsigned)(r >> 32);
+            const float d2 = __uint_as_float(db);
+            if (d_owner) d_owner[ko + t] = bidx[i];
+            if (d_dist) d_dist[ko + t] = sqrtf(d2) / WORLD_SCALE;
+            cost += (long long)rintf(fminf(d2 * 65536.0f, 0x1p40f));
+            far = max(far, db);
+            fill += !(d2 > A.T2) ? 1u : 0u;
+        }
+        if (d_stats) kb_targets_reduce(cost, far, fill, sum + 1, worst + 1, within + 1, tid);
+    }
+    if (!d_stats) return;
+    __syncthreads();
+    if (tid == 0) {
+        float *st = d_stats + 6 * (size_t)e;
+        st[0] = ((float)(long long)sum[0] / 65536.0f) / 625.0f;
+        st[1] = sqrtf(__uint_as_float(worst[0])) / WORLD_SCALE;
+        st[2] = ((float)(long long)sum[1] / 65536.0f) / 625.0f;
+        st[3] = sqrtf(__uint_as_float(worst[1])) / WORLD_SCALE;
+        st[4] = (float)within[1];
+        st[5] = (float)within[0];
     }
 }
 

@@ -44,6 +44,14 @@ def _coverage_obs(value, num_objects):
     return nat.check_coverage(width, height)
 
 
+def _target_obs(value, num_objects):
+    points_m, tol_m = value
+    points = np.ascontiguousarray(np.asarray(points_m.cpu() if torch.is_tensor(points_m) else points_m, dtype=np.float32))
+    if points.ndim not in (2, 3) or points.shape[-1] != 2 or not np.isfinite(points).all():
+        raise ValueError('target_obs: points_m must be finite and have the shape (K, 2) or (E, K, 2)')
+    return (points,) + nat.check_targets(points.shape[-2], tol_m)[1:]
+
+
 def _contact_obs(value, num_objects):
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= value <= nat.MAX_CONTACT_SLOTS:
         raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
@@ -80,6 +88,7 @@ OPTIONS = {
     'object_obs': Option(_object_obs, None, ('objects', 'walls'), 'object_points', 'True', 'observe objects and walls'),
     'grid_obs': Option(_grid_obs, '(width, height) or (width, height, planes)', ('grid',), 'occupancy_grid', '(width, height[, planes])', 'observe occupancy grids'),
     'coverage_obs': Option(_coverage_obs, '(width, height)', ('coverage',), 'coverage', '(width, height)', 'observe nearest-kilobot fields'),
+    'target_obs': Option(_target_obs, '(points_m, tol_m)', ('targets',), 'targets', '(points_m, tol_m)', 'observe the slots of a target shape'),
     'contact_obs': Option(_contact_obs, None, ('contacts',), 'contacts', 'k', 'observe contacts'),
     'ray_obs': Option(_ray_obs, '(radius_m, n_rays) or (radius_m, n_rays, targets)', ('rays',), 'rays', '(radius_m, n_rays[, targets])', 'observe range scans'),
     'edge_obs': Option(_edge_obs, 'radius_m or (radius_m, capacity)', ('edges',), 'edges', 'radius_m or (radius_m, capacity)', 'observe the IR-range graph'),
@@ -95,7 +104,7 @@ class BatchedKilobotsEnv(object):
     def __init__(self, num_envs, num_kilobots, drive_mode=nat.DRIVE_VELOCITY, light_type=nat.LIGHT_NONE,
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
-                 object_obs=None, grid_obs=None, coverage_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
+                 object_obs=None, grid_obs=None, coverage_obs=None, target_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
                  max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
@@ -121,6 +130,13 @@ class BatchedKilobotsEnv(object):
         which kilobot is nearest to every cell centre of the table and how far, the Voronoi cell of every kilobot with its
         centroid in the kilobot's own frame, the locational cost and the worst-covered distance -- and step() puts the tuple in
         its info dict under 'coverage'.  None adds nothing.
+        target_obs: (points_m, tol_m) adds the observation of a shape-formation task, the matching between the kilobots and the K
+        points ("slots") of a target shape: points_m array-like [K, 2] (one shape for all envs) or [E, K, 2], metres, uploaded
+        once; targets() returns the named tuple (index [E, N], rel [E, N, 4], owner [E, K], dist [E, K], stats [E, 6]) of
+        KilobotSim.targets -- the nearest slot of every kilobot in its own frame and whether it holds it, the nearest kilobot
+        of every slot and how far it is, the Chamfer sums, Hausdorff distances and the counts within tol_m the reward is made
+        of -- and step() puts the tuple in its info dict under 'targets'.  set_targets() replaces the points or masks slots
+        out.  None adds nothing.
         contact_obs: k, an int in 0..16, adds touch and push sensing from the contacts the solver acted on in the last world
         step: contacts() returns (partner [E, N, k], impulse [E, N, k], touch [E, N, 4], obj [E, M, 2] or None)
         (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
@@ -163,7 +179,7 @@ class BatchedKilobotsEnv(object):
         self.env_offset = int(env_offset)
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
-        given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs, coverage_obs=coverage_obs,
+        given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs, coverage_obs=coverage_obs, target_obs=target_obs,
                      contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs)
         for name, option in OPTIONS.items():
             value = given[name]
@@ -200,6 +216,9 @@ class BatchedKilobotsEnv(object):
         self.observation_space = Box(np.tile(-b, (self.num_kilobots, 1)), np.tile(b, (self.num_kilobots, 1)), dtype=np.float32)
         dev = self.sim.x.device
         self.episode_returns = torch.zeros(self.num_envs, dtype=torch.float32, device=dev)
+        self._observe_kw = {}       # keyword arguments the sim method of an observation gets besides the stored value
+        if self.target_obs is not None:         # the points live on the device from here on: (tensor, tol_m)
+            self.target_obs = (self._target_points(self.target_obs[0]), self.target_obs[1])
         # episodes of single envs
         if max_episode_steps is not None and not int(max_episode_steps) >= 1:
             raise ValueError('max_episode_steps must be at least 1 or None')
@@ -365,7 +384,7 @@ class BatchedKilobotsEnv(object):
     def _observe(self, name):
         value = self._stored(name)      # the tuple of the sim method's arguments, its one argument, or True for none
         args = value if isinstance(value, tuple) else (value,) if value is not True else ()
-        return getattr(self.sim, OPTIONS[name].method)(*args)
+        return getattr(self.sim, OPTIONS[name].method)(*args, **self._observe_kw.get(name, {}))
 
     def neighbors(self):
         """(index [E, N, k] int32, rel [E, N, k, 4] float32, count [E, N] int32) of the current poses for the
@@ -392,6 +411,30 @@ class BatchedKilobotsEnv(object):
         [E, 2] float32) of the current poses for the coverage_obs=(width, height) the env was created with:
         KilobotSim.coverage."""
         return self._observe('coverage_obs')
+
+    def _target_points(self, points):
+        """Parsed points ([K, 2] or [E, K, 2] float32 array) on the sim's device; ValueError if they do not fit the env."""
+        if points.ndim == 3 and points.shape[0] != self.num_envs:
+            raise ValueError('target_obs: points_m must have the shape (K, 2) or (%d, K, 2)' % self.num_envs)
+        return torch.from_numpy(points).to(self.sim.x.device)
+
+    def set_targets(self, points_m=None, slot_select=None):
+        """Replace the points of target_obs -- array-like [K, 2] or [E, K, 2] metres with the K the env was created with; None
+        keeps them -- and set the slots that take part: slot_select [E, K] bool or uint8 tensor on the sim's device, None:
+        all of them (KilobotSim.targets).  A reward that masks out the slots that are filled sets the mask here."""
+        points, tol_m = self._stored('target_obs')
+        if points_m is not None:
+            new = _target_obs((points_m, tol_m), 0)[0]
+            if new.shape[-2] != points.shape[-2]:
+                raise ValueError('set_targets: the env was created with %d slots, got %d' % (points.shape[-2], new.shape[-2]))
+            self.target_obs = (self._target_points(new), tol_m)
+        self._observe_kw['target_obs'] = {} if slot_select is None else dict(slot_select=slot_select)
+
+    def targets(self):
+        """The named tuple (index [E, N] int32, rel [E, N, 4] float32, owner [E, K] int32, dist [E, K] float32, stats [E, 6]
+        float32) of the current poses for the target_obs=(points_m, tol_m) the env was created with, over the slots
+        set_targets() selected: KilobotSim.targets."""
+        return self._observe('target_obs')
 
     def contacts(self):
         """(partner [E, N, k] int32, impulse [E, N, k] float32, touch [E, N, 4] float32, obj [E, M, 2] float32 or None) of the

@@ -18,6 +18,8 @@ from ._native import (DRIVE_VELOCITY, DRIVE_ACCEL, DRIVE_MOTORS, DRIVE_SIMPLE_PH
 Edges = collections.namedtuple('Edges', ('src', 'dst', 'rel', 'offsets', 'count', 'nnz'))
 # ... and KilobotSim.coverage
 Coverage = collections.namedtuple('Coverage', ('owner', 'dist', 'cells', 'stats'))
+# ... and KilobotSim.targets
+Targets = collections.namedtuple('Targets', ('index', 'rel', 'owner', 'dist', 'stats'))
 
 # the dtypes a caller's tensor may have: floats, a mask (env_mask, seeds) and 32-bit words (colours, episode counters)
 F32, I32, I64, MASK = (torch.float32,), (torch.int32,), (torch.int64,), (torch.bool, torch.uint8)
@@ -480,6 +482,43 @@ class KilobotSim:
             raise ValueError('out: cells must be 16-byte aligned')
         self._call('kb_sense_coverage', width, height, ps, *map(_ptr, parts))
         return Coverage(*parts)
+
+    def targets(self, points_m, tol_m, bot_select=None, slot_select=None, index=True, rel=True, owner=True, dist=True, stats=True, out=None):
+        """Kilobot-to-slot matching on the current poses (kb_sense_targets; no reference counterpart): the two-sided nearest
+        query of shape formation between the kilobots of every env and the K points ("slots") of a target shape.  points_m:
+        contiguous float32 [E, K, 2] or [K, 2] (shared by all envs) on the sim's device, metres, 1 <= K <= MAX_TARGETS.
+        Returns the named tuple Targets(index, rel, owner, dist, stats): index [E, N] int32, the slot nearest to every
+        kilobot (ties to the lower index); rel [E, N, 4] float32 = (that slot metres ahead, metres to the left, its distance in
+        metres, 1.0 if the kilobot is also the one nearest to that slot) in the kilobot's own frame; owner [E, K] int32, the
+        kilobot nearest to every slot (ties to the lower index); dist [E, K] float32, its distance in metres -- a slot is
+        free while that is large; stats [E, 6] float32 = (the sum over the kilobots of the squared distance to their slot in
+        square metres, the largest such distance in metres, the same two over the slots to their owners -- the directed
+        Chamfer sums, fixed-point sums that do not depend on the order, and Hausdorff distances --, the number of slots whose
+        owner is within tol_m, the number of kilobots whose slot is within tol_m).  bot_select [E, N] and slot_select [E, K],
+        bool or uint8 on the sim's device, restrict the two sides (None: all): what is not selected gets -1 and zeros, a
+        selected entry of an env whose other side is empty -1 and a distance of +inf, and the stats of such an env are
+        (+inf, +inf, +inf, +inf, 0, 0).  A part switched off (index=False, ...) is None and is not computed; at least one
+        must be on.  out: the preallocated contiguous tensors to write into, a tuple of the parts that are on; every element
+        is written."""
+        E, N = self.num_envs, self.num_bots
+        if not torch.is_tensor(points_m) or points_m.dim() not in (2, 3):
+            raise ValueError('points_m must be a contiguous float32 cuda tensor of shape (E, K, 2) or (K, 2)')
+        K, tol_m = nat.check_targets(points_m.shape[-2], tol_m)
+        per_env = points_m.dim() == 3
+        pp = self._input(points_m, F32, (E, K, 2) if per_env else (K, 2), 'points_m')
+        wanted = [bool(index), bool(rel), bool(owner), bool(dist), bool(stats)]
+        if not any(wanted):
+            raise ValueError('targets: at least one of index, rel, owner, dist and stats must be on')
+        pb = self._input(bot_select, MASK, (E, N), 'bot_select', optional=True)
+        ps = self._input(slot_select, MASK, (E, K), 'slot_select', optional=True)
+        shapes = [s for s, w in zip([((E, N), torch.int32, 'index'), ((E, N, 4), torch.float32, 'rel'), ((E, K), torch.int32, 'owner'),
+                                     ((E, K), torch.float32, 'dist'), ((E, 6), torch.float32, 'stats')], wanted) if w]
+        given = iter(self._outputs(out, shapes, 'the tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
+        parts = [next(given) if w else None for w in wanted]
+        if parts[1] is not None and parts[1].data_ptr() % 16:
+            raise ValueError('out: rel must be 16-byte aligned')
+        self._call('kb_sense_targets', pp, K, int(per_env), tol_m, pb, ps, *map(_ptr, parts))
+        return Targets(*parts)
 
     def contacts(self, k=8, scale=65536.0, out=None):
         """Touch and push sensing from the contact store of the last step (kb_sense_contacts; Body.collides_with of every

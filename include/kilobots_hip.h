@@ -521,6 +521,54 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
 int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int32_t *d_owner, float *d_dist, float *d_cell,
                       float *d_stats, void *stream);
 
+/* Kilobot-to-slot matching on the CURRENT poses, without stepping: the two-sided nearest-neighbour query of shape formation
+ * between the kilobots of an env and the K points ("slots") of a target shape -- for every kilobot the nearest slot in its own
+ * frame, for every slot the nearest kilobot (which slots are still free), whether a kilobot holds the slot it is nearest to,
+ * and per env the two directed Chamfer sums, the two directed Hausdorff distances and the fill counts a reward is made of.
+ * No reference counterpart.  One launch; asynchronous on `stream`.  Every operation below is one fp32 operation rounded on
+ * its own, nothing is contracted, divisions and square roots are correctly rounded:
+ *   d_points: [num_envs][K][2] float32 with per_env != 0, [K][2] shared by all envs with per_env == 0; METRES;  K = n_targets,
+ *     1 <= K <= KB_MAX_TARGETS.  Slot t in world units: tx = px * 25.0f, ty = py * 25.0f, one multiplication each, on the device.
+ *   Sides: the kilobots b of the env with d_bot_select[e][b] != 0 and the slots t with d_slot_select[e][t] != 0 (bytes, the
+ *     convention of d_select, d_seed and d_env_mask); NULL: all of them.  d_bot_select is [num_envs][num_bots], d_slot_select
+ *     always [num_envs][K], also with shared points.  A kilobot outside the arena takes part with its true position, and so
+ *     does a slot outside it.
+ *   One distance serves both directions: ex = tx - x_b, ey = ty - y_b, d2(b, t) = ex * ex + ey * ey.
+ *   Host constants: Tw = tol_m * 25.0f, T2 = Tw * Tw (as kb_sense takes R2);  tol_m >= 0 and finite.  "Within tolerance" is
+ *     !(d2 > T2).
+ *   Kilobot to slot.  A selected kilobot b gets the selected slot with the smallest (bits of d2(b, t) compared as unsigned
+ *     integers, t): ties go to the lower slot index, and nothing else decides it.
+ *     d_index [num_envs][num_bots] int32: that t.
+ *     d_rel   [num_envs][num_bots][4] float32, 16-byte aligned: with (s, c) = the library's sine and cosine of theta_b and ex,
+ *       ey, d2 those of (b, t) the row is ((c * ex + s * ey) / 25, (c * ey - s * ex) / 25, sqrt(d2) / 25, mutual): the slot ahead
+ *       and to the left in metres, its distance in metres, and mutual = 1.0f iff b is the owner (below) of t, else 0.0f.
+ *     A kilobot that is not selected: d_index = -1 and four +0.0f.  A selected kilobot in an env without a selected slot:
+ *     d_index = -1 and (+0.0f, +0.0f, +inf, +0.0f).
+ *   Slot to kilobot.  A selected slot t gets the selected kilobot with the smallest (bits of d2(b, t), b): its owner.
+ *     d_owner [num_envs][K] int32: that b.
+ *     d_dist  [num_envs][K] float32: sqrt(d2) / 25, metres.
+ *     A slot that is not selected: -1 and +0.0f.  A selected slot in an env without a selected kilobot: -1 and +inf.
+ *   d_stats [num_envs][6] float32.  Words 0 and 2, the directed Chamfer sums: over the selected kilobots of d2 to their slot
+ *     (word 0) and over the selected slots of d2 to their owner (word 2), the fixed-point sum of word 0 of kb_sense_coverage:
+ *     q = (int64) rint(min(d2 * 65536.0f, 0x1p40f)), round half to even;  acc = the int64 sum of q;  the word is
+ *     ((float)acc / 65536.0f) / 625.0f, square metres (int -> float to nearest even): independent of any order.  Words 1 and
+ *     3, the directed Hausdorff distances: sqrt(the largest such d2) / 25, the maximum of the bit patterns.  Word 4: the
+ *     number of selected slots whose owner is within tolerance (filled slots);  word 5: the number of selected kilobots whose
+ *     slot is within tolerance;  both (float) of the integer.  With either side of the env empty words 0..3 are +inf and words
+ *     4 and 5 are +0.0f.
+ * Each output may be NULL and is then neither computed for its own sake nor written; every element of every output given is
+ * written on every call, by a plain store (nothing needs clearing beforehand).  mutual and the stats are right whatever else
+ * was asked for.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim or NULL d_points;  n_targets;  tol_m;  all five
+ * outputs NULL;  a d_rel that is not 16-byte aligned.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, d_points and the two selections, theta only with d_rel; writes the outputs only, and no bound buffer.  The result
+ * of an env does not depend on the other envs.  Poses and points are assumed finite: with one that is not, the result of its
+ * env is unspecified (the call still ends and writes nothing but the outputs). */
+#define KB_MAX_TARGETS 1024
+int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, const uint8_t *d_bot_select,
+                     const uint8_t *d_slot_select, int32_t *d_index, float *d_rel, int32_t *d_owner, float *d_dist,
+                     float *d_stats, void *stream);
+
 /* Touch and push sensing from the contact store, without stepping: who touches whom, and how hard -- what the solver alone
  * knows (Body.collides_with, body.py:87-90, walks b2Body.contacts; the impulses have no reference counterpart).  A pure
  * function of ws_key / ws_acc / ws_cnt as the last kb_step left them: the Box2D contact list of the last world step.
