@@ -336,12 +336,24 @@ int launched(const char *entry) {
     return KB_EHIP;
 }
 
+// the launch a sensing entry ends in: `grid` workgroups of `block` lanes with `lds` bytes of dynamic LDS, and its status
+template <typename Kernel, typename... Args>
+int launch(const char *entry, Kernel kernel, unsigned grid, unsigned block, int lds, void *stream, const Args &...args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), (size_t)lds, (hipStream_t)stream, args...);
+    return launched(entry);
+}
+// whether every one of the pointers lies on 16 bytes (NULL does)
+template <typename... T>
+bool aligned16(const T *...ptr) { return ((reinterpret_cast<uintptr_t>(ptr) | ...) & 15u) == 0; }
+// the reach in cells of the stencil that finds everything within Rw world units (a radius beyond the arena: the stencil is the
+// whole grid, and the reach stays a small integer)
+int reach_cells(const Params &p, float Rw) { return Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh; }
+
 // a sensing radius in metres as the kernels take it: in world units, squared, and as the reach of the stencil in cells
 struct SenseRange { float Rw, R2; int reach; };
 SenseRange sense_range(const Params &p, float radius_m) {
     const float Rw = radius_m * WORLD_SCALE;
-    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
-    return {Rw, Rw * Rw, Rw * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rw, p.inv_cell) : p.gw + p.gh};
+    return {Rw, Rw * Rw, reach_cells(p, Rw)};
 }
 
 // n_sectors of the histogram entries, reported under the caller's name
@@ -733,8 +745,7 @@ int kb_sense(kb_sim *sim, float radius_m, uint32_t *d_count, void *stream) {
     if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense: radius must be positive");
     const Params &p = sim->p;
     const SenseRange r = sense_range(p, radius_m);
-    hipLaunchKernelGGL(kb_sense_kernel, dim3((unsigned)p.E), dim3(256), (size_t)SenseLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, d_count);
-    return launched("kb_sense");
+    return launch("kb_sense", kb_sense_kernel, p.E, 256, SenseLds(p.NP, p.ncell).bytes, stream, p, r.reach, r.R2, d_count);
 }
 
 int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, float *d_rel, uint32_t *d_count, void *stream) {
@@ -742,14 +753,12 @@ int kb_sense_neighbors(kb_sim *sim, float radius_m, int k, int32_t *d_index, flo
     if (k < 1 || k > KB_MAX_NEIGHBORS) return fail(KB_EINVAL, "kb_sense_neighbors: 1 <= k <= KB_MAX_NEIGHBORS (16) required");
     if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_neighbors: radius must be positive");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_neighbors: kb_bind() first");
-    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_neighbors: d_rel must be 16-byte aligned");
+    if (!aligned16(d_rel)) return fail(KB_EINVAL, "kb_sense_neighbors: d_rel must be 16-byte aligned");
     const Params &p = sim->p;
     const SenseRange r = sense_range(p, radius_m);
-    const int vec = k % 4 == 0 && (reinterpret_cast<uintptr_t>(d_index) & 15u) == 0;
+    const int vec = k % 4 == 0 && aligned16(d_index);
     const auto fn = k <= 4 ? kb_neighbors_kernel<4> : k <= 8 ? kb_neighbors_kernel<8> : kb_neighbors_kernel<16>;
-    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)NeighborsLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, k, vec,
-                       d_index, reinterpret_cast<float4 *>(d_rel), d_count);
-    return launched("kb_sense_neighbors");
+    return launch("kb_sense_neighbors", fn, p.E, 256, NeighborsLds(p.NP, p.ncell).bytes, stream, p, r.reach, r.R2, k, vec, d_index, reinterpret_cast<float4 *>(d_rel), d_count);
 }
 
 int kb_sense_edges(kb_sim *sim, float radius_m, const int64_t *d_offsets, int64_t capacity, int32_t *d_src, int32_t *d_dst, float *d_rel,
@@ -759,14 +768,13 @@ int kb_sense_edges(kb_sim *sim, float radius_m, const int64_t *d_offsets, int64_
     if (capacity < 0) return fail(KB_EINVAL, "kb_sense_edges: capacity must not be negative");
     if (capacity > 0 && !d_dst) return fail(KB_EINVAL, "kb_sense_edges: NULL d_dst with a capacity");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_edges: kb_bind() first");
-    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_edges: d_rel must be 16-byte aligned");
+    if (!aligned16(d_rel)) return fail(KB_EINVAL, "kb_sense_edges: d_rel must be 16-byte aligned");
     const Params &p = sim->p;
     if ((long long)p.E * p.N >= (1ll << 31)) return fail(KB_EINVAL, "kb_sense_edges: num_envs * num_bots must be below 2^31 (int32 node ids)");
     if (capacity == 0 && !d_count) return KB_OK;        // nothing to write: nothing is launched
     const SenseRange r = sense_range(p, radius_m);
-    hipLaunchKernelGGL(kb_edges_kernel, dim3((unsigned)p.E), dim3(256), (size_t)EdgesLds(p.N, p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2,
-                       reinterpret_cast<const long long *>(d_offsets), (long long)capacity, d_src, d_dst, reinterpret_cast<float4 *>(d_rel), d_count);
-    return launched("kb_sense_edges");
+    return launch("kb_sense_edges", kb_edges_kernel, p.E, 256, EdgesLds(p.N, p.NP, p.ncell).bytes, stream, p, r.reach, r.R2,
+                  reinterpret_cast<const long long *>(d_offsets), (long long)capacity, d_src, d_dst, reinterpret_cast<float4 *>(d_rel), d_count);
 }
 
 int kb_histogram_sectors(int n_sectors, float *xy) {
@@ -801,9 +809,7 @@ int kb_sense_histogram(kb_sim *sim, float radius_m, int n_rings, int n_sectors, 
     float u[KB_HIST_MAX_SECTORS / 2 - 1][2];
     if (kb_histogram_sectors(n_sectors, &u[0][0]) != KB_OK) return KB_EINVAL;
     for (int m = 1; m < n_sectors / 2; ++m) { h.ux[m - 1] = u[m - 1][0]; h.uy[m - 1] = u[m - 1][1]; }
-    hipLaunchKernelGGL(kb_histogram_kernel, dim3((unsigned)p.E), dim3(256), (size_t)HistLds(p.NP, p.ncell, n_rings * n_sectors).bytes, (hipStream_t)stream,
-                       p, rg.reach, rg.R2, h, d_hist, d_count);
-    return launched("kb_sense_histogram");
+    return launch("kb_sense_histogram", kb_histogram_kernel, p.E, 256, HistLds(p.NP, p.ncell, n_rings * n_sectors).bytes, stream, p, rg.reach, rg.R2, h, d_hist, d_count);
 }
 
 int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float scale, const float *d_values, float *d_out,
@@ -817,11 +823,9 @@ int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float s
     const Params &p = sim->p;
     const SenseRange r = sense_range(p, radius_m);
     const int CP = n_channels <= 2 ? n_channels : n_channels <= 4 ? 4 : 8;
-    const int vec = n_channels % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+    const int vec = n_channels % 4 == 0 && aligned16(d_out);
     const kb_reduce_fn fn = op == KB_REDUCE_SUM ? reduce_kernel<KB_REDUCE_SUM>(CP) : op == KB_REDUCE_MIN ? reduce_kernel<KB_REDUCE_MIN>(CP) : reduce_kernel<KB_REDUCE_MAX>(CP);
-    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ReduceLds(p.NP, p.ncell, CP).bytes, (hipStream_t)stream, p, r.reach, r.R2, n_channels, vec,
-                       scale, d_values, d_out, d_count);
-    return launched("kb_sense_reduce");
+    return launch("kb_sense_reduce", fn, p.E, 256, ReduceLds(p.NP, p.ncell, CP).bytes, stream, p, r.reach, r.R2, n_channels, vec, scale, d_values, d_out, d_count);
 }
 
 int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_hops, int32_t *d_hops, int32_t *d_parent, int32_t *d_root,
@@ -833,9 +837,7 @@ int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_ho
     const Params &p = sim->p;
     const SenseRange r = sense_range(p, radius_m);
     const int lim = max_hops < p.N - 1 ? max_hops : p.N - 1;       // no path has more than N - 1 edges: the level loop's bound
-    hipLaunchKernelGGL(kb_hops_kernel, dim3((unsigned)p.E), dim3(256), (size_t)HopsLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, r.reach, r.R2, lim,
-                       d_seed, d_hops, d_parent, d_root, d_stats);
-    return launched("kb_sense_hops");
+    return launch("kb_sense_hops", kb_hops_kernel, p.E, 256, HopsLds(p.NP, p.ncell).bytes, stream, p, r.reach, r.R2, lim, d_seed, d_hops, d_parent, d_root, d_stats);
 }
 
 int kb_ray_directions(int n_rays, float *xy) {
@@ -872,13 +874,10 @@ int kb_sense_rays(kb_sim *sim, float radius_m, int n_rays, int targets, float *d
     for (int k = 0; k < n_rays; ++k) { a.ux[k] = u[k][0]; a.uy[k] = u[k][1]; }
     kb_outline ol;
     kb_get_outline(sim, &ol);
-    // (a radius beyond the arena: the stencil is the whole grid, and the reach stays a small integer)
-    const int reach = Rc * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Rc, p.inv_cell) : p.gw + p.gh;
-    const int vec = n_rays % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_dist) | reinterpret_cast<uintptr_t>(d_hit)) & 15u) == 0;
+    const int vec = n_rays % 4 == 0 && aligned16(d_dist, d_hit);
     // the rays a lane holds at a time: the count rounded up to 4, 8 or 16; more than that go in passes (17 to 32 rays: two of 16)
     const auto fn = n_rays <= 4 ? kb_rays_kernel<4> : n_rays <= 8 ? kb_rays_kernel<8> : kb_rays_kernel<KB_RAYS_PER_PASS>;
-    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)RaysLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, ol, a, reach, vec, d_dist, d_hit);
-    return launched("kb_sense_rays");
+    return launch("kb_sense_rays", fn, p.E, 256, RaysLds(p.NP, p.ncell).bytes, stream, p, ol, a, reach_cells(p, Rc), vec, d_dist, d_hit);
 }
 
 int kb_get_outline(const kb_sim *sim, kb_outline *out) {
@@ -907,17 +906,15 @@ int kb_sense_objects(kb_sim *sim, float *d_obj, float *d_wall, void *stream) {
     if (!sim) return fail(KB_EINVAL, "kb_sense_objects: NULL handle");
     if (!d_obj && !d_wall) return fail(KB_EINVAL, "kb_sense_objects: d_obj and d_wall are both NULL");
     if (d_obj && sim->cfg.num_objects == 0) return fail(KB_EINVAL, "kb_sense_objects: d_obj given, but the handle has no objects");
-    if ((reinterpret_cast<uintptr_t>(d_obj) | reinterpret_cast<uintptr_t>(d_wall)) & 15u) return fail(KB_EINVAL, "kb_sense_objects: d_obj and d_wall must be 16-byte aligned");
+    if (!aligned16(d_obj, d_wall)) return fail(KB_EINVAL, "kb_sense_objects: d_obj and d_wall must be 16-byte aligned");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_objects: kb_bind() first");
     const Params &p = sim->p;
     kb_outline ol;
     kb_get_outline(sim, &ol);
     const int threads = p.N < OBJ_TILE ? (p.N + 63) & ~63 : OBJ_TILE;      // one kilobot per lane: no idle waves in a small env
     const int tiles = (p.N + threads - 1) / threads;
-    hipLaunchKernelGGL(kb_objects_kernel, dim3((unsigned)p.E * (unsigned)tiles), dim3((unsigned)threads), (size_t)ObjectsLds().bytes, (hipStream_t)stream,
-                       ol, p.N, tiles, p.buf.x, p.buf.y, p.buf.theta, p.buf.ox, p.buf.oy, p.buf.otheta,
-                       reinterpret_cast<float4 *>(d_obj), reinterpret_cast<float4 *>(d_wall));
-    return launched("kb_sense_objects");
+    return launch("kb_sense_objects", kb_objects_kernel, (unsigned)p.E * (unsigned)tiles, threads, ObjectsLds().bytes, stream, ol, p.N, tiles, p.buf.x, p.buf.y,
+                  p.buf.theta, p.buf.ox, p.buf.oy, p.buf.otheta, reinterpret_cast<float4 *>(d_obj), reinterpret_cast<float4 *>(d_wall));
 }
 
 // planes of the grid entries, reported under the caller's name: a non-empty subset of the three bits ...
@@ -949,12 +946,10 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
     const float wx = p.xmax - p.xmin, wy = p.ymax - p.ymin;        // (kb_outline.arena is these four)
     if (bots) {
         const GridLds L(gw, gh, words);
-        const int vec = gw % 4 == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0;
+        const int vec = gw % 4 == 0 && aligned16(d_out);
         const auto fn = bots == KB_GRID_COUNT ? kb_grid_bots_kernel<KB_GRID_COUNT> : bots == KB_GRID_FLOW ? kb_grid_bots_kernel<KB_GRID_FLOW>
                                                                                    : kb_grid_bots_kernel<KB_GRID_COUNT | KB_GRID_FLOW>;
-        hipLaunchKernelGGL(fn, dim3((unsigned)p.E * (unsigned)L.bands), dim3(256), (size_t)L.bytes, (hipStream_t)stream, p.N, gw, gh, L.bands, L.rows, C, vec,
-                           p.xmin, p.ymin, (float)gw / wx, (float)gh / wy, p.buf.x, p.buf.y, p.buf.theta, d_out);
-        const int rc = launched("kb_sense_grid");
+        const int rc = launch("kb_sense_grid", fn, (unsigned)p.E * (unsigned)L.bands, 256, L.bytes, stream, p.N, gw, gh, L.bands, L.rows, C, vec, p.xmin, p.ymin, (float)gw / wx, (float)gh / wy, p.buf.x, p.buf.y, p.buf.theta, d_out);
         if (rc != KB_OK) return rc;
     }
     if (planes & KB_GRID_OBJECTS) {
@@ -963,9 +958,7 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
         const int cells = gw * gh;
         const int threads = cells < 256 ? (cells + 63) & ~63 : 256;        // one cell per lane: no idle waves in a small grid
         const int tiles = (cells + threads - 1) / threads;
-        hipLaunchKernelGGL(kb_grid_objects_kernel, dim3((unsigned)p.E * (unsigned)tiles), dim3((unsigned)threads), (size_t)ObjectsLds().bytes, (hipStream_t)stream,
-                           ol, gw, gh, tiles, C, words, wx / (float)gw, wy / (float)gh, p.buf.ox, p.buf.oy, p.buf.otheta, d_out);
-        return launched("kb_sense_grid");
+        return launch("kb_sense_grid", kb_grid_objects_kernel, (unsigned)p.E * (unsigned)tiles, threads, ObjectsLds().bytes, stream, ol, gw, gh, tiles, C, words, wx / (float)gw, wy / (float)gh, p.buf.ox, p.buf.oy, p.buf.otheta, d_out);
     }
     return KB_OK;
 }
@@ -975,13 +968,11 @@ int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int3
     if (!sim) return fail(KB_EINVAL, "kb_sense_coverage: NULL handle");
     if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_sense_coverage: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
     if (!d_owner && !d_dist && !d_cell && !d_stats) return fail(KB_EINVAL, "kb_sense_coverage: d_owner, d_dist, d_cell and d_stats are all NULL");
-    if (reinterpret_cast<uintptr_t>(d_cell) & 15u) return fail(KB_EINVAL, "kb_sense_coverage: d_cell must be 16-byte aligned");
+    if (!aligned16(d_cell)) return fail(KB_EINVAL, "kb_sense_coverage: d_cell must be 16-byte aligned");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_coverage: kb_bind() first");
     const Params &p = sim->p;
     const CoverageArgs a = {gw, gh, (p.xmax - p.xmin) / (float)gw, (p.ymax - p.ymin) / (float)gh};       // (kb_outline.arena is these four)
-    hipLaunchKernelGGL(kb_coverage_kernel, dim3((unsigned)p.E), dim3(256), (size_t)CoverageLds(p.NP, p.ncell).bytes, (hipStream_t)stream, p, a, d_select,
-                       d_owner, d_dist, reinterpret_cast<float4 *>(d_cell), d_stats);
-    return launched("kb_sense_coverage");
+    return launch("kb_sense_coverage", kb_coverage_kernel, p.E, 256, CoverageLds(p.NP, p.ncell).bytes, stream, p, a, d_select, d_owner, d_dist, reinterpret_cast<float4 *>(d_cell), d_stats);
 }
 
 int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, const uint8_t *d_bot_select,
@@ -990,14 +981,13 @@ int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_
     if (n_targets < 1 || n_targets > KB_MAX_TARGETS) return fail(KB_EINVAL, "kb_sense_targets: 1 <= n_targets <= KB_MAX_TARGETS (1024) required");
     if (!(tol_m >= 0.0f) || !std::isfinite(tol_m)) return fail(KB_EINVAL, "kb_sense_targets: tol_m must be finite and not negative");
     if (!d_index && !d_rel && !d_owner && !d_dist && !d_stats) return fail(KB_EINVAL, "kb_sense_targets: d_index, d_rel, d_owner, d_dist and d_stats are all NULL");
-    if (reinterpret_cast<uintptr_t>(d_rel) & 15u) return fail(KB_EINVAL, "kb_sense_targets: d_rel must be 16-byte aligned");
+    if (!aligned16(d_rel)) return fail(KB_EINVAL, "kb_sense_targets: d_rel must be 16-byte aligned");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_targets: kb_bind() first");
     const Params &p = sim->p;
     const float Tw = tol_m * WORLD_SCALE;
     const TargetsArgs a = {p.N, n_targets, per_env != 0, Tw * Tw};
-    hipLaunchKernelGGL(kb_targets_kernel, dim3((unsigned)p.E), dim3(TARGETS_THREADS), (size_t)TargetsLds(p.N, n_targets).bytes, (hipStream_t)stream, a, p.buf.x,
-                       p.buf.y, p.buf.theta, d_points, d_bot_select, d_slot_select, d_index, reinterpret_cast<float4 *>(d_rel), d_owner, d_dist, d_stats);
-    return launched("kb_sense_targets");
+    return launch("kb_sense_targets", kb_targets_kernel, p.E, TARGETS_THREADS, TargetsLds(p.N, n_targets).bytes, stream, a, p.buf.x, p.buf.y, p.buf.theta, d_points,
+                  d_bot_select, d_slot_select, d_index, reinterpret_cast<float4 *>(d_rel), d_owner, d_dist, d_stats);
 }
 
 int kb_render_default_style(kb_render_style *out) {
@@ -1041,10 +1031,7 @@ int kb_render(kb_sim *sim, int width, int height, int layers, const kb_render_st
     for (int m = 0; m < KB_MAX_OBJECTS; ++m) a.obj[m] = rgb(st.obj[m]);
     kb_outline ol;
     kb_get_outline(sim, &ol);
-    const int reach = Ro * p.inv_cell < (float)(p.gw + p.gh) ? sense_reach(Ro, p.inv_cell) : p.gw + p.gh;
-    hipLaunchKernelGGL(kb_render_kernel, dim3((unsigned)p.E * (unsigned)L.bands), dim3(256), (size_t)L.bytes, (hipStream_t)stream, p, ol, a, reach,
-                       d_body_rgb, d_mark_rgb, d_rgb);
-    return launched("kb_render");
+    return launch("kb_render", kb_render_kernel, (unsigned)p.E * (unsigned)L.bands, 256, L.bytes, stream, p, ol, a, reach_cells(p, Ro), d_body_rgb, d_mark_rgb, d_rgb);
 }
 
 int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float *d_impulse, float *d_touch, float *d_obj, void *stream) {
@@ -1061,12 +1048,9 @@ int kb_sense_contacts(kb_sim *sim, int k, float scale, int32_t *d_partner, float
     a.N = p.N; a.M = p.M; a.F = p.F; a.cap = p.cap;
     for (int f = 0; f < p.F; ++f) a.body[f] = ot_body(p.otab[f]);       // (kb_create checked 0 <= body < M)
     const int lists = d_partner != nullptr;
-    const int vec = (lists && k % 4 == 0 && ((reinterpret_cast<uintptr_t>(d_partner) | reinterpret_cast<uintptr_t>(d_impulse)) & 15u) == 0 ? 1 : 0)
-                  | ((reinterpret_cast<uintptr_t>(d_touch) & 15u) == 0 ? 2 : 0);
+    const int vec = (lists && k % 4 == 0 && aligned16(d_partner, d_impulse) ? 1 : 0) | (aligned16(d_touch) ? 2 : 0);
     const auto fn = !lists ? kb_contacts_kernel<0> : k <= 4 ? kb_contacts_kernel<4> : k <= 8 ? kb_contacts_kernel<8> : kb_contacts_kernel<16>;
-    hipLaunchKernelGGL(fn, dim3((unsigned)p.E), dim3(256), (size_t)ContactsLds(p.N).bytes, (hipStream_t)stream, a, k, vec, scale,
-                       p.buf.ws_key, p.buf.ws_acc, p.buf.ws_cnt, reinterpret_cast<uint2 *>(p.buf.scratch), d_partner, d_impulse, d_touch, d_obj);
-    return launched("kb_sense_contacts");
+    return launch("kb_sense_contacts", fn, p.E, 256, ContactsLds(p.N).bytes, stream, a, k, vec, scale, p.buf.ws_key, p.buf.ws_acc, p.buf.ws_cnt, reinterpret_cast<uint2 *>(p.buf.scratch), d_partner, d_impulse, d_touch, d_obj);
 }
 
 int kb_light_sense(kb_sim *sim, const float *d_light_action, void *stream) {

@@ -12,52 +12,80 @@
 
 namespace kb {
 
-// The cell lists of the broadphase grid off the poses of one env in global memory: pos[b] and cellOf[b] of every kilobot
-// (cell indices clamp to the grid), head[cell] -> nextb chains (plain heads: no hash).  o: index of the env's first kilobot.
+// The cell lists of the broadphase grid of one env in LDS, as the one value the kernels hand to the builder and the walk: pos[b]
+// and cellOf[b] of every kilobot, head[cell] -> nextb chains (plain heads: no hash).  Taken by value: see kb_walk_rows_in_range.
+struct CellLists { float2 *pos; unsigned short *head, *nextb, *cellOf; };
+// Where the three u16 arrays lie in a kernel's LDS image, as byte offsets: nextb[NP], cellOf[NP], head[ncell] from byte `at` on;
+// end: the first byte behind head, on a whole word (kb_exch16 works on whole words of head).  *Lds structs below derive from it, where that cost no time.
+struct CellListsLds {
+    int nextb, cellOf, head, end;
+    __host__ __device__ constexpr CellListsLds(int at, int NP, int ncell) : nextb(at), cellOf(at + 2 * NP), head(at + 4 * NP), end(head + 2 * ((ncell + 1) & ~1)) {}
+    __device__ __forceinline__ CellLists view(unsigned char *smem, int pos = 0) const {      // the lists of the image at smem, the poses at its byte `pos`
+        const auto u16 = [&](int at) { return reinterpret_cast<unsigned short *>(smem + at); };
+        return {reinterpret_cast<float2 *>(smem + pos), u16(head), u16(nextb), u16(cellOf)};
+    }
+};
+// Builds the cell lists C off the poses of one env in global memory (cell indices clamp to the grid).  o: index of the env's first kilobot.
 // The order inside a chain is the order of the exchanges; nothing that reads the lists may depend on it.  Ends on a barrier.
 // keep(b): only these kilobots enter the lists; of the others pos[b] = (NaN, NaN), cellOf[b] = EMPTY16, and no chain holds them.
 template <typename Keep>
-__device__ __forceinline__ void kb_build_cell_lists_of(const Params &p, size_t o, float2 *pos, unsigned short *head,
-                                                       unsigned short *nextb, unsigned short *cellOf, int tid, int nt, Keep keep) {
-    for (int c = tid; c < p.ncell; c += nt) head[c] = EMPTY16;
+__device__ __forceinline__ void kb_build_cell_lists_of(const Params &p, size_t o, const CellLists C, int tid, int nt, Keep keep) {
+    for (int c = tid; c < p.ncell; c += nt) C.head[c] = EMPTY16;
     __syncthreads();
     for (int b = tid; b < p.N; b += nt) {
         if (!keep(b)) {
-            pos[b].x = pos[b].y = __uint_as_float(0x7FC00000u);
-            cellOf[b] = EMPTY16;
+            C.pos[b].x = C.pos[b].y = __uint_as_float(0x7FC00000u);
+            C.cellOf[b] = EMPTY16;
             continue;
         }
         const float bx = p.buf.x[o + b], by = p.buf.y[o + b];
-        pos[b].x = bx; pos[b].y = by;
+        C.pos[b].x = bx; C.pos[b].y = by;
         int cx = (int)floorf((bx - p.xmin) * p.inv_cell);
         int cy = (int)floorf((by - p.ymin) * p.inv_cell);
         cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
         cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
         const int cell = cy * p.gw + cx;
-        cellOf[b] = (unsigned short)cell;
-        nextb[b] = (unsigned short)kb_exch16(head, cell, (unsigned)b);
+        C.cellOf[b] = (unsigned short)cell;
+        C.nextb[b] = (unsigned short)kb_exch16(C.head, cell, (unsigned)b);
     }
     __syncthreads();
 }
 // ... of every kilobot of the env
-__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, float2 *pos, unsigned short *head,
-                                                    unsigned short *nextb, unsigned short *cellOf, int tid, int nt) {
-    kb_build_cell_lists_of(p, o, pos, head, nextb, cellOf, tid, nt, [](int) { return true; });
+__device__ __forceinline__ void kb_build_cell_lists(const Params &p, size_t o, const CellLists C, int tid, int nt) {
+    kb_build_cell_lists_of(p, o, C, tid, nt, [](int) { return true; });
 }
 
 // reach of the sensing stencil in cells: cell indices are monotone in the coordinate, and two kilobots within Rw differ
 // by at most floor(Rw / cell) + 1 cells (the small margin covers the rounding of the cell computation)
 __host__ __device__ inline int sense_reach(float Rw, float inv_cell) { return (int)floorf(Rw * inv_cell + 1e-3f) + 1; }
 
+// The body frame of every row the sensing kernels write: the world vector (ex, ey) seen from a kilobot whose heading has the cosine
+// cs and the sine sn, in metres -- x along the heading, y to its left.  The operations in this order are the definition (-ffp-contract=off).
+__device__ __forceinline__ float2 kb_body_frame(const float cs, const float sn, const float ex, const float ey) {
+    return make_float2((cs * ex + sn * ey) / WORLD_SCALE, (cs * ey - sn * ex) / WORLD_SCALE);
+}
+// The first k of the K words a lane keeps for its row in registers, word(0) .. word(k - 1), to row[0 .. k): 16 bytes per store with vec (k a multiple of
+// 4, row 16-byte aligned).  word sees compile-time constants only (the loops unroll), so its array stays in registers; taken by value, as hit below.
+template <int K, typename T, typename Word>
+__device__ __forceinline__ void kb_store_row(T *row, const int k, const int vec, Word word) {
+    using T4 = HIP_vector_type<T, 4>;
+    if (K >= 4 && vec) {
+#pragma unroll
+        for (int i = 0; i + 3 < K && i < k; i += 4) reinterpret_cast<T4 *>(row)[i >> 2] = T4(word(i), word(i + 1), word(i + 2), word(i + 3));
+    } else {
+#pragma unroll
+        for (int i = 0; i < K && i < k; ++i) row[i] = word(i);
+    }
+}
+
 // The stencil walk of kilobot a (in `cell`, at pa): every cell within reach s of its own, eight list heads per LDS round trip
 // (most cells are empty), down each chain.  Calls hit(b, ex, ey, dd) for every kilobot b != a with !(dd > R2),
 // (ex, ey) = pos[b] - pa, dd = ex^2 + ey^2, and returns how many there were.  ROWS > 0: only ROWS rows of the stencil, from its
 // row r0 on (row 0 = the lowest row that is on the grid) -- the part one lane takes where several share a kilobot
 // (kb_hops_kernel); ROWS = 0: all of them.  hit is taken by value: taken by reference, the 16-slot list kernel needed 156
-// VGPRs instead of 130 and ran 4 % slower.
+// VGPRs instead of 130 and ran 4 % slower; the lists C are taken by value for the same reason.
 template <int ROWS, typename Hit>
-__device__ __forceinline__ unsigned kb_walk_rows_in_range(const Params &p, const float2 *pos, const unsigned short *head,
-                                                          const unsigned short *nextb, const int a, const int cell, const float2 pa,
+__device__ __forceinline__ unsigned kb_walk_rows_in_range(const Params &p, const CellLists C, const int a, const int cell, const float2 pa,
                                                           const int s, const float R2, const int r0, Hit hit) {
     constexpr int W = 8;
     const int cx = cell % p.gw, cy = cell / p.gw;
@@ -68,12 +96,12 @@ __device__ __forceinline__ unsigned kb_walk_rows_in_range(const Params &p, const
         for (int xb = x0; xb <= x1; xb += W) {
             unsigned cur[W];
 #pragma unroll
-            for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
+            for (int i = 0; i < W; ++i) cur[i] = xb + i <= x1 ? (unsigned)C.head[oy * p.gw + xb + i] : (unsigned)EMPTY16;
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 for (unsigned b = cur[i]; b != (unsigned)EMPTY16;) {
-                    const float2 pb = pos[b];
-                    const unsigned nb = nextb[b];
+                    const float2 pb = C.pos[b];
+                    const unsigned nb = C.nextb[b];
                     const float ex = pb.x - pa.x, ey = pb.y - pa.y;
                     const float dd = ex * ex + ey * ey;
                     if ((int)b != a && !(dd > R2)) {
@@ -91,15 +119,19 @@ __device__ __forceinline__ unsigned kb_walk_rows_in_range(const Params &p, const
 // The full-stencil walk of kilobot a: all rows within reach s of its own.  (The half stencil of kb_sense_pass meets every
 // pair once and counts with atomics: a different traversal.)
 template <typename Hit>
-__device__ __forceinline__ unsigned kb_walk_in_range(const Params &p, const float2 *pos, const unsigned short *head,
-                                                     const unsigned short *nextb, const int a, const int cell, const float2 pa,
+__device__ __forceinline__ unsigned kb_walk_in_range(const Params &p, const CellLists C, const int a, const int cell, const float2 pa,
                                                      const int s, const float R2, Hit hit) {
-    return kb_walk_rows_in_range<0>(p, pos, head, nextb, a, cell, pa, s, R2, 0, hit);
+    return kb_walk_rows_in_range<0>(p, C, a, cell, pa, s, R2, 0, hit);
 }
 
+// The pins of the layouts that derive from CellListsLds: each struct L against the closed form of its offsets, at the largest image and
+// at a small odd one.  A wrong offset crashes nothing, it lays two arrays over each other.
+#define KB_LDS_PINNED(name, layout, closed_form) constexpr bool name(int NP, int nc) { const auto L = layout; return closed_form; } \
+    static_assert(name(KB_MAX_BOTS, MAX_CELLS) && name(4, 1), "LDS layout: " #name)
+
 // ---- kb_sense: counts --------------------------------------------------------------------------------------------------
-struct SenseLds {       // byte offsets: pos (float2) at 0, the packed u16 counters, nextb, cellOf, head (u16 each)
-    int cnt16, nextb, cellOf, head, bytes;
+struct SenseLds {       // byte offsets: pos (float2) at 0, the packed u16 counters, nextb, cellOf, head (u16 each) -- spelled out, not
+    int cnt16, nextb, cellOf, head, bytes;      // CellListsLds: with the offsets formed as at + 2 NP the kernel ran 13 % slower
     __host__ __device__ constexpr SenseLds(int NP, int ncell)
         : cnt16(8 * NP), nextb(10 * NP), cellOf(12 * NP), head(14 * NP), bytes(14 * NP + 2 * ncell + 16) {}
 };
@@ -114,20 +146,22 @@ __global__ void __launch_bounds__(256) kb_sense_kernel(const Params p, const int
     unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
     unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
     unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const CellLists cells = {pos, head, nextb, cellOf};
     const size_t o = (size_t)e * N;
     for (int b = tid; b < p.NP / 2; b += nt) cnt16[b] = 0;
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     kb_sense_pass(pos, head, nextb, cellOf, cnt16, N, nt, tid, p.gw, p.gh, s, R2, 0);
     __syncthreads();
     for (int b = tid; b < N; b += nt) out[o + b] = (unsigned)reinterpret_cast<unsigned short *>(cnt16)[b];
 }
 
 // ---- kb_sense_neighbors: the k nearest ---------------------------------------------------------------------------------
-struct NeighborsLds {   // byte offsets: pos (float2) at 0, th (float), nextb, cellOf, head (u16 each)
-    int th, nextb, cellOf, head, bytes;
-    __host__ __device__ constexpr NeighborsLds(int NP, int ncell)
-        : th(8 * NP), nextb(12 * NP), cellOf(14 * NP), head(16 * NP), bytes(16 * NP + 2 * ncell + 16) {}
+struct NeighborsLds : CellListsLds {    // byte offsets: pos (float2) at 0, th (float), the cell lists
+    int th, bytes;
+    __host__ __device__ constexpr NeighborsLds(int NP, int ncell) : CellListsLds(12 * NP, NP, ncell), th(8 * NP), bytes(head + 2 * ncell + 16) {}
 };
+KB_LDS_PINNED(neighbors_lds, NeighborsLds(NP, nc),
+              L.th == 8 * NP && L.nextb == 12 * NP && L.cellOf == 14 * NP && L.head == 16 * NP && L.bytes == 16 * NP + 2 * nc + 16);
 
 // Nearest-neighbour lists with body-frame offsets on the current poses (kb_sense_neighbors): poses, headings and the cell
 // lists in LDS, one kilobot per lane.  Every kilobot walks the FULL stencil of reach s (it needs its own ordered list, so the
@@ -143,21 +177,18 @@ __global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const
     constexpr unsigned long long NONE = ~0ull;
     const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
     const NeighborsLds L(p.NP, p.ncell);
-    float2 *pos = reinterpret_cast<float2 *>(smem);
+    const CellLists cells = L.view(smem);
     float *th = reinterpret_cast<float *>(smem + L.th);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
-    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
-    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
     const size_t o = (size_t)e * N;
     for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     for (int a = tid; a < N; a += nt) {
-        const int cell = cellOf[a];
-        const float2 pa = pos[a];
+        const int cell = cells.cellOf[a];
+        const float2 pa = cells.pos[a];
         unsigned long long best[K];
 #pragma unroll
         for (int i = 0; i < K; ++i) best[i] = NONE;
-        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float dd) {
+        const unsigned cnt = kb_walk_in_range(p, cells, a, cell, pa, s, R2, [&](unsigned b, float, float, float dd) {
             unsigned long long key = ((unsigned long long)__float_as_uint(dd) << 32) | b;
             if (key < best[K - 1]) {
 #pragma unroll
@@ -177,32 +208,15 @@ __global__ void __launch_bounds__(256) kb_neighbors_kernel(const Params p, const
             if (i >= k) break;
             const bool used = best[i] != NONE;
             const unsigned j = used ? (unsigned)best[i] : (unsigned)a;
-            const float2 pb = pos[j];
-            const float ex = pb.x - pa.x, ey = pb.y - pa.y;
+            const float2 pb = cells.pos[j];
             const float d2 = __uint_as_float((unsigned)(best[i] >> 32));
-            float4 r;
-            r.x = (cs * ex + sn * ey) / WORLD_SCALE;
-            r.y = (cs * ey - sn * ex) / WORLD_SCALE;
-            r.z = sqrtf(d2) / WORLD_SCALE;
-            r.w = th[j] - tha;
+            const float2 f = kb_body_frame(cs, sn, pb.x - pa.x, pb.y - pa.y);
+            float4 r = make_float4(f.x, f.y, sqrtf(d2) / WORLD_SCALE, th[j] - tha);
             if (!used) r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             d_rel[row + i] = r;
         }
-        if (vec) {      // k is a multiple of 4 and d_index is 16-byte aligned: four indices per store
-#pragma unroll
-            for (int i = 0; i < K; i += 4) {
-                if (i >= k) break;
-                int4 v;
-                v.x = (int)(unsigned)best[i]; v.y = (int)(unsigned)best[i + 1]; v.z = (int)(unsigned)best[i + 2]; v.w = (int)(unsigned)best[i + 3];
-                reinterpret_cast<int4 *>(d_index + row)[i >> 2] = v;      // (the low word of NONE is -1)
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                if (i >= k) break;
-                d_index[row + i] = (int)(unsigned)best[i];
-            }
-        }
+        // vec: k is a multiple of 4 and d_index is 16-byte aligned, four indices per store (the low word of NONE is -1)
+        kb_store_row<K>(d_index + row, k, vec, [&](int i) { return (int)(unsigned)best[i]; });
         if (d_count) d_count[o + a] = cnt;
     }
 }
@@ -218,13 +232,12 @@ constexpr int HIST_TILE = 256;
 constexpr int HIST_STRIDE = HIST_TILE + 2;
 constexpr int HIST_TABLE_BYTES = 4 * (KB_HIST_MAX_RINGS + KB_HIST_MAX_SECTORS - 3);
 
-struct HistLds {        // byte offsets: pos (float2) at 0, nextb, cellOf, head, hist[bins][HIST_STRIDE] (u16 each), tab (float)
-    int nextb, cellOf, head, hist, tab, bytes;
-    __host__ __device__ constexpr HistLds(int NP, int ncell, int bins)
-        : nextb(8 * NP), cellOf(10 * NP), head(12 * NP),
-          hist(head + 2 * ((ncell + 1) & ~1)),      // (kb_exch16 works on whole words of head)
-          tab(hist + 2 * bins * HIST_STRIDE), bytes(tab + HIST_TABLE_BYTES) {}
+struct HistLds : CellListsLds {     // byte offsets: pos (float2) at 0, the cell lists, hist[bins][HIST_STRIDE] (u16), tab (float)
+    int hist, tab, bytes;
+    __host__ __device__ constexpr HistLds(int NP, int ncell, int bins) : CellListsLds(8 * NP, NP, ncell), hist(end), tab(hist + 2 * bins * HIST_STRIDE), bytes(tab + HIST_TABLE_BYTES) {}
 };
+KB_LDS_PINNED(hist_lds, HistLds(NP, nc, 3),
+              L.nextb == 8 * NP && L.cellOf == 10 * NP && L.head == 12 * NP && L.hist == 12 * NP + 2 * ((nc + 1) & ~1) && L.tab == L.hist + 6 * HIST_STRIDE && L.bytes == L.tab + HIST_TABLE_BYTES);
 // the largest image (1024 kilobots, every cell, 64 bins) stays under the default limit for dynamic LDS: no attribute to raise
 static_assert(HistLds(KB_MAX_BOTS, MAX_CELLS, KB_HIST_MAX_BINS).bytes <= 64 * 1024, "kb_histogram_kernel: LDS image");
 
@@ -248,10 +261,7 @@ __global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const
     const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
     const int B = h.n_rings * h.n_sectors, H = h.n_sectors >> 1;
     const HistLds L(p.NP, p.ncell, B);
-    float2 *pos = reinterpret_cast<float2 *>(smem);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
-    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
-    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const CellLists cells = L.view(smem);
     unsigned short *hist = reinterpret_cast<unsigned short *>(smem + L.hist);
     float *tab = reinterpret_cast<float *>(smem + L.tab);
     const size_t o = (size_t)e * N;
@@ -261,7 +271,7 @@ __global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const
 #pragma unroll
         for (int m = 0; m < NU; ++m) { tab[NE + m] = h.ux[m]; tab[NE + NU + m] = h.uy[m]; }
     }
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     float e2[NE], ux[NU], uy[NU];
 #pragma unroll
     for (int r = 0; r < NE; ++r) e2[r] = tab[r];
@@ -273,11 +283,11 @@ __global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const
         unsigned short *col = hist + tid;
         for (int b = 0; b < B; ++b) col[b * HIST_STRIDE] = 0;
         if (a < N) {
-            const int cell = cellOf[a];
-            const float2 pa = pos[a];
+            const int cell = cells.cellOf[a];
+            const float2 pa = cells.pos[a];
             float sn, cs;
             kb_sincosf(p.buf.theta[o + a], sn, cs);
-            const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned, float ex, float ey, float dd) {
+            const unsigned cnt = kb_walk_in_range(p, cells, a, cell, pa, s, R2, [&](unsigned, float ex, float ey, float dd) {
                 int ring = 0;
 #pragma unroll
                 for (int r = 0; r < NE; ++r) ring += dd > e2[r] ? 1 : 0;
@@ -310,8 +320,8 @@ __global__ void __launch_bounds__(256) kb_histogram_kernel(const Params p, const
 }
 
 // ---- kb_sense_reduce: the messages of the kilobots in range, summed or ordered -----------------------------------------
-struct ReduceLds {      // byte offsets: pos (float2) at 0, nextb, cellOf, head (u16 each), msg[NP][CP] (one 32-bit word per channel)
-    int nextb, cellOf, head, msg, bytes;
+struct ReduceLds {      // byte offsets: pos (float2) at 0, nextb, cellOf, head (u16 each), msg[NP][CP] (one 32-bit word per channel) -- spelled
+    int nextb, cellOf, head, msg, bytes;        // out, not CellListsLds, which cost the one-channel min leg 0.4 %
     __host__ __device__ constexpr ReduceLds(int NP, int ncell, int CP)
         : nextb(8 * NP), cellOf(10 * NP), head(12 * NP),
           msg((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),      // (rows are read 4, 8 or 16 bytes at a time)
@@ -350,6 +360,7 @@ __global__ void __launch_bounds__(256) kb_reduce_kernel(const Params p, const in
     unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
     unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
     unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const CellLists cells = {pos, head, nextb, cellOf};
     unsigned *msg = reinterpret_cast<unsigned *>(smem + L.msg);
     const size_t o = (size_t)e * N;
     const float *val = d_values + o * (size_t)C;
@@ -362,14 +373,14 @@ __global__ void __launch_bounds__(256) kb_reduce_kernel(const Params p, const in
         }
         msg[f] = w;
     }
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     for (int a = tid; a < N; a += nt) {
-        const int cell = cellOf[a];
-        const float2 pa = pos[a];
+        const int cell = cells.cellOf[a];
+        const float2 pa = cells.pos[a];
         unsigned acc[CP];
 #pragma unroll
         for (int c = 0; c < CP; ++c) acc[c] = IDENT;
-        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
+        const unsigned cnt = kb_walk_in_range(p, cells, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
             unsigned w[CP];
             if constexpr (CP == 1) {
                 w[0] = msg[b];
@@ -544,8 +555,8 @@ __global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline o
             const float so = fr.z, co = fr.w;
             float best, brx, bry;
             const bool inside = kb_object_walk(I, m, fr, xi, yi, best, brx, bry);
-            const float gx = co * brx - so * bry, gy = so * brx + co * bry;
-            row[m] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, sqrtf(best) / WORLD_SCALE, inside ? 1.0f : 0.0f);
+            const float2 f = kb_body_frame(ci, si, co * brx - so * bry, so * brx + co * bry);
+            row[m] = make_float4(f.x, f.y, sqrtf(best) / WORLD_SCALE, inside ? 1.0f : 0.0f);
         }
     }
     if (d_wall) {
@@ -554,7 +565,8 @@ __global__ void __launch_bounds__(OBJ_TILE) kb_objects_kernel(const kb_outline o
         if (g1 < g) { g = g1; gx = g1; w = 1.0f; }
         if (g2 < g) { g = g2; gx = 0.0f; gy = -g2; w = 2.0f; }
         if (g3 < g) { g = g3; gx = 0.0f; gy = g3; w = 3.0f; }
-        d_wall[i] = make_float4((ci * gx + si * gy) / WORLD_SCALE, (ci * gy - si * gx) / WORLD_SCALE, g / WORLD_SCALE, w);
+        const float2 f = kb_body_frame(ci, si, gx, gy);
+        d_wall[i] = make_float4(f.x, f.y, g / WORLD_SCALE, w);
     }
 }
 
@@ -666,10 +678,10 @@ struct RenderArgs {         // the host constants of the definition (include/kil
     float cw, ch, Ro2, Ri, Ri2, Lf, Hw, Rl2[KB_MAX_LIGHTS];
     unsigned table, body, ring, mark, light, alpha, obj[KB_MAX_OBJECTS];
 };
-struct RenderLds {      // byte offsets: the ObjectsLds image at 0, ocol[8] (u32), lit[4] (float4: x, y, Rl2), lcol (uint4: the light's share of the blend and 255 - alpha) --
-                        // constants, which cost no register --, then pos (float2), sc (float2: sin, cos), nextb, cellOf, head (u16 each), stage (bytes)
+struct RenderLds : CellListsLds {       // byte offsets: the ObjectsLds image at 0, ocol[8] (u32), lit[4] (float4: x, y, Rl2), lcol (uint4: the light's share of the blend and 255 - alpha) --
+                        // constants, which cost no register --, then pos (float2: the poses start here, not at 0), sc (float2: sin, cos), the cell lists, stage (bytes)
     static constexpr int ocol = ObjectsLds().bytes, lit = ocol + 4 * KB_MAX_OBJECTS, lcol = lit + 16 * KB_MAX_LIGHTS, pos = lcol + 16;
-    int sc, nextb, cellOf, head, stage, bands, rows, bytes;
+    int sc, stage, bands, rows, bytes;
     // the rows of a band: what fits behind the fixed part (3 width bytes each; up to 15 bytes of misalignment of the band in
     // d_rgb in front and the rounding to 16 behind), at most RENDER_BAND_PIXELS pixels, at least one; then the fewest such
     // bands, rows spread evenly over them
@@ -678,11 +690,13 @@ struct RenderLds {      // byte offsets: the ObjectsLds image at 0, ocol[8] (u32
         return fit < cap ? (fit > 1 ? fit : 1) : (cap > 1 ? cap : 1);
     }
     __host__ __device__ constexpr RenderLds(int NP, int ncell, int width, int height)
-        : sc(pos + 8 * NP), nextb(sc + (KB_RENDER_SINCOS ? 8 * NP : 0)), cellOf(nextb + 2 * NP), head(cellOf + 2 * NP),
-          stage((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),
+        : CellListsLds(pos + (KB_RENDER_SINCOS ? 16 : 8) * NP, NP, ncell), sc(pos + 8 * NP), stage((end + 15) & ~15),
           bands((height + max_rows(RENDER_LDS_LIMIT - stage, width) - 1) / max_rows(RENDER_LDS_LIMIT - stage, width)),
           rows((height + bands - 1) / bands), bytes(stage + ((3 * rows * width + 15 + 15) & ~15)) {}
 };
+KB_LDS_PINNED(render_lds, RenderLds(NP, nc, 64, 48),
+              L.sc == RenderLds::pos + 8 * NP && L.nextb == L.sc + (KB_RENDER_SINCOS ? 8 : 0) * NP && L.cellOf == L.nextb + 2 * NP && L.head == L.cellOf + 2 * NP &&
+              L.stage == ((L.head + 2 * ((nc + 1) & ~1) + 15) & ~15) && L.bytes == L.stage + ((3 * L.rows * 64 + 30) & ~15));
 static_assert(ObjectsLds().bytes % 16 == 0, "kb_render_kernel: lit, lcol and pos start on 16 bytes");
 static_assert(RenderLds(KB_MAX_BOTS, MAX_CELLS, KB_RENDER_MAX_SIDE, KB_RENDER_MAX_SIDE).bytes <= RENDER_LDS_LIMIT &&
               RenderLds(KB_MAX_BOTS, MAX_CELLS, 64, 48).bands == 1, "kb_render_kernel: LDS image");
@@ -712,11 +726,8 @@ __global__ void __launch_bounds__(256) kb_render_kernel(const Params p, const kb
     unsigned *ocol = reinterpret_cast<unsigned *>(smem + L.ocol);
     float4 *lit = reinterpret_cast<float4 *>(smem + L.lit);
     uint4 *lcol = reinterpret_cast<uint4 *>(smem + L.lcol);
-    float2 *pos = reinterpret_cast<float2 *>(smem + L.pos);
+    const CellLists cells = L.view(smem, L.pos);
     float2 *sc = reinterpret_cast<float2 *>(smem + L.sc);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
-    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
-    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
     unsigned char *stage = smem + L.stage;
     const size_t o = (size_t)e * N;
     const bool bots = (A.layers & KB_RENDER_BOTS) != 0;
@@ -739,7 +750,7 @@ __global__ void __launch_bounds__(256) kb_render_kernel(const Params p, const kb
                 sc[b] = make_float2(sn, cs);
             }
         }
-        kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+        kb_build_cell_lists(p, o, cells, tid, nt);
     } else {
         __syncthreads();
     }
@@ -758,12 +769,12 @@ __global__ void __launch_bounds__(256) kb_render_kernel(const Params p, const kb
             int cy = (int)floorf((py - p.ymin) * p.inv_cell);
             cx = cx < 0 ? 0 : (cx >= p.gw ? p.gw - 1 : cx);
             cy = cy < 0 ? 0 : (cy >= p.gh ? p.gh - 1 : cy);
-            kb_walk_in_range(p, pos, head, nextb, -1, cy * p.gw + cx, make_float2(px, py), s, A.Ro2, [&](unsigned b, float, float, float dd) {
+            kb_walk_in_range(p, cells, -1, cy * p.gw + cx, make_float2(px, py), s, A.Ro2, [&](unsigned b, float, float, float dd) {
                 if (dd <= A.Ro2) win = max(win, (int)b);
             });
         }
         if (win >= 0) {
-            const float2 pb = pos[win];
+            const float2 pb = cells.pos[win];
             const float qx = px - pb.x, qy = py - pb.y;
             const float dd = qx * qx + qy * qy;
             float sn, cs;
@@ -816,7 +827,7 @@ struct RayArgs {            // the host constants of the definition (include/kil
     float ux[KB_MAX_RAYS], uy[KB_MAX_RAYS];     // (0, 0) behind n_rays: such a ray is computed like any other and never stored
 };
 struct RaysLds {        // byte offsets: pos (float2) at 0, nextb, cellOf, head (u16 each), dir[32] (float2), vert[F][4] (float2: world frame), wall[4][2] (float2), fix[F] (float4)
-    int nextb, cellOf, head, dir, vert, wall, fix, bytes;
+    int nextb, cellOf, head, dir, vert, wall, fix, bytes;       // (spelled out, not CellListsLds, which cost most legs 0.1 - 0.3 %: DESIGN.md 4b)
     __host__ __device__ constexpr RaysLds(int NP, int ncell)
         : nextb(8 * NP), cellOf(10 * NP), head(12 * NP), dir((head + 2 * ((ncell + 1) & ~1) + 15) & ~15),
           vert(dir + 8 * KB_MAX_RAYS), wall(vert + 8 * OBJ_EDGES), fix(wall + 8 * 8), bytes(fix + 16 * KB_MAX_OBJECTS) {}
@@ -948,6 +959,7 @@ __global__ void __launch_bounds__(256) kb_rays_kernel(const Params p, const kb_o
     unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
     unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
     unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const CellLists cells = {pos, head, nextb, cellOf};
     float2 *dir = reinterpret_cast<float2 *>(smem + L.dir);
     float2 *vert = reinterpret_cast<float2 *>(smem + L.vert);
     float2 *wall = reinterpret_cast<float2 *>(smem + L.wall);
@@ -977,7 +989,7 @@ __global__ void __launch_bounds__(256) kb_rays_kernel(const Params p, const kb_o
         const int w = (tid - 128) >> 1, far = (tid - 128) & 1;
         wall[tid - 128] = make_float2(w == 1 || (w >= 2 && far) ? ol.arena[1] : ol.arena[0], (w < 2 ? far : w == 3) ? ol.arena[3] : ol.arena[2]);
     }
-    if (bots) kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    if (bots) kb_build_cell_lists(p, o, cells, tid, nt);
     else __syncthreads();
     for (int a = tid; a < N; a += nt) {
         const float xi = p.buf.x[o + a], yi = p.buf.y[o + a];
@@ -990,7 +1002,7 @@ __global__ void __launch_bounds__(256) kb_rays_kernel(const Params p, const kb_o
 #pragma unroll
             for (int k = 0; k < RP; ++k) best[k] = ((unsigned long long)__float_as_uint(A.Rw) << 32) | 0xFFFFFFFFull;
             if (bots) {
-                kb_walk_in_range(p, pos, head, nextb, a, (int)cellOf[a], make_float2(xi, yi), s, A.Rc2, [&](unsigned j, float ex, float ey, float) {
+                kb_walk_in_range(p, cells, a, (int)cells.cellOf[a], make_float2(xi, yi), s, A.Rc2, [&](unsigned j, float ex, float ey, float) {
                     float b[RP], q[RP];
                     kb_ray_project<RP>(u, sn, cs, ex, ey, b, q);
                     kb_ray_disc<RP>(b, q, A.rb2, j, best);
@@ -1030,6 +1042,9 @@ struct EdgesLds {       // byte offsets: pos (float2) at 0, th (float), nextb, h
         : th(8 * NP), nextb(12 * NP), head(14 * NP), mask(head + 2 * ((ncell + 1) & ~1)), words((N + 31) >> 5), stride(words | 1),
           bytes(mask + (4 * EDGE_TILE * stride > 2 * NP ? 4 * EDGE_TILE * stride : 2 * NP)) {}
 };
+KB_LDS_PINNED(edges_lds, EdgesLds(NP, NP, nc),      // (its own three offsets, not CellListsLds: cellOf has no room between nextb and head)
+              L.th == 8 * NP && L.nextb == 12 * NP && L.head == 14 * NP && L.mask == 14 * NP + 2 * ((nc + 1) & ~1) && L.stride == (((NP + 31) >> 5) | 1) &&
+              L.bytes == L.mask + (4 * EDGE_TILE * L.stride > 2 * NP ? 4 * EDGE_TILE * L.stride : 2 * NP));
 // the largest image (1024 kilobots, every cell) stays under the default limit for dynamic LDS: no attribute to raise
 static_assert(EdgesLds(KB_MAX_BOTS, KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024, "kb_edges_kernel: LDS image");
 static_assert(KB_MAX_BOTS <= 4 * EDGE_TILE, "kb_edges_kernel: a lane keeps the cells of at most four rows");
@@ -1050,21 +1065,20 @@ __global__ void __launch_bounds__(256) kb_edges_kernel(const Params p, const int
     extern __shared__ __align__(16) unsigned char smem[];
     const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
     const EdgesLds L(N, p.NP, p.ncell);
-    float2 *pos = reinterpret_cast<float2 *>(smem);
     float *th = reinterpret_cast<float *>(smem + L.th);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
-    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
-    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.mask);
+    // the view is put together here, not by CellListsLds: cellOf lies over the masks, which are cleared only after its one reading
+    const CellLists cells = {reinterpret_cast<float2 *>(smem), reinterpret_cast<unsigned short *>(smem + L.head),
+                             reinterpret_cast<unsigned short *>(smem + L.nextb), reinterpret_cast<unsigned short *>(smem + L.mask)};
     unsigned *row = reinterpret_cast<unsigned *>(smem + L.mask) + tid * L.stride;
     const size_t o = (size_t)e * N;
     for (int b = tid; b < N; b += nt) th[b] = p.buf.theta[o + b];
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     // the cells of the lane's (at most four) rows, two to a register, before the masks take cellOf's place
     unsigned c01 = 0, c23 = 0;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int a = tid + t * EDGE_TILE;
-        const unsigned c = a < N ? (unsigned)cellOf[a] : 0u;
+        const unsigned c = a < N ? (unsigned)cells.cellOf[a] : 0u;
         if (t < 2) c01 |= c << (16 * t);
         else c23 |= c << (16 * (t - 2));
     }
@@ -1074,9 +1088,9 @@ __global__ void __launch_bounds__(256) kb_edges_kernel(const Params p, const int
         const int a = t * EDGE_TILE + tid;
         if (a >= N) break;      // (no barrier follows)
         const int cell = (int)(((t < 2 ? c01 : c23) >> (16 * (t & 1))) & 0xFFFFu);
-        const float2 pa = pos[a];
+        const float2 pa = cells.pos[a];
         for (int w = 0; w < W; ++w) row[w] = 0u;
-        const unsigned cnt = kb_walk_in_range(p, pos, head, nextb, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
+        const unsigned cnt = kb_walk_in_range(p, cells, a, cell, pa, s, R2, [&](unsigned b, float, float, float) {
             row[b >> 5] |= 1u << (b & 31u);
         });
         if (d_count) d_count[o + a] = cnt;
@@ -1092,12 +1106,12 @@ __global__ void __launch_bounds__(256) kb_edges_kernel(const Params p, const int
         for (int w = 0; w < W && slot < hi; ++w) {
             for (unsigned bits = row[w]; bits != 0u && slot < hi; bits &= bits - 1u, ++slot) {
                 const int j = 32 * w + __builtin_ctz(bits);
-                const float2 pb = pos[j];
+                const float2 pb = cells.pos[j];
                 const float ex = pb.x - pa.x, ey = pb.y - pa.y;
                 const float d2 = ex * ex + ey * ey;
                 d_dst[slot] = node0 + j;
                 if (d_src) d_src[slot] = src;
-                if (d_rel) d_rel[slot] = make_float4((cs * ex + sn * ey) / WORLD_SCALE, (cs * ey - sn * ex) / WORLD_SCALE, sqrtf(d2) / WORLD_SCALE, th[j] - tha);
+                if (d_rel) { const float2 f = kb_body_frame(cs, sn, ex, ey); d_rel[slot] = make_float4(f.x, f.y, sqrtf(d2) / WORLD_SCALE, th[j] - tha); }
             }
         }
         for (; slot < hi; ++slot) {     // offsets that give the row more than it has
@@ -1115,8 +1129,8 @@ __global__ void __launch_bounds__(256) kb_edges_kernel(const Params p, const int
 constexpr int HOPS_ROWS_PER_LANE = KB_HOPS_ROWS_PER_LANE;
 static_assert(HOPS_ROWS_PER_LANE >= 1 && HOPS_ROWS_PER_LANE <= 1024, "kb_hops_kernel: rows per lane");
 constexpr unsigned HOP_UNSET = 0xFFFFFFFFu;         // a link word that no frontier has reached
-struct HopsLds {        // byte offsets: pos (float2) at 0, link (u32), root, q[2][NP], nextb, cellOf, head (u16 each), cnt[3] (u32)
-    int link, root, q, nextb, cellOf, head, cnt, bytes;
+struct HopsLds {        // byte offsets: pos (float2) at 0, link (u32), root, q[2][NP], nextb, cellOf, head (u16 each), cnt[3] (u32) -- spelled out,
+    int link, root, q, nextb, cellOf, head, cnt, bytes;     // not CellListsLds, which cost the short-range legs 0.6 - 1.3 %
     __host__ __device__ constexpr HopsLds(int NP, int ncell)
         : link(8 * NP), root(12 * NP), q(14 * NP), nextb(18 * NP), cellOf(20 * NP), head(22 * NP),
           cnt((head + 2 * ((ncell + 1) & ~1) + 3) & ~3), bytes(cnt + 16) {}
@@ -1151,10 +1165,11 @@ __global__ void __launch_bounds__(256) kb_hops_kernel(const Params p, const int 
     unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
     unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
     unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
+    const CellLists cells = {pos, head, nextb, cellOf};
     unsigned *cnt = reinterpret_cast<unsigned *>(smem + L.cnt);
     const size_t o = (size_t)e * N;
     if (tid < 3) cnt[tid] = 0u;
-    kb_build_cell_lists(p, o, pos, head, nextb, cellOf, tid, nt);
+    kb_build_cell_lists(p, o, cells, tid, nt);
     for (int b = tid; b < N; b += nt) {
         const bool seed = d_seed[o + b] != 0;
         link[b] = seed ? 0xFFFFu : HOP_UNSET;
@@ -1181,7 +1196,7 @@ __global__ void __launch_bounds__(256) kb_hops_kernel(const Params p, const int 
             if (lvl > 0 && r == 0) root[i] = root[link[i] & 0xFFFFu];
             if (lvl == lim) continue;
             const unsigned key = ((unsigned)(lvl + 1) << 16) | (unsigned)i;
-            kb_walk_rows_in_range<HOPS_ROWS_PER_LANE>(p, pos, head, nextb, i, (int)cellOf[i], pos[i], s, R2, r * HOPS_ROWS_PER_LANE, [&](unsigned b, float, float, float) {
+            kb_walk_rows_in_range<HOPS_ROWS_PER_LANE>(p, cells, i, (int)cellOf[i], pos[i], s, R2, r * HOPS_ROWS_PER_LANE, [&](unsigned b, float, float, float) {
                 if (atomicMin(&link[b], key) == HOP_UNSET) {
                     const unsigned slot = atomicAdd(cn, 1u);
                     if (slot < (unsigned)N) qn[slot] = (unsigned short)b;
@@ -1414,11 +1429,12 @@ __global__ void __launch_bounds__(256) kb_contacts_kernel(const ContactsArgs A, 
 constexpr int COVERAGE_RING_COST = KB_COVERAGE_RING_COST;
 static_assert(COVERAGE_RING_COST >= 0 && COVERAGE_RING_COST <= (1 << 20), "kb_coverage_kernel: ring cost");
 struct CoverageArgs { int gw, gh; float cw, ch; };      // the grid and the host constants of the definition (include/kilobots_hip.h)
-struct CoverageLds {    // byte offsets: pos (float2) at 0, acc (u64: n << 42 | SX << 21 | SY), red[4] (u64) + wmax[4] (u32), dmax (u32), nextb, cellOf, head (u16 each)
-    int acc, red, dmax, nextb, cellOf, head, bytes;
-    __host__ __device__ constexpr CoverageLds(int NP, int ncell)
-        : acc(8 * NP), red(16 * NP), dmax(16 * NP + 64), nextb(20 * NP + 64), cellOf(22 * NP + 64), head(24 * NP + 64), bytes(24 * NP + 64 + 2 * ncell + 16) {}
+struct CoverageLds : CellListsLds {     // byte offsets: pos (float2) at 0, acc (u64: n << 42 | SX << 21 | SY), red[4] (u64) + wmax[4] (u32), dmax (u32), the cell lists
+    int acc, red, dmax, bytes;
+    __host__ __device__ constexpr CoverageLds(int NP, int ncell) : CellListsLds(20 * NP + 64, NP, ncell), acc(8 * NP), red(16 * NP), dmax(16 * NP + 64), bytes(head + 2 * ncell + 16) {}
 };
+KB_LDS_PINNED(coverage_lds, CoverageLds(NP, nc),
+              L.acc == 8 * NP && L.red == 16 * NP && L.dmax == 16 * NP + 64 && L.nextb == 20 * NP + 64 && L.cellOf == 22 * NP + 64 && L.head == 24 * NP + 64 && L.bytes == 24 * NP + 64 + 2 * nc + 16);
 // (the image does not grow with the grid; the grid bounds what one accumulator word holds: n <= 128 * 128 < 2^15 and
 // SX, SY <= 128 * 128 * 127 < 2^21 share 64 bits)
 static_assert(CoverageLds(KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024 && KB_GRID_MAX_SIDE * KB_GRID_MAX_SIDE < (1 << 15) &&
@@ -1456,21 +1472,18 @@ __global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const 
     extern __shared__ __align__(16) unsigned char smem[];
     const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N, W = A.gw, H = A.gh;
     const CoverageLds L(p.NP, p.ncell);
-    float2 *pos = reinterpret_cast<float2 *>(smem);
+    const CellLists cells = L.view(smem);
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(smem + L.acc);
     unsigned long long *red = reinterpret_cast<unsigned long long *>(smem + L.red);
     unsigned *wmax = reinterpret_cast<unsigned *>(smem + L.red + 32);
     unsigned *dmax = reinterpret_cast<unsigned *>(smem + L.dmax);
-    unsigned short *nextb = reinterpret_cast<unsigned short *>(smem + L.nextb);
-    unsigned short *cellOf = reinterpret_cast<unsigned short *>(smem + L.cellOf);
-    unsigned short *head = reinterpret_cast<unsigned short *>(smem + L.head);
     const size_t o = (size_t)e * N, po = (size_t)e * H * W;
     const int npix = W * H;
     const float INF = __uint_as_float(0x7F800000u);
     constexpr unsigned NONE = 0x7F800001u;      // above the bits of every d2 that is a number (d2 >= 0: the order of the bits is the order of the values) and below those of a NaN
     for (int b = tid; b < N; b += nt) { acc[b] = 0ull; dmax[b] = 0u; }
     int mine = 0;
-    kb_build_cell_lists_of(p, o, pos, head, nextb, cellOf, tid, nt, [&](int b) {
+    kb_build_cell_lists_of(p, o, cells, tid, nt, [&](int b) {
         const bool keep = !d_select || d_select[o + b] != 0;
         mine |= (int)keep;
         return keep;
@@ -1528,9 +1541,9 @@ __global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const 
                 const int ox = m < 0 ? bx - k + (j < side ? j : j - side) : ((m & 1) ? bx + k : bx - k);
                 const int oy = m < 0 ? (j < side ? by - k : by + k) : by - k + 1 + (m >> 1);
                 if ((unsigned)ox >= (unsigned)p.gw || (unsigned)oy >= (unsigned)p.gh) continue;
-                for (unsigned b = head[oy * p.gw + ox]; b != (unsigned)EMPTY16;) {
-                    const float2 pb = pos[b];
-                    const unsigned nb = nextb[b];
+                for (unsigned b = cells.head[oy * p.gw + ox]; b != (unsigned)EMPTY16;) {
+                    const float2 pb = cells.pos[b];
+                    const unsigned nb = cells.nextb[b];
                     take(b, pb);
                     b = nb;
                 }
@@ -1551,10 +1564,10 @@ __global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const 
             };
             int b = 0;
             for (; b + 4 <= N; b += 4) {
-                const float4 q0 = reinterpret_cast<const float4 *>(pos + b)[0], q1 = reinterpret_cast<const float4 *>(pos + b)[1];
+                const float4 q0 = reinterpret_cast<const float4 *>(cells.pos + b)[0], q1 = reinterpret_cast<const float4 *>(cells.pos + b)[1];
                 scan(b, q0.x, q0.y); scan(b + 1, q0.z, q0.w); scan(b + 2, q1.x, q1.y); scan(b + 3, q1.z, q1.w);
             }
-            for (; b < N; ++b) scan(b, pos[b].x, pos[b].y);
+            for (; b < N; ++b) scan(b, cells.pos[b].x, cells.pos[b].y);
         }
         const float bd = __uint_as_float(bdb);
         if (own) own[f] = (int)bi;
@@ -1588,10 +1601,11 @@ __global__ void __launch_bounds__(256) kb_coverage_kernel(const Params p, const 
             float4 row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (n > 0) {        // (an owner: a selected kilobot, pos[b] its pose)
                 const float mx = p.xmin + (((float)SX / (float)n) + 0.5f) * A.cw, my = p.ymin + (((float)SY / (float)n) + 0.5f) * A.ch;
-                const float dx = mx - pos[b].x, dy = my - pos[b].y;
+                const float dx = mx - cells.pos[b].x, dy = my - cells.pos[b].y;
                 float sn, cs;
                 kb_sincosf(theta[o + b], sn, cs);
-                row = make_float4((cs * dx + sn * dy) / WORLD_SCALE, (cs * dy - sn * dx) / WORLD_SCALE, (float)n, sqrtf(__uint_as_float(dmax[b])) / WORLD_SCALE);
+                const float2 f = kb_body_frame(cs, sn, dx, dy);
+                row = make_float4(f.x, f.y, (float)n, sqrtf(__uint_as_float(dmax[b])) / WORLD_SCALE);
             }
             d_cell[o + b] = row;
         }
@@ -1803,8 +1817,8 @@ __global__ void __launch_bounds__(TARGETS_THREADS) kb_targets_kernel(const Targe
                 const float ex = spos[u].x - bpos[i].x, ey = spos[u].y - bpos[i].y;
                 float sn, cs_;
                 kb_sincosf(theta[o + b], sn, cs_);
-                d_rel[o + b] = make_float4((cs_ * ex + sn * ey) / WORLD_SCALE, (cs_ * ey - sn * ex) / WORLD_SCALE, sqrtf(d2) / WORLD_SCALE,
-                                           (unsigned)sres[u] == (unsigned)i ? 1.0f : 0.0f);
+                const float2 f = kb_body_frame(cs_, sn, ex, ey);
+                d_rel[o + b] = make_float4(f.x, f.y, sqrtf(d2) / WORLD_SCALE, (unsigned)sres[u] == (unsigned)i ? 1.0f : 0.0f);
             }
             cost += (long long)rintf(fminf(d2 * 65536.0f, 0x1p40f));
             far = max(far, db);
