@@ -28,6 +28,7 @@ GRID_COUNT, GRID_FLOW, GRID_OBJECTS = 1, 2, 4     # KB_GRID_*: the planes of kb_
 MAX_CONTACT_SLOTS = 16     # KB_MAX_CONTACT_SLOTS: slots per kilobot of kb_sense_contacts
 GRID_MAX_SIDE = 128     # KB_GRID_MAX_SIDE: cells along either side of the grid of kb_sense_grid
 MAX_TARGETS = 1024     # KB_MAX_TARGETS: slots of the target shape of kb_sense_targets
+FIELD_MAX_CHANNELS, FIELD_MAX_ITERS = 4, 64     # KB_FIELD_MAX_*: channels of a field and iterations per call of kb_field_step
 RENDER_OBJECTS, RENDER_BOTS, RENDER_LIGHT = 1, 2, 4     # KB_RENDER_*: the layers of kb_render, a bit each
 RENDER_MAX_SIDE = 2048     # KB_RENDER_MAX_SIDE: pixels along either side of a frame of kb_render
 RAY_BOTS, RAY_OBJECTS, RAY_WALLS = 1, 2, 4     # KB_RAY_*: what the rays of kb_sense_rays can hit, a bit each
@@ -129,6 +130,7 @@ SIGNATURES = {
     'kb_grid_channels': (_I, [_P, _I]),
     'kb_sense_grid': (_I, [_P, _I, _I, _I, _P, _P]),
     'kb_sense_coverage': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'kb_field_step': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
     'kb_sense_targets': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
@@ -302,6 +304,29 @@ def check_coverage(width, height):
     if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
         raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
     return width, height
+
+
+def check_field(width, height, channels, keep, spread, iters):
+    """The limits of kb_field_step on the grid, the channel count, keep and spread (a number for all channels or one per
+    channel) and the iterations; ValueError where the library would answer KB_EINVAL.  Returns (width, height, channels, keep
+    and spread as tuples of `channels` floats, iters)."""
+    if any(isinstance(v, bool) for v in (width, height, channels, iters)):
+        raise ValueError('width, height, channels and iters must be integers')
+    width, height, channels, iters = int(width), int(height), int(channels), int(iters)
+    if not (1 <= width <= GRID_MAX_SIDE and 1 <= height <= GRID_MAX_SIDE):
+        raise ValueError('width and height must be in 1..%d' % GRID_MAX_SIDE)
+    if not 1 <= channels <= FIELD_MAX_CHANNELS:
+        raise ValueError('channels must be in 1..%d' % FIELD_MAX_CHANNELS)
+
+    def per_channel(v, name, hi):
+        v = tuple(_f32(float(c)) for c in v) if hasattr(v, '__len__') else (_f32(float(v)),) * channels
+        if len(v) != channels or not all(0.0 <= c <= hi for c in v):
+            raise ValueError('%s must be a number or %d numbers in [0, %g]' % (name, channels, hi))
+        return v
+    keep, spread = per_channel(keep, 'keep', 1.0), per_channel(spread, 'spread', 0.25)
+    if not 0 <= iters <= FIELD_MAX_ITERS:
+        raise ValueError('iters must be in 0..%d' % FIELD_MAX_ITERS)
+    return width, height, channels, keep, spread, iters
 
 
 def check_targets(n_targets, tol_m):

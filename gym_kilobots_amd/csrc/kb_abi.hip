@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage, kb_sense_targets) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage, kb_sense_targets, kb_field_step) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -367,6 +367,15 @@ using kb_reduce_fn = void (*)(Params, int, float, int, int, float, const float *
 template <int OP>
 kb_reduce_fn reduce_kernel(int CP) {
     return CP == 1 ? kb_reduce_kernel<OP, 1> : CP == 2 ? kb_reduce_kernel<OP, 2> : CP == 4 ? kb_reduce_kernel<OP, 4> : kb_reduce_kernel<OP, 8>;
+}
+
+// the instantiation of kb_field_kernel that holds a plane of `cells` cells: the fewest cells per lane of 4 x (1, 2, 4, 6, 8)
+using kb_field_fn = void (*)(FieldArgs, const float *, const float *, const float *, const uint8_t *, const float *, float *, float4 *);
+template <bool VEC>
+kb_field_fn field_kernel(int cells) {
+    const int per_lane = (cells + FIELD_THREADS - 1) / FIELD_THREADS;
+    return per_lane <= 4 ? kb_field_kernel<1, VEC> : per_lane <= 8 ? kb_field_kernel<2, VEC> : per_lane <= 16 ? kb_field_kernel<4, VEC>
+         : per_lane <= 24 ? kb_field_kernel<6, VEC> : kb_field_kernel<8, VEC>;
 }
 
 }  // namespace
@@ -973,6 +982,34 @@ int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int3
     const Params &p = sim->p;
     const CoverageArgs a = {gw, gh, (p.xmax - p.xmin) / (float)gw, (p.ymax - p.ymin) / (float)gh};       // (kb_outline.arena is these four)
     return launch("kb_sense_coverage", kb_coverage_kernel, p.E, 256, CoverageLds(p.NP, p.ncell).bytes, stream, p, a, d_select, d_owner, d_dist, reinterpret_cast<float4 *>(d_cell), d_stats);
+}
+
+int kb_field_step(kb_sim *sim, int gw, int gh, int n_channels, const float *keep, const float *spread, int n_iters, const uint8_t *d_env_mask,
+                  const float *d_amount, float *d_field, float *d_sense, void *stream) {
+    if (!sim) return fail(KB_EINVAL, "kb_field_step: NULL handle");
+    if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_field_step: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
+    if (n_channels < 1 || n_channels > KB_FIELD_MAX_CHANNELS) return fail(KB_EINVAL, "kb_field_step: 1 <= n_channels <= KB_FIELD_MAX_CHANNELS (4) required");
+    if (!keep || !spread) return fail(KB_EINVAL, "kb_field_step: keep and spread must not be NULL");
+    for (int c = 0; c < n_channels; ++c)       // (a NaN fails both comparisons)
+        if (!(keep[c] >= 0.0f && keep[c] <= 1.0f) || !(spread[c] >= 0.0f && spread[c] <= 0.25f))
+            return fail(KB_EINVAL, "kb_field_step: keep must lie in [0, 1] and spread in [0, 0.25] for every channel");
+    if (n_iters < 0 || n_iters > KB_FIELD_MAX_ITERS) return fail(KB_EINVAL, "kb_field_step: 0 <= n_iters <= KB_FIELD_MAX_ITERS (64) required");
+    if (!d_field) return fail(KB_EINVAL, "kb_field_step: d_field is NULL");
+    if (!d_amount && !d_sense && n_iters == 0) return fail(KB_EINVAL, "kb_field_step: nothing to do (d_amount and d_sense are NULL and n_iters is 0)");
+    if (!aligned16(d_sense)) return fail(KB_EINVAL, "kb_field_step: d_sense must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_field_step: kb_bind() first");
+    const Params &p = sim->p;
+    FieldArgs a;
+    memset(&a, 0, sizeof(a));
+    a.N = p.N; a.C = n_channels; a.gw = gw; a.gh = gh; a.iters = n_iters;
+    a.xmin = p.xmin; a.ymin = p.ymin;        // (kb_outline.arena is these four)
+    a.icw = (float)gw / (p.xmax - p.xmin); a.ich = (float)gh / (p.ymax - p.ymin);
+    a.hicw = 0.5f * a.icw; a.hich = 0.5f * a.ich;
+    for (int c = 0; c < n_channels; ++c) { a.keep[c] = keep[c]; a.spread[c] = spread[c]; }
+    const bool vec = gw % 4 == 0 && aligned16(d_field);
+    const kb_field_fn fn = vec ? field_kernel<true>(gw * gh) : field_kernel<false>(gw * gh);
+    return launch("kb_field_step", fn, (unsigned)p.E * (unsigned)n_channels, FIELD_THREADS, FieldLds(gw, gh).bytes, stream, a, p.buf.x, p.buf.y, p.buf.theta,
+                  d_env_mask, d_amount, d_field, reinterpret_cast<float4 *>(d_sense));
 }
 
 int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, const uint8_t *d_bot_select,

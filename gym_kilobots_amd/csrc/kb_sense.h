@@ -3,7 +3,9 @@
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_targets, which meets
 // the slots of a target shape, every kilobot against every slot, and needs none either; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
-// the contact store the last step left; and kb_render, which draws every env as an RGB frame, a range query per pixel.
+// the contact store the last step left; kb_field_step, which keeps a pheromone field of the caller's, a plane per workgroup,
+// in registers and LDS while the kilobots add to it, it diffuses and they read it; and kb_render, which draws every env as an
+// RGB frame, a range query per pixel.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -664,6 +666,200 @@ __global__ void __launch_bounds__(256) kb_grid_objects_kernel(const kb_outline o
     for (int m = 0; m < M; ++m) {
         float best, brx, bry;
         out[m * chan] = kb_object_walk(I, m, I.frame[m], cx, cy, best, brx, bry) ? 1.0f : 0.0f;
+    }
+}
+
+// ---- kb_field_step: per-env pheromone fields that the caller owns -------------------------------------------------------------
+constexpr int FIELD_THREADS = 512;
+constexpr int FIELD_BOT_SLOTS = KB_MAX_BOTS / FIELD_THREADS;        // kilobots per lane
+struct FieldArgs {          // the grid and the host constants of the definition (include/kilobots_hip.h)
+    int N, C, gw, gh, iters;
+    float xmin, ymin, icw, ich, hicw, hich, keep[KB_FIELD_MAX_CHANNELS], spread[KB_FIELD_MAX_CHANNELS];
+};
+struct FieldLds {           // the plane of one (env, channel): int32 accumulators during the deposit, floats from then on
+    int bytes;
+    __host__ __device__ constexpr FieldLds(int gw, int gh) : bytes((4 * gw * gh + 15) & ~15) {}
+};
+static_assert(FieldLds(KB_GRID_MAX_SIDE, KB_GRID_MAX_SIDE).bytes <= GRID_LDS_LIMIT, "kb_field_kernel: LDS image");
+static_assert(FIELD_BOT_SLOTS * FIELD_THREADS == KB_MAX_BOTS && 4 * 8 * FIELD_THREADS >= KB_GRID_MAX_SIDE * KB_GRID_MAX_SIDE, "kb_field_kernel: slots per lane");
+
+__device__ __forceinline__ int kb_field_quant(float a) {      // kb_reduce_quant at scale 65536 with the clamp at 2^20: 1024 of them stay below 2^31
+    const float t = a * 65536.0f;
+    return t != t ? 0 : (int)rintf(fminf(fmaxf(t, -1048576.0f), 1048576.0f));
+}
+__device__ __forceinline__ float kb_field_pick(const float (&v)[KB_FIELD_MAX_CHANNELS], int c) {      // (selects: a kernel argument indexed at run time must not become a private copy)
+    return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3];
+}
+// one diffusion and decay step of a cell from its four neighbours: every operation rounds on its own
+__device__ __forceinline__ float kb_field_cell(float u, float w, float e, float s, float n, float keep, float spread) {
+    const float lap = ((w + e) + (s + n)) - 4.0f * u;
+    return keep * (u + spread * lap);
+}
+
+// One workgroup per (env, channel); the plane lives in the lanes' registers and in LDS from the first load to the last store.
+// A lane holds 4 K cells in UL "units": with VEC a unit is four consecutive cells of one row (gw a multiple of 4 and d_field
+// on 16 bytes: 16-byte loads, stores and LDS accesses), otherwise one cell; unit j of a lane is unit j * FIELD_THREADS + tid
+// of the plane, so consecutive lanes hold consecutive words.  K comes from the entry point: the smallest of 1, 2, 4, 6, 8
+// that holds the plane, every loop over the units unrolls and the register arrays are indexed by constants only.  Which
+// neighbours a unit has inside the grid is found once (edge: four bits per unit); a neighbour outside is the cell itself.
+// Deposit: the LDS plane zeroed, one ds_add_u32 without a result per kilobot, a barrier, then every lane converts and adds
+// the words of its units into its registers; a kilobot keeps the accumulator of its cell for its sense row.  Iteration: the
+// neighbours come from LDS (with VEC the rows below and above as 16 bytes, left and right one word each, the rest from the
+// unit's own registers), barrier, store, barrier.  The kilobots sense from the final plane in LDS; poses are read from
+// global memory (at 128 x 128 the plane is all the LDS there is).
+template <int K, bool VEC>
+__global__ void __launch_bounds__(FIELD_THREADS) kb_field_kernel(const FieldArgs a, const float *x, const float *y, const float *theta, const uint8_t *env_mask,
+                                                                 const float *amount, float *field, float4 *sense) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int VW = VEC ? 4 : 1, UL = VEC ? K : 4 * K;       // cells per unit, units per lane
+    float *pl = reinterpret_cast<float *>(smem);
+    int *acc = reinterpret_cast<int *>(smem);
+    const int tid = threadIdx.x, e = blockIdx.x / a.C, c = blockIdx.x - e * a.C;
+    if (env_mask && !env_mask[e]) return;       // (the same for the whole workgroup: no barrier is left waiting)
+    const int gw = a.gw, gh = a.gh, N = a.N, units = gw * gh / VW, uw = gw / VW;
+    float *F = field + ((size_t)e * a.C + c) * ((size_t)gw * gh);
+    const size_t o = (size_t)e * N;
+
+    float u[UL][VW];
+    unsigned edge[(UL + 7) / 8], live = 0;       // four bits per unit: its neighbours inside the grid; a bit per unit: it is a unit of the plane
+#pragma unroll
+    for (int j = 0; j < (UL + 7) / 8; ++j) edge[j] = 0;
+#pragma unroll
+    for (int j = 0; j < UL; ++j) {
+        const int g = j * FIELD_THREADS + tid;
+#pragma unroll
+        for (int w = 0; w < VW; ++w) u[j][w] = 0.0f;
+        if (g < units) {
+            if constexpr (VEC) {
+                const float4 v = reinterpret_cast<const float4 *>(F)[g];
+                u[j][0] = v.x; u[j][1] = v.y; u[j][2] = v.z; u[j][3] = v.w;
+            } else {
+                u[j][0] = F[g];
+            }
+            const int gy = g / uw, gx = g - gy * uw;
+            const unsigned m = (gx > 0 ? 1u : 0u) | (gx < uw - 1 ? 2u : 0u) | (gy > 0 ? 4u : 0u) | (gy < gh - 1 ? 8u : 0u);
+            edge[j / 8] |= m << (4 * (j % 8));
+            live |= 1u << j;
+        }
+    }
+
+    int bcell[FIELD_BOT_SLOTS], bix[FIELD_BOT_SLOTS], biy[FIELD_BOT_SLOTS], bacc[FIELD_BOT_SLOTS];
+#pragma unroll
+    for (int s = 0; s < FIELD_BOT_SLOTS; ++s) {
+        const int b = s * FIELD_THREADS + tid;
+        bcell[s] = -1; bix[s] = 0; biy[s] = 0; bacc[s] = 0;
+        if (b < N) {        // the cell rule of kb_grid_bots_kernel
+            const float tx = (x[o + b] - a.xmin) * a.icw, ty = (y[o + b] - a.ymin) * a.ich;
+            bix[s] = !(tx > 0.0f) ? 0 : tx >= (float)gw ? gw - 1 : (int)tx;
+            biy[s] = !(ty > 0.0f) ? 0 : ty >= (float)gh ? gh - 1 : (int)ty;
+            bcell[s] = biy[s] * gw + bix[s];
+        }
+    }
+
+    // (opaque from phase to phase and from iteration to iteration: otherwise the compiler keeps a predicate per unit and four
+    // neighbour addresses per cell alive across the whole kernel, in scalar and vector registers it then has to spill)
+    const auto fresh = [&]() {
+        asm volatile("" : "+v"(live));
+#pragma unroll
+        for (int j = 0; j < (UL + 7) / 8; ++j) asm volatile("" : "+v"(edge[j]));
+    };
+    if (amount) {
+        fresh();
+#pragma unroll
+        for (int j = 0; j < UL; ++j) {
+            const int g = j * FIELD_THREADS + tid;
+            if (live >> j & 1u) {
+                if constexpr (VEC) reinterpret_cast<int4 *>(acc)[g] = make_int4(0, 0, 0, 0);
+                else acc[g] = 0;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < FIELD_BOT_SLOTS; ++s)
+            if (bcell[s] >= 0) atomicAdd(acc + bcell[s], kb_field_quant(amount[(o + s * FIELD_THREADS + tid) * a.C + c]));
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < FIELD_BOT_SLOTS; ++s)
+            if (bcell[s] >= 0) bacc[s] = acc[bcell[s]];
+        fresh();
+#pragma unroll
+        for (int j = 0; j < UL; ++j) {
+            const int g = j * FIELD_THREADS + tid;
+            if (live >> j & 1u) {
+                if constexpr (VEC) {
+                    const int4 q = reinterpret_cast<const int4 *>(acc)[g];
+                    u[j][0] = u[j][0] + (float)q.x / 65536.0f; u[j][1] = u[j][1] + (float)q.y / 65536.0f;
+                    u[j][2] = u[j][2] + (float)q.z / 65536.0f; u[j][3] = u[j][3] + (float)q.w / 65536.0f;
+                } else {
+                    u[j][0] = u[j][0] + (float)acc[g] / 65536.0f;
+                }
+            }
+        }
+        __syncthreads();        // (every accumulator has been read before the floats go over them)
+    }
+
+    const auto to_lds = [&]() {
+        fresh();
+#pragma unroll
+        for (int j = 0; j < UL; ++j) {
+            const int g = j * FIELD_THREADS + tid;
+            if (live >> j & 1u) {
+                if constexpr (VEC) reinterpret_cast<float4 *>(pl)[g] = make_float4(u[j][0], u[j][1], u[j][2], u[j][3]);
+                else pl[g] = u[j][0];
+            }
+        }
+        __syncthreads();
+    };
+    to_lds();
+
+    const float keep = kb_field_pick(a.keep, c), spread = kb_field_pick(a.spread, c);
+    for (int it = 0; it < a.iters; ++it) {
+        fresh();
+#pragma unroll
+        for (int j = 0; j < UL; ++j) {
+            const int g = j * FIELD_THREADS + tid;
+            if (live >> j & 1u) {
+                const unsigned m = edge[j / 8] >> (4 * (j % 8));
+                if constexpr (VEC) {
+                    const float4 dn = reinterpret_cast<const float4 *>(pl)[m & 4u ? g - uw : g], up = reinterpret_cast<const float4 *>(pl)[m & 8u ? g + uw : g];
+                    const float lf = m & 1u ? pl[4 * g - 1] : u[j][0], rt = m & 2u ? pl[4 * g + 4] : u[j][3];
+                    const float n0 = kb_field_cell(u[j][0], lf, u[j][1], dn.x, up.x, keep, spread);
+                    const float n1 = kb_field_cell(u[j][1], u[j][0], u[j][2], dn.y, up.y, keep, spread);
+                    const float n2 = kb_field_cell(u[j][2], u[j][1], u[j][3], dn.z, up.z, keep, spread);
+                    const float n3 = kb_field_cell(u[j][3], u[j][2], rt, dn.w, up.w, keep, spread);
+                    u[j][0] = n0; u[j][1] = n1; u[j][2] = n2; u[j][3] = n3;
+                } else {
+                    u[j][0] = kb_field_cell(u[j][0], pl[m & 1u ? g - 1 : g], pl[m & 2u ? g + 1 : g], pl[m & 4u ? g - gw : g], pl[m & 8u ? g + gw : g], keep, spread);
+                }
+            }
+        }
+        __syncthreads();        // (every neighbour has been read before the new plane goes over the old one)
+        to_lds();
+    }
+
+    if (amount || a.iters > 0) {
+        fresh();
+#pragma unroll
+        for (int j = 0; j < UL; ++j) {
+            const int g = j * FIELD_THREADS + tid;
+            if (live >> j & 1u) {
+                if constexpr (VEC) reinterpret_cast<float4 *>(F)[g] = make_float4(u[j][0], u[j][1], u[j][2], u[j][3]);
+                else F[g] = u[j][0];
+            }
+        }
+    }
+    if (sense) {
+#pragma unroll
+        for (int s = 0; s < FIELD_BOT_SLOTS; ++s) {
+            if (bcell[s] < 0) continue;
+            const int b = s * FIELD_THREADS + tid, ix = bix[s], iy = biy[s], row = iy * gw;
+            const float val = pl[row + ix];
+            const float dx = (pl[row + min(ix + 1, gw - 1)] - pl[row + max(ix - 1, 0)]) * a.hicw * 25.0f;
+            const float dy = (pl[min(iy + 1, gh - 1) * gw + ix] - pl[max(iy - 1, 0) * gw + ix]) * a.hich * 25.0f;
+            float sn, cs;
+            kb_sincosf(theta[o + b], sn, cs);
+            sense[(o + b) * a.C + c] = make_float4(val, cs * dx + sn * dy, cs * dy - sn * dx, amount ? (float)bacc[s] / 65536.0f : 0.0f);
+        }
     }
 }
 

@@ -44,6 +44,11 @@ def _coverage_obs(value, num_objects):
     return nat.check_coverage(width, height)
 
 
+def _field_obs(value, num_objects):
+    width, height, channels = tuple(value) if len(value) == 3 else tuple(value) + (1,)
+    return nat.check_field(width, height, channels, 1.0, 0.0, 0)[:3]
+
+
 def _target_obs(value, num_objects):
     points_m, tol_m = value
     points = np.ascontiguousarray(np.asarray(points_m.cpu() if torch.is_tensor(points_m) else points_m, dtype=np.float32))
@@ -88,6 +93,7 @@ OPTIONS = {
     'object_obs': Option(_object_obs, None, ('objects', 'walls'), 'object_points', 'True', 'observe objects and walls'),
     'grid_obs': Option(_grid_obs, '(width, height) or (width, height, planes)', ('grid',), 'occupancy_grid', '(width, height[, planes])', 'observe occupancy grids'),
     'coverage_obs': Option(_coverage_obs, '(width, height)', ('coverage',), 'coverage', '(width, height)', 'observe nearest-kilobot fields'),
+    'field_obs': Option(_field_obs, '(width, height) or (width, height, channels)', (), None, '(width, height[, channels])', 'keep a pheromone field'),
     'target_obs': Option(_target_obs, '(points_m, tol_m)', ('targets',), 'targets', '(points_m, tol_m)', 'observe the slots of a target shape'),
     'contact_obs': Option(_contact_obs, None, ('contacts',), 'contacts', 'k', 'observe contacts'),
     'ray_obs': Option(_ray_obs, '(radius_m, n_rays) or (radius_m, n_rays, targets)', ('rays',), 'rays', '(radius_m, n_rays[, targets])', 'observe range scans'),
@@ -105,7 +111,8 @@ class BatchedKilobotsEnv(object):
                  world_size=(2.0, 1.5), spawn_std=0.1, spawn_mean=(0.0, 0.0), seed=0, device=None,
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
                  object_obs=None, grid_obs=None, coverage_obs=None, target_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
-                 max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None, **cfg):
+                 max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None,
+                 field_obs=None, field_keep=1.0, field_spread=0.0, field_iters=1, deposit_fn=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -152,6 +159,15 @@ class BatchedKilobotsEnv(object):
         CSR / COO edge list over the batch, node e * N + i for kilobot i of env e; with a capacity the lists have that fixed
         length and nothing is read back from the device, without one they have nnz entries at the price of one read -- and
         step() puts the tuple in its info dict under 'edges'.  None adds nothing.
+        field_obs: (width, height) or (width, height, channels) gives every env a pheromone field, the memory of a stigmergy
+        task (trails, foraging, area marking): env.field [E, channels, height, width] lies over the arena like the grid of
+        grid_obs.  After the world step, step() lets every kilobot deposit into the cell it stands in, diffuses and decays the
+        field field_iters times with field_keep and field_spread (a number or one per channel) and puts what every kilobot
+        reads, [E, N, channels, 4] = (value, gradient per metre ahead, to the left, what its cell just received), in its info
+        dict under 'field' -- all in one launch (KilobotSim.field_step).  deposit_fn(prev_obs, actions, obs) returns the amounts
+        [E, N] or [E, N, channels]; None: every kilobot deposits 1.0 in every channel.  reset() zeroes the field, reset_envs()
+        that of the envs it selects; with auto_reset the rows of an env that was just reset are read off its zeroed planes.
+        field_sense() reads the rows without changing the field.  None adds nothing.
         Episodes of single envs, all off by default (reset(), step() and the info dict are then what they were):
         max_episode_steps: an env is done once it has taken that many steps since its last reset.
         done_fn: called as done_fn(prev, actions, obs) like reward_fn, returns a bool tensor [E]: the envs that are done.
@@ -180,7 +196,7 @@ class BatchedKilobotsEnv(object):
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
         given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs, coverage_obs=coverage_obs, target_obs=target_obs,
-                     contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs)
+                     contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs, field_obs=field_obs)
         for name, option in OPTIONS.items():
             value = given[name]
             if value is not None:
@@ -219,6 +235,11 @@ class BatchedKilobotsEnv(object):
         self._observe_kw = {}       # keyword arguments the sim method of an observation gets besides the stored value
         if self.target_obs is not None:         # the points live on the device from here on: (tensor, tol_m)
             self.target_obs = (self._target_points(self.target_obs[0]), self.target_obs[1])
+        self.field, self.deposit_fn = None, deposit_fn
+        if self.field_obs is not None:          # the env owns the field; keep, spread and iters are checked once, here
+            self._field_kw = dict(zip(('keep', 'spread', 'iters'), nat.check_field(*self.field_obs, field_keep, field_spread, field_iters)[3:]))
+            self.field = self.sim.new_field(*self.field_obs)
+            self._field_ones = torch.ones(self.num_envs, self.num_kilobots, self.field_obs[2], dtype=torch.float32, device=dev)
         # episodes of single envs
         if max_episode_steps is not None and not int(max_episode_steps) >= 1:
             raise ValueError('max_episode_steps must be at least 1 or None')
@@ -298,6 +319,8 @@ class BatchedKilobotsEnv(object):
         self.episode_returns.zero_()
         self.episode_steps.zero_()
         self.episode_index.zero_()
+        if self.field is not None:
+            self.field.zero_()
         self._steps = 0
         self._check_status('reset()')
         return self.sim.poses()
@@ -337,11 +360,13 @@ class BatchedKilobotsEnv(object):
                             episode=self.episode_index, objects=self._object_init, lights=self._light_init)
         self.episode_returns.masked_fill_(sel, 0.0)
         self.episode_steps.masked_fill_(sel, 0)
+        if self.field is not None:
+            self.field.masked_fill_(sel.view(-1, 1, 1, 1), 0.0)
         return self.sim.poses()
 
     def step(self, actions=None, light_action=None):
         """actions [E, N, 2] float32 tensor on the sim's device (None keeps the previous commands)."""
-        prev = self.sim.poses() if self.reward_fn is not None or self.done_fn is not None else None
+        prev = self.sim.poses() if self.reward_fn is not None or self.done_fn is not None or self.deposit_fn is not None else None
         self.sim.step(self.steps_per_action, actions=actions, light_action=light_action)
         obs = self.sim.poses()
         if self.reward_fn is not None:
@@ -372,6 +397,15 @@ class BatchedKilobotsEnv(object):
                     info.update(zip(option.keys, out))
                 else:       # (object_points of an env without objects returns the walls alone)
                     info[option.keys[-1]] = out
+        if self.field is not None:
+            amount = self._field_ones if self.deposit_fn is None else self.deposit_fn(prev, actions, obs)
+            if self._episodes and self.auto_reset:
+                # the envs that run on take the update; those that were just reset start from their zeroed planes, and their
+                # rows are read off them: two launches into one tensor, the masks stay on the device
+                rows = self.sim.field_step(self.field, amount, env_mask=~done, **self._field_kw)
+                info['field'] = self.sim.field_step(self.field, None, iters=0, env_mask=done, out=rows)
+            else:
+                info['field'] = self.sim.field_step(self.field, amount, **self._field_kw)
         return obs, reward, done, info
 
     def _stored(self, name, purpose=None):
@@ -411,6 +445,13 @@ class BatchedKilobotsEnv(object):
         [E, 2] float32) of the current poses for the coverage_obs=(width, height) the env was created with:
         KilobotSim.coverage."""
         return self._observe('coverage_obs')
+
+    def field_sense(self):
+        """sense [E, N, channels, 4] float32 of the current poses on env.field as it is, for the field_obs=(width, height[,
+        channels]) the env was created with: KilobotSim.field_step as a pure read (nothing is deposited, the field does not
+        change, the fourth word is 0)."""
+        self._stored('field_obs')
+        return self.sim.field_step(self.field, None, iters=0)
 
     def _target_points(self, points):
         """Parsed points ([K, 2] or [E, K, 2] float32 array) on the sim's device; ValueError if they do not fit the env."""

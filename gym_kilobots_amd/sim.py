@@ -483,6 +483,44 @@ class KilobotSim:
         self._call('kb_sense_coverage', width, height, ps, *map(_ptr, parts))
         return Coverage(*parts)
 
+    def new_field(self, width, height, channels=1):
+        """A pheromone field for field_step(): zeros [E, channels, height, width] float32 on the sim's device.  The caller owns
+        it; the sim keeps nothing of it."""
+        width, height, channels = nat.check_field(width, height, channels, 1.0, 0.0, 0)[:3]
+        return torch.zeros(self.num_envs, channels, height, width, dtype=torch.float32, device=self.device)
+
+    def field_step(self, field, amount=None, keep=1.0, spread=0.0, iters=1, env_mask=None, sense=True, out=None):
+        """One update of a pheromone field on the current poses, IN PLACE and in one launch (kb_field_step; no reference
+        counterpart): field [E, C, height, width] contiguous float32 on the sim's device (new_field) lies over the arena like
+        occupancy_grid(), row 0 at ymin and column 0 at xmin.  Deposit: kilobot i adds amount[e, i, c] to the cell it stands in
+        -- amount [E, N, C] or, with one channel, [E, N]; a fixed-point sum at 2^-16 of amounts clamped to +-16 that does not
+        depend on the order, NaN counts as 0; None deposits nothing.  Then `iters` times u' = keep * (u + spread * lap(u)) with
+        the 5-point Laplacian and zero-flux edges: keep in [0, 1] (1 = no decay) and spread in [0, 0.25], a number or one per
+        channel.  Then every kilobot reads the field at its cell: returns sense [E, N, C, 4] float32 = (value, gradient per
+        metre ahead, gradient per metre to the left, what the cell received in this call), or None with sense=False.
+        env_mask: [E] bool or uint8 on the sim's device; of the envs it does not select no byte of field or sense is written.
+        amount=None with iters=0 is a pure read that leaves field untouched.  out: the preallocated contiguous sense tensor."""
+        E, N = self.num_envs, self.num_bots
+        if not torch.is_tensor(field) or field.dim() != 4:
+            raise ValueError('field must be a contiguous float32 cuda tensor of shape (%d, channels, height, width)' % E)
+        C_, height, width = (int(s) for s in field.shape[1:])
+        width, height, C_, keep, spread, iters = nat.check_field(width, height, C_, keep, spread, iters)
+        pf = self._input(field, F32, (E, C_, height, width), 'field')
+        one = C_ == 1 and torch.is_tensor(amount) and amount.dim() == 2
+        pa = self._input(amount, F32, (E, N) if one else (E, N, C_), 'amount', optional=True)
+        pm = self._input(env_mask, MASK, (E,), 'env_mask', optional=True)
+        if sense:
+            out, = self._outputs(out, [((E, N, C_, 4), torch.float32, 'sense')], 'the sense tensor')
+            if out.data_ptr() % 16:
+                raise ValueError('out: sense must be 16-byte aligned')
+        elif out is not None:
+            raise ValueError('out given with sense=False')
+        elif amount is None and iters == 0:
+            raise ValueError('field_step: nothing to do (amount=None, iters=0 and sense=False)')
+        vec = C.c_float * C_
+        self._call('kb_field_step', width, height, C_, vec(*keep), vec(*spread), iters, pm, pa, pf, _ptr(out))
+        return out
+
     def targets(self, points_m, tol_m, bot_select=None, slot_select=None, index=True, rel=True, owner=True, dist=True, stats=True, out=None):
         """Kilobot-to-slot matching on the current poses (kb_sense_targets; no reference counterpart): the two-sided nearest
         query of shape formation between the kilobots of every env and the K points ("slots") of a target shape.  points_m:

@@ -521,6 +521,51 @@ int kb_sense_grid(kb_sim *sim, int gw, int gh, int planes, float *d_out, void *s
 int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int32_t *d_owner, float *d_dist, float *d_cell,
                       float *d_stats, void *stream);
 
+/* Pheromone fields: a grid of floats per env and channel that the kilobots write to and read from, and that diffuses and
+ * decays between the steps -- the medium of stigmergy (trails, "food" and "home" pheromones, area marking, quorum sensing by a
+ * decaying marker), as the augmented-reality Kilobot tables provide it.  The only sensing entry that carries state across
+ * steps: the state is d_field, a tensor the CALLER owns and that this call updates IN PLACE; nothing of it lives in the handle.
+ * No reference counterpart (the reference declares a SmoothGridLight and never implements it).  One launch; asynchronous on
+ * `stream`.  The grid is that of kb_sense_grid: gw x gh equal cells over the arena, row iy = 0 at ymin, column ix = 0 at xmin.
+ * Every operation below is one fp32 operation rounded on its own, nothing is contracted, divisions are correctly rounded.
+ * Per selected env and channel c, in this order:
+ *   Host constants: those of kb_sense_grid: (xmin, xmax, ymin, ymax) = kb_outline.arena;  icw = (float)gw / (xmax - xmin),
+ *     ich = (float)gh / (ymax - ymin);  and hicw = 0.5f * icw, hich = 0.5f * ich.
+ *   Cell of kilobot i: (ix, iy) exactly by the rule of kb_sense_grid (clamped to the edge cells, NaN to 0, truncation).
+ *   Deposit, only with d_amount != NULL:  a = d_amount[e][i][c];  t = a * 65536.0f;  q = 0 if t is NaN, otherwise
+ *     (int32) rint(clamp(t, -2^20, 2^20)), round half to even;  acc = the int32 sum of q over the kilobots of the cell
+ *     (1024 * 2^20 = 2^30: no overflow);  dep = (float)acc / 65536.0f (int -> float to nearest even, one division);
+ *     u = F + dep for EVERY cell of the plane F (a cell nobody stands in adds +0.0f).  No two floats of different kilobots are
+ *     ever added: the result does not depend on their order.  With d_amount == NULL no addition takes place at all, dep is
+ *     +0.0f and the bits of F pass through, a -0.0f included.
+ *   Iteration, n_iters times, each from the plane u of the one before:  W, E, S, N = the four neighbours of the cell (columns
+ *     ix - 1, ix + 1, rows iy - 1, iy + 1), one outside the grid replaced by the cell's own value (a zero-flux edge);
+ *     lap = ((W + E) + (S + N)) - 4.0f * u;  v = u + spread[c] * lap;  u' = keep[c] * v.
+ *     keep[c] in [0, 1], spread[c] in [0, 0.25]; NaN is rejected.
+ *   Sense, only with d_sense != NULL, on the final plane G at the kilobot's cell:  val = G[iy][ix];
+ *     dx = (G[iy][min(ix + 1, gw - 1)] - G[iy][max(ix - 1, 0)]) * hicw * 25.0f, evaluated left to right;  dy likewise along the
+ *     rows (iy + 1 above iy - 1) with hich;  (s, c) = the library's sine and cosine of theta_i;  the row is
+ *     (val, c * dx + s * dy, c * dy - s * dx, dep of the cell): the value, its gradient per metre ahead and to the left, and what
+ *     the cell received in this call.
+ * d_field  [num_envs][n_channels][gh][gw] float32, float aligned: read and, unless the call is a pure read, written.
+ * d_amount [num_envs][num_bots][n_channels] float32, or NULL.
+ * d_sense  [num_envs][num_bots][n_channels][4] float32, 16-byte aligned, or NULL.
+ * d_env_mask [num_envs] bytes, non-zero = selected, NULL = all (the convention of kb_step_envs).  Of an env that is not selected
+ *   no byte of d_field or d_sense is written.
+ * keep, spread: HOST arrays [n_channels], read before the call returns.
+ * With d_amount == NULL and n_iters == 0 the call is a pure read: d_field is not written at all.
+ * The field and the amounts are assumed finite, apart from a NaN amount, which counts as 0; with a field value that is not
+ * finite the result of that env and channel is unspecified (the call still ends and writes nothing else).
+ * 1 <= gw, gh <= KB_GRID_MAX_SIDE;  1 <= n_channels <= KB_FIELD_MAX_CHANNELS;  0 <= n_iters <= KB_FIELD_MAX_ITERS.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim;  gw, gh;  n_channels;  NULL keep / spread or a
+ * value out of range;  n_iters;  NULL d_field;  nothing to do (d_amount and d_sense NULL with n_iters == 0);  a d_sense that is
+ * not 16-byte aligned.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, theta, d_amount and d_env_mask; writes d_field and d_sense only, and no bound buffer. */
+#define KB_FIELD_MAX_CHANNELS 4
+#define KB_FIELD_MAX_ITERS    64
+int kb_field_step(kb_sim *sim, int gw, int gh, int n_channels, const float *keep, const float *spread, int n_iters,
+                  const uint8_t *d_env_mask, const float *d_amount, float *d_field, float *d_sense, void *stream);
+
 /* Kilobot-to-slot matching on the CURRENT poses, without stepping: the two-sided nearest-neighbour query of shape formation
  * between the kilobots of an env and the K points ("slots") of a target shape -- for every kilobot the nearest slot in its own
  * frame, for every slot the nearest kilobot (which slots are still free), whether a kilobot holds the slot it is nearest to,

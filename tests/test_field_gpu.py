@@ -1,0 +1,309 @@
+"""kb_field_step on the GPU against the numpy restatement of its definition (tests/field_ref.py), whose cells are those of
+tests/grid_ref.py and whose arena comes from kb_get_outline alone.
+
+Everything is compared for equality of the bit patterns: every operation of the definition is one fp32 operation rounded on
+its own and the deposit is an integer sum, on the device and in the restatement.  No tolerances."""
+import numpy as np
+import pytest
+import torch
+
+from tests import field_ref as ref
+from tests import objects_ref
+from tests import scenes
+from tests.sensing_common import make_sim, state
+from tests.test_parity_gpu import cpu, dev
+
+pytestmark = pytest.mark.gpu
+
+NAN = float('nan')
+# one cell; a single row and a single column (every cell on two edges); odd sizes on the scalar path; 64 x 48 on the 16-byte
+# path with 8 cells per lane; 127 x 95 scalar with 24 per lane; the largest plane, 32 per lane and all of the dynamic LDS
+GRIDS = [(1, 1), (1, 5), (5, 1), (3, 2), (7, 5), (64, 48), (127, 95), (128, 128)]
+SHAPES = [(5, 1), (2, 7), (3, 333), (2, 1024)]
+ITERS = [0, 1, 2, 7]
+KEEP, SPREAD = {1: (0.95,), 3: (1.0, 0.9, 0.5)}, {1: (0.2,), 3: (0.25, 0.1, 0.0)}
+# every grid with the largest N, every N on 7 x 5 and 127 x 95; iterations and channel counts take turns
+CASES = [(gw, gh, 2, 1024, ITERS[k % 4], (1, 3)[k % 2]) for k, (gw, gh) in enumerate(GRIDS)]
+CASES += [(gw, gh, E, N, ITERS[(k + j + 1) % 4], (3, 1)[(k + j) % 2]) for j, (gw, gh) in enumerate(((7, 5), (127, 95))) for k, (E, N) in enumerate(SHAPES[:3])]
+
+
+def f32(v):
+    return np.asarray(v, dtype=np.float32)
+
+
+def start_plane(E, C, gh, gw, seed):
+    """Random and nowhere zero, of both signs: a plane that was not read shows up."""
+    rng = np.random.RandomState(seed)
+    return f32(rng.uniform(0.25, 1.5, (E, C, gh, gw)) * rng.choice([-1.0, 1.0], (E, C, gh, gw)))
+
+
+def amounts(E, N, C, seed):
+    """In [-2, 2] with zeros, a NaN and one beyond the clamp among them."""
+    am = f32(np.random.RandomState(seed).uniform(-2.0, 2.0, (E, N, C)))
+    am.reshape(-1)[::5] = 0.0
+    am[0, 0, 0] = NAN
+    am[E - 1, N - 1, C - 1] = 17.0
+    return am
+
+
+def same(t, w):
+    return np.array_equal(ref.bits(cpu(t)), ref.bits(w))
+
+
+def check(g, F, am, keep, spread, iters, what='', env_mask=None, sense=True, field=None, tab=None):
+    """One call on a device copy of F (or in place on `field`) against the restatement on the state of the sim; returns (the
+    field tensor, the rows tensor, the restated plane)."""
+    tab = objects_ref.tables(g.outline()) if tab is None else tab
+    wG, wR = ref.restate(tab, F, *state(g), am, keep, spread, iters, None if env_mask is None else cpu(env_mask), sense)
+    field = dev(F) if field is None else field
+    rows = g.field_step(field, None if am is None else dev(am), keep, spread, iters, env_mask, sense)
+    torch.cuda.synchronize()
+    d = ref.bits(cpu(field)) != ref.bits(wG)
+    print('%s E=%d N=%d %s iters %d: %d of %d field words differ' % (what, g.num_envs, g.num_bots, F.shape[1:], iters, int(d.sum()), d.size))
+    assert not d.any(), (what, np.argwhere(d)[:5])
+    if sense:
+        assert rows.dtype == torch.float32 and tuple(rows.shape) == wR.shape and rows.is_contiguous()
+        d = ref.bits(cpu(rows)) != ref.bits(wR)
+        assert not d.any(), (what, 'sense', np.argwhere(d)[:5])
+    else:
+        assert rows is None
+    return field, rows, wG
+
+
+@pytest.mark.parametrize('gw,gh,E,N,iters,C', CASES)
+def test_field_equals_the_restatement(gw, gh, E, N, iters, C):
+    xy, th = scenes.gaussian_spawn(E, N, sigma=0.3, seed=E * N + gw)
+    g = make_sim(E, N, xy, th)
+    F, am = start_plane(E, C, gh, gw, gw * gh + N), amounts(E, N, C, N + iters)
+    field, rows, wG = check(g, F, am, KEEP[C], SPREAD[C], iters, 'deposit')
+    assert (rows[..., 3] != 0).any()
+    # the same tensor again, in place and without a deposit: the fourth word is +0.0f
+    _, rows, _ = check(g, wG, None, KEEP[C], SPREAD[C], max(iters, 1), 'no deposit', field=field)
+    assert not rows[..., 3].view(torch.int32).any()
+    check(g, wG, am[..., 0] if C == 1 else am, KEEP[C][0], SPREAD[C][0], iters, 'scalars, no sense', sense=False)
+
+
+def constructed_positions():
+    """The special points of test_grid_gpu.test_constructed_cases on a 50 x 75 grid (cells of 1 x 0.5 world units, exact
+    constants): interior boundaries, the walls, outside the arena, a NaN x -- (x, y, expected (ix, iy))."""
+    return [(-25.0 + 7.0, 3.3, (7, 44)), (-3.25, -18.75 + 11.0, (21, 22)), (-25.0 + 30.0, -18.75 + 5.5, (30, 11)),
+            (-25.0, 1.3, (0, 40)), (25.0, 1.3, (49, 40)), (2.5, -18.75, (27, 0)), (2.5, 18.75, (27, 74)),
+            (-26.0, -1.3, (0, 34)), (27.5, -1.3, (49, 34)), (-2.5, -20.0, (22, 0)), (-2.5, 40.0, (22, 74)), (26.0, 20.0, (49, 74)),
+            (-1e9, -1e9, (0, 0)), (NAN, 5.1, (0, 47)), (10.25, 10.1, (35, 57)), (10.75, 10.2, (35, 57))]
+
+
+def place(g, x, y, th):
+    g.x.copy_(dev(f32(x)))
+    g.y.copy_(dev(f32(y)))
+    g.theta.copy_(dev(f32(th)))
+
+
+def test_constructed_positions_use_the_cell_rule_of_the_grid():
+    N, gw, gh = 64, 50, 75
+    g = make_sim(1, N)
+    tab = objects_ref.tables(g.outline())
+    cases = constructed_positions()
+    rng = np.random.RandomState(5)
+    k = len(cases)
+    x = np.concatenate([[c[0] for c in cases], rng.uniform(-20.0, -10.0, N - k)])
+    y = np.concatenate([[c[1] for c in cases], rng.uniform(-15.0, -5.0, N - k)])
+    place(g, x[None], y[None], rng.uniform(-np.pi, np.pi, (1, N)))
+    ix, iy = ref.grid_ref.cells(tab, gw, gh, f32(x), f32(y))
+    assert [(a, b) for a, b in zip(ix[:k], iy[:k])] == [c[2] for c in cases]
+    am = np.ones((1, N), np.float32)
+    F = np.zeros((1, 1, gh, gw), np.float32)
+    _, rows, wG = check(g, F, am, 1.0, 0.0, 0, 'constructed', tab=tab)
+    assert wG[0, 0, 57, 35] == 2.0 and all(wG[0, 0, c[2][1], c[2][0]] == 1.0 for c in cases[:k - 2]) and wG.sum() == N
+    assert cpu(rows)[0, :k, 0, 3].tolist() == [1.0] * (k - 2) + [2.0, 2.0]
+    check(g, start_plane(1, 1, gh, gw, 2), am, 0.9, 0.2, 3, 'constructed, iterated', tab=tab)
+    for gw2, gh2 in ((7, 5), (128, 128)):       # the same kilobots on grids whose constants are rounded
+        check(g, start_plane(1, 2, gh2, gw2, 3), amounts(1, N, 2, 4), (1.0, 0.8), (0.25, 0.05), 2, 'constructed', tab=tab)
+
+
+@pytest.mark.parametrize('gw,gh', [(7, 5), (64, 48)])
+def test_corner_and_edge_cells_take_one_sided_differences(gw, gh):
+    """A kilobot in every corner cell and in the middle of every edge, one inside: where a neighbour is missing the cell
+    itself stands in, in the iteration and in the gradient."""
+    g = make_sim(2, 9)
+    tab = objects_ref.tables(g.outline())
+    xmin, ymin, cw, ch, _, _ = ref.grid_ref.constants(tab, gw, gh)
+    cells = [(0, 0), (gw - 1, 0), (0, gh - 1), (gw - 1, gh - 1), (gw // 2, 0), (gw // 2, gh - 1), (0, gh // 2), (gw - 1, gh // 2), (gw // 2, gh // 2)]
+    x = f32([xmin + (ix + 0.5) * cw for ix, _ in cells])
+    y = f32([ymin + (iy + 0.5) * ch for _, iy in cells])
+    th = np.random.RandomState(1).uniform(-np.pi, np.pi, (2, 9))
+    place(g, np.stack([x, x[::-1]]), np.stack([y, y[::-1]]), th)
+    ix, iy = ref.grid_ref.cells(tab, gw, gh, x, y)
+    assert list(zip(ix.tolist(), iy.tolist())) == cells
+    F = start_plane(2, 2, gh, gw, 9)
+    for iters in (0, 1, 3):
+        _, rows, _ = check(g, F, amounts(2, 9, 2, 6), (1.0, 0.7), (0.25, 0.125), iters, 'edges', tab=tab)
+        assert (rows[..., 1:3] != 0).any()
+
+
+def test_all_kilobots_of_an_env_in_one_cell():
+    """1024 adds of 2^20 on one LDS word serialise and reach 2^30 exactly, while a second env is spread out."""
+    E, N, gw, gh = 2, 1024, 128, 128
+    xy, th = scenes.gaussian_spawn(E, N, sigma=0.3, seed=77)
+    xy[0] = np.array([0.1333, -0.0871]) + np.random.RandomState(2).uniform(-0.002, 0.002, size=(N, 2))
+    g = make_sim(E, N, xy, th)
+    am = amounts(E, N, 1, 8)
+    am[0] = 16.0
+    _, rows, wG = check(g, np.zeros((E, 1, gh, gw), np.float32), am, 1.0, 0.0, 0, 'one cell')
+    assert wG[0].max() == 16384.0 and (wG[0] != 0).sum() == 1 and (cpu(rows)[0, :, 0, 3] == 16384.0).all() and (cpu(rows)[0, :, 0, 0] == 16384.0).all()
+    check(g, start_plane(E, 1, gh, gw, 5), am, 0.99, 0.25, 2, 'one cell, iterated')
+
+
+def test_five_calls_in_place_and_a_pure_read():
+    E, N, gw, gh, C = 3, 333, 64, 48, 2
+    xy, th = scenes.gaussian_spawn(E, N, sigma=0.25, seed=12)
+    g = make_sim(E, N, xy, th)
+    tab = objects_ref.tables(g.outline())
+    am, keep, spread = amounts(E, N, C, 13), (0.97, 1.0), (0.2, 0.25)
+    w = start_plane(E, C, gh, gw, 14)
+    field = dev(w)
+    for k in range(5):
+        w = check(g, w, am, keep, spread, 2, 'call %d' % k, field=field, tab=tab)[2]
+    # a pure read: every bit stays, planted -0.0f cells included, and the rows are those of the last plane
+    field[:, :, 3, 5] = -0.0
+    field[0, 1, 0, 0] = -0.0
+    kept = field.clone()
+    assert int((kept.view(torch.int32) == -2 ** 31).sum()) == E * C + 1
+    _, rows, _ = check(g, cpu(kept), None, 1.0, 0.0, 0, 'pure read', field=field, tab=tab)
+    assert torch.equal(field.view(torch.int32), kept.view(torch.int32))
+    x, y, _ = state(g)
+    ix, iy = ref.grid_ref.cells(tab, gw, gh, x[0], y[0])
+    assert np.array_equal(ref.bits(cpu(rows)[0, :, 1, 0]), ref.bits(cpu(kept)[0, 1, iy, ix])) and not rows[..., 3].view(torch.int32).any()
+    # keep and spread are nothing to a pure read
+    again = g.field_step(field, None, 0.5, 0.25, 0)
+    assert torch.equal(again.view(torch.int32), rows.view(torch.int32)) and torch.equal(field.view(torch.int32), kept.view(torch.int32))
+
+
+@pytest.mark.parametrize('gw,gh,C', [(7, 5, 3), (64, 48, 2)])
+def test_env_mask(gw, gh, C):
+    """First env, last env, none and all selected: the planes and rows of the others keep a 0x5A fill byte for byte, the
+    selected ones equal the unmasked call."""
+    E, N = 4, 77
+    xy, th = scenes.gaussian_spawn(E, N, sigma=0.3, seed=21)
+    g = make_sim(E, N, xy, th)
+    F, am = start_plane(E, C, gh, gw, 22), dev(amounts(E, N, C, 23))
+    keep, spread = KEEP[3][:C], SPREAD[3][:C]
+    full = dev(F)
+    full_rows = g.field_step(full, am, keep, spread, 3)
+    for envs in ([0], [E - 1], [], list(range(E)), [1, 2]):
+        rest = torch.tensor([e for e in range(E) if e not in envs], dtype=torch.long, device='cuda')
+        chosen = torch.tensor(envs, dtype=torch.long, device='cuda')
+        for dtype in (torch.bool, torch.uint8):
+            mask = torch.zeros(E, dtype=dtype, device='cuda')
+            mask[chosen] = True if dtype == torch.bool else 3
+            field = dev(F)
+            field[rest] = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device='cuda').view(torch.float32)
+            rows = torch.full((E, N, C, 4), 0x5A5A5A5A, dtype=torch.int32, device='cuda').view(torch.float32)
+            got = g.field_step(field, am, keep, spread, 3, env_mask=mask, out=rows)
+            torch.cuda.synchronize()
+            assert got.data_ptr() == rows.data_ptr()
+            assert bool((field[rest].view(torch.uint8) == 0x5A).all()) and bool((rows[rest].view(torch.uint8) == 0x5A).all()), chosen
+            assert torch.equal(field[chosen].view(torch.int32), full[chosen].view(torch.int32)), chosen
+            assert torch.equal(rows[chosen].view(torch.int32), full_rows[chosen].view(torch.int32)), chosen
+
+
+def test_arguments_streams_and_untouched_state():
+    E, N, gw, gh, C = 3, 64, 64, 48, 2
+    xy, th = scenes.gaussian_spawn(E, N, sigma=0.3, seed=31)
+    g = make_sim(E, N, xy, th)
+    F, am = start_plane(E, C, gh, gw, 32), amounts(E, N, C, 33)
+    fields = ('x', 'y', 'theta', 'v', 'w', 'status', 'ws_cnt', 'ws_key', 'ws_acc')
+    torch.cuda.synchronize()
+    kept = {f: getattr(g, f).clone() for f in fields}
+    field, rows, wG = check(g, F, am, (1.0, 0.9), (0.25, 0.1), 4, 'aligned')
+    for f in fields:        # no state tensor of the sim changes
+        assert torch.equal(kept[f].view(torch.uint8), getattr(g, f).view(torch.uint8)), f
+    # a field view that is only float aligned takes the scalar path and gives the same bits
+    buf = torch.zeros(F.size + 1, device='cuda')
+    odd = buf[1:].view(E, C, gh, gw)
+    odd.copy_(dev(F))
+    assert odd.data_ptr() % 16 == 4 and odd.is_contiguous()
+    odd_rows = g.field_step(odd, dev(am), (1.0, 0.9), (0.25, 0.1), 4)
+    assert torch.equal(odd.view(torch.int32), field.view(torch.int32)) and torch.equal(odd_rows.view(torch.int32), rows.view(torch.int32))
+    assert float(buf[0]) == 0.0
+    # a side stream gives the default stream's answer
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    fs = dev(F)
+    with torch.cuda.stream(side):
+        rs = g.field_step(fs, dev(am), (1.0, 0.9), (0.25, 0.1), 4)
+    side.synchronize()
+    assert torch.equal(fs.view(torch.int32), field.view(torch.int32)) and torch.equal(rs.view(torch.int32), rows.view(torch.int32))
+    # out= is the tensor that comes back; one channel takes amounts [E, N]
+    out = torch.full((E, N, C, 4), NAN, device='cuda')
+    got = g.field_step(dev(F), dev(am), (1.0, 0.9), (0.25, 0.1), 4, out=out)
+    assert got.data_ptr() == out.data_ptr() and same(out, cpu(rows))
+    one = g.new_field(gw, gh)
+    assert tuple(one.shape) == (E, 1, gh, gw) and one.dtype == torch.float32 and not one.any() and tuple(g.new_field(5, 3, 4).shape) == (E, 4, 3, 5)
+    assert tuple(g.field_step(one, torch.ones(E, N, device='cuda')).shape) == (E, N, 1, 4) and float(one.sum()) == E * N
+    assert g.field_step(one, torch.ones(E, N, 1, device='cuda'), sense=False) is None and float(one.sum()) == 2 * E * N
+    ok = dev(F)
+    bad_fields = (torch.zeros(E, C, gh, gw), torch.zeros(E, C, gh, gw, device='cuda', dtype=torch.float64), torch.zeros(E + 1, C, gh, gw, device='cuda'),
+                  torch.zeros(E, C, gw, gh, device='cuda').transpose(2, 3), torch.zeros(E, C, gh * gw, device='cuda'), torch.zeros(E, 5, gh, gw, device='cuda'),
+                  torch.zeros(E, C, 129, gw, device='cuda'), np.zeros((E, C, gh, gw), np.float32))
+    for bad in bad_fields:
+        with pytest.raises(ValueError):
+            g.field_step(bad, None)
+    for kw in (dict(amount=torch.ones(E, N, device='cuda')), dict(amount=torch.ones(E, N, C)), dict(amount=torch.ones(E, N, C, device='cuda', dtype=torch.float64)),
+               dict(amount=torch.ones(E, C, N, device='cuda').transpose(1, 2)), dict(out=torch.zeros(E, N, C, 4)), dict(out=torch.zeros(E, N, C, 3, device='cuda')),
+               dict(out=torch.zeros(E, N, C, 4, device='cuda', dtype=torch.float64)), dict(out=torch.zeros(E * N * C * 4 + 1, device='cuda')[1:].view(E, N, C, 4)),
+               dict(out=out, sense=False), dict(sense=False, iters=0), dict(keep=1.5), dict(spread=0.3), dict(keep=(1.0,)), dict(iters=65), dict(iters=-1),
+               dict(env_mask=torch.ones(E, device='cuda')), dict(env_mask=torch.ones(E + 1, dtype=torch.bool, device='cuda')), dict(env_mask=torch.ones(E, dtype=torch.bool))):
+        with pytest.raises(ValueError):
+            g.field_step(ok, **kw)
+    assert torch.equal(ok.view(torch.int32), dev(F).view(torch.int32))       # nothing was launched
+    for bad in ((0, 4), (4, 129), (4, 4, 5), (4, 4, 0)):
+        with pytest.raises(ValueError):
+            g.new_field(*bad)
+
+
+def test_batched_env_field_obs():
+    from gym_kilobots_amd.envs import BatchedKilobotsEnv
+    E, N, opt = 4, 64, (64, 48, 2)
+    kw = dict(field_keep=(0.9, 1.0), field_spread=(0.1, 0.25), field_iters=2)
+
+    def deposit(prev, actions, obs):
+        return (obs[..., :2] - prev[..., :2]).abs() * 50.0       # [E, N, 2]: what a kilobot moved along x and y
+    env = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12, field_obs=opt, deposit_fn=deposit, **kw)
+    plain = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12)
+    assert torch.equal(env.reset(), plain.reset()) and not env.field.any() and tuple(env.field.shape) == (E, 2, 48, 64)
+    for k in range(3):
+        a = dev(scenes.random_actions(E, N, seed=20 + k))
+        before, prev = env.field.clone(), env.sim.poses()
+        obs, rew, _, info = env.step(a)
+        pobs, prew, _, pinfo = plain.step(a)
+        assert pinfo == {} and torch.equal(obs, pobs) and torch.equal(rew, prew) and sorted(info) == ['field']
+        rows = env.sim.field_step(before, deposit(prev, a, obs), (0.9, 1.0), (0.1, 0.25), 2)
+        assert torch.equal(before.view(torch.int32), env.field.view(torch.int32)) and torch.equal(rows.view(torch.int32), info['field'].view(torch.int32))
+    assert bool(env.field.any())
+    kept = env.field.clone()
+    read = env.field_sense()
+    assert torch.equal(kept.view(torch.int32), env.field.view(torch.int32)) and torch.equal(read[..., :3], info['field'][..., :3]) and not read[..., 3].any()
+    env.reset()
+    assert not env.field.any()
+    with pytest.raises(ValueError):
+        plain.field_sense()
+    # episodes: env 1 ends after its first step, all after two; only the planes of an env that was reset are zero, and its
+    # rows are the pure read of the zeroed planes on the poses of the new episode
+    calls = []
+
+    def done_fn(prev, actions, obs):
+        calls.append(1)
+        return torch.tensor([False, len(calls) == 1, False, False], device=obs.device)
+    ep = BatchedKilobotsEnv(E, N, seed=3, spawn_std=0.12, field_obs=(64, 48), max_episode_steps=2, auto_reset=True, done_fn=done_fn)
+    ep.reset()
+    a = dev(scenes.random_actions(E, N, seed=30))
+    _, _, done, info = ep.step(a)
+    assert done.tolist() == [False, True, False, False]
+    assert not ep.field[1].any() and all(float(ep.field[e].sum()) == N for e in (0, 2, 3))
+    # (zero by value: a product with a negative cosine is -0.0f)
+    assert not info['field'][1].any() and bool((info['field'][[0, 2, 3], :, 0, 3] >= 1).all())
+    assert torch.equal(ep.field_sense()[1].view(torch.int32), info['field'][1].view(torch.int32))
+    _, _, done, info = ep.step(a)
+    assert done.tolist() == [True, False, True, True]
+    assert float(ep.field[1].sum()) == N and not ep.field[[0, 2, 3]].any() and not info['field'][[0, 2, 3]].any()
+    assert bool((info['field'][1, :, 0, 3] >= 1).all()) and torch.equal(ep.field_sense()[1, :, :, :3], info['field'][1, :, :, :3])
