@@ -232,6 +232,18 @@ __device__ __forceinline__ void kb_motor_law(int ml, int mr, float th, float h, 
 
 __device__ __forceinline__ float kb_clampf(float a, float lo, float hi) { return fmaxf(lo, fminf(a, hi)); }
 
+// ---- x/y pairs of the register solver (kb_regsolve_bins.inc) -----------------------------------
+// A two-float vector: component-wise *, + and - on it are v_pk_mul_f32 / v_pk_add_f32, which hold the vector pipe as long as
+// one v_mul_f32 (tools/pk_issue_probe.hip).  Every component is rounded exactly as by the scalar instruction, a
+// product and the sum behind it stay two operations (-ffp-contract=off, and no helper here fuses them), and a - b * c is the
+// subtraction of the rounded product: the same bits as the scalar sequence, signed zeros included.
+typedef float kb_pair __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ kb_pair pk_load(const float2 &p) { return kb_pair{p.x, p.y}; }      // from the float2 body arrays
+__device__ __forceinline__ float2 pk_store(const kb_pair v) { return make_float2(v.x, v.y); }  // ... and back
+__device__ __forceinline__ kb_pair pk_splat(const float s) { return kb_pair{s, s}; }
+__device__ __forceinline__ float pk_dot(const kb_pair a, const kb_pair b) { const kb_pair t = a * b; return t.x + t.y; }   // a.x * b.x + a.y * b.y
+__device__ __forceinline__ kb_pair pk_neg(const kb_pair a) { return -a; }
+
 // LDS operations of one wave execute in program order; this only stops the compiler from moving
 // LDS accesses across the point where other lanes' results are consumed.
 __device__ __forceinline__ void wave_sync() {

@@ -16,7 +16,8 @@
     // the kilobots: velocity (0, 0), inverse mass 0 -- the sweeps need no second code path for it);  staging index (12) |
     // depth (9) << 12 | flipped << 21 | island root << 22;  accumulated impulse;  normal
     unsigned ra[KRB], rb[KRB], rm[KRB];
-    float racc[KRB], rnx[KRB], rny[KRB];
+    float racc[KRB];
+    kb_pair rn[KRB];       // (x, y) in one aligned register pair: the rounds below work on pairs, see kb_common.h
     const unsigned WOFF = 8u * (unsigned)(NB - 5);
     char *const velB = reinterpret_cast<char *>(vel), *const posB = reinterpret_cast<char *>(pos);
 #define RB_WALL(j) (ra[j] >= WOFF)
@@ -28,7 +29,7 @@
 #define RB_FLIP(j) (((rm[j] >> 21) & 1u) != 0u)
 #define RB_ISL(j) ((int)(rm[j] >> 22))
 #pragma unroll
-    for (int j = 0; j < KRB; ++j) { ra[j] = 0u; rb[j] = 0u; rm[j] = 0u; racc[j] = 0.0f; rnx[j] = 1.0f; rny[j] = 0.0f; }
+    for (int j = 0; j < KRB; ++j) { ra[j] = 0u; rb[j] = 0u; rm[j] = 0u; racc[j] = 0.0f; rn[j] = kb_pair{1.0f, 0.0f}; }
     unsigned long long slotLevels[KRB];
     int dlo[KRB], dhi[KRB];         // levels of the slot's contacts (wave-uniform)
 #pragma unroll
@@ -239,7 +240,8 @@
                     pa_[j] = pos[a >= WALL_CODE ? b : a]; pb_[j] = pos[b]; root_[j] = parent[b];
                 }
                 bool pairOn[KRB];
-                float dx[KRB], dy[KRB], dd[KRB], wnx[KRB], wny[KRB];
+                kb_pair d_[KRB];
+                float dd[KRB], wnx[KRB], wny[KRB];
                 bool ieee = false;
 #pragma unroll
                 for (int j = 0; j < KRB; ++j) {
@@ -253,11 +255,11 @@
                     float dist;
                     wall_geom(ca, wallA ? a - WALL_CODE : 0, pb_[j].x, pb_[j].y, dist, wnx[j], wny[j]);
                     if (flip) { wnx[j] = -wnx[j]; wny[j] = -wny[j]; }
-                    dx[j] = pb_[j].x - pa_[j].x; dy[j] = pb_[j].y - pa_[j].y;
-                    dd[j] = dx[j] * dx[j] + dy[j] * dy[j];
+                    d_[j] = pk_load(pb_[j]) - pk_load(pa_[j]);
+                    dd[j] = pk_dot(d_[j], d_[j]);
                     pairOn[j] = v_[j] && !wallA && dd[j] > B2_EPSILON * B2_EPSILON;
                     ieee = ieee || (pairOn[j] && !kb_exact_guard(dd[j]));
-                    if (wallA) { rnx[j] = wnx[j]; rny[j] = wny[j]; } else { rnx[j] = 1.0f; rny[j] = 0.0f; }
+                    rn[j] = wallA ? kb_pair{wnx[j], wny[j]} : kb_pair{1.0f, 0.0f};
                 }
                 // the IEEE sequences of sqrtf and the division are two dozen dependent instructions; with every pair of the wave
                 // inside the proven range one correction step on the hardware seeds gives the same bits (kb_exact.h)
@@ -266,14 +268,14 @@
                     for (int j = 0; j < KRB; ++j) {
                         const float len = kb_sqrt_refine(dd[j], __builtin_amdgcn_sqrtf(dd[j]), __builtin_amdgcn_rsqf(dd[j]));
                         const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
-                        if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                        if (pairOn[j]) rn[j] = d_[j] * pk_splat(inv);
                     }
                 } else {
 #pragma unroll
                     for (int j = 0; j < KRB; ++j) {
                         const float len = sqrtf(dd[j]);
                         const float inv = 1.0f / len;
-                        if (pairOn[j]) { rnx[j] = dx[j] * inv; rny[j] = dy[j] * inv; }
+                        if (pairOn[j]) rn[j] = d_[j] * pk_splat(inv);
                     }
                 }
             }
@@ -316,19 +318,19 @@
                 float dist, wnx, wny;
                 wall_geom(ca, wallA ? a - WALL_CODE : 0, pb_.x, pb_.y, dist, wnx, wny);
                 if (flip) { wnx = -wnx; wny = -wny; }
-                const float dx = pb_.x - pa_.x, dy = pb_.y - pa_.y;
-                const float dd = dx * dx + dy * dy;
+                const kb_pair d_ = pk_load(pb_) - pk_load(pa_);
+                const float dd = pk_dot(d_, d_);
                 const bool pairOn = v_ && !wallA && dd > B2_EPSILON * B2_EPSILON;
-                if (wallA) { rnx[0] = wnx; rny[0] = wny; } else { rnx[0] = 1.0f; rny[0] = 0.0f; }
+                rn[0] = wallA ? kb_pair{wnx, wny} : kb_pair{1.0f, 0.0f};
                 // (one correction step on the hardware seeds where every pair of the wave is inside the proven range: kb_exact.h)
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(pairOn && !kb_exact_guard(dd)) == 0ull, 1)) {
                     const float len = kb_sqrt_refine(dd, __builtin_amdgcn_sqrtf(dd), __builtin_amdgcn_rsqf(dd));
                     const float inv = kb_rcp_refine(len, __builtin_amdgcn_rcpf(len));
-                    if (pairOn) { rnx[0] = dx * inv; rny[0] = dy * inv; }
+                    if (pairOn) rn[0] = d_ * pk_splat(inv);
                 } else {
                     const float len = sqrtf(dd);
                     const float inv = 1.0f / len;
-                    if (pairOn) { rnx[0] = dx * inv; rny[0] = dy * inv; }
+                    if (pairOn) rn[0] = d_ * pk_splat(inv);
                 }
             }
             wave_sync();   // bkMaxRank of this wave
@@ -346,9 +348,9 @@
                 char *const bdB = reinterpret_cast<char *>(islCnt);     // bodyDepth: zeroed before the contacts were grouped
 #define RB_BD(off) (*reinterpret_cast<unsigned *>(bdB + (off)))
                 const unsigned ib4 = rb[0] >> 1, ia4 = wallA ? ib4 : ra[0] >> 1;       // (a wall has no depth: max(d, d) + 1)
-                const float Px = racc[0] * rnx[0], Py = racc[0] * rny[0];
+                const kb_pair P = pk_splat(racc[0]) * rn[0];
                 const float ima = wallA ? 0.0f : ca.im_bot;
-                const float dax = ima * Px, day = ima * Py, dbx = ca.im_bot * Px, dby = ca.im_bot * Py;
+                const kb_pair da = pk_splat(ima) * P, db = pk_splat(ca.im_bot) * P;
                 const unsigned mrow = bkMaxRank[wave * NUM_CLS + min((int)lane, NUM_CLS - 1)];
                 unsigned depth_ = 0;
                 for (unsigned long long m_ = keymask; m_; m_ &= m_ - 1) {
@@ -357,9 +359,9 @@
                         if (rc == code_) {
                             const unsigned d = max(RB_BD(ia4), RB_BD(ib4)) + 1u;
                             if (KB_SETUP_FUSED >= 2) {
-                                const float2 va = RB_VEL(ra[0]), vb = RB_VEL(rb[0]);
-                                RB_VEL(ra[0]) = make_float2(va.x - dax, va.y - day);
-                                RB_VEL(rb[0]) = make_float2(vb.x + dbx, vb.y + dby);
+                                const kb_pair va = pk_load(RB_VEL(ra[0])), vb = pk_load(RB_VEL(rb[0]));
+                                RB_VEL(ra[0]) = pk_store(va - da);
+                                RB_VEL(rb[0]) = pk_store(vb + db);
                             }
                             depth_ = d;
                             RB_BD(ib4) = d;
@@ -412,11 +414,11 @@
             for (int j = 0; j < KRB; ++j) {
                 for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
                     if (RB_ON(j)) {
-                        const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
-                        const float Px = racc[j] * rnx[j], Py = racc[j] * rny[j];
+                        const kb_pair va = pk_load(RB_VEL(ra[j])), vb = pk_load(RB_VEL(rb[j]));
+                        const kb_pair P = pk_splat(racc[j]) * rn[j];
                         const float ima = RB_WALL(j) ? 0.0f : ca.im_bot;
-                        RB_VEL(ra[j]) = make_float2(va.x - ima * Px, va.y - ima * Py);
-                        RB_VEL(rb[j]) = make_float2(vb.x + ca.im_bot * Px, vb.y + ca.im_bot * Py);
+                        RB_VEL(ra[j]) = pk_store(va - pk_splat(ima) * P);
+                        RB_VEL(rb[j]) = pk_store(vb + pk_splat(ca.im_bot) * P);
                     }
                     wave_sync();
                 }
@@ -433,20 +435,21 @@
             for (int j = 0; j < KRB; ++j) {
                 for (int d_ = dlo[j]; d_ <= dhi[j]; ++d_) {
                     if (RB_ON(j)) {
-                        const float2 va = RB_VEL(ra[j]), vb = RB_VEL(rb[j]);
+                        // (every line on a pair is one packed instruction for both components; the order of operations of each
+                        //  component is the scalar one: dv . n as two products and their sum, v -+ im * (lambda * n))
+                        const kb_pair va = pk_load(RB_VEL(ra[j])), vb = pk_load(RB_VEL(rb[j]));
                         const bool wallA = RB_WALL(j);
-                        const float nx = rnx[j], ny = rny[j];
+                        const kb_pair n = rn[j];
                         const float ima = wallA ? 0.0f : ca.im_bot, imb = ca.im_bot;
-                        const float dvx = vb.x - va.x, dvy = vb.y - va.y;
-                        const float vn = dvx * nx + dvy * ny;
+                        const float vn = pk_dot(vb - va, n);
                         float lambda = -((wallA ? nm_wb : nm_bb) * vn);
                         const float accOld = racc[j];
                         const float newimp = fmaxf(accOld + lambda, 0.0f);
                         lambda = newimp - accOld;
                         racc[j] = newimp;
-                        const float Px = lambda * nx, Py = lambda * ny;
-                        RB_VEL(ra[j]) = make_float2(va.x - ima * Px, va.y - ima * Py);
-                        RB_VEL(rb[j]) = make_float2(vb.x + imb * Px, vb.y + imb * Py);
+                        const kb_pair P = pk_splat(lambda) * n;
+                        RB_VEL(ra[j]) = pk_store(va - pk_splat(ima) * P);
+                        RB_VEL(rb[j]) = pk_store(vb + pk_splat(imb) * P);
                     }
                     wave_sync();
                 }
@@ -480,15 +483,16 @@
         // one body: the pose at the start of the substep (continuous step), the clamped velocity and the new position;
         // off8 = byte offset of the body inside the float2 arrays
         auto integrate_xy = [&](const unsigned off8, const float2 v0, const float2 p0) __attribute__((always_inline)) {
-            float vxx = v0.x, vyy = v0.y;
+            kb_pair v = pk_load(v0);
             *reinterpret_cast<float *>(sxB + (off8 >> 1)) = p0.x; *reinterpret_cast<float *>(syB + (off8 >> 1)) = p0.y;
-            const float tx = h * vxx, ty = h * vyy;
-            if (tx * tx + ty * ty > B2_MAX_TRANSLATION_SQ) {
-                const float ratio = B2_MAX_TRANSLATION / sqrtf(tx * tx + ty * ty);
-                vxx *= ratio; vyy *= ratio;
+            const kb_pair t = pk_splat(h) * v;
+            const float tt = pk_dot(t, t);
+            if (tt > B2_MAX_TRANSLATION_SQ) {
+                const float ratio = B2_MAX_TRANSLATION / sqrtf(tt);
+                v = v * pk_splat(ratio);
             }
-            RB_POS(off8) = make_float2(p0.x + h * vxx, p0.y + h * vyy);
-            RB_VEL(off8) = make_float2(vxx, vyy);
+            RB_POS(off8) = pk_store(pk_load(p0) + pk_splat(h) * v);
+            RB_VEL(off8) = pk_store(v);
         };
         // Who integrates: the depths of both bodies of both slots and the owner thread's marker bits are read before anything
         // is written -- startY lies over bodyDepth, and a lane may look at a body whose last contact another lane holds.
@@ -556,6 +560,9 @@
     KB_ABLATE_EXIT(12);    // impulses stored, positions integrated
     // SolvePositionConstraints; an island stops once its minSeparation >= -3 slop.  The island flags are read once per
     // iteration; depth levels without an active contact in this wave are skipped altogether.
+    // (The round stays component by component: on pairs it issued fewer instructions and took wave 0 5 % longer -- its
+    //  chain runs through the refinements of kb_exact.h, and a packed result costs the instruction behind it a wait state --
+    //  and the launch 0.3 % more: profiles/r14_ab_bench.txt.)
     if (solving) {
         for (int it = 0; it < posIters; ++it) {
             unsigned char *act = active + (it & 1) * NB, *nxt = active + ((it + 1) & 1) * NB;

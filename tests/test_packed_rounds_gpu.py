@@ -1,0 +1,41 @@
+"""The rounds of the register solver on x/y pairs (kb_regsolve_bins.inc, kb_common.h: kb_pair) on the device against the
+oracle, on the cases of tests/packed_round_scenes.py: after each of six single substeps and one fused launch of ten, every
+state field and the packed warm-start list (ws_cnt, ws_key, ws_acc) bit for bit, status 0 on both sides.  The scenes of 1024
+kilobots must run the fixed-size instantiations, the one of 200 a generic sorted-bin kernel of two waves
+(tests/test_packed_rounds_cpu.py shows on the oracle that every case has the lanes it is there for)."""
+import pytest
+
+from oracle import oracle as O
+from tests import packed_round_scenes as PR
+from tests import solver_regimes as SR
+from tests import variant_census as VC
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope='module')
+def variants(tmp_path_factory):
+    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
+    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
+    return listed
+
+
+@pytest.mark.parametrize('case', PR.CASES, ids=PR.case_id)
+def test_packed_rounds_are_bit_exact(case, variants):
+    from tests.test_parity_gpu import assert_same, assert_ws_same, cpu, dev
+    from gym_kilobots_amd.sim import KilobotSim
+    name, sleep, toi = case
+    N, xy, th, actions, _ = PR.start(name)
+    gsim = KilobotSim(xy.shape[0], N, O.DRIVE_VELOCITY, O.LIGHT_NONE, debug_outputs=True, **PR.config_kw(sleep, toi))
+    drive, light, obj, fn, tier, poly, vsense, vsleep = variants[gsim.variant_index]
+    assert (obj, vsleep) == (0, sleep) and (vsense == 0 or fn == 0), variants[gsim.variant_index]
+    assert fn == (1024 if N == 1024 else 0), 'the handle runs instantiation %s' % (variants[gsim.variant_index],)
+    assert gsim.block_threads // SR.LANES == (8 if N == 1024 else 2)
+    gsim.set_poses_m(xy, th)
+    for k, (n, (snap, _, _, _)) in enumerate(zip(PR.launches(), PR.reference(case))):
+        gsim.step(n, actions=dev(actions(k)))
+        what = '%s launch %d (%d substeps)' % (PR.case_id(case), k, n)
+        assert_same(snap, gsim, what, PR.fields_of(sleep))
+        assert_ws_same(snap, gsim, what)
+        assert int(snap.status.max()) == 0 and int(cpu(gsim.status).max()) == 0, what
+    gsim.close()
