@@ -125,6 +125,7 @@ SIGNATURES = {
     'kb_histogram_sectors': (_I, [_I, _P]),
     'kb_sense_reduce': (_I, [_P, _F, _I, _I, _F, _P, _P, _P, _P]),
     'kb_sense_hops': (_I, [_P, _F, _P, _I, _P, _P, _P, _P, _P]),
+    'kb_sense_clusters': (_I, [_P, _F, _P, _P, _P, _P, _P, _P]),
     'kb_get_outline': (_I, [_P, C.POINTER(KbOutline)]),
     'kb_sense_objects': (_I, [_P, _P, _P, _P]),
     'kb_grid_channels': (_I, [_P, _I]),
@@ -160,7 +161,7 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 # an older build of the library that KB_HIP_LIB selects for an A/B (tools/ab_bench.py) has not got these: it loads, and calling
 # one of them on it raises AttributeError
-OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds'}
+OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds', 'kb_sense_clusters'}
 
 _lib = None
 

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage, kb_sense_targets, kb_field_step) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage, kb_sense_targets, kb_field_step) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -847,6 +847,18 @@ int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_ho
     const SenseRange r = sense_range(p, radius_m);
     const int lim = max_hops < p.N - 1 ? max_hops : p.N - 1;       // no path has more than N - 1 edges: the level loop's bound
     return launch("kb_sense_hops", kb_hops_kernel, p.E, 256, HopsLds(p.NP, p.ncell).bytes, stream, p, r.reach, r.R2, lim, d_seed, d_hops, d_parent, d_root, d_stats);
+}
+
+int kb_sense_clusters(kb_sim *sim, float radius_m, const uint8_t *d_select, int32_t *d_label, int32_t *d_size, float *d_cluster, int32_t *d_stats,
+                      void *stream) {
+    if (!sim || !d_label) return fail(KB_EINVAL, "kb_sense_clusters: NULL argument");
+    if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_clusters: radius must be positive");
+    if (!aligned16(d_cluster)) return fail(KB_EINVAL, "kb_sense_clusters: d_cluster must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_clusters: kb_bind() first");
+    const Params &p = sim->p;
+    const SenseRange r = sense_range(p, radius_m);
+    return launch("kb_sense_clusters", kb_clusters_kernel, p.E, 256, ClustersLds(p.NP, p.ncell).bytes, stream, p, r.reach, r.R2, d_select, d_label, d_size,
+                  reinterpret_cast<float4 *>(d_cluster), d_stats);
 }
 
 int kb_ray_directions(int n_rays, float *xy) {

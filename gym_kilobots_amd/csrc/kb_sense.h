@@ -1,5 +1,5 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
-// kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_coverage): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
+// kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_targets, which meets
 // the slots of a target shape, every kilobot against every slot, and needs none either; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
@@ -1415,6 +1415,179 @@ __global__ void __launch_bounds__(256) kb_hops_kernel(const Params p, const int 
     if (d_stats && tid == 0) {
         d_stats[2 * e] = reached;
         d_stats[2 * e + 1] = deepest;
+    }
+}
+
+// ---- kb_sense_clusters: the connected components of the IR-range graph ------------------------------------------------------------
+#ifndef KB_CLUSTERS_PAIRS
+#define KB_CLUSTERS_PAIRS 2             // which of the pairs a kilobot meets it unions (the relation is symmetric): 0: all of its full stencil, i.e. every pair twice; 1: those of its full stencil with a lower index; 2: it walks only the rows of its stencil from its own upwards and takes the kilobots above it (A/B knob)
+#endif
+constexpr int CLUSTERS_PAIRS = KB_CLUSTERS_PAIRS;
+static_assert(CLUSTERS_PAIRS >= 0 && CLUSTERS_PAIRS <= 2, "kb_clusters_kernel: pairs");
+struct ClustersLds : CellListsLds {     // byte offsets: pos (float2) at 0, parent (u32), sx, sy (i64), cnt (u32), dmax (u32), label (u16), red[4] (u32), the cell lists
+    int parent, sx, sy, cnt, dmax, label, red, bytes;
+    __host__ __device__ constexpr ClustersLds(int NP, int ncell)
+        : CellListsLds(38 * NP + 16, NP, ncell), parent(8 * NP), sx(12 * NP), sy(20 * NP), cnt(28 * NP), dmax(32 * NP), label(36 * NP), red(38 * NP), bytes(head + 2 * ncell + 16) {}
+};
+KB_LDS_PINNED(clusters_lds, ClustersLds(NP, nc),
+              L.parent == 8 * NP && L.sx == 12 * NP && L.sy == 20 * NP && L.cnt == 28 * NP && L.dmax == 32 * NP && L.label == 36 * NP && L.red == 38 * NP &&
+              L.nextb == 38 * NP + 16 && L.cellOf == 40 * NP + 16 && L.head == 42 * NP + 16 && L.bytes == 42 * NP + 16 + 2 * nc + 16);
+// the largest image (1024 kilobots, every cell) stays under the default limit for dynamic LDS: no attribute to raise; a size and a
+// label share the key of the largest component
+static_assert(ClustersLds(KB_MAX_BOTS, MAX_CELLS).bytes <= 64 * 1024 && KB_MAX_BOTS <= 1024, "kb_clusters_kernel: LDS image");
+
+// The root of x in the forest parent[], halving the path on the way (a kilobot on the path is handed to its grandparent).  Every
+// word obeys parent[i] <= i, and the walk goes on only to a strictly smaller index: it ends within N steps whatever the other
+// lanes do meanwhile.  Halving writes only words that are no roots (parent[x] != x was seen, and a kilobot that has been hooked
+// never becomes a root again) and writes an ancestor of x: whoever reads the word, before or after, stays on x's path to its root.
+__device__ __forceinline__ unsigned kb_cluster_find(unsigned *parent, unsigned x) {
+    for (;;) {
+        const unsigned par = lds_load_relaxed(&parent[x]);
+        if (par == x) return x;
+        const unsigned g = lds_load_relaxed(&parent[par]);
+        if (g == par) return par;
+        *reinterpret_cast<volatile unsigned *>(&parent[x]) = g;
+        x = g;
+    }
+}
+
+// The connected components of the IR-range graph on the current poses (kb_sense_clusters): one workgroup per env, the poses and
+// the cell lists of the SELECTED kilobots in LDS (kb_build_cell_lists_of: a kilobot that is not selected is a NaN pose that no
+// chain holds, and nobody meets it), and a union-find forest parent[] over them, one word per kilobot.
+//  HOOKING.  One stencil walk per selected kilobot a.  The relation is symmetric bit for bit, so every in-range pair needs to be
+//   unioned once only: a walks the rows of its stencil from its own row upwards (kb_walk_rows_in_range; cell rows are monotone in
+//   y, clamped or not, so every b with y_b >= y_a lies there) and takes b iff (ey, ex, b - a) is positive in this order -- of the
+//   two kilobots of a pair exactly one takes the other (CLUSTERS_PAIRS).  The union climbs from an ancestor of a
+//   (the root it found last) and from b, a step of each per LDS round trip, as in the step kernel's label pass: the same word
+//   on both sides is a common ancestor, nothing to do -- in a swarm that hangs together that is the first round trip of most
+//   pairs --; two different roots, and the LARGER one goes under the smaller by atomicCAS(&parent[hi], hi, lo).  Invariants:
+//   parent[i] <= i always (a word starts as i and only ever receives a smaller index of its own tree), and the root of a tree is
+//   the lowest index in it (true of single kilobots; the tree that results from a hook has the smaller of the two roots).  When
+//   all pairs are unioned a tree is a component, and its root the component's lowest index -- whichever lane hooked first
+//   and whatever order the chains had.  After its walk a kilobot that is no root is handed to the last root it saw (an ancestor).
+//  WHY EVERY LOOP ENDS.  No lane ever waits for another: there is no lock and no flag.  A climb goes on only to a strictly
+//   smaller index on at least one side.  The exchange fails only if parent[hi] was no longer hi, i.e. another lane HAS hooked hi
+//   in between; a kilobot is hooked at most once in a launch (it is no root afterwards), so all failures of all lanes together
+//   number less than N, and a lane retries at most that often.  A chain of the cell lists holds a kilobot at most once
+//   (kb_build_cell_lists_of).
+//  LABELS.  After a barrier nothing hooks any more: label[b] = find(b), -1 for a kilobot that is not selected.
+//  SIZES, TABLE, STATS (each only if its output was given: uniform branches).  Every selected kilobot adds 1, and with the table
+//   its quantised x and y, to the accumulators of its root by LDS atomics whose result is not used -- integers, so any order gives the
+//   same bits.  After a second barrier every member forms the centroid of its component from the sums (the same bits in every member)
+//   and raises the root's dmax to the bits of its own d2 (atomicMax: d2 >= 0, the order of the bits is the order of the values);
+//   the roots are counted through the waves into red[], the largest by one atomicMax per wave on size << 10 | (1023 - label), which
+//   orders by size and then by the LOWER label.  After a third barrier the rows and the stats go out.  Every output word is
+//   written exactly once, by a plain store.
+__global__ void __launch_bounds__(256) kb_clusters_kernel(const Params p, const int s, const float R2, const unsigned char *d_select, int *d_label,
+                                                          int *d_size, float4 *d_cluster, int *d_stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, N = p.N;
+    const ClustersLds L(p.NP, p.ncell);
+    const CellLists cells = L.view(smem);
+    unsigned *parent = reinterpret_cast<unsigned *>(smem + L.parent);
+    unsigned long long *sx = reinterpret_cast<unsigned long long *>(smem + L.sx);
+    unsigned long long *sy = reinterpret_cast<unsigned long long *>(smem + L.sy);
+    unsigned *cnt = reinterpret_cast<unsigned *>(smem + L.cnt);
+    unsigned *dmax = reinterpret_cast<unsigned *>(smem + L.dmax);
+    unsigned short *label = reinterpret_cast<unsigned short *>(smem + L.label);
+    unsigned *red = reinterpret_cast<unsigned *>(smem + L.red);      // components, components of one, the key of the largest
+    const size_t o = (size_t)e * N;
+    const bool sizes = d_size || d_cluster || d_stats;       // (uniform)
+    for (int b = tid; b < N; b += nt) {
+        parent[b] = (unsigned)b;
+        if (sizes) cnt[b] = 0u;
+        if (d_cluster) { sx[b] = 0ull; sy[b] = 0ull; dmax[b] = 0u; }
+    }
+    if (tid < 4) red[tid] = 0u;
+    kb_build_cell_lists_of(p, o, cells, tid, nt, [&](int b) { return !d_select || d_select[o + b] != 0; });
+    for (int a = tid; a < N; a += nt) {
+        const int cell = cells.cellOf[a];
+        if (cell == (int)EMPTY16) continue;     // not selected
+        unsigned ra = (unsigned)a;      // an ancestor of a: where the next climb of a starts
+        const auto hook = [&](unsigned b, float ex, float ey, float) {
+            if (CLUSTERS_PAIRS == 1 && b > (unsigned)a) return;
+            if (CLUSTERS_PAIRS == 2 && !(ey > 0.0f || (ey == 0.0f && (ex > 0.0f || (ex == 0.0f && b > (unsigned)a))))) return;
+            unsigned rb = b;
+            for (;;) {
+                const unsigned ta = lds_load_relaxed(&parent[ra]), tb = lds_load_relaxed(&parent[rb]);
+                if (ta == tb) { ra = ta; break; }       // a common ancestor
+                if (ta != ra || tb != rb) { ra = ta; rb = tb; continue; }
+                const unsigned hi = max(ra, rb), lo = min(ra, rb);
+                if (atomicCAS(&parent[hi], hi, lo) == hi) { ra = lo; break; }
+            }
+        };
+        const float2 pa = cells.pos[a];
+        if (CLUSTERS_PAIRS == 2) {
+            const int cy = cell / p.gw;
+            kb_walk_rows_in_range<KB_MAX_BOTS>(p, cells, a, cell, pa, s, R2, cy - max(cy - s, 0), hook);
+        } else {
+            kb_walk_in_range(p, cells, a, cell, pa, s, R2, hook);
+        }
+        if (ra != (unsigned)a) *reinterpret_cast<volatile unsigned *>(&parent[a]) = ra;
+    }
+    __syncthreads();
+    for (int b = tid; b < N; b += nt) {
+        const bool sel = cells.cellOf[b] != EMPTY16;
+        const unsigned r = sel ? kb_cluster_find(parent, (unsigned)b) : 0xFFFFu;
+        label[b] = (unsigned short)r;
+        d_label[o + b] = sel ? (int)r : -1;
+        if (sel && sizes) atomicAdd(&cnt[r], 1u);
+        if (sel && d_cluster) {
+            const float2 pb = cells.pos[b];
+            const long long qx = (long long)rintf(fmaxf(fminf(pb.x * 65536.0f, 0x1p40f), -0x1p40f));
+            const long long qy = (long long)rintf(fmaxf(fminf(pb.y * 65536.0f, 0x1p40f), -0x1p40f));
+            atomicAdd(&sx[r], (unsigned long long)qx);
+            atomicAdd(&sy[r], (unsigned long long)qy);
+        }
+    }
+    if (!sizes) return;     // (uniform)
+    __syncthreads();
+    unsigned comps = 0u, ones = 0u, key = 0u;
+    for (int b = tid; b < N; b += nt) {
+        const unsigned r = label[b];
+        const bool sel = r != 0xFFFFu;
+        const unsigned n = sel ? cnt[r] : 0u;
+        if (d_size) d_size[o + b] = (int)n;
+        if (sel && d_cluster) {
+            const float cxw = ((float)(long long)sx[r] / (float)n) / 65536.0f, cyw = ((float)(long long)sy[r] / (float)n) / 65536.0f;
+            const float2 pb = cells.pos[b];
+            const float ex = pb.x - cxw, ey = pb.y - cyw;
+            atomicMax(&dmax[r], __float_as_uint(ex * ex + ey * ey));
+        }
+        if (sel && r == (unsigned)b) {
+            comps++;
+            ones += n == 1u ? 1u : 0u;
+            key = max(key, n << 10 | (1023u - r));
+        }
+    }
+    if (d_stats) {
+        for (int off = 32; off > 0; off >>= 1) {
+            comps += __shfl_down(comps, off);
+            ones += __shfl_down(ones, off);
+            key = max(key, __shfl_down(key, off));
+        }
+        if ((tid & 63) == 0) { atomicAdd(&red[0], comps); atomicAdd(&red[1], ones); atomicMax(&red[2], key); }
+    }
+    if (!d_cluster && !d_stats) return;     // (uniform)
+    __syncthreads();
+    if (d_cluster) {
+        for (int b = tid; b < N; b += nt) {
+            float4 row = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (label[b] == (unsigned short)b) {        // a root: the row of the component whose label is b
+                const float n = (float)cnt[b];
+                const float cxw = ((float)(long long)sx[b] / n) / 65536.0f, cyw = ((float)(long long)sy[b] / n) / 65536.0f;
+                row = make_float4(n, cxw / WORLD_SCALE, cyw / WORLD_SCALE, sqrtf(__uint_as_float(dmax[b])) / WORLD_SCALE);
+            }
+            d_cluster[o + b] = row;
+        }
+    }
+    if (d_stats && tid == 0) {
+        const unsigned k = red[2];
+        int *st = d_stats + 4 * (size_t)e;
+        st[0] = (int)red[0];
+        st[1] = (int)(k >> 10);
+        st[2] = k ? (int)(1023u - (k & 1023u)) : -1;
+        st[3] = (int)red[1];
     }
 }
 

@@ -124,8 +124,8 @@ class BatchedKilobotsEnv(object):
         distance and bearing in the kilobot's own frame (KilobotSim.neighbor_histogram): neighbor_histogram() returns it,
         step() puts it in its info dict under 'neighbor_histogram'.  Independent of neighbor_obs; None adds nothing.
         comm_radius: the IR range in metres over which neighbor_reduce(values) aggregates what the kilobots broadcast
-        (KilobotSim.neighbor_reduce) and over which hops(seeds) forms hop-count gradients (KilobotSim.hops).  reset() and
-        step() do not change with it.
+        (KilobotSim.neighbor_reduce) and over which hops(seeds) forms hop-count gradients (KilobotSim.hops) and clusters() labels the
+        connected components (KilobotSim.clusters).  reset() and step() do not change with it.
         object_obs: True adds what a kilobot sees of the objects and the walls: object_points() returns the nearest point of
         every object and of the arena walls in every kilobot's own frame (KilobotSim.object_points), and step() puts them in
         its info dict under 'objects' (envs with objects only) and 'walls'.  None (or False): nothing is added.
@@ -510,6 +510,12 @@ class BatchedKilobotsEnv(object):
         comm_radius the env was created with: KilobotSim.hops."""
         radius_m = self._stored('comm_radius', 'form hop-count gradients')
         return self.sim.hops(seeds, radius_m, max_hops=max_hops, parent=parent, root=root, stats=stats)
+
+    def clusters(self, select=None, size=False, table=False, stats=False):
+        """The connected components of the kilobots (those of `select`, [E, N] bool or uint8 on the device; None: all) over the
+        comm_radius the env was created with: KilobotSim.clusters."""
+        radius_m = self._stored('comm_radius', 'label connected components')
+        return self.sim.clusters(radius_m, select=select, size=size, table=table, stats=stats)
 
     def gather_episode_returns(self, dist=None):
         """Per-env returns of every rank's shard in global env order (the only collective)."""

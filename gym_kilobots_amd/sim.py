@@ -405,6 +405,32 @@ class KilobotSim:
         self._call('kb_sense_hops', radius_m, ps, min(int(max_hops), nat.HOPS_UNLIMITED), *(next(given).data_ptr() if w else None for w in wanted))
         return tuple(out) if len(out) > 1 else out[0]
 
+    def clusters(self, radius_m, select=None, size=False, table=False, stats=False, out=None):
+        """Connected components of the IR-range graph on the current poses (kb_sense_clusters; no reference counterpart):
+        which kilobots hang together through edges of at most radius_m, centre to centre, by one union-find per env in one
+        launch.  Returns label [E, N] int32: the LOWEST index of the kilobot's component.  select: [E, N] bool or uint8 on the
+        sim's device, the kilobots that are in the graph (None: all); one that is not has label -1 and connects nothing.
+        size=True adds size [E, N] int32, the kilobots in the component (0 where label is -1); table=True table [E, N, 4]
+        float32, row r = (size, centroid x, centroid y, distance of the farthest member from the centroid), metres in the world
+        frame, of the component whose label is r and zeros in every other row -- a kilobot's own row is table[e, label] --, from
+        fixed-point sums at 2^-16 world units that do not depend on the order; stats=True stats [E, 4] int32 = (components, size
+        of the largest, its label with ties to the lowest and -1 without a kilobot, components of one).  stats[:, 1] / N is the
+        aggregation metric.  With any of them the result is the tuple (label, size, table, stats) of the ones asked for.  out:
+        the preallocated contiguous tensor(s) to write into, in the shape of the result; every element is written."""
+        E, N = self.num_envs, self.num_bots
+        radius_m = nat.check_radius(radius_m)
+        ps = self._input(select, MASK, (E, N), 'select', optional=True)
+        wanted = [True, bool(size), bool(table), bool(stats)]
+        shapes = [s for s, w in zip([((E, N), torch.int32, 'label'), ((E, N), torch.int32, 'size'), ((E, N, 4), torch.float32, 'table'),
+                                     ((E, 4), torch.int32, 'stats')], wanted) if w]
+        out = list(self._outputs(out, shapes, 'the label tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
+        given = iter(out)
+        parts = [next(given) if w else None for w in wanted]
+        if parts[2] is not None and parts[2].data_ptr() % 16:
+            raise ValueError('out: table must be 16-byte aligned')
+        self._call('kb_sense_clusters', radius_m, ps, *map(_ptr, parts))
+        return tuple(out) if len(out) > 1 else out[0]
+
     def outline(self):
         """The geometry object_points() reads (kb_get_outline) as a KbOutline: the arena bounds and the fixtures grouped by
         body in stable order -- the order that decides ties -- in world units."""

@@ -397,6 +397,42 @@ int kb_sense_reduce(kb_sim *sim, float radius_m, int op, int n_channels, float s
 int kb_sense_hops(kb_sim *sim, float radius_m, const uint8_t *d_seed, int max_hops, int32_t *d_hops, int32_t *d_parent,
                   int32_t *d_root, int32_t *d_stats, void *stream);
 
+/* Connected components of the IR-range graph on the CURRENT poses, without stepping: which kilobots hang together, in how
+ * many groups, and how large the largest one is -- "largest cluster / num_bots" is the aggregation metric of the swarm
+ * literature -- settled by one union-find per env in ONE launch, where kb_sense_hops needs a seed per component and a sweep
+ * over kb_sense_edges needs as many rounds as the graph's diameter.  Every env is labelled independently.  No reference
+ * counterpart.  Labels, sizes and stats are integers; the float arithmetic is the predicate and the table:
+ *   Nodes: the kilobots b of the env with d_select[e][b] != 0 (bytes, the convention of d_seed; a bool tensor works as it
+ *     stands); NULL: all of them.  A kilobot that is not selected is not in the graph: it connects nothing.
+ *   Edges: as kb_sense and kb_sense_hops -- Rw = radius_m * 25, R2 = Rw * Rw (on the host);  ex = x_j - x_i, ey = y_j - y_i,
+ *     d2 = ex * ex + ey * ey (each one fp32 operation rounded on its own);  nodes i and j are joined iff j != i && !(d2 > R2).
+ *     The relation is symmetric bit for bit.  Poses are assumed finite, as everywhere else.
+ * d_label   [num_envs][num_bots] int32, required: for a node the LOWEST index of its connected component, -1 for a kilobot
+ *           that is not selected.  Nothing else decides it: not the order of the cell lists and not the order in which the
+ *           kernel joins the pairs.
+ * d_size    [num_envs][num_bots] int32 or NULL: the number of nodes in the kilobot's component; 0 for one that is not selected.
+ * d_cluster [num_envs][num_bots][4] float32, 16-byte aligned, or NULL: row r of env e describes the component whose label is r;
+ *           every other row is four +0.0f.  A kilobot finds the row of its component at d_cluster[e][label].  With n the
+ *           number of members:
+ *     q = (int64) rint(max(min(v * 65536.0f, 0x1p40f), -0x1p40f)), round half to even, for each member coordinate v (x or y);
+ *     SX, SY = the int64 sums of q over the members;
+ *     cxw = ((float)SX / (float)n) / 65536.0f, cyw likewise (int64 -> float to nearest even, correctly rounded divisions);
+ *     per member:  ex = x_b - cxw, ey = y_b - cyw, d2 = ex * ex + ey * ey;  D = the largest d2 of a member (the maximum of
+ *     the bit patterns);
+ *     the row is ((float)n, cxw / 25.0f, cyw / 25.0f, sqrt(D) / 25.0f): the size, the centroid in metres in the world frame, the
+ *     distance of the farthest member from it in metres.  Exact on the quantised values and independent of any order.
+ * d_stats   [num_envs][4] int32 or NULL: word 0 the number of components; word 1 the size of the largest, 0 without a node;
+ *           word 2 the label of the largest, ties to the LOWEST label, -1 without a node; word 3 the number of components of
+ *           size 1 (isolated kilobots).  stats[1] / num_bots is the aggregation metric; stats[0] == 1 says: connected.
+ * Each optional output may be NULL and is then not computed; every element of every output given is written on every call, by
+ * a plain store (nothing needs clearing beforehand).  The result of an env does not depend on the other envs: a shard
+ * reproduces its rows.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_label;  radius_m not > 0;  a d_cluster
+ * that is not 16-byte aligned.  Then KB_ENOTBOUND.  A radius beyond the arena is fine (the reach clamps to the grid).
+ * Reads x, y and d_select; writes the outputs only.  One launch.  Asynchronous on `stream`. */
+int kb_sense_clusters(kb_sim *sim, float radius_m, const uint8_t *d_select, int32_t *d_label, int32_t *d_size, float *d_cluster,
+                      int32_t *d_stats, void *stream);
+
 /* Object and wall points on the CURRENT poses, without stepping: for every kilobot i and every pushable object m of its env
  * the nearest point of the object's outline in the body frame of i, and the nearest point of the arena walls -- what a
  * decentralised policy sees of the thing it pushes and of what confines it.  Rows are fixed-size, one per object, in object
