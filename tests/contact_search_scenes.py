@@ -22,6 +22,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from tests import scenes
+from tests.scenes import scene_id  # noqa: F401
 
 CELL = 0.035                    # kb_abi.hip: CELL_SIZE of the 2 x 1.5 m arena, origin at its lower left corner
 XMIN, YMIN = -1.0, -0.75
@@ -66,10 +67,6 @@ SCENES = [
 ]
 E = 2
 SEEDS = (1, 2, 3)               # seed s: planted, then s single-substep launches
-
-
-def scene_id(s):
-    return s.name
 
 
 def planted_bots(s):

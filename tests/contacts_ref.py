@@ -2,12 +2,13 @@
 store (ws_cnt, ws_key, ws_acc).  Plain loops over the packed list, python sorting, no code shared with the kernel."""
 import numpy as np
 
+from tests import objects_ref
+
 KEY_WALL, KEY_OBJ = 0x10000, 0x20000
 WALL_PUBLIC = (0, 2, 1, 3)      # store: xmin ymin xmax ymax -> public (kb_sense_objects): xmin xmax ymin ymax
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+bits = objects_ref.bits
 
 
 def quant(acc, scale):

@@ -4,17 +4,12 @@ select): float32 [E, N] in world units and radians as the state tensors hold the
 import numpy as np
 
 from tests import scenes
+from tests.scenes import world
 from tests.sensing_common import wall_scene
 
 f32 = np.float32
 DENSE_GRIDS = [(16, 12), (64, 48), (128, 128)]      # of dense(): cells wider than the lattice, where most kilobots own nothing, and narrower
 TIE_GRID = (50, 75)         # on the default arena of 50 x 37.5 world units: cw = 1, ch = 0.5 exactly
-
-
-def world(xy_m, th):
-    """Metres to the state tensors, as KilobotSim.set_poses_m converts."""
-    xy = np.asarray(xy_m, np.float64) * 25.0
-    return xy[..., 0].astype(np.float32), xy[..., 1].astype(np.float32), np.asarray(th, np.float32)
 
 
 def ties():

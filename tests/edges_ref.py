@@ -6,14 +6,10 @@ are stale."""
 import numpy as np
 
 from oracle import oracle as O
+from tests import objects_ref
+from tests.scenes import world  # noqa: F401
 
 W = np.float32(25)
-
-
-def world(xy_m, th):
-    """Poses in metres and radians as KilobotSim.set_poses_m stores them: (x, y, th) float32, world units."""
-    xy = np.asarray(xy_m, np.float64) * 25.0
-    return xy[..., 0].astype(np.float32), xy[..., 1].astype(np.float32), np.asarray(th, np.float32)
 
 
 def in_range(x, y, R):
@@ -84,5 +80,4 @@ def contract(true, offsets, capacity, before):
     return src, dst, rel, owned
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+bits = objects_ref.bits

@@ -10,7 +10,7 @@ import numpy as np
 from oracle import oracle as O
 from tests import limits_model as LM
 from tests import scenes
-from tests.test_parity_gpu import OBJ_FIELDS, TRIANGLE
+from tests.gpu_common import OBJ_FIELDS
 
 DEFAULT_SEEDS = 40
 LAUNCHES = 12
@@ -32,7 +32,7 @@ def _random_objects(rng):
         elif kind == 'box':
             fixtures.append((O.SHAPE_BOX, [[float(rng.uniform(0.03, 0.09)) * 25.0, float(rng.uniform(0.03, 0.09)) * 25.0]], 0.0, b))
         elif kind == 'tri':
-            fixtures.append((O.SHAPE_POLYGON, [[x * 25.0, y * 25.0] for x, y in TRIANGLE], 0.0, b))
+            fixtures.append((O.SHAPE_POLYGON, [[x * 25.0, y * 25.0] for x, y in scenes.TRIANGLE_M], 0.0, b))
         else:
             parts = 2 if kind == 'two' else 3
             w, h = float(rng.uniform(0.04, 0.07)), float(rng.uniform(0.02, 0.04))
@@ -55,7 +55,7 @@ def _random_objects(rng):
 
 def scene(seed):
     """Everything test_random_scene needs of seed `seed`:
-      E, N, mode, light, kw     arguments of tests.test_parity_gpu.make_pair / oracle.default_config
+      E, N, mode, light, kw     arguments of tests.gpu_common.make_pair / oracle.default_config
       xy, th                    kilobot poses
       objs, oth, ovx            object poses and their velocity at the start (None without objects)
       light_x                   None without a light

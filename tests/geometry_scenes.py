@@ -18,6 +18,7 @@ import numpy as np
 
 from oracle import oracle as O
 from tests import scenes
+from tests.scenes import put_numpy  # noqa: F401
 
 E = 2
 WORLD_SCALE, CELL_SIZE, MAX_CELLS = 25.0, 0.875, 8192         # kb_common.h
@@ -271,7 +272,7 @@ def start(g, seed=11):
 
 def scene(g, seed=11):
     """Everything a run of one row needs:
-      E, N, mode, kw         arguments of tests.test_parity_gpu.make_pair / oracle.default_config
+      E, N, mode, kw         arguments of tests.gpu_common.make_pair / oracle.default_config
       xy, th                 kilobot poses
       objects, ovel          object poses [E, M, 3] (metres, radians) and velocities (ovx, ovy, ow) [E, M] each, or None
       state                  {buffer name: array} written into both sims before the first substep (laws, motors)
@@ -310,10 +311,6 @@ def scene(g, seed=11):
     return s
 
 
-def put_numpy(sim, name, val):
-    getattr(sim, name)[...] = val
-
-
 def apply_start(s, sim, put):
     """Objects and start state of scene s into one sim (the kilobot poses are set before); put(sim, name, array) writes
     one buffer."""
@@ -336,6 +333,26 @@ def oracle_contacts(osim):
     """(kilobot-kilobot, wall, kilobot-fixture) contacts of the last substep, the least over the envs."""
     c = np.array([osim.count_contacts(e, True) for e in range(osim.cfg.num_envs)])
     return tuple(int(v) for v in c.min(0))
+
+
+def _sensing_rows():
+    """One row per (arena, radius, swarm size): those of up to 200 kilobots, and 1024 in the 1.6 x 1.2 m and 3.6 x 2.7 m arenas."""
+    seen, rows = set(), []
+    for g in GEOMETRY:
+        key = (g.W, g.H, g.r, g.N)
+        if key not in seen and (g.N <= 200 or (g.N == 1024 and g.W in (1.6, 3.6))):
+            rows.append(g)
+        seen.add(key)
+    return rows
+
+
+SENSING_ROWS = _sensing_rows()      # the rows that the sensing kernels are run on
+
+
+def sensing_radius(g, kind):
+    """metres"""
+    cell = g.cell / WORLD_SCALE
+    return {'half-cell': 0.5 * cell, 'cell-and-a-half': 1.5 * cell, 'arena': float(np.hypot(g.W, g.H))}[kind]
 
 
 # ---- the constants table -----------------------------------------------------------------------------------------------

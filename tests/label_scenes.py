@@ -31,6 +31,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from tests import scenes
+from tests.scenes import scene_id  # noqa: F401
 
 CELL = 0.035                    # kb_abi.hip: CELL_SIZE of the 2 x 1.5 m arena, origin at its lower left corner
 XMIN, YMIN = -1.0, -0.75
@@ -52,10 +53,6 @@ SCENES = [
     _S('chains-1024', 1024, -1, True, ('islands', 'walls')),
     _S('cluster-200', 200, 3, False, ('long lists', 'owner changes', 'islands')),      # (its cluster thins out below three per cell: no claim on its cells)
 ]
-
-
-def scene_id(s):
-    return s.name
 
 
 def hexagon(rings):

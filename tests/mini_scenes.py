@@ -33,6 +33,9 @@ def load_fixture():
     return scenes
 
 
+FIX = load_fixture()      # what the oracle test and the GPU test of the scenes parametrise over
+
+
 def _body_of(o):
     """The lib.body object of a scene object described by class (None for the plain circle / box descriptions)."""
     if o['shape'] in ('circle', 'box'):

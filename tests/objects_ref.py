@@ -8,6 +8,7 @@ and cosine): the quantity the float32 evaluation approximates.  The geometry com
 import numpy as np
 
 from oracle import oracle as O
+from tests import scenes
 
 
 def tables(ol):
@@ -139,7 +140,7 @@ def restate(tab, x, y, th, ox=None, oy=None, oth=None, ft=np.float32):
 # ---- the object sets of the tests, as kb_config keywords -------------------------------------------------------------------
 def fixtures_kw(num_objects, fixtures):
     """kb_config keywords for fixtures = [(kb_shape, vertices in world units or None, body, radius in metres)] in declaration
-    order (tests/test_parity_gpu.py::_compound_kw)."""
+    order (tests/scenes.py: compound_kw)."""
     return dict(num_objects=num_objects, num_fixtures=len(fixtures), obj_fixture_body=[f[2] for f in fixtures],
                 obj_shape=[f[0] for f in fixtures], obj_nverts=[0 if f[1] is None or f[0] == 1 else len(f[1]) for f in fixtures],
                 obj_radius=[f[3] for f in fixtures], obj_verts=[[[0.0, 0.0]] if f[1] is None else f[1] for f in fixtures])
@@ -156,9 +157,8 @@ QUAD = [[-2.0, -1.25], [2.0, -1.5], [1.5, 1.5], [-1.5, 1.25]]
 def forms_kw():
     """The reference's LForm (object 0), TForm (1), CForm (2) and a disc (3): 7 + 1 fixtures declared interleaved."""
     from gym_kilobots_amd.lib.body import TForm
-    from tests.test_parity_gpu import CFORM, LFORM, _reference_polygon_fixtures
-    lf, cf = _reference_polygon_fixtures(LFORM), _reference_polygon_fixtures(CFORM)
-    tf = _reference_polygon_fixtures(TForm._shape_vertices().tolist())
+    lf, cf = scenes.reference_polygon_fixtures(scenes.LFORM), scenes.reference_polygon_fixtures(scenes.CFORM)
+    tf = scenes.reference_polygon_fixtures(TForm._shape_vertices().tolist())
     return fixtures_kw(4, [(2, cf[0], 2, 0.0), (2, lf[0], 0, 0.0), (2, tf[0], 1, 0.0), (0, None, 3, 0.05), (2, cf[1], 2, 0.0),
                            (2, tf[1], 1, 0.0), (2, lf[1], 0, 0.0), (2, cf[2], 2, 0.0)])
 
@@ -193,3 +193,20 @@ def spawn_over_objects(E, N, centres_m, seed, sigma=0.06):
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# The rounding bound of the float32 evaluation against the same formulas in float64, derived, not observed.  u = 2^-24 is
+# the unit roundoff of one fp32 operation.  Coordinates are at most 32 world units, so |dx|, |dy| <= 64, the kilobot in the
+# object's frame and the vector to the nearest point are shorter than 128 =: L, and every vector of the chain
+# (d -> p -> w -> q -> r -> g -> rel x 25) is a length of at most L.  Each link costs a few operations, each of which errs by
+# at most u times the magnitude of its terms relative to the vector it produces: the projection q = a + t e is backward
+# stable (an error dt of t moves q by dt |e|, and dt |e| <= 3 u |w| + 2 u |e|; a clamp decision that differs between the two
+# evaluations does not matter, q being continuous in t), and so are the three rotations, the differences, the norm and the
+# final division.  Fewer than 40 roundings lie on the longest path (3 rotations of 6, the projection 11, the subtractions 6,
+# norm and divisions 5), so their sum is below 40 u L.  The library's sine and cosine are within 2 ulp of the exact ones,
+# 2^-22 absolute, and each of the three rotations multiplies two such errors with lengths of at most L: 6 x 2^-22 L.
+# Together (40 x 2^-24 + 6 x 2^-22) x 128 = 4.9e-4 world units = 1.95e-5 m.  One step is not covered by this: the direction
+# p / n of a disc amplifies the error of p by |g| / n, which exceeds 1 only within half a radius of the disc's centre (at the
+# centre every direction is equally near: a tie among all of them).  The kilobots placed inside the disc keep out of there.
+BOUND_WU = (40 * 2.0 ** -24 + 6 * 2.0 ** -22) * 128.0
+BOUND_M = BOUND_WU / 25.0

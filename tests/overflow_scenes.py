@@ -133,7 +133,7 @@ def row_id(r):
 
 
 def config_kw(r, ws_slots=None, solver_mode=0):
-    """Keywords of oracle.default_config / KilobotSim / tests.test_parity_gpu.make_pair (drive mode and light go by position)."""
+    """Keywords of oracle.default_config / KilobotSim / tests.gpu_common.make_pair (drive mode and light go by position)."""
     kw = dict(ws_slots=r.S if ws_slots is None else ws_slots, allow_sleep=r.allow_sleep, contact_capacity=r.capacity, solver_mode=solver_mode)
     if r.mode == O.DRIVE_MIXED:
         kw.update(mode_density=DENS)

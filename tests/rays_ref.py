@@ -11,6 +11,7 @@ import math
 import numpy as np
 
 from tests.objects_ref import sincos
+from tests.scenes import world  # noqa: F401
 
 BOTS, OBJECTS, WALLS = 1, 2, 4
 NONE = 1 << 40          # the code of "nothing hit" while the candidates are met: above every real code
@@ -167,12 +168,6 @@ def restate(tab, x, y, th, ox, oy, oth, radius_m, bot_radius_m, n_rays, targets,
 
 
 # ---- what the CPU and the GPU tests share of their scenes ----------------------------------------------------------------------
-def world(xy_m, th):
-    """Poses in metres and radians as KilobotSim.set_poses_m stores them: (x, y, th) float32, world units."""
-    xy = np.asarray(xy_m, np.float64) * 25.0
-    return xy[..., 0].astype(np.float32), xy[..., 1].astype(np.float32), np.asarray(th, np.float32)
-
-
 OBJECT_SCENE = dict(E=4, N=64, R=0.15, K=16)
 OBJECT_SEEDS = {'disc': 31, 'boxes': 32, 'mixed': 33, 'forms': 34}
 

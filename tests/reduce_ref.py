@@ -5,6 +5,8 @@ float32 arrays only where the definition rounds in fp32, so every operation roun
 unsigned keys of the bit patterns.  Comparisons with the device are by equality of the bit patterns."""
 import numpy as np
 
+from tests import objects_ref
+
 SUM, MIN, MAX = 0, 1, 2
 OPS = {'sum': SUM, 'min': MIN, 'max': MAX}
 CLAMP = np.float32(2.0 ** 21)
@@ -102,5 +104,4 @@ def breadth_first(inr, root=0):
     return hop
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+bits = objects_ref.bits

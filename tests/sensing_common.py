@@ -1,11 +1,13 @@
-"""What the tests of kb_sense_neighbors and kb_sense_histogram share: the scenes and the sweep of the GPU tests, and the
-reader of the code object's metadata of the CPU tests."""
+"""What the tests of every sensing kernel share and that needs neither torch nor a device to import: the scenes and the
+sweep of the GPU tests, the sim they run on, and the reader of the code object's metadata of the CPU tests.  What touches
+the device is in tests/gpu_common.py, the comparers against the restatements in tests/sensing_checks.py."""
 import os
 import re
 
 import numpy as np
 
 from gym_kilobots_amd import build as kb_build
+from tests import hops_ref
 from tests import scenes
 
 # (E, N, R): cfg2 / cfg3 slices, odd sizes, N = 1; R from one cell to the whole arena (test_sense_equals_brute_force_oracle).
@@ -43,11 +45,23 @@ def wall_scene(random_headings=False):
     return xy, rng.uniform(-np.pi, np.pi, size=(4, N)) if random_headings else np.zeros((4, N))
 
 
-def state(g):
-    import torch
-    from tests.test_parity_gpu import cpu
-    torch.cuda.synchronize()
-    return cpu(g.x), cpu(g.y), cpu(g.theta)
+def chain_scene():
+    """The serpentine chain, its indices permuted, in two envs; returns (xy [2, 1024, 2], position of every index in the chain)."""
+    pts = hops_ref.serpentine()
+    perm = np.random.RandomState(5).permutation(1024)      # index i sits at chain position perm[i]
+    return np.stack([pts[perm], pts[perm]]), perm
+
+
+def world_xy(xy):
+    return tuple((xy[:, k] * 25.0).astype(np.float32) for k in (0, 1))
+
+
+def cloud():
+    return world_xy(scenes.gaussian_spawn(1, 333, sigma=0.2, seed=4)[0][0])
+
+
+def f32(v):
+    return np.asarray(v, dtype=np.float32)
 
 
 def kernel_metadata(name_substring):

@@ -31,12 +31,14 @@ depth shows in what the oracle returns, so the rules are restated here from the 
 
 Shared by tests/test_setup_pass_cpu.py (every scene has its property on the oracle) and tests/test_setup_pass_gpu.py (every
 launch bit for bit against the oracle)."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
 
 from tests import label_scenes as LS
 from tests import scenes
+from tests.scenes import case_id, scene_id  # noqa: F401
 
 LANES, KREG_BINS, GIANT_ISLAND, RK = 64, 2, 256, 4      # kb_common.h, kb_launch.h
 WAVE_CONTACTS = LANES * KREG_BINS
@@ -75,17 +77,7 @@ SCENES = [
 WAVE_COUNTS_FIRST = [[64] * 8, [65] * 8, [128, 14, 71, 71, 71, 71, 71, 71]]      # 'wave-counts-1024', contacts per wave at launch 0
 
 
-def scene_id(s):
-    return s.name
-
-
-def cases():
-    """(scene, allow_sleep) of both test files"""
-    return [(s, sl) for s in SCENES for sl in (0, 1) if sl or not s.sleep_only]
-
-
-def case_id(c):
-    return '%s-%s' % (c[0].name, 'sleep' if c[1] else 'nosleep')
+cases = functools.partial(scenes.sleep_cases, SCENES)      # (scene, allow_sleep) of both test files
 
 
 # ---- planted structures (metres) -----------------------------------------------------------------------------------------

@@ -26,6 +26,7 @@ import numpy as np
 
 from oracle import oracle as O
 from tests import scenes
+from tests.scenes import scene_id  # noqa: F401
 
 LANES = 64
 KREG_BINS = 2               # kb_common.h: KB_KREG_BINS, contacts a lane of the register solver holds
@@ -82,10 +83,6 @@ REPLICA_SCENE = SCENES[6]       # the CU-filling replicas: R3 in every substep
 REPLICA_ENVS = 4                # distinct envs that are tiled
 R0_MIN_CONTACTS = 64            # an R0 scene must reach this many contacts (more than one per lane), not rest at none
 FUSED_SUBSTEPS = 10
-
-
-def scene_id(s):
-    return s.name
 
 
 def config_kw(s, allow_sleep):

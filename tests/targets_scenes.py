@@ -8,18 +8,13 @@ import collections
 import numpy as np
 
 from tests import scenes
+from tests.scenes import world
 from tests.sensing_common import wall_scene
 
 f32 = np.float32
 Scene = collections.namedtuple('Scene', ('x', 'y', 'th', 'points', 'tol', 'bsel', 'ssel'))
 ODD_SIZES = [(1, 1), (7, 5), (5, 7), (333, 129), (64, 1024), (1024, 3)]
 SHARING_SIZES = [(64, 65), (65, 64), (128, 129), (129, 128), (300, 100)]      # of coarse(): around the sizes at which a side is shared out among the waves
-
-
-def world(xy_m, th):
-    """Metres to the state tensors, as KilobotSim.set_poses_m converts."""
-    xy = np.asarray(xy_m, np.float64) * 25.0
-    return xy[..., 0].astype(np.float32), xy[..., 1].astype(np.float32), np.asarray(th, np.float32)
 
 
 def headings(seed, shape):

@@ -1,22 +1,15 @@
 """C-ABI checks that need no GPU: the library builds, loads and exports every symbol that
 include/kilobots_hip.h declares; host-side argument validation and error reporting."""
 import ctypes as C
-import functools
 import os
 import re
 
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
+from tests.host_common import abi_mismatches, lib  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_exports_every_declared_symbol(lib):
@@ -26,53 +19,6 @@ def test_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.kb_version().startswith(b'kilobots_hip')
-
-
-SCALARS = {'int': C.c_int, 'float': C.c_float, 'int64_t': C.c_int64, 'uint32_t': C.c_uint32, 'size_t': C.c_size_t}
-MIRRORS = {'kb_config': nat.KbConfig, 'kb_buffers': nat.KbBuffers, 'kb_outline': nat.KbOutline, 'kb_render_style': nat.KbRenderStyle,
-           'kb_reset_params': nat.KbResetParams, 'kb_episode_init': nat.KbEpisodeInit}
-
-
-def ctypes_of(c_type, returned=False):
-    """The ctypes types that may stand for a C type of the header (qualifiers and the parameter's name taken off)."""
-    base, stars = c_type.replace('*', ' ').split(), c_type.count('*')
-    base = ' '.join(w for w in base if w != 'const')
-    if stars == 0:
-        return (None,) if base == 'void' and returned else (SCALARS[base],)
-    if returned and (base, stars) == ('char', 1):
-        return (C.c_char_p,)
-    if stars == 1 and base in MIRRORS:
-        return (C.c_void_p, C.POINTER(MIRRORS[base]))
-    return (C.c_void_p,)
-
-
-@functools.lru_cache(None)
-def prototypes():
-    """{name: (return type, [parameter types])} as C text, of every function include/kilobots_hip.h declares."""
-    hdr = re.sub(r'/\*.*?\*/', ' ', open(os.path.join(ROOT, 'include', 'kilobots_hip.h')).read(), flags=re.S)
-    found = {}
-    for ret, name, params in re.findall(r'^([\w \*]+?)\s*\b(kb_[a-z_]+)\s*\(([^()]*)\)\s*;', hdr, flags=re.M):
-        params = [] if params.strip() == 'void' else [re.sub(r'\w+\s*$', '', p.strip()) for p in params.split(',')]
-        assert name not in found and all(p.strip() for p in params), name
-        found[name] = (ret, params)
-    return found
-
-
-def abi_mismatches(signatures, bound):
-    """Where `signatures` (a table like nat.SIGNATURES) or what `bound(name)` returns as (restype, argtypes) departs from
-    the header's prototypes: one line per return type or parameter."""
-    protos, bad = prototypes(), []
-    if set(protos) != set(signatures):
-        bad.append('names: %s' % sorted(set(protos) ^ set(signatures)))
-    for name, (ret, params) in protos.items():
-        for what, (restype, argtypes) in (('table', signatures.get(name, (0, []))), ('library', bound(name))):
-            if restype not in ctypes_of(ret, returned=True):
-                bad.append('%s: %s returns %r for %r' % (what, name, restype, ret))
-            if len(argtypes or []) != len(params):
-                bad.append('%s: %s takes %d arguments for %d' % (what, name, len(argtypes or []), len(params)))
-            bad += ['%s: %s argument %d is %r for %r' % (what, name, k, a, p) for k, (a, p) in enumerate(zip(argtypes or [], params))
-                    if a not in ctypes_of(p)]
-    return bad
 
 
 def test_every_binding_has_the_types_of_its_prototype(lib):

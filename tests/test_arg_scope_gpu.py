@@ -17,8 +17,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import geometry_scenes as GS
-from tests import solver_regimes as SR
-from tests import variant_census as VC
+from tests.host_common import variants  # noqa: F401
 
 E, N = 3, 1024
 W, H, R = 1.6, 1.2, 0.015
@@ -102,17 +101,10 @@ def test_the_moved_arguments_change_the_oracle_result():
         assert not (np.array_equal(osim.x, base.x) and np.array_equal(osim.y, base.y)), swap
 
 
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('case', CASES, ids=case_id)
 def test_fixed_size_kernels_read_every_argument_where_it_is_used(case, variants):
-    from tests.test_parity_gpu import assert_same, assert_ws_same, cpu, dev
+    from tests.gpu_common import assert_same, assert_ws_same, cpu, dev
     from gym_kilobots_amd.sim import KilobotSim
     sleep, sense, toi = case
     gsim = KilobotSim(E, N, O.DRIVE_VELOCITY, O.LIGHT_NONE, debug_outputs=True, **config_kw(sleep, sense, toi))

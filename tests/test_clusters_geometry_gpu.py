@@ -7,8 +7,9 @@ import numpy as np
 import pytest
 
 from tests import geometry_scenes as GS
+from tests.gpu_common import ranges
+from tests.sensing_checks import check_clusters
 from tests.sensing_common import make_sim
-from tests.test_clusters_gpu import check, ranges
 
 pytestmark = pytest.mark.gpu
 
@@ -32,5 +33,5 @@ def test_clusters_equal_brute_force(g):
     for R in (0.05, 0.12):
         inr = ranges(sim, R)
         for sel in (None, select):
-            want = check(sim, inr, R, sel, what=g.name)
+            want = check_clusters(sim, inr, R, sel, what=g.name)
             assert (want[3][:, 0] >= 2).all() and (want[3][:, 1] >= 2).all()

@@ -8,49 +8,14 @@ import pytest
 import torch
 
 from tests import clusters_ref as ref
-from tests import reduce_ref
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_hops_gpu import Spy, chain_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import Spy, cpu, dev, ranges, state
+from tests.sensing_checks import CLUSTERS_DTYPES as DTYPES, CLUSTERS_NAMES as NAMES, check_clusters as check, float_bits as bits, restate_clusters as restate
+from tests.sensing_common import SWEEP, chain_scene, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
 
 NAN = float('nan')
-NAMES = ('label', 'size', 'table', 'stats')
-DTYPES = (torch.int32, torch.int32, torch.float32, torch.int32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32) if a.dtype == np.float32 else a
-
-
-def ranges(g, R):
-    """The range matrix of every env of the sim, once per (scene, radius)."""
-    x, y = state(g)[:2]
-    return [reduce_ref.in_range(x[e], y[e], R) for e in range(g.num_envs)]
-
-
-def restate(g, inr, select=None):
-    x, y = state(g)[:2]
-    envs = [ref.clusters_env(inr[e], x[e], y[e], None if select is None else select[e]) for e in range(len(inr))]
-    return tuple(np.stack([env[k] for env in envs]) for k in range(4))
-
-
-def check(g, inr, R, select=None, what=''):
-    """clusters() with all four outputs equals the restatement.  select: numpy [E, N] bool or uint8, or None.  Returns the
-    restatement."""
-    s = None if select is None else dev(select)
-    got = g.clusters(R, select=s, size=True, table=True, stats=True)
-    torch.cuda.synchronize()
-    want = restate(g, inr, select)
-    assert s is None or torch.equal(s, dev(select))
-    for name, dtype, t, w in zip(NAMES, DTYPES, got, want):
-        assert t.dtype == dtype and tuple(t.shape) == w.shape, name
-        differ = bits(cpu(t)) != bits(w)
-        print('%s E=%d N=%d R=%g select=%s %s: %d of %d words differ' % (what, g.num_envs, g.num_bots, R, select is not None, name, int(differ.sum()), w.size))
-        assert not differ.any(), (what, name, np.argwhere(differ)[:5])
-    return want
 
 
 def three_in_four(E, N, rng_seed=16):

@@ -10,19 +10,12 @@ import pytest
 from oracle import oracle as O
 from tests import contact_search_scenes as CS
 from tests import solver_regimes as SR
-from tests import variant_census as VC
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.host_common import variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 WAVES = {40: (1, 1), 64: (1, 1), 200: (2, 8), 1024: (8, 8)}         # N -> waves per workgroup, from .. to
-
-
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
 
 
 @pytest.mark.parametrize('allow_sleep', [0, 1], ids=['nosleep', 'sleep'])

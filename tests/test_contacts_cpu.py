@@ -12,19 +12,12 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import contacts_ref as ref
 from tests import contacts_scenes as cs
+from tests.host_common import Handle, lib  # noqa: F401
 from tests.sensing_common import kernel_metadata
-from tests.test_objects_cpu import Handle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_symbols_are_exported_and_declared(lib):

@@ -8,8 +8,9 @@ import torch
 from tests import contacts_ref as ref
 from tests import contacts_scenes as cs
 from tests import scenes
+from tests.gpu_common import assert_ws_same, cpu, dev
+from tests.sensing_checks import same_contacts as same, want_contacts as want
 from tests.sensing_common import make_sim
-from tests.test_parity_gpu import MIXED_SHAPES, _compound_kw, _shape_kw, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -24,25 +25,6 @@ def run(sc, steps=None, **more):
     for _ in range(sc['steps'] if steps is None else steps):
         g.step(10, actions=dev(sc['actions']))
     return g
-
-
-def want(g, k, scale=65536.0):
-    torch.cuda.synchronize()
-    return ref.contacts_ref(cpu(g.ws_cnt), cpu(g.ws_key), cpu(g.ws_acc), g.contact_capacity, g.num_bots, g.num_objects,
-                            cs.fixture_body(g.cfg), k, scale)
-
-
-def same(got, exp, what=''):
-    """The four outputs against the restatement: partner by equality, the floats by bit pattern, None where None."""
-    torch.cuda.synchronize()
-    for name, a, b in zip(('partner', 'impulse', 'touch', 'obj'), got, exp):
-        assert (a is None) == (b is None), (what, name)
-        if a is None:
-            continue
-        a = cpu(a)
-        assert a.shape == b.shape and a.dtype == b.dtype, (what, name, a.shape, b.shape)
-        ia, ib = a.view(np.int32), b.view(np.int32)
-        assert np.array_equal(ia, ib), '%s: %s differs in %d of %d words, first at %s' % (what, name, (ia != ib).sum(), ia.size, np.argwhere(ia != ib)[0])
 
 
 def check(g, ks=(8,), what=''):
@@ -106,7 +88,7 @@ def test_one_kilobot_per_env_and_an_empty_store():
 def test_box_scene():
     E, N = 2, 128
     xy, _ = scenes.gaussian_spawn(E, N, sigma=0.3, seed=62)
-    g = make_sim(E, N, xy, scenes.toward_objects_theta(xy), num_objects=4, **_shape_kw(MIXED_SHAPES))
+    g = make_sim(E, N, xy, scenes.toward_objects_theta(xy), num_objects=4, **scenes.shape_kw(scenes.MIXED_SHAPES))
     g.set_objects_m(np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1)), np.tile(np.array([0.3, 0.0, -0.7, 1.1])[None], (E, 1)))
     g.step(1, flags=cs.STEP_NO_DRIVE)
     a = torch.zeros(E, N, 2, device='cuda')
@@ -118,11 +100,11 @@ def test_box_scene():
 
 
 def compound_scene():
-    """Objects of _compound_kw at the cfg4 positions, unrotated; kilobot 0 sits in the inner corner of the LForm (object 0,
+    """Objects of scenes.compound_kw at the cfg4 positions, unrotated; kilobot 0 sits in the inner corner of the LForm (object 0,
     fixtures 0 and 3 of the config) and drives into it, kilobot 1 touches the disc (fixture 1), kilobot 2 the box (fixture 5),
     kilobots 3 and 4 each other."""
     E, N = 2, 6
-    corner = np.array([-0.01875, -0.0125])      # of the LForm scaled to 0.15 x 0.15 and recentred (_reference_polygon_fixtures)
+    corner = np.array([-0.01875, -0.0125])      # of the LForm scaled to 0.15 x 0.15 and recentred (scenes.reference_polygon_fixtures)
     xy, th = np.zeros((E, N, 2)), np.zeros((E, N))
     xy[:, 0] = scenes.CFG4_OBJECTS[0] + corner + np.array([-0.016, 0.016])
     th[:, 0] = -np.pi / 4
@@ -132,7 +114,7 @@ def compound_scene():
     xy[1] += 1e-3
     a = np.zeros((E, N, 2), np.float32)
     a[..., 0] = 0.01
-    return dict(E=E, N=N, xy=xy, th=th, actions=a, steps=2, objects=np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1)), kw=_compound_kw())
+    return dict(E=E, N=N, xy=xy, th=th, actions=a, steps=2, objects=np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1)), kw=scenes.compound_kw())
 
 
 def test_compound_scene_needs_the_fixture_to_body_table():

@@ -12,30 +12,16 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import coverage_ref as ref
 from tests import coverage_scenes as CS
 from tests import grid_ref
 from tests import objects_ref
+from tests.host_common import abi_mismatches, Handle, lib, prototypes, tab  # noqa: F401
 from tests.sensing_common import kernel_metadata
-from tests.test_abi_cpu import abi_mismatches, prototypes
-from tests.test_objects_cpu import Handle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRIDS = [(1, 1), (3, 2), (7, 5), (64, 48), (127, 95), (128, 128)]
 U = 2.0 ** -24      # the unit roundoff of float32
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-@pytest.fixture(scope='module')
-def tab(lib):
-    with Handle(lib) as h:
-        return objects_ref.tables(nat.outline(h))
 
 
 def test_symbol_is_exported_and_declared(lib):

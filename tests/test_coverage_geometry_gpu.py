@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 
 from tests import geometry_scenes as GS
+from tests.sensing_checks import check_coverage
 from tests.sensing_common import make_sim
-from tests.test_coverage_gpu import check
 
 pytestmark = pytest.mark.gpu
 
@@ -29,5 +29,5 @@ def test_coverage_equals_brute_force(g):
     half_w = np.float32(0.5) * (np.float32(g.W) * np.float32(25.0))
     assert sim.outline().arena[1] == half_w
     for gw, gh in ((64, 48), (7, 5)):
-        w = check(sim, gw, gh, what=g.name, alone=False)
+        w = check_coverage(sim, gw, gh, what=g.name, alone=False)
         assert (w.owner >= 0).all() and np.isfinite(w.stats).all()

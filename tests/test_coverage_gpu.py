@@ -7,15 +7,13 @@ import numpy as np
 import pytest
 import torch
 
-from tests import coverage_ref as ref
 from tests import coverage_scenes as CS
-from tests import objects_ref
+from tests.gpu_common import dev
+from tests.sensing_checks import COVERAGE_PARTS as PARTS, check_coverage as check, differing, want_coverage as want
 from tests.sensing_common import make_sim
-from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
 
-PARTS = ('owner', 'dist', 'cells', 'stats')
 GRIDS = [(1, 1), (3, 2), (7, 5), (64, 48), (127, 95), (128, 128)]
 
 
@@ -27,38 +25,6 @@ def sim_of(scene, **kw):
     g.y.copy_(dev(y))
     g.theta.copy_(dev(th))
     return g, None if sel is None else dev(sel)
-
-
-def want(g, gw, gh, sel=None):
-    """The restatement on the state of the sim as it is on the device."""
-    torch.cuda.synchronize()
-    return ref.restate(objects_ref.tables(g.outline()), gw, gh, cpu(g.x), cpu(g.y), cpu(g.theta), None if sel is None else cpu(sel))
-
-
-def differing(t, w):
-    """Elements of a device tensor whose bits differ from the array's."""
-    a = cpu(t)
-    assert a.dtype == w.dtype and a.shape == w.shape, (a.dtype, w.dtype, a.shape, w.shape)
-    return a.view(np.uint32) != w.view(np.uint32)
-
-
-def check(g, gw, gh, sel=None, what='', w=None, alone=True):
-    """All four outputs in one call, then each alone with the others NULL, against the restatement w."""
-    w = want(g, gw, gh, sel) if w is None else w
-    got = g.coverage(gw, gh, select=sel)
-    torch.cuda.synchronize()
-    assert got._fields == PARTS and got.owner.dtype == torch.int32 and all(t.is_contiguous() for t in got)
-    for name in PARTS:
-        d = differing(getattr(got, name), getattr(w, name))
-        print('%s E=%d N=%d %d x %d %s: %d of %d words differ' % (what, g.num_envs, g.num_bots, gw, gh, name, int(d.sum()), d.size))
-        assert not d.any(), (what, gw, gh, name, np.argwhere(d)[:5])
-    if alone:
-        for name in PARTS:
-            part = g.coverage(gw, gh, select=sel, **{n: n == name for n in PARTS})
-            torch.cuda.synchronize()
-            assert [t is None for t in part] == [n != name for n in PARTS]
-            assert not differing(getattr(part, name), getattr(w, name)).any(), (what, gw, gh, name, 'alone')
-    return w
 
 
 def test_ties_go_to_the_lower_index():

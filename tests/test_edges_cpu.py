@@ -12,35 +12,13 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import edges_ref as ref
+from tests.host_common import Handle, lib  # noqa: F401
 from tests.sensing_common import SWEEP, kernel_metadata, sweep_scene, wall_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMPLETE_N = (32, 33, 65, 257, 1024)        # the complete-graph shapes of the GPU tests, all at (2, N, 4.0)
 WALL_R = (0.04, 0.09, 0.15)
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-class Handle(object):
-    """A kb_sim without buffers: what the validation of kb_sense_edges needs."""
-
-    def __init__(self, lib, E=4, N=64, **kw):
-        self.lib, self.h = lib, C.c_void_p()
-        cfg = nat.default_config(E, N, **kw)
-        rc = lib.kb_create(C.byref(cfg), C.byref(self.h))
-        assert rc == 0, lib.kb_last_error()
-
-    def __enter__(self):
-        return self.h
-
-    def __exit__(self, *exc):
-        self.lib.kb_destroy(self.h)
 
 
 def header_block():
@@ -171,7 +149,7 @@ def test_restatement_properties(restated, kind, E, N, R):
     assert np.array_equal(ref.bits(rel[:, 2]), ref.bits(rel[back, 2]))
     assert np.array_equal(ref.bits(rel[:, 3]), ref.bits(-rel[back, 3]))             # (a - b = -(b - a) exactly)
     # the counts, and the rows of at most 16, are those of the neighbours restatement
-    from tests.test_neighbors_gpu import restate as restate_neighbors
+    from tests.sensing_checks import restate_neighbors
     index, nrel, ncount, _ = restate_neighbors(x, y, th, R, 16)
     assert np.array_equal(count, ncount)
     for r in np.flatnonzero(count.ravel() <= 16)[:200]:

@@ -11,9 +11,10 @@ import pytest
 import torch
 
 from tests import edges_ref as ref
+from tests import geometry_scenes as GS
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import cpu, dev, geometry_pair, state
+from tests.sensing_common import SWEEP, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -318,18 +319,12 @@ def test_a_shard_reproduces_its_rows():
         assert torch.equal(shard.count, whole.count[2 * k:2 * k + 2])
 
 
-def _geometry_rows():
-    from tests.test_sensing_geometry_gpu import ROWS
-    return ROWS
-
-
-@pytest.mark.parametrize('row', _geometry_rows(), ids=lambda g: g.name)
+@pytest.mark.parametrize('row', GS.SENSING_ROWS, ids=lambda g: g.name)
 def test_edges_off_the_default_arena(row):
     """The arenas of tests/geometry_scenes.py that the sensing kernels are run on: cells of 0.875, 1.75 and 3.5, 103 x 78 cells
     with 1024 kilobots (the largest LDS image), grids one and two cells thin.  A radius of a cell and a half of the row's own cell."""
-    from tests.test_sensing_geometry_gpu import pair, radius
-    _, _, g = pair(row)
-    check(g, radius(row, 'cell-and-a-half'), row.name)
+    _, _, g = geometry_pair(row)
+    check(g, GS.sensing_radius(row, 'cell-and-a-half'), row.name)
 
 
 def test_batched_env_edge_obs():

@@ -10,19 +10,10 @@ from gym_kilobots_amd.envs import (KilobotsEnv, DirectControlKilobotsEnv, Batche
 from gym_kilobots_amd.lib import (SimpleVelocityControlKilobot, SimpleAccelerationControlKilobot, PhototaxisKilobot,
                                   SimplePhototaxisKilobot, CircularGradientLight, Body, Circle, Light)
 from gym_kilobots_amd import dist as kdist
+from tests.env_scenes import VelEnv
 from tests.oracle_backend import OracleBackend
 
 O_DRIVE_SP = 3   # KB_DRIVE_SIMPLE_PHOTOTAXIS
-
-
-class VelEnv(DirectControlKilobotsEnv):
-    def _configure_environment(self):
-        for i in range(6):
-            self._add_kilobot(SimpleVelocityControlKilobot(self.world, position=(-0.25 + 0.1 * i, 0.05 * i),
-                                                           orientation=0.3 * i, velocity=[0.005, 0.1]))
-
-    def get_reward(self, state, action, new_state):
-        return float(np.linalg.norm(new_state['kilobots'][:, :2] - state['kilobots'][:, :2]))
 
 
 class PhotoEnv(KilobotsEnv):

@@ -6,6 +6,7 @@ import torch
 
 from gym_kilobots_amd.envs import DirectControlKilobotsEnv, KilobotsEnv, BatchedKilobotsEnv
 from gym_kilobots_amd.lib import SimpleVelocityControlKilobot, PhototaxisKilobot, CircularGradientLight
+from tests.env_scenes import YAML_BOXES
 from tests.oracle_backend import OracleBackend
 
 pytestmark = pytest.mark.gpu
@@ -69,21 +70,6 @@ def test_batched_env_on_gpu():
         obs, r, done, info = env.step(a)
     assert (r > 0).all() and torch.isfinite(obs).all()
     assert env.gather_episode_returns().shape == (32,)
-
-
-YAML_BOXES = """
-!EvalEnv
-width: 1.0
-height: 0.8
-resolution: 600
-objects:
-    - !ObjectConf {idx: 0, shape: square, width: 0.15, height: 0.15, init: [0.05, 0.0, 0.2], color: [10, 20, 255], symmetry: 4}
-    - !ObjectConf {idx: 1, shape: corner_quad, width: 0.1, height: 0.2, init: [0.3, 0.1, -0.4], color: ~, symmetry: 1}
-    - !ObjectConf {idx: 2, shape: triangle, width: 0.15, height: 0.15, init: [-0.2, -0.2, 1.0], color: ~, symmetry: 1}
-    - !ObjectConf {idx: 3, shape: circle, width: 0.05, height: 0.05, init: [0.42, -0.3, 0.0], color: ~, symmetry: 1}
-light: !LightConf {type: circular, init: [0.3, 0.0], radius: 0.4}
-kilobots: !KilobotsConf {num: 40, mean: [-0.05, 0.0], std: 0.04}
-"""
 
 
 def test_yaml_scene_with_boxes_on_gpu_equals_oracle_env():

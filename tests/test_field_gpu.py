@@ -10,8 +10,8 @@ import torch
 from tests import field_ref as ref
 from tests import objects_ref
 from tests import scenes
-from tests.sensing_common import make_sim, state
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import cpu, dev, same_as_f32 as same, state
+from tests.sensing_common import f32, make_sim
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +27,6 @@ CASES = [(gw, gh, 2, 1024, ITERS[k % 4], (1, 3)[k % 2]) for k, (gw, gh) in enume
 CASES += [(gw, gh, E, N, ITERS[(k + j + 1) % 4], (3, 1)[(k + j) % 2]) for j, (gw, gh) in enumerate(((7, 5), (127, 95))) for k, (E, N) in enumerate(SHAPES[:3])]
 
 
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
-
-
 def start_plane(E, C, gh, gw, seed):
     """Random and nowhere zero, of both signs: a plane that was not read shows up."""
     rng = np.random.RandomState(seed)
@@ -44,10 +40,6 @@ def amounts(E, N, C, seed):
     am[0, 0, 0] = NAN
     am[E - 1, N - 1, C - 1] = 17.0
     return am
-
-
-def same(t, w):
-    return np.array_equal(ref.bits(cpu(t)), ref.bits(w))
 
 
 def check(g, F, am, keep, spread, iters, what='', env_mask=None, sense=True, field=None, tab=None):

@@ -15,39 +15,12 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from oracle import oracle as O
 from tests import geometry_scenes as GS
-from tests.test_launch_cpu import plan_rows
+from tests.host_common import compile_host, lib, plans_of, word_bits  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEY_OBJ = 0x20000
-
-# per input row of stdin (the columns of tests/golden/launch_plan.txt): the status of plan_launch, where islMin lies
-# (1 over the bin boundaries, 2 over the staged pairs, 3 behind the image, 0 not a sorted-bin kernel, -1 none of these)
-# and whether the NB words at the place the kernel takes end inside the image
-BRANCH_PROGRAM = r'''
-#include <cstdio>
-#include "kb_launch.h"
-using namespace kb;
-int main() {
-    int v[11];
-    while (scanf("%d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) == 11) {
-        const Plan p = plan_launch({v[0], v[1], v[2], v[3] != 0, v[4], v[5], v[6] != 0, v[7] != 0, v[8], v[9], v[10]});
-        const int NP = (v[0] + 3) & ~3, NB = NP + KB_MAX_OBJECTS + 4;
-        int branch = 0, inside = 1;
-        if (p.status == KB_OK && v[1] == 0 && v[4] != KB_DRIVE_MIXED) {
-            const bool hashed = p.hmask != 0;
-            branch = p.islmin_off == ldsb::binE(NB, NP, hashed, p.capL) ? 1 : p.islmin_off == ldsb::con32(NB, NP, hashed, p.capL, 0) ? 2
-                   : p.islmin_off == ldsb::total(NB, NP, hashed, p.capL, p.nhead, p.threads / 64) ? 3 : -1;
-            const int at = p.variant.fn ? ldsb::binE(NB, NP, false, p.capL) : p.islmin_off;
-            inside = !v[7] || at + 4 * NB <= p.lds_total;
-        }
-        printf("%d %d %d\n", p.status, branch, inside);
-    }
-    return 0;
-}
-'''
 
 # every cell count 1 .. 8192 with the sleep state: the fixed-size kernel (1024 kilobots) and the generic kernels of every
 # swarm size (kb_create's width, and every other width kb_set_block_threads accepts for the swarm at the cell counts of the
@@ -87,38 +60,6 @@ int main(int argc, char **argv) {
     return 0;
 }
 '''.replace('MAX_CELLS_', str(GS.MAX_CELLS))
-
-
-def compile_host(tmp_path, name, program, include=None):
-    src = tmp_path / (name + '.cpp')
-    src.write_text(program)
-    exe = str(tmp_path / name)
-    include = include or os.path.join(ROOT, 'gym_kilobots_amd', 'csrc')
-    subprocess.check_call(['g++', '-std=c++17', '-O2', '-I', os.path.join(ROOT, 'include'), '-I', include, str(src), '-o', exe])
-    return exe
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-def plans_of(tmp, rows, threads=None):
-    """plan_launch of the header for rows of either table, at kb_create's width or at threads[i] (0: kb_create's):
-    [(row, fields of the plan as ints, template arguments of the instantiation, its index, islMin branch, inside)]"""
-    inputs = [(GS.plan_inputs(g, threads[i] if threads else 0), '') for i, g in enumerate(rows)]
-    plans = plan_rows(tmp, inputs)
-    exe = compile_host(tmp, 'branch', BRANCH_PROGRAM)
-    stdin = '\n'.join(' '.join(map(str, v)) for v, _ in inputs).encode()
-    out = subprocess.run([exe], input=stdin, stdout=subprocess.PIPE, check=True).stdout.decode().split('\n')
-    result = []
-    for g, (plan, index), line in zip(rows, plans, out):
-        status, branch, inside = (int(x) for x in line.split())
-        shape, _, variant = plan.partition(' : ')
-        assert status == nat.KB_OK and index is not None, (g.name, plan)
-        result.append((g, [int(x) for x in shape.split()], [int(x) for x in variant.split()], index, branch, inside))
-    return result
 
 
 @pytest.fixture(scope='module')
@@ -254,10 +195,6 @@ def test_geometry_rows_are_not_vacuous_on_the_oracle(g):
         assert rested >= 2 and woken < rested, 'asleep after the rest %d, after the wake launches %d' % (rested, woken)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 _runs = {}
 
 
@@ -285,7 +222,7 @@ def test_constants_rows_act_on_the_oracle(c):
     else:
         objs = list(c.acts)
         fields = [(f, getattr(osim, f)[:, objs], getattr(control, f)[:, objs]) for f in ('ox', 'oy', 'otheta', 'ows_acc')]
-    differ = {f: int((bits(a) != bits(b)).sum()) for f, a, b in fields}
+    differ = {f: int((word_bits(a) != word_bits(b)).sum()) for f, a, b in fields}
     print(c.name, differ)
     if c.acts == 'bots':
         # (equal masses cancel in a kilobot pair, so a density may show in the impulses alone.)  Not one stray word: as many

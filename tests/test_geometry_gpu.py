@@ -8,19 +8,10 @@ import numpy as np
 import pytest
 
 from tests import geometry_scenes as GS
-from tests import variant_census as VC
-from tests import solver_regimes as SR
-from tests.test_geometry_cpu import plans_of
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev, put_device
+from tests.host_common import plans_of, variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
 
 
 @pytest.fixture(scope='module')
@@ -28,10 +19,6 @@ def planned(tmp_path_factory):
     """row name -> (plan fields, template arguments, index, islMin branch) at kb_create's width"""
     rows = GS.GEOMETRY + GS.CONSTANTS
     return {g.name: (shape, variant, index, branch) for g, shape, variant, index, branch, _ in plans_of(tmp_path_factory.mktemp('geometry'), rows)}
-
-
-def put_device(sim, name, val):
-    getattr(sim, name).copy_(dev(val))
 
 
 def run_row(g, plan, variants, threads=0):

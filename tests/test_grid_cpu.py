@@ -11,22 +11,15 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import grid_ref as ref
 from tests import objects_ref
 from tests import reduce_ref
 from tests import scenes
-from tests.sensing_common import kernel_metadata, wall_scene
-from tests.test_objects_cpu import BOUND_M, Handle
+from tests.host_common import Handle, lib  # noqa: F401
+from tests.sensing_common import f32, kernel_metadata, wall_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRIDS = [(1, 1), (3, 2), (7, 5), (64, 48), (127, 95), (128, 128)]
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -101,10 +94,6 @@ def test_kernels_use_no_scratch_and_spill_nothing(lib):
             assert fields[key] == 0, (name, key, fields[key])
 
 
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
-
-
 def world(xy_m):
     xy = np.asarray(xy_m, np.float64) * 25.0        # (KilobotSim.set_poses_m)
     return f32(xy[..., 0]), f32(xy[..., 1])
@@ -172,7 +161,7 @@ def test_restated_object_masks_equal_the_float64_evaluation(lib, name):
         m32, _ = ref.object_masks(tab, gw, gh, ox, oy, oth)
         m64, d64 = ref.object_masks(tab, gw, gh, ox, oy, oth, ft=np.float64)
         assert m32.dtype == np.float32 and m32.shape == (tab['M'], gh, gw) and set(np.unique(m32)) == {0.0, 1.0}
-        near = d64 < BOUND_M
+        near = d64 < objects_ref.BOUND_M
         print('%s %d x %d: %d cells within the bound of an outline, %d cells differ, cells covered per object %s'
               % (name, gw, gh, near.sum(), (m32 != m64).sum(), m32.sum((1, 2)).astype(int).tolist()))
         assert not (m32 != m64)[~near].any()

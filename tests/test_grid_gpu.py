@@ -11,8 +11,8 @@ from gym_kilobots_amd import _native as nat
 from tests import grid_ref as ref
 from tests import objects_ref
 from tests import scenes
-from tests.sensing_common import make_sim
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import cpu, dev, object_state as state, same_as_f32 as same
+from tests.sensing_common import f32, make_sim
 
 pytestmark = pytest.mark.gpu
 
@@ -25,22 +25,9 @@ GRIDS = [(1, 1), (3, 2), (7, 5), (64, 48), (127, 95), (128, 128)]
 BOTS = ref.COUNT | ref.FLOW
 
 
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
-
-
-def state(g):
-    torch.cuda.synchronize()
-    return [cpu(getattr(g, f)) if getattr(g, f) is not None else None for f in STATE]
-
-
 def want(g, gw, gh, planes):
     """The restatement on the state of the sim as it is on the device."""
     return ref.restate(objects_ref.tables(g.outline()), gw, gh, planes, *state(g))
-
-
-def same(t, w):
-    return np.array_equal(ref.bits(cpu(t)), ref.bits(w))
 
 
 def check(g, gw, gh, planes, what='', w=None):

@@ -8,32 +8,13 @@ import torch
 
 from tests import histogram_ref as ref
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import Spy, cpu, dev, state
+from tests.sensing_checks import check_histogram as check
+from tests.sensing_common import SWEEP, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = [(1, 1), (1, 2), (5, 1), (3, 6), (4, 8), (8, 8), (4, 16)]
-
-
-def check(g, R, rings, sectors, what=''):
-    """hist equals the restatement; its rows sum to count, which is what sense(R) gives."""
-    hist, cnt = g.neighbor_histogram(R, rings, sectors, count=True)
-    sensed = g.sense(R)
-    torch.cuda.synchronize()
-    E, N = g.num_envs, g.num_bots
-    assert hist.dtype == torch.float32 and cnt.dtype == torch.int32
-    assert tuple(hist.shape) == (E, N, rings, sectors) and tuple(cnt.shape) == (E, N)
-    hist, cnt = cpu(hist), cpu(cnt).view(np.uint32)
-    want, wcnt = ref.restate(*state(g), R, rings, sectors)
-    print('%s E=%d N=%d R=%g grid=%dx%d: %d of %d bins differ, %d counts differ, max count %d, bins hit %d of %d'
-          % (what, E, N, R, rings, sectors, int((hist != want).sum()), hist.size, int((cnt != wcnt).sum()), int(wcnt.max()),
-             int((want.sum((0, 1)) > 0).sum()), rings * sectors))
-    assert np.array_equal(cnt, wcnt), what
-    assert np.array_equal(cnt, cpu(sensed).view(np.uint32)), what
-    assert np.array_equal(hist, want), (what, np.argwhere(hist != want)[:5])
-    assert np.array_equal(hist.sum((2, 3)), cnt.astype(np.float32)), what
-    return hist, cnt
 
 
 @pytest.mark.parametrize('E,N,R', SWEEP)
@@ -99,21 +80,6 @@ def test_stepped_poses_with_unaligned_headings():
     assert (th != 0).all() and th.std() > 0.5
     hist, cnt = check(g, R, 4, 8, 'stepped')
     assert cnt.max() > 0
-
-
-class Spy(object):
-    """Records the calls that go through a ctypes library."""
-
-    def __init__(self, lib):
-        self.lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return fn(*args)
-        return call
 
 
 def test_outputs_streams_and_untouched_state():

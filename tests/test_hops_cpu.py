@@ -10,29 +10,14 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import hops_ref as ref
 from tests import reduce_ref
 from tests import scenes
-from tests.sensing_common import kernel_metadata
+from tests.host_common import handle, lib  # noqa: F401
+from tests.sensing_common import cloud, kernel_metadata, world_xy as world
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float('nan')
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-@pytest.fixture()
-def handle(lib):
-    h = C.c_void_p()
-    cfg = nat.default_config(4, 64)
-    assert lib.kb_create(C.byref(cfg), C.byref(h)) == 0
-    yield h
-    lib.kb_destroy(h)
 
 
 def test_symbol_is_exported_and_declared(lib):
@@ -84,14 +69,6 @@ def test_kernel_uses_no_scratch_and_spills_nothing(lib):
     for name, fields in found:
         for key in ('.private_segment_fixed_size', '.sgpr_spill_count', '.vgpr_spill_count'):
             assert fields[key] == 0, (name, key, fields[key])
-
-
-def world(xy):
-    return tuple((xy[:, k] * 25.0).astype(np.float32) for k in (0, 1))
-
-
-def cloud():
-    return world(scenes.gaussian_spawn(1, 333, sigma=0.2, seed=4)[0][0])
 
 
 def lattice():

@@ -8,21 +8,14 @@ import torch
 
 from gym_kilobots_amd import _native as nat
 from tests import hops_ref as ref
-from tests import reduce_ref
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import Spy, cpu, dev, ranges, state
+from tests.sensing_common import SWEEP, chain_scene, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
 
 NAN = float('nan')
 NAMES = ('hops', 'parent', 'root', 'stats')
-
-
-def ranges(g, R):
-    """The range matrix of every env of the sim, once per (scene, radius)."""
-    x, y = state(g)[:2]
-    return [reduce_ref.in_range(x[e], y[e], R) for e in range(g.num_envs)]
 
 
 def restate(inr, seeds, max_hops=ref.UNLIMITED):
@@ -49,21 +42,6 @@ def seed_sets(E, N, rng_seed=16):
     first = np.zeros((E, N), dtype=bool)
     first[:, 0] = True
     return first, np.random.RandomState(rng_seed).rand(E, N) < 1.0 / 16
-
-
-class Spy(object):
-    """Records the calls that go through a ctypes library."""
-
-    def __init__(self, lib):
-        self.lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return fn(*args)
-        return call
 
 
 @pytest.mark.parametrize('E,N,R', SWEEP)
@@ -94,13 +72,6 @@ def test_hops_equal_the_restatement(E, N, R):
         for k, pair in enumerate(some):
             assert isinstance(pair, tuple) and len(pair) == 2
             assert np.array_equal(cpu(pair[0]), want[0]) and np.array_equal(cpu(pair[1]), want[1 + k]), NAMES[1 + k]
-
-
-def chain_scene():
-    """The serpentine chain, its indices permuted, in two envs; returns (xy [2, 1024, 2], position of every index in the chain)."""
-    pts = ref.serpentine()
-    perm = np.random.RandomState(5).permutation(1024)      # index i sits at chain position perm[i]
-    return np.stack([pts[perm], pts[perm]]), perm
 
 
 @pytest.mark.parametrize('max_hops', [0, 1, 500, nat.HOPS_UNLIMITED])

@@ -8,16 +8,10 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from oracle import oracle as O
 from tests import label_scenes as LS
 from tests import solver_regimes as SR
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
+from tests.host_common import lib  # noqa: F401
 
 
 def test_the_planted_structures_are_what_the_docstring_says():

@@ -7,18 +7,10 @@ LDS read form of the union-find parents), the one of 200 a generic kernel (the v
 import pytest
 
 from tests import label_scenes as LS
-from tests import solver_regimes as SR
-from tests import variant_census as VC
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.host_common import variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
 
 
 @pytest.mark.parametrize('allow_sleep', [0, 1], ids=['nosleep', 'sleep'])

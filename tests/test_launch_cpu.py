@@ -7,30 +7,11 @@ import ctypes as C
 import os
 import subprocess
 
-import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
+from tests.host_common import lib, plan_rows  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-PROGRAM = r'''
-#include <cstdio>
-#include "kb_launch.h"
-using namespace kb;
-int main() {
-    int v[11];
-    while (scanf("%d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) == 11) {
-        const Plan p = plan_launch({v[0], v[1], v[2], v[3] != 0, v[4], v[5], v[6] != 0, v[7] != 0, v[8], v[9], v[10]});
-        if (p.status != KB_OK) { printf("%d\n", p.status); continue; }
-        const Variant &k = p.variant;
-        printf("%d %d %d %d %d %d %d %d %d %d : %d %d %d %d %d %d %d %d # %d\n", p.status, p.cap, p.capL, p.nhead, p.hmask, p.threads,
-               p.lds_total, p.islmin_off, p.botlaw_off, p.tier, k.drive, k.light, k.obj, k.fn, k.tier, k.poly, k.sense, k.sleep,
-               variant_index(p.variant));
-    }
-    return 0;
-}
-'''
 
 # the arenas of the golden grid by their cell count (2 x 1.5 m: 58 x 43 cells of 0.875 world units, 0.6 x 0.6 m: 18 x 18)
 ARENAS = {2494: (2.0, 1.5), 324: (0.6, 0.6)}
@@ -44,24 +25,6 @@ def golden_rows():
         inputs, result = line.split(':', 1)
         rows.append(([int(x) for x in inputs.split()], ' '.join(result.split())))
     return rows
-
-
-def plan_rows(tmp_path, rows):
-    """plan_launch of the header on the inputs of `rows`: [(result in the format of the golden file, position of the
-    instantiation in kb_variants or None for a refused configuration)]"""
-    src = tmp_path / 'launch.cpp'
-    src.write_text(PROGRAM)
-    exe = str(tmp_path / 'launch')
-    subprocess.check_call(['g++', '-std=c++17', '-I', os.path.join(ROOT, 'include'), '-I', os.path.join(ROOT, 'gym_kilobots_amd', 'csrc'),
-                           str(src), '-o', exe])
-    stdin = '\n'.join(' '.join(map(str, inputs)) for inputs, _ in rows).encode()
-    out = subprocess.run([exe], input=stdin, stdout=subprocess.PIPE, check=True).stdout.decode().split('\n')
-    assert len(out) >= len(rows)
-    plans = []
-    for line in out[:len(rows)]:
-        result, _, index = line.partition(' # ')
-        plans.append((result, int(index) if index else None))
-    return plans
 
 
 def test_plan_matches_the_recorded_shapes(tmp_path):
@@ -86,12 +49,6 @@ def config(inputs):
         cfg.obj_radius[f] = 0.05
         cfg.obj_verts[f][0][0], cfg.obj_verts[f][0][1] = 0.05, 0.03
     return cfg
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_library_matches_the_recorded_shapes(lib, tmp_path):

@@ -11,19 +11,13 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from oracle import oracle as O
 from tests import fuzz_scenes as FS
 from tests import limit_scenes as LS
 from tests import limits_model as LM
 from tests import solver_regimes as SR
 from tests import variant_census as VC
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
+from tests.host_common import lib  # noqa: F401
 
 
 # ---- the model against plain geometry -----------------------------------------------------------------------------------

@@ -16,7 +16,7 @@ from tests import guarded as GD
 from tests import limit_scenes as LS
 from tests import limits_model as LM
 from tests import scenes
-from tests.test_parity_gpu import make_pair, cpu, dev, OBJ_FIELDS
+from tests.gpu_common import make_pair, cpu, dev, OBJ_FIELDS
 
 pytestmark = pytest.mark.gpu
 

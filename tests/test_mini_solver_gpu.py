@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from tests import mini_scenes as MS
-from tests.test_oracle_vs_mini_solver import FIX
+from tests.mini_scenes import FIX
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +54,7 @@ def test_hip_path_follows_the_independent_solver(name):
 def test_hip_path_equals_the_oracle_bit_for_bit(name):
     """Poses, object poses and velocities, the manifold impulses with their feature ids (`ows_acc`), the kilobots' warm-start
     store and `status`, after every single-substep launch."""
-    from tests.test_parity_gpu import OBJ_FIELDS, assert_same, assert_ws_same
+    from tests.gpu_common import OBJ_FIELDS, assert_same, assert_ws_same
     sc = FIX[name]
     assert len(sc['kilobots']) <= 3 and len(sc['trajectory']) <= 80
     o, g = MS.oracle_for(sc), MS.sim_for(sc, debug_outputs=True)

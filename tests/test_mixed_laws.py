@@ -79,7 +79,7 @@ def test_masses_differ_by_law_in_a_collision():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 def _pair(E, N, light=O.LIGHT_NONE, xy=None, th=None, objects=None, seed=0, **kw):
-    from tests.test_parity_gpu import make_pair, dev
+    from tests.gpu_common import make_pair, dev
     osim, gsim = make_pair(E, N, O.DRIVE_MIXED, light, xy=xy, th=th, objects=objects, mode_density=DENS, **kw)
     modes = _modes(E, N, seed)
     osim.bot_mode[...] = modes
@@ -104,7 +104,7 @@ MIX_FIELDS = ('x', 'y', 'theta', 'v', 'w', 'cmd_vx', 'cmd_vy', 'cmd_w')
                                            # beyond 128 kilobots: the full workgroup at 256 VGPRs
                                            (129, O.LIGHT_NONE, 1), (300, O.LIGHT_CIRCULAR, 0), (1024, O.LIGHT_MOMENTUM, 1)])
 def test_mixed_swarm_equals_oracle(N, light, sleep):
-    from tests.test_parity_gpu import assert_same, assert_ws_same, dev
+    from tests.gpu_common import assert_same, assert_ws_same, dev
     E = 3
     xy, th = scenes.gaussian_spawn(E, N, sigma=min(0.04 + 0.001 * N, 0.35), seed=N)
     kw = dict(light_max_velocity=0.05) if light == O.LIGHT_MOMENTUM else {}
@@ -133,7 +133,7 @@ def test_mixed_swarm_equals_oracle(N, light, sleep):
 @pytest.mark.gpu
 @pytest.mark.parametrize('solver_mode', [0, 1, 2, 3, 4])
 def test_mixed_swarm_with_objects_on_every_solver_path(solver_mode):
-    from tests.test_parity_gpu import assert_same, dev, OBJ_FIELDS
+    from tests.gpu_common import assert_same, dev, OBJ_FIELDS
     E, N = 2, 90
     xy, th = scenes.gaussian_spawn(E, N, sigma=0.12, seed=8)
     objs = np.tile(np.array([[0.1, 0.05], [-0.15, -0.1]])[None], (E, 1, 1))

@@ -7,70 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import oracle as O
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import cpu, dev, state
+from tests.sensing_checks import check_neighbors as check, restate_neighbors as restate
+from tests.sensing_common import SWEEP, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def restate(x, y, th, R, k):
-    """The definition, brute force.  x, y [E, N] float32 world units, th [E, N] float32.
-    Returns (index [E, N, k] int32, rel [E, N, k, 4] float32, count [E, N] uint32, zero-distance neighbours [E, N])."""
-    assert x.dtype == y.dtype == th.dtype == np.float32
-    E, N = x.shape
-    W = np.float32(25)
-    Rw = np.float32(R) * W
-    R2 = Rw * Rw
-    index = np.full((E, N, k), -1, np.int32)
-    rel = np.zeros((E, N, k, 4), np.float32)
-    count = np.zeros((E, N), np.uint32)
-    zeros = np.zeros((E, N), np.int64)
-    for e in range(E):
-        ex = x[e][None, :] - x[e][:, None]          # [i, j] = x_j - x_i
-        ey = y[e][None, :] - y[e][:, None]
-        d2 = ex * ex + ey * ey
-        assert ex.dtype == d2.dtype == np.float32
-        inr = ~(d2 > R2)
-        np.fill_diagonal(inr, False)
-        count[e] = inr.sum(1)
-        zeros[e] = (inr & (d2 == 0)).sum(1)
-        for i in range(N):
-            js = np.nonzero(inr[i])[0]
-            js = js[np.lexsort((js, d2[i, js]))][:k]
-            m = len(js)
-            s, c = (np.float32(v) for v in O.sincosf(float(th[e, i])))
-            exi, eyi = ex[i, js], ey[i, js]
-            index[e, i, :m] = js
-            rel[e, i, :m, 0] = (c * exi + s * eyi) / W
-            rel[e, i, :m, 1] = (c * eyi - s * exi) / W
-            rel[e, i, :m, 2] = np.sqrt(d2[i, js]) / W
-            rel[e, i, :m, 3] = th[e, js] - th[e, i]
-    return index, rel, count, zeros
-
-
-def check(g, R, k, what=''):
-    """Items 3-5 of the sweep: values, count == sense(R), padding."""
-    idx, rel, cnt = g.neighbors(R, k)
-    sensed = g.sense(R)
-    torch.cuda.synchronize()
-    assert idx.dtype == torch.int32 and rel.dtype == torch.float32 and cnt.dtype == torch.int32
-    E, N = g.num_envs, g.num_bots
-    assert tuple(idx.shape) == (E, N, k) and tuple(rel.shape) == (E, N, k, 4) and tuple(cnt.shape) == (E, N)
-    idx, rel, cnt = cpu(idx), cpu(rel), cpu(cnt).view(np.uint32)
-    widx, wrel, wcnt, zeros = restate(*state(g), R, k)
-    bad = np.argwhere(idx != widx)
-    print('%s E=%d N=%d R=%g k=%d: %d index mismatches, %d rel words differ, %d counts differ, max count %d'
-          % (what, E, N, R, k, len(bad), int((rel.view(np.uint32) != wrel.view(np.uint32)).sum()), int((cnt != wcnt).sum()), int(wcnt.max())))
-    assert np.array_equal(cnt, wcnt), what
-    assert np.array_equal(cnt, cpu(sensed).view(np.uint32)), what
-    assert np.array_equal(idx, widx), (what, bad[:5])
-    assert np.array_equal(rel.view(np.uint32), wrel.view(np.uint32)), what
-    pad = np.arange(k)[None, None, :] >= np.minimum(cnt, k)[..., None]
-    assert (idx[pad] == -1).all() and (rel.view(np.uint32)[pad] == 0).all(), what
-    assert (idx[~pad] >= 0).all() and (idx[~pad] < N).all()
-    return idx, rel, cnt, zeros
 
 
 @pytest.mark.parametrize('k', [1, 4, 8, 16])

@@ -12,49 +12,11 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import objects_ref as ref
-from tests.sensing_common import kernel_metadata
+from tests.host_common import Handle, lib  # noqa: F401
+from tests.sensing_common import f32, kernel_metadata
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# The rounding bound of the float32 evaluation against the same formulas in float64, derived, not observed.  u = 2^-24 is
-# the unit roundoff of one fp32 operation.  Coordinates are at most 32 world units, so |dx|, |dy| <= 64, the kilobot in the
-# object's frame and the vector to the nearest point are shorter than 128 =: L, and every vector of the chain
-# (d -> p -> w -> q -> r -> g -> rel x 25) is a length of at most L.  Each link costs a few operations, each of which errs by
-# at most u times the magnitude of its terms relative to the vector it produces: the projection q = a + t e is backward
-# stable (an error dt of t moves q by dt |e|, and dt |e| <= 3 u |w| + 2 u |e|; a clamp decision that differs between the two
-# evaluations does not matter, q being continuous in t), and so are the three rotations, the differences, the norm and the
-# final division.  Fewer than 40 roundings lie on the longest path (3 rotations of 6, the projection 11, the subtractions 6,
-# norm and divisions 5), so their sum is below 40 u L.  The library's sine and cosine are within 2 ulp of the exact ones,
-# 2^-22 absolute, and each of the three rotations multiplies two such errors with lengths of at most L: 6 x 2^-22 L.
-# Together (40 x 2^-24 + 6 x 2^-22) x 128 = 4.9e-4 world units = 1.95e-5 m.  One step is not covered by this: the direction
-# p / n of a disc amplifies the error of p by |g| / n, which exceeds 1 only within half a radius of the disc's centre (at the
-# centre every direction is equally near: a tie among all of them).  The kilobots placed inside the disc keep out of there.
-BOUND_WU = (40 * 2.0 ** -24 + 6 * 2.0 ** -22) * 128.0
-BOUND_M = BOUND_WU / 25.0
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-class Handle(object):
-    """A kb_sim without buffers: what kb_get_outline and the validation of kb_sense_objects need."""
-
-    def __init__(self, lib, E=4, N=64, **kw):
-        self.lib, self.h = lib, C.c_void_p()
-        cfg = nat.default_config(E, N, **kw)
-        rc = lib.kb_create(C.byref(cfg), C.byref(self.h))
-        assert rc == 0, lib.kb_last_error()
-
-    def __enter__(self):
-        return self.h
-
-    def __exit__(self, *exc):
-        self.lib.kb_destroy(self.h)
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -106,10 +68,6 @@ def test_kernel_uses_no_scratch_and_spills_nothing(lib):
     for name, fields in found:
         for key in ('.private_segment_fixed_size', '.sgpr_spill_count', '.vgpr_spill_count'):
             assert fields[key] == 0, (name, key, fields[key])
-
-
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
 
 
 def test_outline_of_a_circle(lib):
@@ -207,8 +165,8 @@ def forms(lib):
 
 
 def test_restatement_is_within_the_rounding_bound_of_float64(forms):
-    """The float32 restatement against the same formulas in float64, bound BOUND_M = 1.95e-5 m (derived at the top of this
-    file from the operation count and coordinates of at most 32 world units).  The distance is continuous and is compared
+    """The float32 restatement against the same formulas in float64, bound ref.BOUND_M = 1.95e-5 m (derived in
+    tests/objects_ref.py from the operation count and coordinates of at most 32 world units).  The distance is continuous and is compared
     everywhere.  The point is not: where two candidates are nearly as close, the two evaluations may pick different ones.
     There, and only there, the vectors may differ by more than the bound, and then the float64 evaluation itself must show
     the near tie (its two best candidates within 2 bounds of each other).  The inside flag may differ only on the boundary,
@@ -223,17 +181,17 @@ def test_restatement_is_within_the_rounding_bound_of_float64(forms):
     derr = np.abs(o32[..., 2] - o64[..., 2])
     verr = np.abs(o32[..., :2] - o64[..., :2]).max(-1)
     werr = np.abs(w32[:, :3] - w64[:, :3]).max(-1)
-    print('largest errors in metres: distance %.3g, point %.3g, wall %.3g; bound %.3g' % (derr.max(), verr.max(), werr.max(), BOUND_M))
-    assert (derr <= BOUND_M).all()
-    assert (werr <= BOUND_M).all() and np.array_equal(w32[:, 3], w64[:, 3])
-    far = verr > BOUND_M
+    print('largest errors in metres: distance %.3g, point %.3g, wall %.3g; bound %.3g' % (derr.max(), verr.max(), werr.max(), ref.BOUND_M))
+    assert (derr <= ref.BOUND_M).all()
+    assert (werr <= ref.BOUND_M).all() and np.array_equal(w32[:, 3], w64[:, 3])
+    far = verr > ref.BOUND_M
     margin = a64['second'] - o64[..., 2] * 25.0
     print('%d of %d points differ by more than the bound, all of them near ties: largest margin %.3g world units'
           % (far.sum(), far.size, margin[far].max(initial=0.0)))
-    assert (a32['winner'][far] != a64['winner'][far]).all() and (margin[far] <= 2 * BOUND_WU).all()
+    assert (a32['winner'][far] != a64['winner'][far]).all() and (margin[far] <= 2 * ref.BOUND_WU).all()
     assert far.sum() < 0.01 * far.size
     flip = o32[..., 3] != o64[..., 3]
-    assert (o64[..., 2][flip] <= BOUND_M).all() and flip.sum() < 0.01 * flip.size
+    assert (o64[..., 2][flip] <= ref.BOUND_M).all() and flip.sum() < 0.01 * flip.size
     assert derr.max() > 0       # (the bound is not met trivially)
 
 
@@ -272,8 +230,8 @@ def test_distance_outside_equals_a_dense_sampling_of_the_outline(forms):
         print('object %d: %d outside, spacing %.3g, distance - sampled in [%.3g, %.3g] world units'
               % (m, outside.sum(), spacing, (d - sampled)[outside].min(), (d - sampled)[outside].max()))
         assert outside.sum() > 600
-        assert (d[outside] <= sampled[outside] + BOUND_WU).all()
-        assert (d[outside] >= sampled[outside] - spacing / 2 - BOUND_WU).all()
+        assert (d[outside] <= sampled[outside] + ref.BOUND_WU).all()
+        assert (d[outside] >= sampled[outside] - spacing / 2 - ref.BOUND_WU).all()
         checked += outside.sum()
     assert checked > 3000
 

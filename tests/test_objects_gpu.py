@@ -9,8 +9,8 @@ import torch
 
 from tests import objects_ref as ref
 from tests import scenes
+from tests.gpu_common import Spy, cpu, dev, same_as_f32 as same
 from tests.sensing_common import make_sim
-from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +32,6 @@ def want(g):
     torch.cuda.synchronize()
     s = [cpu(getattr(g, f)) if getattr(g, f) is not None else None for f in STATE]
     return ref.restate(ref.tables(g.outline()), *s)
-
-
-def same(t, w):
-    return np.array_equal(ref.bits(cpu(t)), ref.bits(w))
 
 
 def check(g, what=''):
@@ -69,8 +65,7 @@ def test_constructed_cases():
     """One env of 64: an axis-aligned box of half extents (2, 1) at the origin, a disc of radius 2 at (12.5, 0), a CForm at
     (-12.5, 0), world units; the first kilobots sit on the special points, the rest around the objects.  Every case is
     asserted on the restatement (the tie, the clamp, the inside flag) before the device is compared with it."""
-    from tests.test_parity_gpu import CFORM, _reference_polygon_fixtures
-    cf = _reference_polygon_fixtures(CFORM)
+    cf = scenes.reference_polygon_fixtures(scenes.CFORM)
     kw = ref.fixtures_kw(3, [(1, [[2.0, 1.0]], 0, 0.0), (0, None, 1, 0.08), (2, cf[0], 2, 0.0), (2, cf[1], 2, 0.0), (2, cf[2], 2, 0.0)])
     N = 64
     g = make_sim(1, N, **kw)
@@ -145,21 +140,6 @@ def test_after_motion_and_untouched_state():
     torch.cuda.synchronize()
     for f in fields:
         assert torch.equal(before[f].view(torch.uint8), getattr(g, f).view(torch.uint8)), f
-
-
-class Spy(object):
-    """Records the calls that go through a ctypes library."""
-
-    def __init__(self, lib):
-        self.lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return fn(*args)
-        return call
 
 
 def test_outputs_streams_and_arguments():

@@ -30,7 +30,7 @@ import pytest
 from tests import mini_scenes as MS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIX = MS.load_fixture()
+FIX = MS.FIX
 _oracle_for = MS.oracle_for
 TOL_CLASSES = (2e-5, 5e-5, 2e-4, 2e-3)
 COMPOUND = ('LForm', 'TForm', 'CForm')

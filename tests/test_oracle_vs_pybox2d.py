@@ -23,9 +23,9 @@ LINEAR = abs(REC.get('damping_factor_at_c0.8_h0.1', 0.9259259) - 0.92) < 1e-4   
 
 @pytest.mark.parametrize('name', sorted(REC['scenes']))
 def test_oracle_follows_real_box2d(name):
-    from tests.test_oracle_vs_mini_solver import _oracle_for
+    from tests.mini_scenes import oracle_for
     sc = dict(REC['scenes'][name], damping='linear' if LINEAR else 'pade')
-    o = _oracle_for(sc)
+    o = oracle_for(sc)
     tol = sc['tol']
     for k, ref in enumerate(sc['trajectory']):
         for first, cmds in sc.get('commands', []):

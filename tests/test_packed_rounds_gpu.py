@@ -8,21 +8,14 @@ import pytest
 from oracle import oracle as O
 from tests import packed_round_scenes as PR
 from tests import solver_regimes as SR
-from tests import variant_census as VC
+from tests.host_common import variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
-
-
 @pytest.mark.parametrize('case', PR.CASES, ids=PR.case_id)
 def test_packed_rounds_are_bit_exact(case, variants):
-    from tests.test_parity_gpu import assert_same, assert_ws_same, cpu, dev
+    from tests.gpu_common import assert_same, assert_ws_same, cpu, dev
     from gym_kilobots_amd.sim import KilobotSim
     name, sleep, toi = case
     N, xy, th, actions, _ = PR.start(name)

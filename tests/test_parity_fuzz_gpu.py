@@ -17,7 +17,7 @@ import torch
 from oracle import oracle as O
 from tests import fuzz_scenes as FS
 from tests import limits_model as LM
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 

@@ -11,56 +11,9 @@ import torch
 
 from oracle import oracle as O
 from tests import scenes
+from tests.gpu_common import OBJ_FIELDS, assert_same, assert_ws_same, cpu, dev, make_pair
 
 pytestmark = pytest.mark.gpu
-
-
-def make_pair(E, N, mode=O.DRIVE_VELOCITY, light=O.LIGHT_NONE, xy=None, th=None, objects=None, **kw):
-    from gym_kilobots_amd.sim import KilobotSim
-    if objects is not None:
-        kw['num_objects'] = objects.shape[-2]
-    kw.setdefault('allow_sleep', 0)      # (the library default is the reference's doSleep=True; the sleeping tests and the fuzz ask for it)
-    osim = O.OracleSim(O.default_config(E, N, mode, light, **kw))
-    gsim = KilobotSim(E, N, mode, light, debug_outputs=True, **kw)
-    if xy is not None:
-        osim.set_poses_m(xy, th)
-        gsim.set_poses_m(xy, th)
-    if objects is not None:
-        osim.set_objects_m(objects)
-        gsim.set_objects_m(objects)
-    return osim, gsim
-
-
-OBJ_FIELDS = ('x', 'y', 'theta', 'ox', 'oy', 'otheta', 'ovx', 'ovy', 'ow', 'ows_acc')
-
-
-def cpu(t):
-    return t.detach().cpu().numpy()
-
-
-def assert_same(osim, gsim, what='', fields=('x', 'y', 'theta')):
-    torch.cuda.synchronize()
-    for f in fields:
-        a, b = getattr(osim, f), cpu(getattr(gsim, f))
-        if not np.array_equal(a, b.reshape(a.shape)):
-            d = np.abs(a.astype(np.float64) - b.reshape(a.shape).astype(np.float64))
-            raise AssertionError('%s: field %s differs: max |d| = %.3e at %s (%d of %d elements)'
-                                 % (what, f, d.max(), np.unravel_index(d.argmax(), d.shape), (d > 0).sum(), d.size))
-
-
-def assert_ws_same(osim, gsim, what=''):
-    torch.cuda.synchronize()
-    cnt_o, cnt_g = osim.ws_cnt, cpu(gsim.ws_cnt)
-    assert np.array_equal(cnt_o, cnt_g), what + ': ws_cnt differs'
-    key_g, acc_g = cpu(gsim.ws_key).view(np.uint32), cpu(gsim.ws_acc)
-    assert key_g.shape == osim.ws_key.shape, 'contact capacity differs between oracle and kernel'
-    used = np.arange(osim.cap)[None, :] < cnt_o.astype(np.int64).sum(1)[:, None]     # packed list: first sum(cnt) entries
-    assert np.array_equal(osim.ws_key[used], key_g[used]), what + ': ws_key differs'
-    assert np.array_equal(osim.ws_acc[used], acc_g[used]), what + ': ws_acc differs'
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -266,7 +219,7 @@ def test_continuous_step_of_polygon_objects(toi):
     verts = np.array([[-hw, -hw], [hw, -hw], [hw, hw], [-hw, hw]])
     pairs = []
     for fused in (False, True):
-        osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=M, toi_walls=toi, **_shape_kw(shapes))
+        osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=M, toi_walls=toi, **scenes.shape_kw(shapes))
         osim.set_objects_m(objs, oth)
         gsim.set_objects_m(objs, oth)
         osim.ovx[...] = v0; osim.ovy[...] = vy0; osim.ow[...] = w0
@@ -512,25 +465,7 @@ def test_cfg4_slice_1024_bots_4_objects(mode):
     assert int(cpu(gsim.status).max()) == 0
 
 
-
-# ---- boxes / polygons with friction and rotation -----------------------------------------------
-def _shape_kw(shapes):
-    """shapes: list of ('box', w, h) | ('circle', r) | ('poly', [(x, y), ...]) -> config keywords (metres)."""
-    kw = dict(obj_shape=[], obj_verts=[], obj_radius=[], obj_nverts=[])
-    for sh in shapes:
-        if sh[0] == 'box':
-            kw['obj_shape'].append(O.SHAPE_BOX); kw['obj_verts'].append([[sh[1] / 2 * 25.0, sh[2] / 2 * 25.0]]); kw['obj_radius'].append(0.0); kw['obj_nverts'].append(4)
-        elif sh[0] == 'circle':
-            kw['obj_shape'].append(O.SHAPE_CIRCLE); kw['obj_verts'].append([[0.0, 0.0]]); kw['obj_radius'].append(sh[1]); kw['obj_nverts'].append(0)
-        else:
-            kw['obj_shape'].append(O.SHAPE_POLYGON); kw['obj_verts'].append([[v[0] * 25.0, v[1] * 25.0] for v in sh[1]]); kw['obj_radius'].append(0.0); kw['obj_nverts'].append(len(sh[1]))
-    return kw
-
-
-TRIANGLE = [(0.05, -0.05), (0.05, 0.10), (-0.10, -0.05)]      # body.py:265-275 scaled to 0.15 x 0.15, recentred
-MIXED_SHAPES = [('box', 0.15, 0.15), ('circle', 0.06), ('box', 0.2, 0.1), ('poly', TRIANGLE)]
-
-
+# ---- boxes / polygons with friction and rotation (shapes in tests/scenes.py) -----------------------
 @pytest.mark.parametrize('mode', [0, 1, 2, 3, 4])
 def test_boxes_pushed_by_a_crowd(mode):
     """Two boxes, a disc and a triangle at the cfg4 positions inside a 256-bot crowd: kilobot-polygon contacts with
@@ -540,7 +475,7 @@ def test_boxes_pushed_by_a_crowd(mode):
     th = scenes.toward_objects_theta(xy)
     objs = np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1))
     oth = np.tile(np.array([0.3, 0.0, -0.7, 1.1])[None], (E, 1))
-    osim, gsim = make_pair(E, N, xy=xy, th=th, solver_mode=mode, num_objects=4, **_shape_kw(MIXED_SHAPES))
+    osim, gsim = make_pair(E, N, xy=xy, th=th, solver_mode=mode, num_objects=4, **scenes.shape_kw(scenes.MIXED_SHAPES))
     osim.set_objects_m(objs, oth)
     gsim.set_objects_m(objs, oth)
     a = np.zeros((E, N, 2), np.float32)
@@ -561,8 +496,8 @@ def test_box_wall_box_box_and_disc_manifolds():
     solver, friction, feature-id warm starting; bit-exact every substep."""
     E, N = 4, 4
     xy = np.tile(np.array([[-0.9, 0.7], [-0.85, 0.7], [-0.8, 0.7], [-0.75, 0.7]])[None], (E, 1, 1))
-    shapes = [('box', 0.15, 0.15), ('box', 0.2, 0.1), ('circle', 0.05), ('poly', TRIANGLE), ('box', 0.1, 0.1)]
-    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=5, **_shape_kw(shapes))
+    shapes = [('box', 0.15, 0.15), ('box', 0.2, 0.1), ('circle', 0.05), ('poly', scenes.TRIANGLE_M), ('box', 0.1, 0.1)]
+    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=5, **scenes.shape_kw(shapes))
     rng = np.random.default_rng(9)
     objs = np.tile(np.array([[0.7, 0.0], [0.45, 0.02], [0.3, -0.05], [0.6, 0.3], [0.8, -0.5]])[None], (E, 1, 1))
     objs = objs + rng.uniform(-0.01, 0.01, objs.shape)
@@ -588,36 +523,6 @@ def test_box_wall_box_box_and_disc_manifolds():
     assert_same(osim, gsim, 'manifolds fused', OBJ_FIELDS)
 
 
-def _reference_polygon_fixtures(raw, width=0.15, height=0.15):
-    """Sub-polygons of a lib.body.Polygon subclass -> hull-ordered fixtures in world units (what the env uploads)."""
-    from gym_kilobots_amd.lib.body import _hull_order
-    v = np.array(raw, dtype=np.float64)
-    v = v / (v.max((0, 1)) - v.min((0, 1))) * np.array((width, height))
-    cen, area = np.zeros(2), 0.0
-    for vs in v:
-        a = 0.5 * abs(np.dot(vs[:, 0], np.roll(vs[:, 1], 1)) - np.dot(vs[:, 1], np.roll(vs[:, 0], 1)))
-        area += a
-        cen += vs.mean(0) * a
-    v = v - cen / area
-    return [[list(q) for q in _hull_order([tuple(x) for x in vs * 25.0])] for vs in v]
-
-
-LFORM = [[(-0.05, 0.0), (0.1, 0.0), (0.1, 0.3), (-0.05, 0.3)], [(0.1, 0.0), (0.1, -0.15), (-0.2, -0.15), (-0.2, 0.0)]]
-CFORM = [[(0.09, 0.15), (0.09, -0.15), (-0.01, -0.15), (-0.01, 0.15)], [(-0.01, -0.15), (-0.11, -0.15), (-0.11, -0.08), (-0.01, -0.05)],
-         [(-0.01, 0.15), (-0.11, 0.15), (-0.11, 0.08), (-0.01, 0.05)]]
-
-
-def _compound_kw():
-    """Objects: 0 = LForm (2 fixtures), 1 = disc, 2 = CForm (3 fixtures), 3 = box: 7 fixtures, not adjacent per body."""
-    lf, cf = _reference_polygon_fixtures(LFORM), _reference_polygon_fixtures(CFORM)
-    fixtures = [(2, lf[0], 0), (0, None, 1), (2, cf[0], 2), (2, lf[1], 0), (2, cf[1], 2), (1, [[0.05 * 25.0, 0.1 * 25.0]], 3), (2, cf[2], 2)]
-    kw = dict(num_objects=4, num_fixtures=len(fixtures), obj_fixture_body=[f[2] for f in fixtures] + [0],
-              obj_shape=[f[0] for f in fixtures], obj_nverts=[0 if f[1] is None else len(f[1]) for f in fixtures],
-              obj_radius=[0.05 if f[0] == 0 else 0.0 for f in fixtures],
-              obj_verts=[[[0.0, 0.0]] if f[1] is None else f[1] for f in fixtures])
-    return kw
-
-
 @pytest.mark.parametrize('mode', [0, 1, 2, 3])
 def test_multi_fixture_bodies_in_a_crowd(mode):
     """LForm / CForm bodies (several convex fixtures, centre of mass off the body origin) among 256 kilobots."""
@@ -626,7 +531,7 @@ def test_multi_fixture_bodies_in_a_crowd(mode):
     th = scenes.toward_objects_theta(xy)
     objs = np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1))
     oth = np.tile(np.array([0.4, 0.0, -1.2, 0.8])[None], (E, 1))
-    osim, gsim = make_pair(E, N, xy=xy, th=th, solver_mode=mode, **_compound_kw())
+    osim, gsim = make_pair(E, N, xy=xy, th=th, solver_mode=mode, **scenes.compound_kw())
     osim.set_objects_m(objs, oth)
     gsim.set_objects_m(objs, oth)
     a = np.zeros((E, N, 2), np.float32)
@@ -645,7 +550,7 @@ def test_multi_fixture_bodies_in_a_crowd(mode):
 def test_multi_fixture_bodies_collide_with_walls_and_each_other():
     E, N = 4, 2
     xy = np.tile(np.array([[-0.9, 0.7], [-0.85, 0.7]])[None], (E, 1, 1))
-    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), **_compound_kw())
+    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), **scenes.compound_kw())
     rng = np.random.default_rng(19)
     objs = np.tile(np.array([[0.55, 0.0], [0.3, 0.05], [0.8, -0.1], [0.75, 0.35]])[None], (E, 1, 1)) + rng.uniform(-0.01, 0.01, (E, 4, 2))
     oth = rng.uniform(-1.5, 1.5, (E, 4))
@@ -674,8 +579,8 @@ def test_eight_objects_every_candidate_index():
     E, N = 2, 2
     xy = np.tile(np.array([[0.0, 0.0], [0.04, 0.0]])[None], (E, 1, 1))
     shapes = [('box', 0.1, 0.1), ('circle', 0.04), ('box', 0.12, 0.06), ('circle', 0.05),
-              ('poly', TRIANGLE), ('box', 0.08, 0.08), ('circle', 0.03), ('box', 0.1, 0.05)]
-    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=8, **_shape_kw(shapes))
+              ('poly', scenes.TRIANGLE_M), ('box', 0.08, 0.08), ('circle', 0.03), ('box', 0.1, 0.05)]
+    osim, gsim = make_pair(E, N, xy=xy, th=np.zeros((E, N)), num_objects=8, **scenes.shape_kw(shapes))
     ang = np.linspace(0, 2 * np.pi, 8, endpoint=False) + 0.2
     objs = np.tile(np.stack([0.45 * np.cos(ang), 0.4 * np.sin(ang)], -1)[None], (E, 1, 1))
     objs[1] *= 0.97
@@ -702,7 +607,7 @@ def test_1024_bots_with_boxes():
     xy, th = scenes.lattice_spawn(E, N, seed=72)
     th = scenes.toward_objects_theta(xy)
     objs = np.tile(scenes.CFG4_OBJECTS[None], (E, 1, 1))
-    osim, gsim = make_pair(E, N, xy=xy, th=th, num_objects=4, **_shape_kw(MIXED_SHAPES))
+    osim, gsim = make_pair(E, N, xy=xy, th=th, num_objects=4, **scenes.shape_kw(scenes.MIXED_SHAPES))
     osim.set_objects_m(objs)
     gsim.set_objects_m(objs)
     osim.step(1, flags=O.STEP_NO_DRIVE)

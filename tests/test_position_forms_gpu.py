@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from tests import solver_regimes as SR
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 

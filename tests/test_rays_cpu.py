@@ -13,9 +13,9 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import objects_ref
 from tests import rays_ref as ref
+from tests.host_common import Handle, lib  # noqa: F401
 from tests.sensing_common import SWEEP, kernel_metadata, sweep_scene, wall_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,28 +42,6 @@ U, L_MAX, COND_MAX = 2.0 ** -24, 128.0, 2.0
 D_BQ = math.sqrt(2.0) * (3 * U * L_MAX + 2 * 2.0 ** -22 * L_MAX) + 5 * U * L_MAX
 BOUND_WU = (3 + 3 * COND_MAX) * D_BQ + 4 * U * L_MAX
 BOUND_M = BOUND_WU / 25.0
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-class Handle(object):
-    """A kb_sim without buffers: what kb_get_outline and the validation of kb_sense_rays need."""
-
-    def __init__(self, lib, E=4, N=64, **kw):
-        self.lib, self.h = lib, C.c_void_p()
-        cfg = nat.default_config(E, N, **kw)
-        rc = lib.kb_create(C.byref(cfg), C.byref(self.h))
-        assert rc == 0, lib.kb_last_error()
-
-    def __enter__(self):
-        return self.h
-
-    def __exit__(self, *exc):
-        self.lib.kb_destroy(self.h)
 
 
 def tables(lib, **kw):

@@ -10,11 +10,12 @@ import pytest
 import torch
 
 from gym_kilobots_amd import _native as nat
+from tests import geometry_scenes as GS
 from tests import rays_ref as ref
 from tests import scenes
 from tests.objects_ref import bits, tables
+from tests.gpu_common import cpu, dev, geometry_pair, object_state as state
 from tests.sensing_common import SWEEP, make_sim, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +23,6 @@ NAN = float('nan')
 SENTINEL = -77
 STATE = ('x', 'y', 'theta', 'ox', 'oy', 'otheta')
 ALL_K = (1, 3, 4, 7, 8, 16, 32)             # every instantiation, the padded ray counts, 16-byte and 4-byte stores, two passes
-
-
-def state(g):
-    torch.cuda.synchronize()
-    return [cpu(getattr(g, f)) if getattr(g, f) is not None else None for f in STATE]
 
 
 def default_targets(g):
@@ -156,19 +152,13 @@ def test_a_pile_in_one_cell():
     assert (wd[0, 1:40] <= rb / np.float32(25)).all() and (wh[0, 1:40] >= 0).all()
 
 
-def _geometry_rows():
-    from tests.test_sensing_geometry_gpu import ROWS
-    return ROWS
-
-
-@pytest.mark.parametrize('row', _geometry_rows(), ids=lambda g: g.name)
+@pytest.mark.parametrize('row', GS.SENSING_ROWS, ids=lambda g: g.name)
 def test_rays_off_the_default_arena(row):
     """The arenas and radii of tests/geometry_scenes.py that the sensing kernels are run on: cells of 0.875, 1.75 and 3.5,
     103 x 78 cells, grids one and two cells thin.  One env, eight rays, a radius of a cell and a half of the row's own cell."""
-    from tests.test_sensing_geometry_gpu import pair, radius
-    _, _, g = pair(row)
+    _, _, g = geometry_pair(row)
     assert abs(g.cfg.bot_radius - row.r) < 1e-8
-    check(g, radius(row, 'cell-and-a-half'), 8, what=row.name, envs=(0,))
+    check(g, GS.sensing_radius(row, 'cell-and-a-half'), 8, what=row.name, envs=(0,))
 
 
 def test_a_shard_reproduces_its_rows():

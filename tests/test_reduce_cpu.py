@@ -11,28 +11,13 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import reduce_ref as ref
 from tests import scenes
+from tests.host_common import handle, lib  # noqa: F401
 from tests.sensing_common import kernel_metadata
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF, NAN = float('inf'), float('nan')
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-@pytest.fixture()
-def handle(lib):
-    h = C.c_void_p()
-    cfg = nat.default_config(4, 64)
-    assert lib.kb_create(C.byref(cfg), C.byref(h)) == 0
-    yield h
-    lib.kb_destroy(h)
 
 
 def test_symbol_is_exported_and_declared(lib):

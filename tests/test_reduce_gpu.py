@@ -8,44 +8,14 @@ import torch
 
 from tests import reduce_ref as ref
 from tests import scenes
-from tests.sensing_common import SWEEP, make_sim, state, sweep_scene, wall_scene
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import Spy, cpu, dev, ranges, state
+from tests.sensing_checks import check_reduce as check, messages
+from tests.sensing_common import SWEEP, make_sim, sweep_scene, wall_scene
 
 pytestmark = pytest.mark.gpu
 
 OPS = ('sum', 'min', 'max')
 INF, NAN = float('inf'), float('nan')
-
-
-def ranges(g, R):
-    """The range matrix of every env of the sim, once per (scene, radius)."""
-    x, y = state(g)[:2]
-    return [ref.in_range(x[e], y[e], R) for e in range(g.num_envs)]
-
-
-def check(g, inr, R, op, values, scale=65536.0, what=''):
-    """neighbor_reduce equals the restatement bit for bit; its count is what sense(R) gives.  values: numpy [E, N(, C)]."""
-    v = dev(values)
-    out, cnt = g.neighbor_reduce(v, R, op=op, scale=scale, count=True)
-    sensed = g.sense(R)
-    torch.cuda.synchronize()
-    assert out.dtype == torch.float32 and cnt.dtype == torch.int32
-    assert tuple(out.shape) == values.shape and tuple(cnt.shape) == values.shape[:2]
-    assert torch.equal(v.view(torch.int32), dev(values).view(torch.int32))          # out of place: the messages are untouched
-    out, cnt = cpu(out), cpu(cnt).view(np.uint32)
-    envs = [ref.reduce_env(inr[e], values[e], op, scale) for e in range(g.num_envs)]
-    want, wcnt = np.stack([o for o, _ in envs]), np.stack([c for _, c in envs])
-    differ = ref.bits(out) != ref.bits(want)
-    print('%s E=%d N=%d R=%g op=%s shape=%s scale=%g: %d of %d words differ, %d counts differ, at most %d heard'
-          % (what, g.num_envs, g.num_bots, R, op, values.shape[2:], scale, int(differ.sum()), out.size, int((cnt != wcnt).sum()), int(wcnt.max())))
-    assert np.array_equal(cnt, wcnt), what
-    assert np.array_equal(cnt, cpu(sensed).view(np.uint32)), what
-    assert not differ.any(), (what, op, np.argwhere(differ)[:5])
-    return out, cnt
-
-
-def messages(E, N, C, seed):
-    return np.random.RandomState(seed).uniform(-4.0, 4.0, size=(E, N, C) if C else (E, N)).astype(np.float32)
 
 
 @pytest.mark.parametrize('E,N,R', SWEEP)
@@ -146,21 +116,6 @@ def test_saturation_cannot_overflow():
     assert (ref.bits(out[..., 2]) == 0).all()
     want, _ = ref.restate(*state(g)[:2], cpu(values), 4.0, 'sum', 1.0)
     assert np.array_equal(ref.bits(out), ref.bits(want))
-
-
-class Spy(object):
-    """Records the calls that go through a ctypes library."""
-
-    def __init__(self, lib):
-        self.lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self.lib, name)
-
-        def call(*args):
-            self.calls.append((name, args))
-            return fn(*args)
-        return call
 
 
 def test_outputs_in_place_streams_and_untouched_state():

@@ -11,24 +11,13 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import objects_ref
 from tests import render_ref as ref
-from tests.sensing_common import kernel_metadata
-from tests.test_objects_cpu import Handle
+from tests.host_common import Handle, lib  # noqa: F401
+from tests.sensing_common import f32, kernel_metadata
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R_BOT = 0.0165
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -137,7 +126,7 @@ def test_check_render_and_the_env_layers():
 
 def test_kilobots_env_render_modes_without_a_gpu():
     from tests.oracle_backend import OracleBackend
-    from tests.test_env_api_cpu import VelEnv
+    from tests.env_scenes import VelEnv
     assert VelEnv.metadata['render.modes'] == ['human', 'rgb_array']
     env = VelEnv(sim_factory=OracleBackend)
     assert env.render_mode == 'human'

@@ -12,8 +12,9 @@ from gym_kilobots_amd import _native as nat
 from tests import objects_ref
 from tests import render_ref as ref
 from tests import scenes
-from tests.sensing_common import make_sim
-from tests.test_parity_gpu import cpu, dev
+from tests.gpu_common import cpu, dev
+from tests.sensing_checks import check_render as check, colour_words as words, want_render as want
+from tests.sensing_common import f32, make_sim
 
 pytestmark = pytest.mark.gpu
 
@@ -24,44 +25,6 @@ SIZES = [(1, 1), (3, 2), (7, 5), (64, 48), (128, 96), (127, 95)]
 BANDED = (400, 297)     # at N = 64: 15 bands of 20 rows, the last of 17 (400 x 300 would be 15 full bands)
 OWN_STYLE = dict(table=(12, 34, 56), body=(1, 2, 3), ring=(200, 100, 0), mark=(9, 250, 9), light=(0, 128, 255), light_alpha=77,
                  obj=[(10 * m + 5, 255 - 20 * m, 7 * m) for m in range(8)])
-
-
-def f32(v):
-    return np.asarray(v, dtype=np.float32)
-
-
-def scene_of(g):
-    """What the restatement needs of a sim, as it is on the device: keywords of ref.restate."""
-    torch.cuda.synchronize()
-    E = g.num_envs
-    kw = dict(bot_radius=g.cfg.bot_radius, x=cpu(g.x), y=cpu(g.y), th=cpu(g.theta))
-    if g.num_objects:
-        kw.update(ox=cpu(g.ox), oy=cpu(g.oy), oth=cpu(g.otheta))
-    if g.light_type in (nat.LIGHT_CIRCULAR, nat.LIGHT_MOMENTUM):
-        kw['lights'] = ([g.cfg.light_radius], cpu(g.light_x).reshape(E, 1), cpu(g.light_y).reshape(E, 1))
-    elif g.light_type == nat.LIGHT_COMPOSITE:
-        n = g.cfg.light_count
-        kw['lights'] = (list(g.cfg.lightc_radius)[:n], cpu(g.light_x).reshape(E, n), cpu(g.light_y).reshape(E, n))
-    return kw
-
-
-def want(g, width, height, layers=ref.ALL, style=None, body=None, mark=None):
-    return ref.restate(objects_ref.tables(g.outline()), width, height, layers, style=style, body=body, mark=mark, **scene_of(g))
-
-
-def words(t):
-    return None if t is None else dev(np.ascontiguousarray(t, dtype=np.int64).astype(np.int32))
-
-
-def check(g, width, height, layers=ref.ALL, style=None, body=None, mark=None, what='', w=None):
-    w = want(g, width, height, layers, style, body, mark) if w is None else w
-    got = g.render(width, height, layers, style=style, body_rgb=words(body), mark_rgb=words(mark))
-    torch.cuda.synchronize()
-    assert got.dtype == torch.uint8 and tuple(got.shape) == w.shape == (g.num_envs, height, width, 3) and got.is_contiguous()
-    d = cpu(got) != w
-    print('%s E=%d N=%d %d x %d layers %d: %d of %d bytes differ' % (what, g.num_envs, g.num_bots, width, height, layers, int(d.sum()), d.size))
-    assert not d.any(), (what, width, height, layers, np.argwhere(d)[:5])
-    return w
 
 
 def colours(E, N, seed):

@@ -9,15 +9,11 @@ import pytest
 import torch
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from gym_kilobots_amd.envs import BatchedKilobotsEnv
 from oracle import oracle as O
 from tests import reset_envs_ref as R
 from tests import scenes
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+from tests.host_common import lib, word_bits  # noqa: F401
 
 
 # ---------------------------------------------------------------------------------------------- the restated spawn
@@ -32,7 +28,7 @@ def test_restated_spawn_at_word_zero_is_kbo_reset(mode):
         osim.reset(resolve=False, **kw)
         x, y, th, v, w = R.spawn(cfg, z=0, **kw)
         for name, a in (('x', x), ('y', y), ('theta', th)) + ((('v', v), ('w', w)) if mode != O.DRIVE_MOTORS else ()):
-            assert np.array_equal(bits(getattr(osim, name)), bits(a)), (name, rt, rv, seed)
+            assert np.array_equal(word_bits(getattr(osim, name)), word_bits(a)), (name, rt, rv, seed)
         if std > 0.5:       # (the clip onto the bounds -/+ 0.02 is exercised)
             assert np.abs(osim.y).max() == (np.float32(0.5) * np.float32(1.5) - np.float32(0.02)) * np.float32(25.0)
         if mode == O.DRIVE_MOTORS:
@@ -49,16 +45,10 @@ def test_other_counter_words_give_other_spawns_in_every_env():
     # a word per env: env e of the mixed draw is env e of the draw with that word everywhere
     mixed = R.spawn(cfg, z=[0, 1, 2, 1, 0], **kw)
     for e, z in enumerate((z0, z1, z2, z1, z0)):
-        assert all(np.array_equal(bits(mixed[k][e]), bits(z[k][e])) for k in range(5))
+        assert all(np.array_equal(word_bits(mixed[k][e]), word_bits(z[k][e])) for k in range(5))
 
 
 # ---------------------------------------------------------------------------------------------- argument checks
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
-
-
 def test_argument_errors_in_their_order_on_an_unbound_handle(lib):
     plain, rich = C.c_void_p(), C.c_void_p()
     cfg = nat.default_config(4, 32)

@@ -13,7 +13,7 @@ from gym_kilobots_amd import _native as nat
 from oracle import oracle as O
 from tests import reset_envs_ref as R
 from tests import scenes
-from tests.test_parity_gpu import OBJ_FIELDS, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import OBJ_FIELDS, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 

@@ -8,7 +8,7 @@ import torch
 from oracle import oracle as O
 from tests import scenes
 from tests.sensing_common import SWEEP
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 

@@ -11,48 +11,18 @@ import torch
 
 from tests import geometry_scenes as GS
 from tests import scenes
-from tests.test_geometry_gpu import put_device
-from tests.test_histogram_gpu import check as check_histogram
-from tests.test_neighbors_gpu import check as check_neighbors
-from tests.test_parity_gpu import make_pair, assert_same, cpu, dev
-from tests.test_reduce_gpu import check as check_reduce, messages, ranges
-from tests.test_render_gpu import check as check_render
+from tests.gpu_common import assert_same, cpu, dev, geometry_pair as pair, ranges
+from tests.sensing_checks import check_histogram, check_neighbors, check_reduce, check_render, messages
 
 pytestmark = pytest.mark.gpu
 
-
-def _rows():
-    """One row per (arena, radius, swarm size): those of up to 200 kilobots, and 1024 in the 1.6 x 1.2 m and 3.6 x 2.7 m arenas."""
-    seen, rows = set(), []
-    for g in GS.GEOMETRY:
-        key = (g.W, g.H, g.r, g.N)
-        if key not in seen and (g.N <= 200 or (g.N == 1024 and g.W in (1.6, 3.6))):
-            rows.append(g)
-        seen.add(key)
-    return rows
-
-
-ROWS = _rows()
-RADII = ('half-cell', 'cell-and-a-half', 'arena')
+ROWS = GS.SENSING_ROWS
+RADII =('half-cell', 'cell-and-a-half', 'arena')
 CASES = [(g, kind) for g in ROWS for kind in RADII]
-
-
-def radius(g, kind):
-    """metres"""
-    cell = g.cell / GS.WORLD_SCALE
-    return {'half-cell': 0.5 * cell, 'cell-and-a-half': 1.5 * cell, 'arena': float(np.hypot(g.W, g.H))}[kind]
 
 
 def case_id(case):
     return '%s-%s' % (case[0].name, case[1])
-
-
-def pair(g, **kw):
-    s = GS.scene(g)
-    osim, gsim = make_pair(s.E, s.N, s.mode, xy=s.xy, th=s.th, **dict(s.kw, **kw))
-    GS.apply_start(s, osim, GS.put_numpy)
-    GS.apply_start(s, gsim, put_device)
-    return s, osim, gsim
 
 
 def test_the_rows_cover_the_grids():
@@ -65,7 +35,7 @@ def test_the_rows_cover_the_grids():
 @pytest.mark.parametrize('case', CASES, ids=case_id)
 def test_sensing_entry_points_equal_brute_force(case):
     g, kind = case
-    R = radius(g, kind)
+    R = GS.sensing_radius(g, kind)
     s, osim, gsim = pair(g)
     got = cpu(gsim.sense(R)).view(np.uint32)
     want = osim.sense(R)
@@ -88,7 +58,7 @@ def test_fused_sensing_in_the_step(case):
     """kb_config.sense_radius: the counts of the last substep's sensing point equal the oracle's and kb_sense of the poses
     before that substep; the step itself stays bit exact."""
     g, kind = case
-    R = radius(g, kind)
+    R = GS.sensing_radius(g, kind)
     s, osim, gsim = pair(g, sense_radius=R)
     for k in range(2):
         a = scenes.random_actions(s.E, s.N, seed=60 + k)

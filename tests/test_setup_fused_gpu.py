@@ -32,8 +32,8 @@ from oracle import oracle as O
 from tests import scenes
 from tests import setup_scenes as SS
 from tests import solver_regimes as SR
-import tests.test_placement_gpu as TP
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests import placement_scenes as TP
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
 import placement_model as PM  # noqa: E402

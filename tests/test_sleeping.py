@@ -139,7 +139,7 @@ def test_a_pushed_disc_comes_to_rest_and_sleeps_with_zero_velocity():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
 def _pair(E, N, xy, th, objects=None, **kw):
-    from tests.test_parity_gpu import make_pair
+    from tests.gpu_common import make_pair
     return make_pair(E, N, O.DRIVE_VELOCITY, O.LIGHT_NONE, xy=xy, th=th, objects=objects, allow_sleep=1, **kw)
 
 
@@ -149,7 +149,7 @@ SLEEP_FIELDS = ('x', 'y', 'theta', 'sleep_time')
 @pytest.mark.gpu
 @pytest.mark.parametrize('N,solver_mode', [(40, 0), (64, 0), (100, 0), (256, 0), (256, 1), (256, 2), (200, 3), (128, 4), (1024, 0)])
 def test_sleeping_swarm_equals_oracle(N, solver_mode):
-    from tests.test_parity_gpu import assert_same, assert_ws_same, dev
+    from tests.gpu_common import assert_same, assert_ws_same, dev
     E = 3
     xy, th = scenes.gaussian_spawn(E, N, sigma=0.05 + 0.0004 * N, seed=N + solver_mode)
     osim, gsim = _pair(E, N, xy, th, solver_mode=solver_mode)
@@ -174,7 +174,7 @@ def test_sleeping_swarm_equals_oracle(N, solver_mode):
 
 @pytest.mark.gpu
 def test_fused_launch_with_sleeping_equals_single_substeps_and_oracle():
-    from tests.test_parity_gpu import assert_same, dev, make_pair
+    from tests.gpu_common import assert_same, dev, make_pair
     E, N = 4, 96
     xy, th = scenes.gaussian_spawn(E, N, sigma=0.08, seed=11)
     osim, gsim = _pair(E, N, xy, th)
@@ -195,7 +195,7 @@ def test_fused_launch_with_sleeping_equals_single_substeps_and_oracle():
 @pytest.mark.gpu
 @pytest.mark.parametrize('boxes,N', [(False, 48), (True, 48), (True, 200), (False, 1024)])
 def test_sleeping_with_objects_equals_oracle(boxes, N):
-    from tests.test_parity_gpu import assert_same, dev, OBJ_FIELDS
+    from tests.gpu_common import assert_same, dev, OBJ_FIELDS
     E = 2
     xy, th = scenes.gaussian_spawn(E, N, sigma=0.12 + 0.0002 * N, seed=5 + N)
     objs = np.tile(np.array([[0.1, 0.05], [-0.15, -0.1], [0.3, -0.25]])[None], (E, 1, 1))
@@ -260,7 +260,7 @@ def test_benchmark_kernel_without_the_sleep_state_equals_the_sleeping_kernel_on_
     """cfg3 slice (1024 kilobots, every kilobot commanded to move in every substep): the fixed-size benchmark instantiation
     (no sleep state) and the instantiation with the sleep state give the same bits -- kilobots do fall asleep
     (pressed against their neighbours they rest for 0.5 s) and are woken by their next command before anything is simulated."""
-    from tests.test_parity_gpu import dev, make_pair
+    from tests.gpu_common import dev, make_pair
     from gym_kilobots_amd.sim import KilobotSim
     E, N = 6, 1024
     xy, th = scenes.lattice_spawn(E, N, seed=9)
@@ -313,7 +313,7 @@ def test_a_contact_that_stops_touching_wakes_the_sleeping_partner():
 
 @pytest.mark.gpu
 def test_contact_end_wake_rule_on_the_device():
-    from tests.test_parity_gpu import assert_same, assert_ws_same, dev, make_pair
+    from tests.gpu_common import assert_same, assert_ws_same, dev, make_pair
     xy, th, a = _creeper_scene()
     E = 3                                                 # the same pair three times, padded with far-away kilobots in envs 1 and 2
     N = 8

@@ -7,17 +7,11 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from oracle import oracle as O
 from tests import solver_regimes as SR
+from tests.host_common import lib  # noqa: F401
 
 E = 2
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_regime_follows_the_table():

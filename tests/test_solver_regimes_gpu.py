@@ -12,7 +12,7 @@ import torch
 from oracle import oracle as O
 from tests import solver_regimes as SR
 from tests import variant_census as VC
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
 
 pytestmark = pytest.mark.gpu
 

@@ -21,6 +21,7 @@ from tests import overflow_scenes as OV
 from tests import scenes
 from tests import solver_regimes as SR
 from tests import variant_census as VC
+from tests.gpu_common import put_device
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +30,6 @@ HOWS = ('ones', 'stale')
 
 def dev(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def put_device(sim, name, val):
-    getattr(sim, name).copy_(dev(val))
 
 
 def new_sim(E, N, mode=O.DRIVE_VELOCITY, light=O.LIGHT_NONE, threads=0, **kw):

@@ -13,8 +13,8 @@ import torch
 
 from tests import overflow_scenes as OS
 from tests import variant_census as VC
-from tests.test_contacts_gpu import same as contacts_same, want as contacts_want
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.sensing_checks import same_contacts as contacts_same, want_contacts as contacts_want
 
 pytestmark = pytest.mark.gpu
 

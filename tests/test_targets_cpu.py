@@ -12,21 +12,13 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from tests import targets_ref as ref
 from tests import targets_scenes as TS
+from tests.host_common import abi_mismatches, Handle, lib, prototypes  # noqa: F401
 from tests.sensing_common import kernel_metadata
-from tests.test_abi_cpu import abi_mismatches, prototypes
-from tests.test_objects_cpu import Handle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24      # the unit roundoff of float32
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 @pytest.fixture(scope='module')

@@ -7,9 +7,9 @@ import numpy as np
 import pytest
 
 from tests import geometry_scenes as GS
+from tests.gpu_common import dev
+from tests.sensing_checks import check_targets
 from tests.sensing_common import make_sim
-from tests.test_parity_gpu import dev
-from tests.test_targets_gpu import check
 
 pytestmark = pytest.mark.gpu
 
@@ -22,5 +22,5 @@ def test_targets_equal_brute_force_on_the_largest_grid():
     s = GS.scene(g)
     sim = make_sim(s.E, s.N, s.xy, s.th, **s.kw)
     points = np.random.RandomState(80).uniform([-g.W / 2, -g.H / 2], [g.W / 2, g.H / 2], size=(129, 2)).astype(np.float32)
-    w = check(sim, dev(points), 0.05, what=g.name, alone=False)
+    w = check_targets(sim, dev(points), 0.05, what=g.name, alone=False)
     assert (w.index >= 0).all() and (w.owner >= 0).all() and np.isfinite(w.stats).all()

@@ -7,14 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import targets_ref as ref
 from tests import targets_scenes as TS
+from tests.gpu_common import cpu, dev
+from tests.sensing_checks import TARGETS_PARTS as PARTS, check_targets as check, differing, want_targets as want
 from tests.sensing_common import make_sim
-from tests.test_parity_gpu import cpu, dev
 
 pytestmark = pytest.mark.gpu
-
-PARTS = ('index', 'rel', 'owner', 'dist', 'stats')
 
 
 def sim_of(sc):
@@ -24,39 +22,6 @@ def sim_of(sc):
     g.y.copy_(dev(sc.y))
     g.theta.copy_(dev(sc.th))
     return g, dict(bot_select=None if sc.bsel is None else dev(sc.bsel), slot_select=None if sc.ssel is None else dev(sc.ssel))
-
-
-def want(g, points, tol, bot_select=None, slot_select=None):
-    """The restatement on the state of the sim as it is on the device."""
-    torch.cuda.synchronize()
-    host = lambda t: None if t is None else cpu(t.to(torch.uint8))
-    return ref.restate(cpu(g.x), cpu(g.y), cpu(g.theta), cpu(points), tol, host(bot_select), host(slot_select))
-
-
-def differing(t, w):
-    """Elements of a device tensor whose bits differ from the array's."""
-    a = cpu(t)
-    assert a.dtype == w.dtype and a.shape == w.shape, (a.dtype, w.dtype, a.shape, w.shape)
-    return a.view(np.uint32) != w.view(np.uint32)
-
-
-def check(g, points, tol, what='', w=None, alone=True, **sel):
-    """All five outputs in one call, then each alone with the others NULL, against the restatement w."""
-    w = want(g, points, tol, **sel) if w is None else w
-    got = g.targets(points, tol, **sel)
-    torch.cuda.synchronize()
-    assert got._fields == PARTS and got.index.dtype == got.owner.dtype == torch.int32 and all(t.is_contiguous() for t in got)
-    for name in PARTS:
-        d = differing(getattr(got, name), getattr(w, name))
-        print('%s E=%d N=%d K=%d %s: %d of %d words differ' % (what, g.num_envs, g.num_bots, points.shape[-2], name, int(d.sum()), d.size))
-        assert not d.any(), (what, name, np.argwhere(d)[:5])
-    if alone:
-        for name in PARTS:
-            part = g.targets(points, tol, **sel, **{n: n == name for n in PARTS})
-            torch.cuda.synchronize()
-            assert [t is None for t in part] == [n != name for n in PARTS]
-            assert not differing(getattr(part, name), getattr(w, name)).any(), (what, name, 'alone')
-    return w
 
 
 @pytest.mark.parametrize('name', sorted(TS.SCENES))

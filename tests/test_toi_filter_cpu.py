@@ -15,13 +15,10 @@ import pytest
 
 from oracle import oracle as O
 from tests import toi_scenes as TS
+from tests.host_common import word_bits
 
 f32 = TS.f32
 FIELDS = ('x', 'y', 'theta', 'v', 'w', 'sleep_time')
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def lockstep(s, allow_sleep):
@@ -49,8 +46,8 @@ def lockstep(s, allow_sleep):
         d0, d1 = TS.sweep_dists(x0, y0, b.x, b.y)
         differs = np.zeros(x0.shape, bool)
         for f in FIELDS:
-            differs |= bits(getattr(a, f)) != bits(getattr(b, f))
-        assert np.array_equal(a.ws_cnt, b.ws_cnt) and np.array_equal(a.ws_key, b.ws_key) and np.array_equal(bits(a.ws_acc), bits(b.ws_acc))
+            differs |= word_bits(getattr(a, f)) != word_bits(getattr(b, f))
+        assert np.array_equal(a.ws_cnt, b.ws_cnt) and np.array_equal(a.ws_key, b.ws_key) and np.array_equal(word_bits(a.ws_acc), word_bits(b.ws_acc))
         collected = ~(a.sleep_time < 0) if allow_sleep else awake       # the collection looks behind the substep's sleep bookkeeping
         yield k, awake, d0, d1, differs, x0, y0, b, collected
     assert int(a.status.max()) == 0 and int(b.status.max()) == 0
@@ -133,7 +130,7 @@ def test_threshold_is_the_sum_kb_toi_wall_compares_with():
         tot = f32(float(r) + float(f32(2.0 * float(f32(0.005)))))
         target = max(f32(0.005), f32(float(tot) - float(f32(3.0 * float(f32(0.005))))))
         want = f32(float(target) + float(f32(0.25 * float(f32(0.005)))))
-        assert bits(tot) == bits(total) and bits(want) == bits(tt), (radius, total, tt, tot, want)
+        assert word_bits(tot) == word_bits(total) and word_bits(want) == word_bits(tt), (radius, total, tt, tot, want)
         closed_form_differs += int(f32(total - f32(2.75) * f32(0.005)).tobytes() != tt.tobytes())
     assert float(TS.thresholds(0.0001)[1]) == float(f32(0.005) + f32(0.25) * f32(0.005))      # the fmaxf decides for a tiny body
     print('total - 2.75 slop differs from the sum for %d of 6 radii' % closed_form_differs)

@@ -13,19 +13,11 @@ state, that of 200 a generic sorted-bin kernel of two waves, that of 16 a generi
 import numpy as np
 import pytest
 
-from tests import solver_regimes as SR
 from tests import toi_scenes as TS
-from tests import variant_census as VC
-from tests.test_parity_gpu import make_pair, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_ws_same, cpu, dev
+from tests.host_common import variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
 
 
 def assert_same_bits(osim, gsim, what, fields):

@@ -8,13 +8,9 @@ import pytest
 import torch
 
 from tests import variant_census as VC
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev, put_device
 
 pytestmark = pytest.mark.gpu
-
-
-def put_device(sim, name, val):
-    getattr(sim, name).copy_(dev(val))
 
 
 @pytest.mark.parametrize('row', VC.rows(), ids=VC.row_id)

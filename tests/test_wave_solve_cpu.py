@@ -7,23 +7,17 @@ import numpy as np
 import pytest
 
 from gym_kilobots_amd import _native as nat
-from gym_kilobots_amd import build as kb_build
 from oracle import oracle as O
 from tests import label_scenes as LS
 from tests import setup_scenes as SS
 from tests import solver_regimes as SR
 from tests import toi_scenes as TS
 from tests import wave_solve_scenes as WS
+from tests.host_common import lib  # noqa: F401
 
 # distances in world units from float32 coordinates of up to 25: a float has steps of 2e-6 there, a distance is a few
 # operations on them; two closed forms one iteration apart differ by 0.2 (2 slop) = 2e-3 at least
 DIST_TOL, FORM_GAP = 2e-5, 1e-3
-
-
-@pytest.fixture(scope='module')
-def lib():
-    kb_build.build()
-    return nat.load()
 
 
 def test_closed_form_of_a_pair_at_rest():

@@ -7,19 +7,11 @@ status --, then one fused launch of ten substeps.  The scenes of 1024 kilobots m
 generic sorted-bin kernel of two waves, those of 64 a one-wave workgroup."""
 import pytest
 
-from tests import solver_regimes as SR
-from tests import variant_census as VC
 from tests import wave_solve_scenes as WS
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, cpu, dev
+from tests.host_common import variants  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def variants(tmp_path_factory):
-    """kb_variants as tuples (drive, light, obj, fn, tier, poly, sense, sleep), from the header compiled on the host"""
-    listed, _ = VC.host_census(tmp_path_factory.mktemp('plan'), [SR.plan_inputs(64, 0, 0)])
-    return listed
 
 
 @pytest.mark.parametrize('case', WS.cases(), ids=WS.case_id)

@@ -38,6 +38,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from tests.scenes import case_id  # noqa: F401
+
 f32 = np.float32
 WORLD = 25.0                                # world units per metre
 WS, SLOP = f32(25.0), f32(0.005)
@@ -89,10 +91,6 @@ def scenes():
 def cases():
     """(scene, allow_sleep): the scene of 16 kilobots has no sleepers and runs without the sleep state only"""
     return [(s, sl) for s in scenes() for sl in (0, 1) if s.sleepers or not sl]
-
-
-def case_id(c):
-    return '%s-%s' % (c[0].name, 'sleep' if c[1] else 'nosleep')
 
 
 # ---- the rule, restated ----------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import numpy as np
 
 from oracle import oracle as O
 from tests import scenes
+from tests.scenes import put_numpy  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CENSUS = os.path.join(ROOT, 'tests', 'golden', 'variant_census.txt')
@@ -137,7 +138,7 @@ def spawn(N, seed_shift=0):
 
 def scene(row):
     """Everything a run of one census row needs:
-      E, N, mode, light, kw     arguments of tests.test_parity_gpu.make_pair / oracle.default_config
+      E, N, mode, light, kw     arguments of tests.gpu_common.make_pair / oracle.default_config
       block_threads             what to ask of kb_set_block_threads (0: keep kb_create's width)
       xy, th                    kilobot poses
       objects, ovx              object positions and their velocity at the start (None without objects)
@@ -240,10 +241,6 @@ def apply_start(s, sim, put):
         put(sim, 'ovx', s.ovx)
     for name, val in s.state.items():
         put(sim, name, val)
-
-
-def put_numpy(sim, name, val):
-    getattr(sim, name)[...] = val
 
 
 def oracle_sim(s):

@@ -33,6 +33,7 @@ contact is deeper than 3 slop = 0.6 mm):
 Which wave holds an island and how many iterations its position sweeps take does not show in what the oracle returns; the
 placement rule is the one restated in tests/setup_scenes.py (wave_loads), the iterations of a pair at rest follow from the
 closed form below (pair_after).  Shared by tests/test_wave_solve_cpu.py and tests/test_wave_solve_gpu.py."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
@@ -41,6 +42,7 @@ from tests import label_scenes as LS
 from tests import scenes
 from tests import setup_scenes as SS
 from tests import toi_scenes as TS
+from tests.scenes import case_id  # noqa: F401
 
 f32 = np.float32
 WORLD = 25.0
@@ -74,13 +76,7 @@ SCENES = [
 ]
 
 
-def cases():
-    """(scene, allow_sleep) of both test files"""
-    return [(s, sl) for s in SCENES for sl in (0, 1) if sl or not s.sleep_only]
-
-
-def case_id(c):
-    return '%s-%s' % (c[0].name, 'sleep' if c[1] else 'nosleep')
+cases = functools.partial(scenes.sleep_cases, SCENES)      # (scene, allow_sleep) of both test files
 
 
 # ---- structures: (xy [n, 2] metres around the lower left of the structure, role [n], heading or None) ------------------------

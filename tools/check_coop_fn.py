@@ -7,7 +7,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle as O
 from tests import scenes
-from tests.test_parity_gpu import make_pair, assert_same, assert_ws_same, dev
+from tests.gpu_common import make_pair, assert_same, assert_ws_same, dev
 
 for mode in (2, 4, 0):
     for pitch in (0.040, 0.034):

@@ -1,13 +1,15 @@
-"""Debug helper: one scene of tests/test_parity_fuzz_gpu.py (SEED=...), stepped like the test; prints every field that differs
-after each step.  KB_HIP_LIB selects an experiment build."""
+"""Debug helper: one scene of tests/test_parity_fuzz_gpu.py (SEED=...), started and stepped like the test; prints every field
+that differs after each launch.  SINGLE=1 splits every launch into single substeps and compares after each one, WS=1 compares
+the packed warm-start list as well.  KB_HIP_LIB selects an experiment build."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, '.')
-import tests.test_parity_fuzz_gpu as F
-from tests.test_parity_gpu import cpu, OBJ_FIELDS
+from tests import fuzz_scenes as FS
+from tests.gpu_common import assert_ws_same, cpu, dev, make_pair
 
 seed = int(os.environ.get('SEED', '0'))
-real_assert = F.assert_same
+
+
 def loud(osim, gsim, what='', fields=()):
     torch.cuda.synchronize()
     bad = False
@@ -25,28 +27,29 @@ def loud(osim, gsim, what='', fields=()):
             if getattr(osim, f, None) is not None and getattr(gsim, f, None) is not None:
                 print(f, 'oracle', np.asarray(getattr(osim, f)).ravel()[:16]); print(f, 'gpu   ', cpu(getattr(gsim, f)).ravel()[:16])
         raise SystemExit(1)
-F.assert_same = loud
-if os.environ.get('SINGLE'):
-    # split every fused step into single-substep launches and compare after each one
-    real_make = F.make_pair
-    def make_pair(*a, **k):
-        osim, gsim = real_make(*a, **k)
-        ostep, gstep = osim.step, gsim.step
-        state = {'n': 0}
-        def o_step(n=1, **kw):
-            state['pending'] = (n, kw)
-        def g_step(n=1, actions=None, light_action=None, **kw):
-            on, okw = state['pending']
-            for i in range(n):
-                ostep(1, **okw)
-                gstep(1, actions=actions, light_action=light_action, **kw)
-                state['n'] += 1
-                loud(osim, gsim, 'substep %d' % state['n'], ('x', 'y', 'theta') + (('sleep_time',) if osim.cfg.allow_sleep else ()) + (tuple(OBJ_FIELDS[3:]) if osim.cfg.num_objects else ()))
-                if os.environ.get('WS'):
-                    from tests.test_parity_gpu import assert_ws_same
-                    assert_ws_same(osim, gsim, 'substep %d' % state['n'])
-        osim.step, gsim.step = o_step, g_step
-        return osim, gsim
-    F.make_pair = make_pair
-F.test_random_scene.__wrapped__(seed) if hasattr(F.test_random_scene, '__wrapped__') else F.test_random_scene(seed)
+    if os.environ.get('WS'):
+        assert_ws_same(osim, gsim, what)
+
+s = FS.scene(seed)
+osim, gsim = make_pair(s.E, s.N, s.mode, s.light, xy=s.xy, th=s.th, **s.kw)
+written = FS.start(s, osim)
+if s.nobj:
+    gsim.set_objects_m(s.objs, s.oth)
+for name in written:
+    getattr(gsim, name).copy_(dev(getattr(osim, name)).reshape(getattr(gsim, name).shape))
+substeps = 0
+for k, (n_sub, a, la) in enumerate(s.launches):
+    if a is not None:
+        osim.set_actions(a)
+    ga, gla = None if a is None else dev(a), None if la is None else dev(la)
+    for n in [1] * n_sub if os.environ.get('SINGLE') else [n_sub]:
+        osim.step(n, light_action=la)
+        gsim.step(n, actions=ga, light_action=gla)
+        substeps += n
+        torch.cuda.synchronize()
+        if ((osim.status | cpu(gsim.status)) & ~2).any():
+            # capacity or a staging limit: what the flagged env computes is unspecified, the test ends the scene here
+            print('%s launch %d: status oracle %s gpu %s, the scene ends' % (s.what, k, osim.status, cpu(gsim.status)))
+            raise SystemExit(0)
+        loud(osim, gsim, '%s launch %d substep %d' % (s.what, k, substeps), s.fields)
 print('seed', seed, 'ok')

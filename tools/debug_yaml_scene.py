@@ -3,7 +3,8 @@ on the oracle-backed env; prints the first field that differs.  Knobs: TOI, MODE
 KB_HIP_LIB (experiment build)."""
 import os, sys, numpy as np, torch, yaml
 sys.path.insert(0, '.')
-from tests.test_env_api_gpu import YAML_BOXES
+from tests.env_scenes import YAML_BOXES
+from tests.gpu_common import assert_ws_same
 from tests.oracle_backend import OracleBackend
 from gym_kilobots_amd.envs import YamlKilobotsEnv
 from gym_kilobots_amd.sim import KilobotSim
@@ -34,7 +35,6 @@ for k in range(10):
     gs.step(1, light_action=la.cuda()); os_.step(1, light_action=la)
     bad = cmp('substep %d' % k)
     try:
-        from tests.test_parity_gpu import assert_ws_same
         assert_ws_same(os_.o, gs, 'substep %d' % k)
     except AssertionError as ex:
         print('WS', ex); bad = True
