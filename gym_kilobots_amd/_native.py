@@ -132,6 +132,8 @@ SIGNATURES = {
     'kb_sense_grid': (_I, [_P, _I, _I, _I, _P, _P]),
     'kb_sense_coverage': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P]),
     'kb_field_step': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'kb_path_costs': (_I, [_P, _I, _I, _P]),
+    'kb_sense_paths': (_I, [_P, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_sense_targets': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
@@ -161,7 +163,7 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 # an older build of the library that KB_HIP_LIB selects for an A/B (tools/ab_bench.py) has not got these: it loads, and calling
 # one of them on it raises AttributeError
-OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds', 'kb_sense_clusters'}
+OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds', 'kb_sense_clusters', 'kb_sense_paths'}
 
 _lib = None
 
@@ -328,6 +330,63 @@ def check_field(width, height, channels, keep, spread, iters):
     if not 0 <= iters <= FIELD_MAX_ITERS:
         raise ValueError('iters must be in 0..%d' % FIELD_MAX_ITERS)
     return width, height, channels, keep, spread, iters
+
+
+def check_paths(width, height, clearance_m=0.0):
+    """The limits of kb_sense_paths on the grid and the clearance; ValueError where the library would answer KB_EINVAL.
+    Returns (width, height, clearance_m)."""
+    width, height = check_coverage(width, height)
+    clearance_m = float(clearance_m)
+    if not 0.0 <= clearance_m < float('inf'):
+        raise ValueError('clearance_m must be finite and not negative')
+    return width, height, clearance_m
+
+
+def check_path_objects(objects, num_objects):
+    """The objects that block the paths of kb_sense_paths as a mask: 'all', a mask below 2^num_objects or an iterable of object
+    indices; ValueError where the library would answer KB_EINVAL."""
+    if isinstance(objects, str):
+        if objects != 'all':
+            raise ValueError("objects must be 'all', a mask or an iterable of object indices")
+        return (1 << num_objects) - 1
+    if isinstance(objects, bool):
+        raise ValueError("objects must be 'all', a mask or an iterable of object indices")
+    if not isinstance(objects, int):
+        mask = 0
+        for m in objects:
+            if isinstance(m, bool) or not 0 <= int(m) < num_objects:
+                raise ValueError('objects: object indices must be in 0..%d' % (num_objects - 1))
+            mask |= 1 << int(m)
+        objects = mask
+    if not 0 <= objects < (1 << num_objects):
+        raise ValueError('objects must be a mask below 2^num_objects (%d objects)' % num_objects)
+    return objects
+
+
+def path_cells(arena, points_m, width, height):
+    """The uint8 mask [E, height, width] ([1, height, width] for shared points) of the cells of kb_sense_grid's width x height
+    grid over arena = (xmin, xmax, ymin, ymax) in world units (kb_outline.arena) that points in metres fall in: points_m
+    array-like [E, K, 2] or [K, 2].  The cell rule of the header in float32, every operation rounded on its own: world
+    units = metres * 25.0f;  t = (v - min) * ((float)n / (max - min));  cell 0 if !(t > 0) (NaN included), n - 1 if t >= n,
+    otherwise the truncation of t.  Host only."""
+    import numpy as np
+    width, height = check_coverage(width, height)
+    f32 = np.float32
+    pts = np.asarray(points_m, dtype=f32)
+    if pts.ndim not in (2, 3) or pts.shape[-1] != 2:
+        raise ValueError('points_m must have the shape (K, 2) or (E, K, 2)')
+    pts = pts.reshape((-1,) + pts.shape[-2:])
+    xmin, xmax, ymin, ymax = (f32(v) for v in arena)
+
+    def axis(v, lo, hi, n):
+        with np.errstate(invalid='ignore', over='ignore'):
+            t = (v * f32(WORLD_SCALE) - lo) * (f32(n) / (hi - lo))
+            low, high = ~(t > 0), t >= f32(n)
+            return np.where(low, 0, np.where(high, n - 1, np.where(low | high, f32(0), t).astype(np.int64)))
+    ix, iy = axis(pts[..., 0], xmin, xmax, width), axis(pts[..., 1], ymin, ymax, height)
+    mask = np.zeros((pts.shape[0], height * width), dtype=np.uint8)
+    np.put_along_axis(mask, iy * width + ix, 1, axis=1)
+    return mask.reshape(-1, height, width)
 
 
 def check_targets(n_targets, tol_m):

@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage, kb_sense_targets, kb_field_step) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage, kb_sense_targets, kb_field_step, kb_sense_paths) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -1022,6 +1022,55 @@ int kb_field_step(kb_sim *sim, int gw, int gh, int n_channels, const float *keep
     const kb_field_fn fn = vec ? field_kernel<true>(gw * gh) : field_kernel<false>(gw * gh);
     return launch("kb_field_step", fn, (unsigned)p.E * (unsigned)n_channels, FIELD_THREADS, FieldLds(gw, gh).bytes, stream, a, p.buf.x, p.buf.y, p.buf.theta,
                   d_env_mask, d_amount, d_field, reinterpret_cast<float4 *>(d_sense));
+}
+
+// the step costs of kb_sense_paths and the unit vector of its diagonals, from the host constants of kb_sense_grid
+static void path_costs(const Params &p, int gw, int gh, PathsArgs &a) {
+    const float cw = (p.xmax - p.xmin) / (float)gw, ch = (p.ymax - p.ymin) / (float)gh;      // (kb_outline.arena is these four)
+    const float dg = sqrtf(cw * cw + ch * ch);
+    const auto q = [](float len) { return (int)rintf(fminf(fmaxf(len * 1024.0f, 1.0f), 65536.0f)); };
+    a.cw = cw; a.ch = ch;
+    a.qx = q(cw); a.qy = q(ch); a.qd = q(dg);
+    a.udx = cw / dg; a.udy = ch / dg;
+}
+
+int kb_path_costs(const kb_sim *sim, int gw, int gh, int32_t *out) {
+    if (!sim || !out) return fail(KB_EINVAL, "kb_path_costs: NULL argument");
+    if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_path_costs: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
+    PathsArgs a;
+    path_costs(sim->p, gw, gh, a);
+    out[0] = a.qx; out[1] = a.qy; out[2] = a.qd;
+    return KB_OK;
+}
+
+int kb_sense_paths(kb_sim *sim, int gw, int gh, const uint8_t *d_source, const uint8_t *d_blocked, int objects, float clear_m, float *d_dist,
+                   int8_t *d_next, float *d_bot, float *d_stats, void *stream) {
+    if (!sim || !d_source) return fail(KB_EINVAL, "kb_sense_paths: NULL argument");
+    if (gw < 1 || gw > KB_GRID_MAX_SIDE || gh < 1 || gh > KB_GRID_MAX_SIDE) return fail(KB_EINVAL, "kb_sense_paths: 1 <= gw, gh <= KB_GRID_MAX_SIDE (128) required");
+    if (objects < 0 || objects >= (1 << sim->cfg.num_objects)) return fail(KB_EINVAL, "kb_sense_paths: objects must be a mask of the handle's objects (0 <= objects < 2^num_objects)");
+    if (!(clear_m >= 0.0f) || !std::isfinite(clear_m)) return fail(KB_EINVAL, "kb_sense_paths: clear_m must be finite and not negative");
+    if (!d_dist && !d_next && !d_bot && !d_stats) return fail(KB_EINVAL, "kb_sense_paths: d_dist, d_next, d_bot and d_stats are all NULL");
+    if (!aligned16(d_bot)) return fail(KB_EINVAL, "kb_sense_paths: d_bot must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_paths: kb_bind() first");
+    const Params &p = sim->p;
+    PathsArgs a;
+    memset(&a, 0, sizeof(a));
+    path_costs(p, gw, gh, a);
+    a.N = p.N; a.gw = gw; a.gh = gh; a.objects = objects; a.clear = clear_m > 0.0f;
+    a.xmin = p.xmin; a.ymin = p.ymin;
+    a.icw = (float)gw / (p.xmax - p.xmin); a.ich = (float)gh / (p.ymax - p.ymin);
+    const float Cw = clear_m * WORLD_SCALE;
+    a.C2 = Cw * Cw;
+    kb_outline ol;
+    kb_get_outline(sim, &ol);
+    const int lds = PathsLds(gw, gh).bytes;
+    if (lds > GRID_LDS_LIMIT) {
+        // the attribute belongs to the kernel on the current device: raised to the hardware limit, as for the step kernels
+        const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kb_paths_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
+        if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_paths: hipFuncSetAttribute: %s", hipGetErrorString(err));
+    }
+    return launch("kb_sense_paths", kb_paths_kernel, p.E, PATHS_THREADS, lds, stream, ol, a, p.buf.x, p.buf.y, p.buf.theta, p.buf.ox, p.buf.oy, p.buf.otheta,
+                  d_source, d_blocked, d_dist, reinterpret_cast<signed char *>(d_next), reinterpret_cast<float4 *>(d_bot), d_stats);
 }
 
 int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, const uint8_t *d_bot_select,

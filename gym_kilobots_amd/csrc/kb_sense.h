@@ -4,8 +4,9 @@
 // the slots of a target shape, every kilobot against every slot, and needs none either; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; kb_field_step, which keeps a pheromone field of the caller's, a plane per workgroup,
-// in registers and LDS while the kilobots add to it, it diffuses and they read it; and kb_render, which draws every env as an
-// RGB frame, a range query per pixel.
+// in registers and LDS while the kilobots add to it, it diffuses and they read it; kb_sense_paths, which relaxes the
+// shortest-path distances of an env's grid to its goal cells round the objects, a plane per workgroup in LDS until nothing
+// changes; and kb_render, which draws every env as an RGB frame, a range query per pixel.
 // Each kernel's LDS image is defined once, in the struct in front of it: the kernel takes its pointers from it, the entry
 // point (kb_abi.hip) the dynamic-LDS size.  Included by kb_abi.hip only.
 #pragma once
@@ -859,6 +860,167 @@ __global__ void __launch_bounds__(FIELD_THREADS) kb_field_kernel(const FieldArgs
             float sn, cs;
             kb_sincosf(theta[o + b], sn, cs);
             sense[(o + b) * a.C + c] = make_float4(val, cs * dx + sn * dy, cs * dy - sn * dx, amount ? (float)bacc[s] / 65536.0f : 0.0f);
+        }
+    }
+}
+
+// ---- kb_sense_paths: obstacle-aware distance-to-goal fields of every env ------------------------------------------------------
+constexpr int PATHS_THREADS = 512;
+constexpr int PATH_BLOCKED = 0x7FFFFFFF, PATH_NONE = 0x7FFFFFFE;    // the two words of the plane that are no distance: never added to
+constexpr int PATH_LIMIT = 1 << 30;                                 // every distance lies below it, both sentinels above
+struct PathsArgs {          // the grid, the host constants and the step costs of the definition (include/kilobots_hip.h)
+    int N, gw, gh, objects, clear, qx, qy, qd;
+    float xmin, ymin, cw, ch, icw, ich, C2, udx, udy;
+};
+struct PathsLds {           // byte offsets: the int32 plane at 0, aux (u32 flag[3], dmax; u64 sum; u32 count, reached), the ObjectsLds image
+    int aux, obj, bytes;
+    __host__ __device__ constexpr PathsLds(int gw, int gh) : aux((4 * gw * gh + 15) & ~15), obj(aux + 32), bytes(obj + ObjectsLds().bytes) {}
+};
+// The plane alone is the whole default limit for dynamic LDS at the largest grid: the entry point raises the limit of this
+// kernel (hipFuncAttributeMaxDynamicSharedMemorySize) for the grids that need it; two workgroups still share a CU.
+static_assert(PathsLds(KB_GRID_MAX_SIDE, KB_GRID_MAX_SIDE).bytes > GRID_LDS_LIMIT && 2 * PathsLds(KB_GRID_MAX_SIDE, KB_GRID_MAX_SIDE).bytes <= LDS_CU,
+              "kb_paths_kernel: LDS image, above the default limit at the largest grid: the limit is raised");
+static_assert(KB_GRID_MAX_SIDE * KB_GRID_MAX_SIDE * 65536ll <= PATH_LIMIT && OBJ_EDGES <= PATHS_THREADS && KB_MAX_BOTS <= 2 * PATHS_THREADS,
+              "kb_paths_kernel: distances below 2^30, one lane per staged edge");
+
+// The least D(b) + w_k over the moves from cell (ix, iy) of the plane to a neighbour b that is inside the grid and reached
+// (PATH_NONE if there is none), and in kbest the lowest direction k that attains it.  CORNER: a diagonal move needs both
+// axial cells beside it free.  The eight neighbours are read once; one outside the grid counts as blocked.
+template <bool CORNER>
+__device__ __forceinline__ int kb_path_relax(const int *pl, const PathsArgs &a, const int ix, const int iy, int &kbest) {
+    constexpr int DX[8] = {1, 1, 0, -1, -1, -1, 0, 1}, DY[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+    int n[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int bx = ix + DX[k], by = iy + DY[k];
+        n[k] = (unsigned)bx < (unsigned)a.gw && (unsigned)by < (unsigned)a.gh ? pl[by * a.gw + bx] : PATH_BLOCKED;
+    }
+    int best = PATH_NONE;
+    kbest = -1;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        bool ok = n[k] < PATH_LIMIT;
+        if (CORNER && (k & 1)) ok = ok && n[k - 1] != PATH_BLOCKED && n[(k + 1) & 7] != PATH_BLOCKED;
+        const int cand = ok ? n[k] + (k & 1 ? a.qd : k & 2 ? a.qy : a.qx) : PATH_NONE;        // (a sentinel is never added to)
+        if (cand < best) { best = cand; kbest = k; }
+    }
+    return best;
+}
+
+// One workgroup per env; the integer plane D lives in LDS from the blocked-plane pass to the last store.  Blocked plane: the
+// env's object frames and the fixture table are staged (kb_stage_objects) and every lane asks kb_object_walk about the centres
+// of its cells (cell g of the plane belongs to lane g % PATHS_THREADS: consecutive lanes, consecutive words); a blocked cell
+// holds PATH_BLOCKED, a free source 0, any other free cell PATH_NONE.  Sweeps: every lane relaxes its cells in place from
+// their eight neighbours in LDS (kb_path_relax) and stores a value only where it fell.  Values only ever fall, so a stale read
+// is harmless, and a sweep in which no lane stored has read the fixed point: the lanes that stored raise the sweep's flag
+// word, one barrier, every lane reads it (three words in rotation: the word of sweep s + 2 is cleared after the barrier of
+// sweep s, when its last readers have passed and its next writers have not started).  The loop runs at most gw * gh + 1 times
+// whatever the plane holds.  next, the kilobot rows and the stats are taken from the final plane in LDS.
+__global__ void __launch_bounds__(PATHS_THREADS) kb_paths_kernel(const kb_outline ol, const PathsArgs a, const float *x, const float *y, const float *theta,
+                                                                 const float *ox, const float *oy, const float *otheta, const uint8_t *source,
+                                                                 const uint8_t *blocked, float *dist, signed char *next, float4 *bot, float *stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int tid = threadIdx.x, e = blockIdx.x;
+    const int gw = a.gw, gh = a.gh, cells = gw * gh;
+    const PathsLds L(gw, gh);
+    int *pl = reinterpret_cast<int *>(smem);
+    unsigned *flag = reinterpret_cast<unsigned *>(smem + L.aux), *dmax = flag + 3, *count = flag + 6, *reached = flag + 7;
+    unsigned long long *sum = reinterpret_cast<unsigned long long *>(smem + L.aux + 16);
+    const ObjectsImage I(smem + L.obj);
+    const size_t co = (size_t)e * cells, o = (size_t)e * a.N;
+    // a lane's cells g = tid, tid + PATHS_THREADS, ...: (ix, iy) advance by (sx, sy) with one carry, no division per cell
+    const int iy0 = tid / gw, ix0 = tid - iy0 * gw, sy = PATHS_THREADS / gw, sx = PATHS_THREADS - sy * gw;
+    const auto advance = [&](int &ix, int &iy) { ix += sx; iy += sy; if (ix >= gw) { ix -= gw; ++iy; } };
+
+    if (a.objects) kb_stage_objects(ol, I, e, tid, ox, oy, otheta);
+    if (tid < 8) flag[tid] = 0u;
+    for (int g = tid, ix = ix0, iy = iy0; g < cells; g += PATHS_THREADS, advance(ix, iy)) {
+        bool blk = blocked && blocked[co + g] != 0;
+        if (a.objects) {
+            const float cx = a.xmin + ((float)ix + 0.5f) * a.cw, cy = a.ymin + ((float)iy + 0.5f) * a.ch;
+            for (int m = 0; m < ol.num_objects; ++m) {
+                if (!(a.objects >> m & 1)) continue;
+                float best, brx, bry;
+                const bool inside = kb_object_walk(I, m, I.frame[m], cx, cy, best, brx, bry);
+                blk = blk || inside || (a.clear && !(best > a.C2));
+            }
+        }
+        pl[g] = blk ? PATH_BLOCKED : source[co + g] != 0 ? 0 : PATH_NONE;
+    }
+    __syncthreads();
+
+    for (int sweep = 0; sweep <= cells; ++sweep) {
+        bool changed = false;
+        for (int g = tid, ix = ix0, iy = iy0; g < cells; g += PATHS_THREADS, advance(ix, iy)) {
+            const int u = pl[g];
+            if (u == PATH_BLOCKED || u == 0) continue;
+            int k;
+            const int v = kb_path_relax<true>(pl, a, ix, iy, k);
+            if (v < u) { pl[g] = v; changed = true; }
+        }
+        unsigned *f = flag + sweep % 3;
+        if (changed) *f = 1u;
+        __syncthreads();
+        const unsigned any = *f;
+        if (tid == 0) flag[(sweep + 2) % 3] = 0u;
+        if (!any) break;        // (the same word in every lane: the workgroup leaves together)
+    }
+
+    if (dist || next || stats) {
+        unsigned n = 0u;
+        for (int g = tid, ix = ix0, iy = iy0; g < cells; g += PATHS_THREADS, advance(ix, iy)) {
+            const int u = pl[g];
+            const bool fin = u < PATH_LIMIT;
+            n += fin ? 1u : 0u;
+            if (dist) dist[co + g] = fin ? ((float)u / 1024.0f) / 25.0f : INFINITY;
+            if (next) {
+                int k = u == PATH_BLOCKED ? -3 : u == PATH_NONE ? -2 : -1;
+                if (fin && u != 0) kb_path_relax<true>(pl, a, ix, iy, k);
+                next[co + g] = (signed char)k;
+            }
+        }
+        if (stats && n) atomicAdd(reached, n);
+    }
+    if (bot || stats) {
+        unsigned cnt = 0u, far = 0u;
+        unsigned long long tot = 0ull;
+        for (int b = tid; b < a.N; b += PATHS_THREADS) {        // the cell rule of kb_grid_bots_kernel
+            const float tx = (x[o + b] - a.xmin) * a.icw, ty = (y[o + b] - a.ymin) * a.ich;
+            const int ix = !(tx > 0.0f) ? 0 : tx >= (float)gw ? gw - 1 : (int)tx;
+            const int iy = !(ty > 0.0f) ? 0 : ty >= (float)gh ? gh - 1 : (int)ty;
+            const int u = pl[iy * gw + ix];
+            int Db = PATH_NONE, k = -1;
+            float fl = 3.0f;
+            if (u == PATH_BLOCKED) {
+                Db = kb_path_relax<false>(pl, a, ix, iy, k);
+                if (Db < PATH_LIMIT) fl = 2.0f;
+            } else if (u < PATH_LIMIT) {
+                Db = u;
+                fl = 1.0f;
+                if (u != 0) { kb_path_relax<true>(pl, a, ix, iy, k); fl = 0.0f; }
+            }
+            const bool fin = Db < PATH_LIMIT;
+            if (fin) { ++cnt; tot += (unsigned long long)Db; far = max(far, (unsigned)Db); }
+            if (bot) {
+                float fx = 0.0f, fy = 0.0f;
+                if (fin && k >= 0) {
+                    const int dx = (k <= 1 || k == 7) ? 1 : (k >= 3 && k <= 5) ? -1 : 0, dy = (k >= 1 && k <= 3) ? 1 : k >= 5 ? -1 : 0;
+                    const float ux = (float)dx * (k & 1 ? a.udx : 1.0f), uy = (float)dy * (k & 1 ? a.udy : 1.0f);
+                    float sn, cs;
+                    kb_sincosf(theta[o + b], sn, cs);
+                    fx = cs * ux + sn * uy;
+                    fy = cs * uy - sn * ux;
+                }
+                bot[o + b] = make_float4(fin ? ((float)Db / 1024.0f) / 25.0f : INFINITY, fx, fy, fl);
+            }
+        }
+        if (stats && cnt) { atomicAdd(count, cnt); atomicAdd(sum, tot); atomicMax(dmax, far); }
+    }
+    if (stats) {
+        __syncthreads();
+        if (tid == 0) {
+            float *row = stats + 4 * (size_t)e;
+            row[0] = (float)*count; row[1] = ((float)(long long)*sum / 1024.0f) / 25.0f; row[2] = ((float)*dmax / 1024.0f) / 25.0f; row[3] = (float)*reached;
         }
     }
 }

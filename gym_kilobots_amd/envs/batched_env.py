@@ -57,6 +57,11 @@ def _target_obs(value, num_objects):
     return (points,) + nat.check_targets(points.shape[-2], tol_m)[1:]
 
 
+def _path_obs(value, num_objects):
+    width, height, clearance_m = tuple(value) if len(value) == 3 else tuple(value) + (0.0,)
+    return nat.check_paths(width, height, clearance_m)
+
+
 def _contact_obs(value, num_objects):
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= value <= nat.MAX_CONTACT_SLOTS:
         raise ValueError('contact_obs must be an int in 0..%d or None' % nat.MAX_CONTACT_SLOTS)
@@ -95,6 +100,7 @@ OPTIONS = {
     'coverage_obs': Option(_coverage_obs, '(width, height)', ('coverage',), 'coverage', '(width, height)', 'observe nearest-kilobot fields'),
     'field_obs': Option(_field_obs, '(width, height) or (width, height, channels)', (), None, '(width, height[, channels])', 'keep a pheromone field'),
     'target_obs': Option(_target_obs, '(points_m, tol_m)', ('targets',), 'targets', '(points_m, tol_m)', 'observe the slots of a target shape'),
+    'path_obs': Option(_path_obs, '(width, height) or (width, height, clearance_m)', ('paths',), 'paths', '(width, height[, clearance_m])', 'observe distance-to-goal fields'),
     'contact_obs': Option(_contact_obs, None, ('contacts',), 'contacts', 'k', 'observe contacts'),
     'ray_obs': Option(_ray_obs, '(radius_m, n_rays) or (radius_m, n_rays, targets)', ('rays',), 'rays', '(radius_m, n_rays[, targets])', 'observe range scans'),
     'edge_obs': Option(_edge_obs, 'radius_m or (radius_m, capacity)', ('edges',), 'edges', 'radius_m or (radius_m, capacity)', 'observe the IR-range graph'),
@@ -112,7 +118,7 @@ class BatchedKilobotsEnv(object):
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
                  object_obs=None, grid_obs=None, coverage_obs=None, target_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
                  max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None,
-                 field_obs=None, field_keep=1.0, field_spread=0.0, field_iters=1, deposit_fn=None, **cfg):
+                 field_obs=None, field_keep=1.0, field_spread=0.0, field_iters=1, deposit_fn=None, path_obs=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -150,6 +156,12 @@ class BatchedKilobotsEnv(object):
         'contacts'.  None adds nothing.
         render_size: (width, height) in pixels lets render('rgb_array') return the frames of every env, [E, height, width, 3]
         uint8 on the device (KilobotSim.render).  reset(), step() and the info dict do not change with it.
+        path_obs: (width, height) or (width, height, clearance_m) adds the obstacle-aware distance-to-goal field of a pushing or
+        navigation task: paths() returns the named tuple (dist [E, height, width], step [E, height, width], bots [E, N, 4],
+        stats [E, 4]) of KilobotSim.paths -- the shortest-path distance of every cell to the goal round the objects, the
+        direction of descent, and for every kilobot the metres still to go and the way in its own frame -- and step() puts
+        the tuple in its info dict under 'paths'.  set_path_goal() sets the goal (positions or cells), set_path_blocked()
+        further blocked cells; without a goal every kilobot is unreachable.
         ray_obs: (radius_m, n_rays) or (radius_m, n_rays, targets) adds the range scan of a decentralised policy: rays() returns
         (dist [E, N, n_rays], hit [E, N, n_rays]), how far the first kilobot, object or wall along each of n_rays bearings in
         every kilobot's own frame is and what it is (KilobotSim.rays; targets made of 'bots', 'objects' and 'walls', default:
@@ -196,7 +208,7 @@ class BatchedKilobotsEnv(object):
         self._on_status, self._status_interval, self._steps = on_status, max(1, int(status_interval)), 0
         self.reward_fn = reward_fn
         given = dict(neighbor_obs=neighbor_obs, histogram_obs=histogram_obs, comm_radius=comm_radius, object_obs=object_obs, grid_obs=grid_obs, coverage_obs=coverage_obs, target_obs=target_obs,
-                     contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs, field_obs=field_obs)
+                     contact_obs=contact_obs, render_size=render_size, ray_obs=ray_obs, edge_obs=edge_obs, field_obs=field_obs, path_obs=path_obs)
         for name, option in OPTIONS.items():
             value = given[name]
             if value is not None:
@@ -235,6 +247,11 @@ class BatchedKilobotsEnv(object):
         self._observe_kw = {}       # keyword arguments the sim method of an observation gets besides the stored value
         if self.target_obs is not None:         # the points live on the device from here on: (tensor, tol_m)
             self.target_obs = (self._target_points(self.target_obs[0]), self.target_obs[1])
+        if self.path_obs is not None:           # (width, height) from here on; the goal and the blocked cells live on the device
+            width, height, clearance_m = self.path_obs
+            self.path_obs = (width, height)
+            self._observe_kw['path_obs'] = dict(source=torch.zeros(self.num_envs, height, width, dtype=torch.uint8, device=dev), blocked=None,
+                                                clearance_m=clearance_m)
         self.field, self.deposit_fn = None, deposit_fn
         if self.field_obs is not None:          # the env owns the field; keep, spread and iters are checked once, here
             self._field_kw = dict(zip(('keep', 'spread', 'iters'), nat.check_field(*self.field_obs, field_keep, field_spread, field_iters)[3:]))
@@ -476,6 +493,36 @@ class BatchedKilobotsEnv(object):
         float32) of the current poses for the target_obs=(points_m, tol_m) the env was created with, over the slots
         set_targets() selected: KilobotSim.targets."""
         return self._observe('target_obs')
+
+    def _path_mask(self, cells, name):
+        """A caller's cell mask, array-like or tensor [height, width] or [E, height, width], as uint8 [E, height, width] on the
+        sim's device."""
+        width, height = self._stored('path_obs')
+        t = torch.as_tensor(cells.cpu().numpy() if torch.is_tensor(cells) else np.asarray(cells))
+        if t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (height, width) or (t.dim() == 3 and t.shape[0] != self.num_envs):
+            raise ValueError('%s: cells must have the shape (%d, %d) or (%d, %d, %d)' % (name, height, width, self.num_envs, height, width))
+        return t.ne(0).to(torch.uint8).expand(self.num_envs, height, width).contiguous().to(self.sim.x.device)
+
+    def set_path_goal(self, points_m=None, cells=None):
+        """Set the goal of path_obs: points_m array-like [K, 2] or [E, K, 2] metres, the cells they fall in
+        (KilobotSim.path_cells), or cells, a mask [height, width] or [E, height, width] of the goal cells; exactly one of
+        the two.  An env is created without a goal: every kilobot is unreachable until one is set."""
+        width, height = self._stored('path_obs')
+        if (points_m is None) == (cells is None):
+            raise ValueError('set_path_goal: give either points_m or cells')
+        self._observe_kw['path_obs']['source'] = self.sim.path_cells(points_m, width, height) if cells is None else self._path_mask(cells, 'set_path_goal')
+
+    def set_path_blocked(self, cells):
+        """Set the cells that block the paths of path_obs besides the objects: a mask [height, width] or [E, height, width];
+        None: none."""
+        self._stored('path_obs')
+        self._observe_kw['path_obs']['blocked'] = None if cells is None else self._path_mask(cells, 'set_path_blocked')
+
+    def paths(self):
+        """The named tuple (dist [E, height, width] float32, step [E, height, width] int8, bots [E, N, 4] float32, stats [E, 4]
+        float32) of the current poses for the path_obs=(width, height[, clearance_m]) the env was created with, to the goal
+        of set_path_goal() round the objects and the cells of set_path_blocked(): KilobotSim.paths."""
+        return self._observe('path_obs')
 
     def contacts(self):
         """(partner [E, N, k] int32, impulse [E, N, k] float32, touch [E, N, 4] float32, obj [E, M, 2] float32 or None) of the

@@ -20,6 +20,8 @@ Edges = collections.namedtuple('Edges', ('src', 'dst', 'rel', 'offsets', 'count'
 Coverage = collections.namedtuple('Coverage', ('owner', 'dist', 'cells', 'stats'))
 # ... and KilobotSim.targets
 Targets = collections.namedtuple('Targets', ('index', 'rel', 'owner', 'dist', 'stats'))
+# ... and KilobotSim.paths
+Paths = collections.namedtuple('Paths', ('dist', 'step', 'bots', 'stats'))
 
 # the dtypes a caller's tensor may have: floats, a mask (env_mask, seeds) and 32-bit words (colours, episode counters)
 F32, I32, I64, MASK = (torch.float32,), (torch.int32,), (torch.int64,), (torch.bool, torch.uint8)
@@ -583,6 +585,59 @@ class KilobotSim:
             raise ValueError('out: rel must be 16-byte aligned')
         self._call('kb_sense_targets', pp, K, int(per_env), tol_m, pb, ps, *map(_ptr, parts))
         return Targets(*parts)
+
+    def path_costs(self, width, height):
+        """The integer step costs (qx, qy, qd) of paths() on a width x height grid (kb_path_costs): a move along x, along y and
+        along a diagonal in 1/1024 world units, i.e. 1 / 25600 metres.  Host only."""
+        width, height = nat.check_paths(width, height)[:2]
+        q = (C.c_int32 * 3)()
+        nat.check(self._lib.kb_path_costs(self._h, width, height, q), 'kb_path_costs')
+        return tuple(q)
+
+    def path_cells(self, points_m, width, height):
+        """The uint8 mask [E, height, width] of the cells of the width x height grid that points in metres fall in: points_m
+        array-like or tensor [E, K, 2] or [K, 2] (shared by all envs), binned on the host by the grid's cell rule
+        (nat.path_cells: a point outside the arena lands in the nearest edge cell) and uploaded.  What lets the goal of
+        paths() be given as positions; not for the inner loop."""
+        points = np.asarray(points_m.cpu() if torch.is_tensor(points_m) else points_m, dtype=np.float32)
+        if points.ndim == 3 and points.shape[0] != self.num_envs:
+            raise ValueError('points_m must have the shape (K, 2) or (%d, K, 2)' % self.num_envs)
+        mask = nat.path_cells(self.outline().arena, points, width, height)
+        return torch.from_numpy(np.broadcast_to(mask, (self.num_envs, height, width)).copy(order='C')).to(self.device)
+
+    def paths(self, width, height, source, blocked=None, objects='all', clearance_m=0.0, dist=True, step=True, bots=True, stats=True, out=None):
+        """Obstacle-aware distance-to-goal fields on the current poses (kb_sense_paths; no reference counterpart): the arena of
+        every env cut into width x height cells as in occupancy_grid(), and for every cell the length of the shortest
+        8-connected path to the nearest cell of `source` that crosses no blocked cell and cuts no corner.  source, blocked:
+        [E, height, width] bool or uint8 on the sim's device (path_cells() makes one from positions); blocked None blocks
+        nothing.  objects: which objects of the sim block as well -- 'all', a mask or an iterable of object indices (0 or ():
+        none); a cell is blocked where its centre is inside the object or, with clearance_m > 0, within clearance_m of its
+        outline (a kilobot radius keeps the path wide enough for a kilobot).  Returns the named tuple Paths(dist, step, bots,
+        stats): dist [E, height, width] float32, metres to go, +inf where blocked or cut off; step [E, height, width] int8, the
+        direction 0..7 of the next cell (counter-clockwise from +x in steps of 45 degrees), -1 at a goal cell, -2 where cut
+        off, -3 where blocked; bots [E, N, 4] float32 = (metres to go from the kilobot's cell, the unit vector of the next move
+        ahead and to the left in the kilobot's own frame, flag: 0 on a free reached cell, 1 on a goal cell, 2 on a blocked cell
+        with a free reached neighbour -- the normal case for a kilobot pressing on an object: it gets the best way out --, 3
+        unreachable with +inf and a zero direction); stats [E, 4] float32 = (kilobots that can reach the goal, the sum of their
+        metres to go, the largest of them, free cells reached).  All distances are integer sums: nothing depends on any
+        order.  A part switched off (dist=False, ...) is None and is not computed; at least one must be on.  out: the
+        preallocated contiguous tensors to write into, a tuple of the parts that are on; every element is written."""
+        E, N = self.num_envs, self.num_bots
+        width, height, clearance_m = nat.check_paths(width, height, clearance_m)
+        objects = nat.check_path_objects(objects, self.num_objects)
+        wanted = [bool(dist), bool(step), bool(bots), bool(stats)]
+        if not any(wanted):
+            raise ValueError('paths: at least one of dist, step, bots and stats must be on')
+        ps = self._input(source, MASK, (E, height, width), 'source')
+        pb = self._input(blocked, MASK, (E, height, width), 'blocked', optional=True)
+        shapes = [s for s, w in zip([((E, height, width), torch.float32, 'dist'), ((E, height, width), torch.int8, 'step'),
+                                     ((E, N, 4), torch.float32, 'bots'), ((E, 4), torch.float32, 'stats')], wanted) if w]
+        given = iter(self._outputs(out, shapes, 'the tensor' if len(shapes) == 1 else 'the tuple (%s)' % ', '.join(n for _, _, n in shapes)))
+        parts = [next(given) if w else None for w in wanted]
+        if parts[2] is not None and parts[2].data_ptr() % 16:
+            raise ValueError('out: bots must be 16-byte aligned')
+        self._call('kb_sense_paths', width, height, ps, pb, objects, clearance_m, *map(_ptr, parts))
+        return Paths(*parts)
 
     def contacts(self, k=8, scale=65536.0, out=None):
         """Touch and push sensing from the contact store of the last step (kb_sense_contacts; Body.collides_with of every

@@ -602,6 +602,63 @@ int kb_sense_coverage(kb_sim *sim, int gw, int gh, const uint8_t *d_select, int3
 int kb_field_step(kb_sim *sim, int gw, int gh, int n_channels, const float *keep, const float *spread, int n_iters,
                   const uint8_t *d_env_mask, const float *d_amount, float *d_field, float *d_sense, void *stream);
 
+/* Obstacle-aware distance-to-goal fields on the CURRENT poses, without stepping: the shortest-path distance of every cell of a
+ * gw x gh grid over the arena to the nearest goal cell when the objects on the table (and any cells the caller marks) cannot
+ * be crossed, the direction of descent per cell, and for every kilobot how far it still has to go and which way, in its own
+ * frame -- what a scripted pusher follows to get BEHIND a box, and the "metres still to go" a reward is shaped with.  No
+ * reference counterpart.  One launch; asynchronous on `stream`.  Every fp32 operation below is rounded on its own, nothing is
+ * contracted, divisions and square roots are correctly rounded.  The distances themselves are integers: the result does not
+ * depend on the order in which the kernel relaxes the cells.
+ *   Grid: that of kb_sense_grid.  Host constants: (xmin, xmax, ymin, ymax) = kb_outline.arena;  cw = (xmax - xmin) / (float)gw,
+ *     icw = (float)gw / (xmax - xmin);  ch, ich likewise from ymin, ymax and gh.  Row iy = 0 is the ymin edge.  The centre of cell
+ *     (iy, ix) is that of KB_GRID_OBJECTS: cx = xmin + ((float)ix + 0.5f) * cw, cy = ymin + ((float)iy + 0.5f) * ch.  The cell of a
+ *     kilobot is that of KB_GRID_COUNT: clamped to the edge cells, NaN to 0, truncation.
+ *   Step costs (host; kb_path_costs returns them):  q(l) = (int32) rint(min(max(l * 1024.0f, 1.0f), 65536.0f));  qx = q(cw),
+ *     qy = q(ch), qd = q(dg) with dg = sqrt(cw * cw + ch * ch).  Directions k = 0..7 are (dx, dy) = (1,0), (1,1), (0,1), (-1,1),
+ *     (-1,0), (-1,-1), (0,-1), (1,-1);  w_k = qx for k in {0, 4}, qy for k in {2, 6}, qd for odd k.  A shortest path visits a
+ *     cell at most once: a finite distance is below 16384 * 65536 = 2^30 and D + w fits int32.  "No path" is never added to.
+ *   Blocked cells: cell c is blocked iff d_blocked[e][iy][ix] != 0 (NULL blocks none);  or, for an object m with bit m of
+ *     `objects` set, the cell centre is inside ANY fixture of m (the inside flag of kb_sense_objects, taken over unchanged);
+ *     or, with clear_m > 0 and for such an object, !(d2 > C2), where d2 is the squared distance of the winning candidate of
+ *     kb_sense_objects for a kilobot standing on the cell centre and Cw = clear_m * 25.0f, C2 = Cw * Cw (host).  With
+ *     clear_m == 0 the d2 test is not made: the object part is exactly the OR of the selected KB_GRID_OBJECTS planes.
+ *   Moves: from a free cell a to its neighbour b in direction k iff b is inside the grid and free and, for odd k, both
+ *     (ax + dx, ay) and (ax, ay + dy) are free as well -- no cutting of corners, no squeezing between two obstacles that touch
+ *     diagonally.  The relation is symmetric.
+ *   Sources: cell c is a source iff d_source[e][iy][ix] != 0 and c is free.
+ *   Distance: D(c) of a free cell is the least sum of w_k along allowed moves from any source, 0 at a source, "none" without a
+ *     path.  D is unique.
+ *   d_dist [num_envs][gh][gw] float32: ((float)D / 1024.0f) / 25.0f metres for a reached cell (int -> float to nearest even);
+ *     +inf for a blocked cell and for a free cell without a path.
+ *   d_next [num_envs][gh][gw] int8: for a reached cell that is no source the lowest k with an allowed move to b and
+ *     D(b) + w_k == D(c);  -1 at a source, -2 at a free cell without a path, -3 at a blocked cell.
+ *   d_bot  [num_envs][num_bots][4] float32, 16-byte aligned.  For kilobot i in its cell c:  c free and reached: Db = D(c),
+ *     kb = next(c).  c blocked (a kilobot pressing on an object stands inside the clearance band: the normal case for a
+ *     pusher): the candidates are the directions k whose neighbour b is inside the grid, free and reached -- no corner rule --
+ *     with the value D(b) + w_k; the least value wins, ties go to the lowest k, Db and kb are the winner's.  Otherwise the
+ *     kilobot is unreachable.  Unit vectors (host): (ux, uy) = ((float)dx, (float)dy) for even k and ((float)dx * (cw / dg),
+ *     (float)dy * (ch / dg)) for odd k.  With (s, c) = the library's sine and cosine of theta_i the row is
+ *     (((float)Db / 1024.0f) / 25.0f, c * ux + s * uy, c * uy - s * ux, flag);  the direction words are +0.0f at a source and
+ *     when unreachable;  flag = 0.0f for a free reached cell, 1.0f for a source cell, 2.0f for a blocked cell with a way out,
+ *     3.0f for unreachable, whose distance is +inf.
+ *   d_stats [num_envs][4] float32.  Word 0: the number of kilobots with a finite Db.  Word 1: ((float)(the int64 sum of those
+ *     Db) / 1024.0f) / 25.0f, the swarm's metres to go, independent of any order.  Word 2: the largest such Db in metres as
+ *     above, +0.0f with none.  Word 3: the number of free cells reached, sources included.
+ * d_source, d_blocked [num_envs][gh][gw] bytes, non-zero = set (the convention of d_seed and d_env_mask); d_blocked may be NULL.
+ * Each output may be NULL and is then neither computed nor written; every element of every output given is written on every
+ * call, by a plain store.  1 <= gw, gh <= KB_GRID_MAX_SIDE;  0 <= objects < 2^num_objects;  clear_m >= 0 and finite.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim / d_source;  gw, gh;  objects;  clear_m;  all
+ * four outputs NULL;  a d_bot that is not 16-byte aligned.  Only then comes KB_ENOTBOUND.
+ * Reads x, y (theta only with d_bot), ox, oy, otheta (only with objects != 0), d_source and d_blocked; writes the outputs only,
+ * and no bound buffer.  The result of an env does not depend on the other envs.  Poses are assumed finite apart from what the
+ * cell rule says of a NaN.
+ *
+ * kb_path_costs: out = (qx, qy, qd) for this handle's arena and this grid, or KB_EINVAL (NULL argument; gw, gh).  Host only:
+ * needs no device and no bound buffers. */
+int kb_path_costs(const kb_sim *sim, int gw, int gh, int32_t *out /* host, [3]: qx, qy, qd */);
+int kb_sense_paths(kb_sim *sim, int gw, int gh, const uint8_t *d_source, const uint8_t *d_blocked, int objects, float clear_m,
+                   float *d_dist, int8_t *d_next, float *d_bot, float *d_stats, void *stream);
+
 /* Kilobot-to-slot matching on the CURRENT poses, without stepping: the two-sided nearest-neighbour query of shape formation
  * between the kilobots of an env and the K points ("slots") of a target shape -- for every kilobot the nearest slot in its own
  * frame, for every slot the nearest kilobot (which slots are still free), whether a kilobot holds the slot it is nearest to,
