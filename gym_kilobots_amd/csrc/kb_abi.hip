@@ -776,10 +776,11 @@ int kb_sense_edges(kb_sim *sim, float radius_m, const int64_t *d_offsets, int64_
     if (!(radius_m > 0.0f)) return fail(KB_EINVAL, "kb_sense_edges: radius must be positive");
     if (capacity < 0) return fail(KB_EINVAL, "kb_sense_edges: capacity must not be negative");
     if (capacity > 0 && !d_dst) return fail(KB_EINVAL, "kb_sense_edges: NULL d_dst with a capacity");
+    const Params &p = sim->p;
+    // (a property of the handle: refused before anything is asked of its buffers, which at this size nobody can bind)
+    if ((long long)p.E * p.N >= (1ll << 31)) return fail(KB_EINVAL, "kb_sense_edges: num_envs * num_bots must be below 2^31 (int32 node ids)");
     if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_edges: kb_bind() first");
     if (!aligned16(d_rel)) return fail(KB_EINVAL, "kb_sense_edges: d_rel must be 16-byte aligned");
-    const Params &p = sim->p;
-    if ((long long)p.E * p.N >= (1ll << 31)) return fail(KB_EINVAL, "kb_sense_edges: num_envs * num_bots must be below 2^31 (int32 node ids)");
     if (capacity == 0 && !d_count) return KB_OK;        // nothing to write: nothing is launched
     const SenseRange r = sense_range(p, radius_m);
     return launch("kb_sense_edges", kb_edges_kernel, p.E, 256, EdgesLds(p.N, p.NP, p.ncell).bytes, stream, p, r.reach, r.R2,

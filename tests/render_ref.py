@@ -101,15 +101,18 @@ def bot_layer(c, px, py, x, y, th):
     return win, kind
 
 
-def restate_env(tab, width, height, layers, bot_radius, x, y, th, ox=None, oy=None, oth=None, lights=None, style=None, body=None, mark=None):
+def restate_env(tab, width, height, layers, bot_radius, x, y, th, ox=None, oy=None, oth=None, lights=None, style=None, body=None, mark=None, rows=None):
     """One env: x, y, th [N] float32 (world units, radians); ox, oy, oth [M] float32; lights = (radii [L] in metres, lx [L], ly
     [L] float32 in metres) of the positional components or None; body, mark [N] 0x00RRGGBB words or None -> [height, width, 3]
-    uint8."""
+    uint8.  rows: the rows of the frame to restate (an index array), for frames too large to restate whole -> [len(rows),
+    width, 3]."""
     for v in (x, y, th):
         assert v.dtype == np.float32
     st = style_of(style)
     c = constants(tab, bot_radius, width, height)
     px, py = centres(tab, bot_radius, width, height)
+    if rows is not None:
+        py, height = py[rows], len(rows)
     img = np.empty((height, width, 3), dtype=np.uint8)
     img[:] = np.array(st['table'], dtype=np.uint8)
     if layers & OBJECTS and tab['M']:
