@@ -135,6 +135,7 @@ SIGNATURES = {
     'kb_path_costs': (_I, [_P, _I, _I, _P]),
     'kb_sense_paths': (_I, [_P, _I, _I, _P, _P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_sense_targets': (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'kb_sense_assign': (_I, [_P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     'kb_sense_contacts': (_I, [_P, _I, _F, _P, _P, _P, _P, _P]),
     'kb_render_default_style': (_I, [C.POINTER(KbRenderStyle)]),
     'kb_render': (_I, [_P, _I, _I, _I, C.POINTER(KbRenderStyle), _P, _P, _P, _P]),
@@ -163,7 +164,7 @@ SIGNATURES = {
 EXPORTS = list(SIGNATURES)
 # an older build of the library that KB_HIP_LIB selects for an A/B (tools/ab_bench.py) has not got these: it loads, and calling
 # one of them on it raises AttributeError
-OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds', 'kb_sense_clusters', 'kb_sense_paths'}
+OPTIONAL = {'kb_step_envs', 'kb_reset_envs', 'kb_debug_lds', 'kb_sense_clusters', 'kb_sense_paths', 'kb_sense_assign'}
 
 _lib = None
 
@@ -400,6 +401,18 @@ def check_targets(n_targets, tol_m):
     if not 0.0 <= tol_m < float('inf'):
         raise ValueError('tol_m must be finite and not negative')
     return n_targets, tol_m
+
+
+def check_assign(n_targets, tol_m, cutoff_m):
+    """The limits of kb_sense_assign: those of kb_sense_targets, and a cutoff in metres that is a number and not negative
+    (None and +inf: no cutoff); ValueError where the library would answer KB_EINVAL.  Returns (n_targets, tol_m, cutoff_m)."""
+    n_targets, tol_m = check_targets(n_targets, tol_m)
+    if isinstance(cutoff_m, bool):
+        raise ValueError('cutoff_m must be a number or None')
+    cutoff_m = float('inf') if cutoff_m is None else float(cutoff_m)
+    if not cutoff_m >= 0.0:
+        raise ValueError('cutoff_m must not be negative (None or inf: no cutoff)')
+    return n_targets, tol_m, cutoff_m
 
 
 RENDER_LAYERS = {'objects': RENDER_OBJECTS, 'bots': RENDER_BOTS, 'light': RENDER_LIGHT}

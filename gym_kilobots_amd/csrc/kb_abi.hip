@@ -2,7 +2,7 @@
 // point, kb_create's derivation of the kernel parameters (Params: grid, masses, damping, object and light tables) from a
 // kb_config, and the small kernels that need no LDS image: set_actions, the pose / state read-backs, kb_reset's spawn and
 // kb_light_sense.  The sensing kernels (kb_sense, kb_sense_neighbors, kb_sense_histogram, kb_sense_reduce, kb_sense_objects,
-// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage, kb_sense_targets, kb_field_step, kb_sense_paths) and the rasteriser of kb_render are in kb_sense.h.
+// kb_sense_grid, kb_sense_contacts, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage, kb_sense_targets, kb_sense_assign, kb_field_step, kb_sense_paths) and the rasteriser of kb_render are in kb_sense.h.
 //
 // The hot kernel is kb_step_kernel (kb_step_kernel.h, instantiated per drive law in kb_inst_*.hip, picked by kb_variant.h):
 // one workgroup owns one env for the whole launch: poses are loaded once from HBM into LDS, `n_substeps` iterations
@@ -1086,6 +1086,22 @@ int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_
     const float Tw = tol_m * WORLD_SCALE;
     const TargetsArgs a = {p.N, n_targets, per_env != 0, Tw * Tw};
     return launch("kb_sense_targets", kb_targets_kernel, p.E, TARGETS_THREADS, TargetsLds(p.N, n_targets).bytes, stream, a, p.buf.x, p.buf.y, p.buf.theta, d_points,
+                  d_bot_select, d_slot_select, d_index, reinterpret_cast<float4 *>(d_rel), d_owner, d_dist, d_stats);
+}
+
+int kb_sense_assign(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, float cutoff_m, const uint8_t *d_bot_select,
+                    const uint8_t *d_slot_select, int32_t *d_index, float *d_rel, int32_t *d_owner, float *d_dist, float *d_stats, void *stream) {
+    if (!sim || !d_points) return fail(KB_EINVAL, "kb_sense_assign: NULL argument");
+    if (n_targets < 1 || n_targets > KB_MAX_TARGETS) return fail(KB_EINVAL, "kb_sense_assign: 1 <= n_targets <= KB_MAX_TARGETS (1024) required");
+    if (!(tol_m >= 0.0f) || !std::isfinite(tol_m)) return fail(KB_EINVAL, "kb_sense_assign: tol_m must be finite and not negative");
+    if (!(cutoff_m >= 0.0f)) return fail(KB_EINVAL, "kb_sense_assign: cutoff_m must be a number and not negative (+inf: no cutoff)");
+    if (!d_index && !d_rel && !d_owner && !d_dist && !d_stats) return fail(KB_EINVAL, "kb_sense_assign: d_index, d_rel, d_owner, d_dist and d_stats are all NULL");
+    if (!aligned16(d_rel)) return fail(KB_EINVAL, "kb_sense_assign: d_rel must be 16-byte aligned");
+    if (!sim->bound) return fail(KB_ENOTBOUND, "kb_sense_assign: kb_bind() first");
+    const Params &p = sim->p;
+    const float Tw = tol_m * WORLD_SCALE, Cw = cutoff_m * WORLD_SCALE;
+    const AssignArgs a = {p.N, n_targets, per_env != 0, Tw * Tw, Cw * Cw};
+    return launch("kb_sense_assign", kb_assign_kernel, p.E, TARGETS_THREADS, AssignLds(p.N, n_targets).bytes, stream, a, p.buf.x, p.buf.y, p.buf.theta, d_points,
                   d_bot_select, d_slot_select, d_index, reinterpret_cast<float4 *>(d_rel), d_owner, d_dist, d_stats);
 }
 

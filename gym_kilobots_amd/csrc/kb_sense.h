@@ -1,7 +1,8 @@
 // kb_sense.h -- the kernels that sense on the current poses without stepping (kb_sense, kb_sense_neighbors,
 // kb_sense_histogram, kb_sense_reduce, kb_sense_rays, kb_sense_edges, kb_sense_hops, kb_sense_clusters, kb_sense_coverage): one workgroup per env, poses and the cell lists of the broadphase grid in LDS;
 // kb_sense_objects, which meets objects and walls instead of kilobots and needs no cell lists; kb_sense_targets, which meets
-// the slots of a target shape, every kilobot against every slot, and needs none either; kb_sense_grid, which bins
+// the slots of a target shape, every kilobot against every slot, and needs none either, and kb_sense_assign, which goes on from
+// those choices in rounds until kilobots and slots are matched one to one; kb_sense_grid, which bins
 // a whole env into an image of the table for an observer outside it; kb_sense_contacts, which reads no poses at all but
 // the contact store the last step left; kb_field_step, which keeps a pheromone field of the caller's, a plane per workgroup,
 // in registers and LDS while the kilobots add to it, it diffuses and they read it; kb_sense_paths, which relaxes the
@@ -2233,7 +2234,65 @@ __device__ __forceinline__ void kb_targets_reduce(long long cost, unsigned far, 
     }
 }
 
-// Kilobot-to-slot matching (kb_sense_targets): one workgroup of 256 lanes per env.  STAGING: lane tid looks at the ceil(N / 256)
+// STAGING of kb_targets_kernel and kb_assign_kernel (described with the former, below): the selected entries of both sides of one
+// env, compacted in ascending index, into bpos / spos (world units) and bidx / sidx; the constants of what is not selected into
+// the outputs given; nb, ns: the sizes of the sides, uniform.  o, ko: the env's first kilobot and slot; pts: its points.  One barrier inside; the
+// LDS it wrote is the caller's to read after the caller's next one.
+__device__ __forceinline__ void kb_targets_stage(const int N, const int K, const size_t o, const size_t ko, const float *x, const float *y, const float *pts,
+                                                 const unsigned char *d_bot_select, const unsigned char *d_slot_select, int *d_index, float4 *d_rel, int *d_owner,
+                                                 float *d_dist, float2 *bpos, float2 *spos, unsigned short *bidx, unsigned short *sidx, unsigned *wsum, const int tid,
+                                                 int &nb, int &ns) {
+    // which of this lane's consecutive entries are selected, and where they go
+    const int cb = (N + TARGETS_THREADS - 1) / TARGETS_THREADS, cs = (K + TARGETS_THREADS - 1) / TARGETS_THREADS;
+    unsigned mb = 0u, ms = 0u;
+    for (int j = 0; j < cb; ++j) {
+        const int b = tid * cb + j;
+        if (b < N && (!d_bot_select || d_bot_select[o + b] != 0)) mb |= 1u << j;
+    }
+    for (int j = 0; j < cs; ++j) {
+        const int t = tid * cs + j;
+        if (t < K && (!d_slot_select || d_slot_select[ko + t] != 0)) ms |= 1u << j;
+    }
+    const unsigned cnt = (unsigned)__popc(mb) | (unsigned)__popc(ms) << 16;        // (a wave sums to at most 256 in either half: no carry)
+    const unsigned incl = wave_incl_scan(cnt);
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    unsigned base = 0u, total = 0u;
+    for (int w = 0; w < TARGETS_THREADS / 64; ++w) {
+        const unsigned s = wsum[w];
+        if (w < (tid >> 6)) base += s;
+        total += s;
+    }
+    nb = __builtin_amdgcn_readfirstlane((int)(total & 0xFFFFu));
+    ns = __builtin_amdgcn_readfirstlane((int)(total >> 16));
+    int ib = (int)((base + incl - cnt) & 0xFFFFu), is = (int)((base + incl - cnt) >> 16);
+    for (int j = 0; j < cb; ++j) {
+        const int b = tid * cb + j;
+        if (b >= N) break;
+        if ((mb >> j) & 1u) {
+            bpos[ib] = make_float2(x[o + b], y[o + b]);
+            bidx[ib] = (unsigned short)b;
+            ++ib;
+        } else {
+            if (d_index) d_index[o + b] = -1;
+            if (d_rel) d_rel[o + b] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
+    for (int j = 0; j < cs; ++j) {
+        const int t = tid * cs + j;
+        if (t >= K) break;
+        if ((ms >> j) & 1u) {
+            spos[is] = make_float2(pts[2 * t] * WORLD_SCALE, pts[2 * t + 1] * WORLD_SCALE);
+            sidx[is] = (unsigned short)t;
+            ++is;
+        } else {
+            if (d_owner) d_owner[ko + t] = -1;
+            if (d_dist) d_dist[ko + t] = 0.0f;
+        }
+    }
+}
+
+// Kilobot-to-slot matching (kb_sense_targets): one workgroup of 256 lanes per env.  STAGING (kb_targets_stage): lane tid looks at the ceil(N / 256)
 // consecutive kilobots from tid * ceil(N / 256) on and at as many consecutive slots; a prefix sum of the two counts over the
 // workgroup (one packed word: kilobots low, slots high) gives every lane where its selected entries go, so that each side is
 // COMPACTED to its selected entries in ascending index: bpos / spos hold the positions (the slots converted to world units,
@@ -2268,53 +2327,8 @@ __global__ void __launch_bounds__(TARGETS_THREADS) kb_targets_kernel(const Targe
     const float INF = __uint_as_float(0x7F800000u);
     const bool toSlot = d_index || d_rel || d_stats, toBot = d_owner || d_dist || d_stats || d_rel;     // the directions some output needs
     if (tid < 2) { sum[tid] = 0ull; worst[tid] = 0u; within[tid] = 0u; }
-    // staging: which of this lane's consecutive entries are selected, and where they go
-    const int cb = (N + TARGETS_THREADS - 1) / TARGETS_THREADS, cs = (K + TARGETS_THREADS - 1) / TARGETS_THREADS;
-    unsigned mb = 0u, ms = 0u;
-    for (int j = 0; j < cb; ++j) {
-        const int b = tid * cb + j;
-        if (b < N && (!d_bot_select || d_bot_select[o + b] != 0)) mb |= 1u << j;
-    }
-    for (int j = 0; j < cs; ++j) {
-        const int t = tid * cs + j;
-        if (t < K && (!d_slot_select || d_slot_select[ko + t] != 0)) ms |= 1u << j;
-    }
-    const unsigned cnt = (unsigned)__popc(mb) | (unsigned)__popc(ms) << 16;        // (a wave sums to at most 256 in either half: no carry)
-    const unsigned incl = wave_incl_scan(cnt);
-    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-    __syncthreads();
-    unsigned base = 0u, total = 0u;
-    for (int w = 0; w < TARGETS_THREADS / 64; ++w) {
-        const unsigned s = wsum[w];
-        if (w < (tid >> 6)) base += s;
-        total += s;
-    }
-    const int nb = __builtin_amdgcn_readfirstlane((int)(total & 0xFFFFu)), ns = __builtin_amdgcn_readfirstlane((int)(total >> 16));
-    int ib = (int)((base + incl - cnt) & 0xFFFFu), is = (int)((base + incl - cnt) >> 16);
-    for (int j = 0; j < cb; ++j) {
-        const int b = tid * cb + j;
-        if (b >= N) break;
-        if ((mb >> j) & 1u) {
-            bpos[ib] = make_float2(x[o + b], y[o + b]);
-            bidx[ib] = (unsigned short)b;
-            ++ib;
-        } else {
-            if (d_index) d_index[o + b] = -1;
-            if (d_rel) d_rel[o + b] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-    }
-    for (int j = 0; j < cs; ++j) {
-        const int t = tid * cs + j;
-        if (t >= K) break;
-        if ((ms >> j) & 1u) {
-            spos[is] = make_float2(pts[2 * t] * WORLD_SCALE, pts[2 * t + 1] * WORLD_SCALE);
-            sidx[is] = (unsigned short)t;
-            ++is;
-        } else {
-            if (d_owner) d_owner[ko + t] = -1;
-            if (d_dist) d_dist[ko + t] = 0.0f;
-        }
-    }
+    int nb, ns;
+    kb_targets_stage(N, K, o, ko, x, y, pts, d_bot_select, d_slot_select, d_index, d_rel, d_owner, d_dist, bpos, spos, bidx, sidx, wsum, tid, nb, ns);
     for (int i = tid; i < nb; i += TARGETS_THREADS) bres[i] = ~0ull;       // (above every key: what waves that share owners take the least against)
     for (int u = tid; u < ns; u += TARGETS_THREADS) sres[u] = ~0ull;
     __syncthreads();
@@ -2383,6 +2397,238 @@ __global__ void __launch_bounds__(TARGETS_THREADS) kb_targets_kernel(const Targe
         st[3] = sqrtf(__uint_as_float(worst[1])) / WORLD_SCALE;
         st[4] = (float)within[1];
         st[5] = (float)within[0];
+    }
+}
+
+// ---- kb_sense_assign: the greedy one-to-one matching of kilobots and slots of every env ----------------------------------------
+constexpr unsigned long long ASSIGN_NOKEY = ~0ull;      // the choice of an entry that has no admissible partner left: above every key
+constexpr unsigned ASSIGN_FREE = 0xFFFFu;               // the mate of an entry that is not matched
+struct AssignArgs { int N, K, per_env; float T2, C2; };     // as TargetsArgs, and the squared cutoff in world units (+inf: none)
+struct AssignLds {      // byte offsets: bpos (float2) at 0, spos (float2), bkey, skey (u64: bits of d2 << 32 | compacted index of the chosen partner, or ASSIGN_NOKEY), red (u64 sum[2]; u32 worst[2], within[2], cnt[2], wsum[4]), then u16 each: bidx, sidx, bmate, smate (compacted index of the partner matched, or ASSIGN_FREE), blist, slist (the entries to rescan)
+    int spos, bkey, skey, red, bidx, sidx, bmate, smate, blist, slist, bytes;
+    __host__ __device__ constexpr AssignLds(int N, int K)       // (every array padded to four entries, as TargetsLds)
+        : spos(8 * ((N + 3) & ~3)), bkey(spos + 8 * ((K + 3) & ~3)), skey(bkey + spos), red(2 * bkey), bidx(red + 64), sidx(bidx + spos / 4),
+          bmate(sidx + (bkey - spos) / 4), smate(bmate + spos / 4), blist(smate + (bkey - spos) / 4), slist(blist + spos / 4),
+          bytes((slist + (bkey - spos) / 4 + 15) & ~15) {}
+};
+static_assert(AssignLds(KB_MAX_BOTS, KB_MAX_TARGETS).bytes <= 64 * 1024 && KB_MAX_BOTS < (int)ASSIGN_FREE && KB_MAX_TARGETS < (int)ASSIGN_FREE,
+              "kb_assign_kernel: LDS image within the default dynamic limit, two envs per CU");
+
+// A key of kb_assign_kernel off the least (bits of d2, index) a scan found: ASSIGN_NOKEY if it found none or the least is beyond
+// the cutoff (then so is every other).
+__device__ __forceinline__ unsigned long long kb_assign_key(const unsigned least, const unsigned who, const float C2) {
+    return least <= 0x7F800000u && !(__uint_as_float(least) > C2) ? (unsigned long long)least << 32 | who : ASSIGN_NOKEY;
+}
+// The position of a matched entry from then on: its d2 to anything is a NaN, whose bits are above TARGETS_NONE whatever its sign,
+// so no scan's "<" ever takes it -- a scan needs no look at the mates.
+__device__ __forceinline__ float2 kb_assign_gone() { return make_float2(__uint_as_float(0x7FC00000u), __uint_as_float(0x7FC00000u)); }
+// FEW rescans of kb_assign_kernel, one whole wave each: the least (bits of d2, index) of the entry at m over other[0 .. nother)
+// -- lane l takes l, l + 64, ... in ascending order, "<" alone keeps the lower index, and the wave takes the least d2 and
+// among its holders the least index (two DPP ladders: min = ~max~).  The squares make d2 the same bits whichever side m is
+// of.  All 64 lanes must be active.
+__device__ __forceinline__ unsigned long long kb_assign_rescan(const float2 m, const float2 *other, const int nother, const float C2, const int lane) {
+    unsigned bd = TARGETS_NONE, bi = 0xFFFFFFFFu;
+    for (int k = lane; k < nother; k += 64) {
+        const float2 q = other[k];
+        const float ex = q.x - m.x, ey = q.y - m.y;
+        const unsigned db = __float_as_uint(ex * ex + ey * ey);
+        const bool less = db < bd;
+        bd = less ? db : bd;
+        bi = less ? (unsigned)k : bi;
+    }
+    const unsigned least = ~wave_umax(~bd);
+    const unsigned who = ~wave_umax(~(bd == least ? bi : 0xFFFFFFFFu));
+    return kb_assign_key(least, who, C2);
+}
+// MANY rescans, the walk of kb_targets_nearest: a lane owns the listed entry tid + 256 j of mine and walks ALL of other in
+// ascending order, four positions per round trip at an address every lane shares (a broadcast); a wave none of whose lanes
+// has an entry skips the walk.  No barrier inside.
+__device__ __forceinline__ void kb_assign_rescan_many(const unsigned short *list, const int nlist, const float2 *mine, const float2 *other, const int nother,
+                                                      const float C2, unsigned long long *res, const int tid) {
+    for (int at = tid & ~63; at < nlist; at += TARGETS_THREADS) {      // (uniform in a wave)
+        const int it = at + (tid & 63);
+        const int i = list[min(it, nlist - 1)];
+        const float2 m = mine[i];
+        unsigned bd = TARGETS_NONE, bi = 0xFFFFFFFFu;
+        auto take = [&](const unsigned k, const float ox, const float oy) {
+            const float ex = ox - m.x, ey = oy - m.y;
+            const unsigned db = __float_as_uint(ex * ex + ey * ey);
+            const bool less = db < bd;
+            bd = less ? db : bd;
+            bi = less ? k : bi;
+        };
+        int k = 0;
+        for (; k + 4 <= nother; k += 4) {
+            const float4 q0 = reinterpret_cast<const float4 *>(other + k)[0], q1 = reinterpret_cast<const float4 *>(other + k)[1];
+            take(k, q0.x, q0.y); take(k + 1, q0.z, q0.w); take(k + 2, q1.x, q1.y); take(k + 3, q1.z, q1.w);
+        }
+        for (; k < nother; ++k) take(k, other[k].x, other[k].y);
+        if (it < nlist) res[i] = kb_assign_key(bd, bi, C2);
+    }
+}
+// An entry onto a rescan list: one LDS atomic per wave (the ballot's count), the lanes that push in ascending order behind it.
+__device__ __forceinline__ void kb_assign_push(unsigned short *list, unsigned *count, const bool push, const int value) {
+    const unsigned long long m = __ballot(push);
+    if (m == 0ull) return;      // (uniform)
+    const unsigned ahead = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    unsigned base = 0u;
+    if (push && ahead == 0u) base = atomicAdd(count, (unsigned)__popcll(m));
+    base = __shfl(base, __ffsll((long long)m) - 1);
+    if (push) list[base + ahead] = (unsigned short)value;
+}
+constexpr int ASSIGN_MANY = 32;     // from this many listed entries of a side on the lanes own them; below, a wave takes each
+
+// Greedy one-to-one matching (kb_sense_assign): one workgroup of 256 lanes per env, the whole state in LDS.  STAGING is that of
+// kb_targets_kernel (kb_targets_stage).  ROUND 1 is its two passes (kb_targets_side): every entry's least (bits of d2, index)
+// over the whole other side, as a key; a key beyond the cutoff becomes ASSIGN_NOKEY -- the least is inadmissible, so all are.
+// A ROUND: (a) a lane takes the unmatched kilobots i, i + 256, ...; kilobot i and the slot u it chose are matched iff u chose i
+// (the low words of bkey[i] and skey[u]; a matched entry keeps its key for good, so a matched u names its mate, never the free
+// i).  Only the lane of i writes bmate[i] and smate[u], nobody reads either here; the positions of both become kb_assign_gone(),
+// which no later scan takes.  No match in the whole workgroup (__syncthreads_or, uniform): no admissible pair is left, the loop
+// ends.  (b) An unmatched entry whose chosen partner has just been matched to someone else goes on its side's list
+// (kb_assign_push); every other choice is still free and therefore still the least of a set that only shrank -- it is NOT
+// recomputed, which is exact, not a heuristic.  (c) The listed entries are scanned again: a side with ASSIGN_MANY or more by
+// lanes that own one entry each and walk the whole other side (kb_assign_rescan_many), fewer by one whole wave per entry
+// (kb_assign_rescan), where owning lanes would leave most of the workgroup idle.  After (c) every unmatched entry holds the
+// least admissible unmatched partner again: the rounds are those of the definition one for one, and their count is R.  A
+// round that matches nothing ends the loop and one that matches takes a pair: the bound min(nb, ns) of the for loop is never
+// the reason it ends, and it is in the code so that no input can keep a workgroup here.  EPILOGUE: the mate and the d2 of its
+// key give every output but the frame of d_rel, whose offsets are formed again from x, y and the points as the staging formed
+// them; the partials of d_stats meet as integers (kb_targets_reduce).  Indices come from keys that a "<" set, below the size
+// of their side.  Every output word is written exactly once, by a plain store.
+__global__ void __launch_bounds__(TARGETS_THREADS) kb_assign_kernel(const AssignArgs A, const float *x, const float *y, const float *theta, const float *d_points,
+                                                                    const unsigned char *d_bot_select, const unsigned char *d_slot_select, int *d_index,
+                                                                    float4 *d_rel, int *d_owner, float *d_dist, float *d_stats) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int e = blockIdx.x, tid = threadIdx.x, N = A.N, K = A.K;
+    const AssignLds L(N, K);
+    float2 *bpos = reinterpret_cast<float2 *>(smem);
+    float2 *spos = reinterpret_cast<float2 *>(smem + L.spos);
+    unsigned long long *bkey = reinterpret_cast<unsigned long long *>(smem + L.bkey);
+    unsigned long long *skey = reinterpret_cast<unsigned long long *>(smem + L.skey);
+    unsigned long long *sum = reinterpret_cast<unsigned long long *>(smem + L.red);
+    unsigned *worst = reinterpret_cast<unsigned *>(smem + L.red + 16);
+    unsigned *within = worst + 2, *cnt = worst + 4, *wsum = worst + 6;
+    unsigned short *bidx = reinterpret_cast<unsigned short *>(smem + L.bidx);
+    unsigned short *sidx = reinterpret_cast<unsigned short *>(smem + L.sidx);
+    unsigned short *bmate = reinterpret_cast<unsigned short *>(smem + L.bmate);
+    unsigned short *smate = reinterpret_cast<unsigned short *>(smem + L.smate);
+    unsigned short *blist = reinterpret_cast<unsigned short *>(smem + L.blist);
+    unsigned short *slist = reinterpret_cast<unsigned short *>(smem + L.slist);
+    const size_t o = (size_t)e * N, ko = (size_t)e * K;
+    const float *pts = d_points + (A.per_env ? 2 * ko : 0);
+    const float INF = __uint_as_float(0x7F800000u);
+    if (tid < 2) { sum[tid] = 0ull; worst[tid] = 0u; within[tid] = 0u; }
+    int nb, ns;
+    kb_targets_stage(N, K, o, ko, x, y, pts, d_bot_select, d_slot_select, d_index, d_rel, d_owner, d_dist, bpos, spos, bidx, sidx, wsum, tid, nb, ns);
+    for (int i = tid; i < nb; i += TARGETS_THREADS) { bkey[i] = ASSIGN_NOKEY; bmate[i] = (unsigned short)ASSIGN_FREE; }
+    for (int u = tid; u < ns; u += TARGETS_THREADS) { skey[u] = ASSIGN_NOKEY; smate[u] = (unsigned short)ASSIGN_FREE; }
+    __syncthreads();
+    const int rounds = min(nb, ns);
+    if (rounds > 0) {       // round 1's choices (uniform)
+        kb_targets_side(bpos, nb, spos, ns, bkey, tid);
+        kb_targets_side(spos, ns, bpos, nb, skey, tid);
+        __syncthreads();
+        for (int i = tid; i < nb; i += TARGETS_THREADS) {
+            const unsigned db = (unsigned)(bkey[i] >> 32);
+            if (db > 0x7F800000u || __uint_as_float(db) > A.C2) bkey[i] = ASSIGN_NOKEY;
+        }
+        for (int u = tid; u < ns; u += TARGETS_THREADS) {
+            const unsigned db = (unsigned)(skey[u] >> 32);
+            if (db > 0x7F800000u || __uint_as_float(db) > A.C2) skey[u] = ASSIGN_NOKEY;
+        }
+        __syncthreads();
+    }
+    int R = 0;
+    for (int r = 0; r < rounds; ++r) {
+        if (tid < 2) cnt[tid] = 0u;
+        int matched = 0;
+        for (int i = tid; i < nb; i += TARGETS_THREADS) {       // (a)
+            const unsigned long long k = bkey[i];
+            if (bmate[i] == ASSIGN_FREE && k != ASSIGN_NOKEY) {
+                const unsigned u = (unsigned)k;
+                if ((unsigned)skey[u] == (unsigned)i) {
+                    bmate[i] = (unsigned short)u;
+                    smate[u] = (unsigned short)i;
+                    bpos[i] = spos[u] = kb_assign_gone();
+                    matched = 1;
+                }
+            }
+        }
+        if (!__syncthreads_or(matched)) break;
+        ++R;
+        for (int i = tid; i < nb; i += TARGETS_THREADS) {       // (b)
+            const unsigned long long k = bkey[i];
+            kb_assign_push(blist, &cnt[0], bmate[i] == ASSIGN_FREE && k != ASSIGN_NOKEY && smate[(unsigned)k] != ASSIGN_FREE, i);
+        }
+        for (int u = tid; u < ns; u += TARGETS_THREADS) {
+            const unsigned long long k = skey[u];
+            kb_assign_push(slist, &cnt[1], smate[u] == ASSIGN_FREE && k != ASSIGN_NOKEY && bmate[(unsigned)k] != ASSIGN_FREE, u);
+        }
+        __syncthreads();
+        const int nrb = __builtin_amdgcn_readfirstlane((int)cnt[0]), nrs = __builtin_amdgcn_readfirstlane((int)cnt[1]);
+        const int few_b = nrb < ASSIGN_MANY ? nrb : 0, few_s = nrs < ASSIGN_MANY ? nrs : 0;      // (c), every branch uniform in a wave
+        if (nrb >= ASSIGN_MANY) kb_assign_rescan_many(blist, nrb, bpos, spos, ns, A.C2, bkey, tid);
+        if (nrs >= ASSIGN_MANY) kb_assign_rescan_many(slist, nrs, spos, bpos, nb, A.C2, skey, tid);
+        for (int it = __builtin_amdgcn_readfirstlane(tid >> 6); it < few_b + few_s; it += TARGETS_THREADS / 64) {
+            if (it < few_b) {
+                const int i = blist[it];
+                const unsigned long long k = kb_assign_rescan(bpos[i], spos, ns, A.C2, tid & 63);
+                if ((tid & 63) == 0) bkey[i] = k;
+            } else {
+                const int u = slist[it - few_b];
+                const unsigned long long k = kb_assign_rescan(spos[u], bpos, nb, A.C2, tid & 63);
+                if ((tid & 63) == 0) skey[u] = k;
+            }
+        }
+        __syncthreads();
+    }
+    // epilogue: the pairs are counted on the kilobots' side
+    long long cost = 0, length = 0;
+    unsigned far = 0u, fill = 0u, pairs = 0u;
+    for (int i = tid; i < nb; i += TARGETS_THREADS) {
+        const int b = bidx[i];
+        const unsigned u = bmate[i];
+        if (u == ASSIGN_FREE) {
+            if (d_index) d_index[o + b] = -1;
+            if (d_rel) d_rel[o + b] = make_float4(0.0f, 0.0f, INF, 0.0f);
+            continue;
+        }
+        const unsigned db = (unsigned)(bkey[i] >> 32);
+        const float d2 = __uint_as_float(db), dm = sqrtf(d2) / WORLD_SCALE;
+        if (d_index) d_index[o + b] = sidx[u];
+        if (d_rel) {        // (the positions in LDS are gone: the operands again, by the operations of the staging)
+            const int t = sidx[u];
+            const float ex = pts[2 * t] * WORLD_SCALE - x[o + b], ey = pts[2 * t + 1] * WORLD_SCALE - y[o + b];
+            float sn, cs_;
+            kb_sincosf(theta[o + b], sn, cs_);
+            const float2 f = kb_body_frame(cs_, sn, ex, ey);
+            d_rel[o + b] = make_float4(f.x, f.y, dm, 1.0f);
+        }
+        cost += (long long)rintf(fminf(d2 * 65536.0f, 0x1p40f));
+        length += (long long)rintf(fminf(dm * 65536.0f, 0x1p40f));
+        far = max(far, db);
+        fill += !(d2 > A.T2) ? 1u : 0u;
+        ++pairs;
+    }
+    for (int u = tid; u < ns; u += TARGETS_THREADS) {
+        const int t = sidx[u];
+        const unsigned i = smate[u];
+        if (d_owner) d_owner[ko + t] = i == ASSIGN_FREE ? -1 : (int)bidx[i];
+        if (d_dist) d_dist[ko + t] = i == ASSIGN_FREE ? INF : sqrtf(__uint_as_float((unsigned)(skey[u] >> 32))) / WORLD_SCALE;
+    }
+    if (!d_stats) return;
+    kb_targets_reduce(cost, far, fill, sum, worst, within, tid);
+    kb_targets_reduce(length, 0u, pairs, sum + 1, worst + 1, within + 1, tid);
+    __syncthreads();
+    if (tid == 0) {
+        float *st = d_stats + 6 * (size_t)e;
+        st[0] = ((float)(long long)sum[0] / 65536.0f) / 625.0f;
+        st[1] = sqrtf(__uint_as_float(worst[0])) / WORLD_SCALE;
+        st[2] = (float)(long long)sum[1] / 65536.0f;
+        st[3] = (float)R;
+        st[4] = (float)within[0];
+        st[5] = (float)within[1];
     }
 }
 

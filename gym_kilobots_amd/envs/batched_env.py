@@ -57,6 +57,15 @@ def _target_obs(value, num_objects):
     return (points,) + nat.check_targets(points.shape[-2], tol_m)[1:]
 
 
+def _target_match(value):
+    """target_match -- 'greedy' or ('greedy', cutoff_m) -- as the keywords KilobotSim.targets gets for it."""
+    match, cutoff_m = (value, None) if isinstance(value, str) else tuple(value) if hasattr(value, '__len__') and len(value) == 2 else (None, None)
+    if match != 'greedy':
+        raise ValueError("target_match must be None, 'greedy' or ('greedy', cutoff_m)")
+    cutoff_m = nat.check_assign(1, 0.0, cutoff_m)[2]
+    return dict(match='greedy') if cutoff_m == float('inf') else dict(match='greedy', cutoff_m=cutoff_m)
+
+
 def _path_obs(value, num_objects):
     width, height, clearance_m = tuple(value) if len(value) == 3 else tuple(value) + (0.0,)
     return nat.check_paths(width, height, clearance_m)
@@ -118,7 +127,7 @@ class BatchedKilobotsEnv(object):
                  sim_factory=None, reward_fn=None, env_offset=0, on_status='raise', status_interval=1, neighbor_obs=None, histogram_obs=None, comm_radius=None,
                  object_obs=None, grid_obs=None, coverage_obs=None, target_obs=None, contact_obs=None, render_size=None, ray_obs=None, edge_obs=None,
                  max_episode_steps=None, done_fn=None, auto_reset=False, object_init=None, light_init=None,
-                 field_obs=None, field_keep=1.0, field_spread=0.0, field_iters=1, deposit_fn=None, path_obs=None, **cfg):
+                 field_obs=None, field_keep=1.0, field_spread=0.0, field_iters=1, deposit_fn=None, path_obs=None, target_match=None, **cfg):
         """env_offset: global index of this shard's first env (multi-GPU: the Philox counters of reset() are keyed by the
         GLOBAL env index, so a shard equals the corresponding rows of the unsharded batch).
         on_status / status_interval: capacity overflows of the device step (kb_buffers.status) are checked after
@@ -150,6 +159,10 @@ class BatchedKilobotsEnv(object):
         of every slot and how far it is, the Chamfer sums, Hausdorff distances and the counts within tol_m the reward is made
         of -- and step() puts the tuple in its info dict under 'targets'.  set_targets() replaces the points or masks slots
         out.  None adds nothing.
+        target_match: 'greedy' or ('greedy', cutoff_m) makes targets() and info['targets'] the ONE-TO-ONE greedy matching of
+        kilobots and slots instead (KilobotSim.targets with match='greedy': index the slot matched to a kilobot or -1, owner the
+        kilobot matched to a slot or -1, stats the sums over the matched pairs, no pair further apart than cutoff_m).  Needs
+        target_obs.  None: the nearest queries, as before.
         contact_obs: k, an int in 0..16, adds touch and push sensing from the contacts the solver acted on in the last world
         step: contacts() returns (partner [E, N, k], impulse [E, N, k], touch [E, N, 4], obj [E, M, 2] or None)
         (KilobotSim.contacts; k = 0: no lists, partner and impulse are None), and step() puts the tuple in its info dict under
@@ -220,6 +233,9 @@ class BatchedKilobotsEnv(object):
                     raise ValueError('%s must be %s: %s' % (name, option.shape, err))
             setattr(self, name, value)
         self.object_obs = bool(self.object_obs)         # (the one keyword that is off as False)
+        self._target_kw = {} if target_match is None else _target_match(target_match)       # what targets() gets besides the slot mask
+        if target_match is not None and self.target_obs is None:
+            raise ValueError('target_match needs target_obs=(points_m, tol_m)')
         kw = dict(cfg)
         if 'contact_capacity' not in kw:
             # a Gaussian cloud of std s overlaps N (N - 1) / 2 * (1 - exp(-r^2 / s^2)) pairs at spawn: size the contact
@@ -247,6 +263,8 @@ class BatchedKilobotsEnv(object):
         self._observe_kw = {}       # keyword arguments the sim method of an observation gets besides the stored value
         if self.target_obs is not None:         # the points live on the device from here on: (tensor, tol_m)
             self.target_obs = (self._target_points(self.target_obs[0]), self.target_obs[1])
+            if self._target_kw:
+                self._observe_kw['target_obs'] = dict(self._target_kw)
         if self.path_obs is not None:           # (width, height) from here on; the goal and the blocked cells live on the device
             width, height, clearance_m = self.path_obs
             self.path_obs = (width, height)
@@ -486,12 +504,12 @@ class BatchedKilobotsEnv(object):
             if new.shape[-2] != points.shape[-2]:
                 raise ValueError('set_targets: the env was created with %d slots, got %d' % (points.shape[-2], new.shape[-2]))
             self.target_obs = (self._target_points(new), tol_m)
-        self._observe_kw['target_obs'] = {} if slot_select is None else dict(slot_select=slot_select)
+        self._observe_kw['target_obs'] = dict(self._target_kw) if slot_select is None else dict(self._target_kw, slot_select=slot_select)
 
     def targets(self):
         """The named tuple (index [E, N] int32, rel [E, N, 4] float32, owner [E, K] int32, dist [E, K] float32, stats [E, 6]
         float32) of the current poses for the target_obs=(points_m, tol_m) the env was created with, over the slots
-        set_targets() selected: KilobotSim.targets."""
+        set_targets() selected: KilobotSim.targets, the nearest queries or with target_match the greedy matching."""
         return self._observe('target_obs')
 
     def _path_mask(self, cells, name):

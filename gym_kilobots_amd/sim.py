@@ -549,7 +549,8 @@ class KilobotSim:
         self._call('kb_field_step', width, height, C_, vec(*keep), vec(*spread), iters, pm, pa, pf, _ptr(out))
         return out
 
-    def targets(self, points_m, tol_m, bot_select=None, slot_select=None, index=True, rel=True, owner=True, dist=True, stats=True, out=None):
+    def targets(self, points_m, tol_m, bot_select=None, slot_select=None, index=True, rel=True, owner=True, dist=True, stats=True, out=None,
+                match='nearest', cutoff_m=None):
         """Kilobot-to-slot matching on the current poses (kb_sense_targets; no reference counterpart): the two-sided nearest
         query of shape formation between the kilobots of every env and the K points ("slots") of a target shape.  points_m:
         contiguous float32 [E, K, 2] or [K, 2] (shared by all envs) on the sim's device, metres, 1 <= K <= MAX_TARGETS.
@@ -565,11 +566,26 @@ class KilobotSim:
         selected entry of an env whose other side is empty -1 and a distance of +inf, and the stats of such an env are
         (+inf, +inf, +inf, +inf, 0, 0).  A part switched off (index=False, ...) is None and is not computed; at least one
         must be on.  out: the preallocated contiguous tensors to write into, a tuple of the parts that are on; every element
-        is written."""
+        is written.
+        match='greedy' (kb_sense_assign) returns a ONE-TO-ONE matching in the same tuple instead of the two nearest queries:
+        of all pairs of a selected kilobot and a selected slot no further apart than cutoff_m (metres; None: no limit), in
+        ascending order of (distance, kilobot, slot), a pair is taken iff neither end has been taken -- the greedy matching,
+        on the device in one launch.  index is then the slot matched to a kilobot or -1, rel its row with a fourth word of 1.0
+        (an unmatched selected kilobot: (0, 0, +inf, 0)), owner and dist the kilobot matched to a slot and its distance (an
+        unmatched selected slot: -1 and +inf), and stats = (the sum of the squared distances of the matched pairs in square
+        metres, the largest distance, the sum of the distances in metres, the number of rounds of mutual choices the
+        matching takes, the number of pairs within tol_m, the number of pairs); all zero in an env without a pair."""
         E, N = self.num_envs, self.num_bots
+        if match not in ('nearest', 'greedy'):
+            raise ValueError("match must be 'nearest' or 'greedy'")
+        if match == 'nearest' and cutoff_m is not None:
+            raise ValueError("cutoff_m needs match='greedy'")
         if not torch.is_tensor(points_m) or points_m.dim() not in (2, 3):
             raise ValueError('points_m must be a contiguous float32 cuda tensor of shape (E, K, 2) or (K, 2)')
-        K, tol_m = nat.check_targets(points_m.shape[-2], tol_m)
+        if match == 'greedy':
+            K, tol_m, cutoff_m = nat.check_assign(points_m.shape[-2], tol_m, cutoff_m)
+        else:
+            K, tol_m = nat.check_targets(points_m.shape[-2], tol_m)
         per_env = points_m.dim() == 3
         pp = self._input(points_m, F32, (E, K, 2) if per_env else (K, 2), 'points_m')
         wanted = [bool(index), bool(rel), bool(owner), bool(dist), bool(stats)]
@@ -583,7 +599,10 @@ class KilobotSim:
         parts = [next(given) if w else None for w in wanted]
         if parts[1] is not None and parts[1].data_ptr() % 16:
             raise ValueError('out: rel must be 16-byte aligned')
-        self._call('kb_sense_targets', pp, K, int(per_env), tol_m, pb, ps, *map(_ptr, parts))
+        if match == 'greedy':
+            self._call('kb_sense_assign', pp, K, int(per_env), tol_m, cutoff_m, pb, ps, *map(_ptr, parts))
+        else:
+            self._call('kb_sense_targets', pp, K, int(per_env), tol_m, pb, ps, *map(_ptr, parts))
         return Targets(*parts)
 
     def path_costs(self, width, height):

@@ -707,6 +707,43 @@ int kb_sense_targets(kb_sim *sim, const float *d_points, int n_targets, int per_
                      const uint8_t *d_slot_select, int32_t *d_index, float *d_rel, int32_t *d_owner, float *d_dist,
                      float *d_stats, void *stream);
 
+/* One-to-one kilobot-to-slot matching on the CURRENT poses, without stepping: the GREEDY (locally dominant) matching between the
+ * kilobots of an env and the K slots of a target shape -- who goes where, which slots stay free, and the sums a formation
+ * reward is made of -- where kb_sense_targets gives the two nearest queries, in which twenty kilobots may all name one slot.
+ * No reference counterpart.  One launch; asynchronous on `stream`.  It is not the optimal assignment.
+ * Points, sides, d2(b, t), T2 and the shapes and alignment of the five outputs are exactly those of kb_sense_targets; every
+ * operation is one fp32 operation rounded on its own.
+ *   Cutoff: Cw = cutoff_m * 25.0f, C2 = Cw * Cw;  cutoff_m >= 0, +inf allowed (C2 = +inf: no cutoff); a NaN or a negative
+ *     value is KB_EINVAL.  A pair (b, t) is ADMISSIBLE if b and t are selected and !(d2(b, t) > C2).
+ *   Total order on pairs: (bits of d2 compared as unsigned integers, b, t), lexicographic.  Nothing else decides anything.
+ *   The matching M: walk the admissible pairs of the env in ascending order and take a pair iff neither its kilobot nor its
+ *     slot has been taken.  M is unique.
+ *   Rounds: R is the number of rounds of this process -- among the still unmatched selected entries every kilobot chooses the
+ *     admissible slot with the least (bits of d2, t) and every slot the admissible kilobot with the least (bits of d2, b);
+ *     pairs that choose each other are matched at once; repeat until no admissible pair is left.  The process yields M (a pair
+ *     that is the least at both its ends is exactly a pair the walk takes), every round with an admissible pair matches at
+ *     least the least one, so R <= min(selected kilobots, selected slots).  R is a property of the scene.
+ *   d_index [num_envs][num_bots] int32: the slot matched to b, or -1.
+ *   d_rel   [num_envs][num_bots][4] float32, 16-byte aligned: for a matched b, with (s, c), ex, ey, d2 as in kb_sense_targets,
+ *     ((c * ex + s * ey) / 25, (c * ey - s * ex) / 25, sqrt(d2) / 25, 1.0f).  Selected but unmatched: (+0.0f, +0.0f, +inf,
+ *     +0.0f).  Not selected: four +0.0f.
+ *   d_owner [num_envs][K] int32, d_dist [num_envs][K] float32: the kilobot matched to t and sqrt(d2) / 25.  Selected but
+ *     unmatched: -1 and +inf.  Not selected: -1 and +0.0f.
+ *   d_stats [num_envs][6] float32, over the pairs of M.  Word 0: the fixed-point sum of d2, exactly word 0 of kb_sense_targets
+ *     (q = (int64) rint(min(d2 * 65536.0f, 0x1p40f)), the int64 sum acc, ((float)acc / 65536.0f) / 625.0f), square metres.
+ *     Word 1: sqrt(the largest bits of d2) / 25, the bottleneck distance.  Word 2: the fixed-point sum of the distances,
+ *     dm = sqrt(d2) / 25.0f, q = (int64) rint(min(dm * 65536.0f, 0x1p40f)), the int64 sum acc, (float)acc / 65536.0f, metres.
+ *     Word 3: (float)R.  Word 4: the number of pairs with !(d2 > T2).  Word 5: (float)|M|.  With no pair all six are +0.0f.
+ * Each output may be NULL and is then not written; every element of every output given is written on every call, by a plain
+ * store.
+ * Argument errors are reported before an unbound handle, in this order: NULL sim or NULL d_points;  n_targets;  tol_m;
+ * cutoff_m;  all five outputs NULL;  a d_rel that is not 16-byte aligned.  Only then comes KB_ENOTBOUND.
+ * Reads x, y, d_points and the two selections, theta only with d_rel; writes the outputs only, and no bound buffer.  The result
+ * of an env does not depend on the other envs.  Poses and points are assumed finite, as for kb_sense_targets. */
+int kb_sense_assign(kb_sim *sim, const float *d_points, int n_targets, int per_env, float tol_m, float cutoff_m,
+                    const uint8_t *d_bot_select, const uint8_t *d_slot_select, int32_t *d_index, float *d_rel, int32_t *d_owner,
+                    float *d_dist, float *d_stats, void *stream);
+
 /* Touch and push sensing from the contact store, without stepping: who touches whom, and how hard -- what the solver alone
  * knows (Body.collides_with, body.py:87-90, walks b2Body.contacts; the impulses have no reference counterpart).  A pure
  * function of ws_key / ws_acc / ws_cnt as the last kb_step left them: the Box2D contact list of the last world step.
