@@ -229,6 +229,23 @@ def call(lib, name, *args):
     check(getattr(lib, name)(*args), name)
 
 
+def capturing():
+    """Whether the current stream is being captured into a graph (torch.cuda.graph); False where there is no device."""
+    import torch
+    try:
+        return bool(torch.cuda.is_current_stream_capturing())
+    except (RuntimeError, AssertionError):      # (no device, or torch built without one: nothing can be capturing)
+        return False
+
+
+def refuse_capture(what, instead):
+    """ValueError if the current stream is being captured into a graph: `what` has to read the device, which a capture cannot
+    hold -- the runtime would invalidate the whole capture with an error that names nothing.  instead: what the caller can
+    do.  Called before the first launch of the path, so that the capture stays valid and can go on."""
+    if capturing():
+        raise ValueError('%s reads the device back and cannot be captured in a graph: %s' % (what, instead))
+
+
 def check_radius(radius_m, name='radius_m'):
     """A radius in metres as a float; ValueError unless it is positive."""
     radius_m = float(radius_m)

@@ -385,6 +385,7 @@ struct kb_sim {
     Params p;
     bool bound;
     const void *attr_fn;   // kernel whose dynamic-LDS limit has been raised
+    const void *paths_attr_fn;     // ... and the same for kb_sense_paths above GRID_LDS_LIMIT
     int threads;
     kb_step_fn fn;         // the instantiation that runs the handle (plan_launch), nullptr if the library has none
     int variant;           // ... and its position in kb_variants, -1 likewise (kb_variant_index)
@@ -486,6 +487,7 @@ int kb_create(const kb_config *cfg, kb_sim **out) {
     s->cfg = *cfg;
     s->bound = false;
     s->attr_fn = nullptr;
+    s->paths_attr_fn = nullptr;
     Params &p = s->p;
     memset(&p, 0, sizeof(p));
     p.N = cfg->num_bots; p.E = cfg->num_envs; p.S = cfg->ws_slots;
@@ -1065,10 +1067,12 @@ int kb_sense_paths(kb_sim *sim, int gw, int gh, const uint8_t *d_source, const u
     kb_outline ol;
     kb_get_outline(sim, &ol);
     const int lds = PathsLds(gw, gh).bytes;
-    if (lds > GRID_LDS_LIMIT) {
-        // the attribute belongs to the kernel on the current device: raised to the hardware limit, as for the step kernels
+    if (lds > GRID_LDS_LIMIT && sim->paths_attr_fn != reinterpret_cast<const void *>(kb_paths_kernel)) {
+        // the attribute belongs to the kernel on the current device: raised to the hardware limit, as for the step kernels, and
+        // once per handle like theirs -- it is no stream operation, so a call that is captured into a graph launches only
         const hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void *>(kb_paths_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
         if (err != hipSuccess) return fail(KB_EHIP, "kb_sense_paths: hipFuncSetAttribute: %s", hipGetErrorString(err));
+        sim->paths_attr_fn = reinterpret_cast<const void *>(kb_paths_kernel);
     }
     return launch("kb_sense_paths", kb_paths_kernel, p.E, PATHS_THREADS, lds, stream, ol, a, p.buf.x, p.buf.y, p.buf.theta, p.buf.ox, p.buf.oy, p.buf.otheta,
                   d_source, d_blocked, d_dist, reinterpret_cast<signed char *>(d_next), reinterpret_cast<float4 *>(d_bot), d_stats);

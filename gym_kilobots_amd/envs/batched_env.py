@@ -314,6 +314,7 @@ class BatchedKilobotsEnv(object):
     def _check_status(self, where):
         if self._on_status == 'ignore':
             return
+        nat.refuse_capture('%s with on_status=%r' % (where, self._on_status), "create the env with on_status='ignore' and check sim.status outside the capture")
         bits = self.sim.status_bits()
         if not bits:
             return
@@ -400,8 +401,12 @@ class BatchedKilobotsEnv(object):
         return self.sim.poses()
 
     def step(self, actions=None, light_action=None):
-        """actions [E, N, 2] float32 tensor on the sim's device (None keeps the previous commands)."""
-        prev = self.sim.poses() if self.reward_fn is not None or self.done_fn is not None or self.deposit_fn is not None else None
+        """actions [E, N, 2] float32 tensor on the sim's device (None keeps the previous commands).
+        With on_status='ignore' the whole call can be captured into a graph (torch.cuda.graph) and replayed: INTEGRATION.md,
+        "Capturing a step in a graph"."""
+        if self._on_status != 'ignore':         # (the count of steps that decides when the status is read stops at capture: refused before any launch)
+            nat.refuse_capture('step() with on_status=%r' % self._on_status, "create the env with on_status='ignore' and check sim.status outside the capture")
+        prev =self.sim.poses() if self.reward_fn is not None or self.done_fn is not None or self.deposit_fn is not None else None
         self.sim.step(self.steps_per_action, actions=actions, light_action=light_action)
         obs = self.sim.poses()
         if self.reward_fn is not None:
@@ -500,6 +505,7 @@ class BatchedKilobotsEnv(object):
         all of them (KilobotSim.targets).  A reward that masks out the slots that are filled sets the mask here."""
         points, tol_m = self._stored('target_obs')
         if points_m is not None:
+            nat.refuse_capture('set_targets(points_m)', 'it checks the points on the host and uploads them; call it before the capture and write into env.target_obs[0] in place')
             new = _target_obs((points_m, tol_m), 0)[0]
             if new.shape[-2] != points.shape[-2]:
                 raise ValueError('set_targets: the env was created with %d slots, got %d' % (points.shape[-2], new.shape[-2]))
@@ -516,6 +522,7 @@ class BatchedKilobotsEnv(object):
         """A caller's cell mask, array-like or tensor [height, width] or [E, height, width], as uint8 [E, height, width] on the
         sim's device."""
         width, height = self._stored('path_obs')
+        nat.refuse_capture(name + '()', 'it takes the cells through the host; call it before the capture and write into the mask in place')
         t = torch.as_tensor(cells.cpu().numpy() if torch.is_tensor(cells) else np.asarray(cells))
         if t.dim() not in (2, 3) or tuple(t.shape[-2:]) != (height, width) or (t.dim() == 3 and t.shape[0] != self.num_envs):
             raise ValueError('%s: cells must have the shape (%d, %d) or (%d, %d, %d)' % (name, height, width, self.num_envs, height, width))
@@ -526,6 +533,7 @@ class BatchedKilobotsEnv(object):
         (KilobotSim.path_cells), or cells, a mask [height, width] or [E, height, width] of the goal cells; exactly one of
         the two.  An env is created without a goal: every kilobot is unreachable until one is set."""
         width, height = self._stored('path_obs')
+        nat.refuse_capture('set_path_goal()', 'it takes the goal through the host; call it before the capture and write into the mask in place')
         if (points_m is None) == (cells is None):
             raise ValueError('set_path_goal: give either points_m or cells')
         self._observe_kw['path_obs']['source'] = self.sim.path_cells(points_m, width, height) if cells is None else self._path_mask(cells, 'set_path_goal')

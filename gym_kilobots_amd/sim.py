@@ -255,6 +255,7 @@ class KilobotSim:
     def host_state(self):
         """(kilobot poses [num_envs, num_bots, 3], object poses [num_envs, num_objects, 3], status [num_envs]) as numpy
         arrays, metres / radians: one launch and ONE copy to the host (kb_get_state), for get_state() after every step."""
+        nat.refuse_capture('host_state()', 'call it outside the capture, or capture poses() and object_poses(), which stay on the device')
         N, M = self.num_bots, self.num_objects
         out = torch.empty(self.num_envs, 3 * (N + M) + 1, dtype=torch.float32, device=self.device)
         self._call('kb_get_state', out.data_ptr())
@@ -265,6 +266,7 @@ class KilobotSim:
 
     def status_bits(self):
         """OR of the status flags of all envs (one device read; synchronises the stream)."""
+        nat.refuse_capture('status_bits()', "call it outside the capture (kb_buffers.status accumulates over the replays); an env takes on_status='ignore'")
         s = self.status
         if s.numel() <= (1 << 16):           # one small copy; OR on the host (4 reductions + 4 syncs cost 0.1 ms per env.step)
             return int(np.bitwise_or.reduce(s.cpu().numpy(), initial=0)) & sum(STATUS_BITS)
@@ -277,6 +279,7 @@ class KilobotSim:
         """Surface capacity overflows of the device step: mode 'raise' | 'warn' | 'ignore'.  Returns the bits."""
         if mode == 'ignore':
             return 0
+        nat.refuse_capture('check_status(%r)' % (mode,), "call it outside the capture (kb_buffers.status accumulates over the replays), or with mode='ignore'")
         bits = self.status_bits()
         if bits:
             bad = int((self.status != 0).sum().item())
@@ -321,6 +324,8 @@ class KilobotSim:
         nnz are left alone.  For an int64 edge_index [2, nnz] stack and cast in torch: torch.stack((src, dst)).long()."""
         E, N = self.num_envs, self.num_bots
         radius_m, capacity = nat.check_edges(radius_m, capacity)
+        if capacity is None:
+            nat.refuse_capture('edges(capacity=None)', 'pass capacity=int, which sizes the lists on the host and leaves nnz on the device')
         count = self.sense(radius_m)
         offsets = torch.zeros(E * N + 1, dtype=torch.int64, device=self.device)
         torch.cumsum(count.view(-1), 0, dtype=torch.int64, out=offsets[1:])
@@ -618,6 +623,7 @@ class KilobotSim:
         array-like or tensor [E, K, 2] or [K, 2] (shared by all envs), binned on the host by the grid's cell rule
         (nat.path_cells: a point outside the arena lands in the nearest edge cell) and uploaded.  What lets the goal of
         paths() be given as positions; not for the inner loop."""
+        nat.refuse_capture('path_cells()', 'it bins the points on the host and uploads the mask; call it before the capture and write into the mask in place')
         points = np.asarray(points_m.cpu() if torch.is_tensor(points_m) else points_m, dtype=np.float32)
         if points.ndim == 3 and points.shape[0] != self.num_envs:
             raise ValueError('points_m must have the shape (K, 2) or (%d, K, 2)' % self.num_envs)

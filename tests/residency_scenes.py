@@ -81,6 +81,7 @@ FIELD_CHANNELS, FIELD_ITERS, FIELD_KEEP, FIELD_SPREAD = 2, 3, (0.95, 0.8), (0.2,
 FIELD_MASK = np.array([1, 1, 1, 0, 1], dtype=np.uint8)
 REDUCE_CHANNELS = 3
 TARGET_SLOTS, TARGET_TOL = 40, 0.02
+ASSIGN_CUTOFF = 0.25        # metres: the slots in the corners of the table find no kilobot within it and stay unmatched
 CLEARANCE = 0.0165
 RAYS = (0.2, 16)
 NEIGHBORS_K, HIST, CONTACTS_K = 8, (4, 8), 8
@@ -179,6 +180,8 @@ SENSORS = [
     Row('field_step', 'field_step', ('field', 'sense'), _field, ()),
     Row('paths', 'paths', ('dist', 'step', 'bots', 'stats'), _paths(GRID), ()),
     Row('targets', 'targets', ('index', 'rel', 'owner', 'dist', 'stats'), lambda sim, out: tuple(sim.targets(tiled(sim, 'points'), TARGET_TOL, out=out)), ()),
+    Row('assign', 'targets', ('index', 'rel', 'owner', 'dist', 'stats'),
+        lambda sim, out: tuple(sim.targets(tiled(sim, 'points'), TARGET_TOL, out=out, match='greedy', cutoff_m=ASSIGN_CUTOFF)), ()),
     Row('contacts', 'contacts', ('partner', 'impulse', 'touch', 'obj'), lambda sim, out: sim.contacts(CONTACTS_K, out=out), ()),
     Row('render', 'render', ('rgb',), lambda sim, out: (sim.render(GRID[0], GRID[1], out=_first(out)),), ()),
     Row('light_sense', 'light_sense', ('light_value', 'light_gx', 'light_gy', 'light_x', 'light_y'), _light_sense, ()),

@@ -16,6 +16,7 @@ import torch
 
 from gym_kilobots_amd import _native as nat
 from oracle import oracle as O
+from tests import assign_ref
 from tests import edges_ref
 from tests import field_ref
 from tests import grid_ref
@@ -174,6 +175,7 @@ WANT = {
     'field_step': want_field,
     'paths': want_paths(RS.GRID),
     'targets': lambda g: tuple(SC.check_targets(g, RS.tiled(g, 'points'), RS.TARGET_TOL, what='residency')),
+    'assign': lambda g: tuple(assign_ref.restate(*state(g), RS.inputs(g.num_bots)['points'], RS.TARGET_TOL, RS.ASSIGN_CUTOFF)),
     'contacts': lambda g: SC.want_contacts(g, RS.CONTACTS_K),
     'render': lambda g: (SC.check_render(g, RS.GRID[0], RS.GRID[1], what='residency'),),
     'light_sense': want_light_sense,
